@@ -190,7 +190,12 @@ def main():
     ap.add_argument("--force-collective", action="store_true", help="initialise RCCL and run the all-gather even with one rank (rehearsal)")
     ap.add_argument("--settle-steps", type=int, default=40, help="untimed steps before the warm-up while the GPU leaves its idle power state (0: none)")
     ap.add_argument("--opt", action="append", default=[], help="engine option name=value (tuning experiments)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (keys, hamming, prefix_bits, count) as "
+                         "DIR/<name>.npy in float64 / float32, to compare two builds output for output (e.g. DIR = bench_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ONE JSON line on stdout: RCCL prints a version banner to stdout when a communicator is created, so everything
     # below runs with fd 1 pointing at stderr and the line is written to the real stdout at the end
@@ -280,6 +285,7 @@ def main():
         gate.append(ans)
     first = gate[0]
     batches_compared = set()
+    final = [None, None]   # (batch, answer) of the last step of the latest measure()
 
     def measure(steps):
         """`steps` steps with per-launch HIP events; returns (seconds, statistics).  Every batch's LAST answer must equal its gate answer."""
@@ -294,6 +300,7 @@ def main():
             b, out = step()
             last[b] = out
         fence()
+        final[:] = [b, out]
         el = time.perf_counter() - t0
         engine.set_option("profile", 0)
         st = engine.stats(reset=True)
@@ -332,10 +339,15 @@ def main():
             settle_steps += 1
             if world == 1 and len(hist) >= 10 and abs(sum(hist[-5:]) - sum(hist[-10:-5])) <= 0.01 * sum(hist[-10:-5]):
                 break
+    # the settle loop's length depends on timing: a few more untimed steps of the rotation let the timed steps start at batch 0
+    # whatever it took, so the same arguments give the timed region (and --dump-outputs) the same batches on every run
+    while (turn[0] + args.warmup) % n_batches:
+        step()
     for _ in range(args.warmup):
         step()
     elapsed, st = measure(args.steps)
     elapsed = max_over_ranks(elapsed)
+    timed_batch, timed_answer = final
 
     batched = args.queries > args.tq
     # (64-bit codes take the packed matrix-core kernel from 9 queries: engine option mfma_pack_min_queries)
@@ -453,6 +465,9 @@ def main():
         out["cpu_baseline"] = cpu_baseline(args, q, words, first, second)
         out["parity_checked_queries"] = out["cpu_baseline"]["parity_checked_queries"]
 
+    if rank == 0 and args.dump_outputs:
+        out["dump_outputs"] = dump_outputs(args.dump_outputs, timed_batch, timed_answer)
+
     sys.stdout.flush()
     if rank == 0:
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
@@ -460,6 +475,38 @@ def main():
     engine.close()
     if dist.is_initialized():
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+SEED_DUMP = 0x1511CC04
+
+
+def dump_outputs(out_dir, batch, answer):
+    """
+    --dump-outputs: the answer of the last timed step (keys as float64, exact below 2**53; hamming, prefix_bits and count as
+    float32) as out_dir/<name>.npy.  Answers above DUMP_LIMIT_BYTES keep a fixed, seeded sample of query rows, listed in
+    query_index.npy.
+    """
+    names = ("keys", "hamming", "prefix_bits", "count")
+    dtypes = (np.float64, np.float32, np.float32, np.float32)
+    arrays = [np.asarray(a) for a in answer]
+    nq = arrays[0].shape[0]
+    row_bytes = sum(np.dtype(t).itemsize * (a.size // max(nq, 1)) for a, t in zip(arrays, dtypes))
+    rows = None
+    if nq * row_bytes > DUMP_LIMIT_BYTES:
+        keep = max(1, (DUMP_LIMIT_BYTES - 8 * nq) // row_bytes)
+        rows = np.sort(np.random.default_rng(SEED_DUMP).choice(nq, size=min(keep, nq), replace=False))
+        arrays = [a[rows] for a in arrays]
+    os.makedirs(out_dir, exist_ok=True)
+    files = []
+    for name, a, t in zip(names, arrays, dtypes):
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(t))
+        files.append(name + ".npy")
+    if rows is not None:
+        np.save(os.path.join(out_dir, "query_index.npy"), rows.astype(np.float64))
+        files.append("query_index.npy")
+    return {"dir": out_dir, "files": files, "batch": int(batch), "queries": nq,
+            "queries_written": nq if rows is None else int(len(rows))}
 
 
 def usable_cores(omp_threads):

@@ -31,3 +31,32 @@ def test_bench_fails_loudly_when_results_differ_from_the_oracle():
     bad[0][5, 3] ^= np.uint64(1)
     with pytest.raises(SystemExit, match="PARITY FAILURE"):
         bench.cpu_baseline(Args, q, 1, bad)
+
+
+def test_dump_outputs_writes_float_arrays_and_caps_their_size(tmp_path, monkeypatch):
+    """`--dump-outputs`: the four arrays of an answer as float64 / float32 .npy; above the cap, a fixed seeded sample of rows."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    rng = np.random.default_rng(7)
+    nq, k = 300, 10
+    answer = (rng.integers(0, 2**40, size=(nq, k), dtype=np.uint64), rng.integers(0, 64, size=(nq, k), dtype=np.uint32),
+              rng.integers(0, 64, size=(nq, k), dtype=np.uint16), np.full(nq, k, dtype=np.uint32))
+    info = bench.dump_outputs(str(tmp_path / "all"), 3, answer)
+    assert info["batch"] == 3 and info["queries_written"] == nq and "query_index.npy" not in info["files"]
+    for name, a in zip(("keys", "hamming", "prefix_bits", "count"), answer):
+        got = np.load(tmp_path / "all" / f"{name}.npy")
+        assert got.dtype in (np.float32, np.float64)
+        assert np.array_equal(got.astype(np.uint64), a.astype(np.uint64))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100 * (8 + 4 + 4) * k)
+    sizes = []
+    for run in ("a", "b"):
+        info = bench.dump_outputs(str(tmp_path / run), 0, answer)
+        sizes.append(sum(os.path.getsize(tmp_path / run / f) for f in info["files"]))
+        assert 0 < info["queries_written"] < nq
+    rows = np.load(tmp_path / "a" / "query_index.npy").astype(np.int64)
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "query_index.npy").astype(np.int64))
+    assert np.array_equal(np.load(tmp_path / "a" / "keys.npy").astype(np.uint64), answer[0][rows])
+    assert sizes[0] - 4 * 128 <= bench.DUMP_LIMIT_BYTES   # (.npy headers aside)

@@ -91,3 +91,26 @@ def test_a_one_rank_collective_run_reports_what_the_communicator_saw(one_queue):
     out = json.loads([l for l in proc.stdout.splitlines() if l.strip()][-1])
     assert out["world_size_seen"] == 1 and out["collective_backend"] == "nccl" and out["rccl_version"]
     assert out["batches_gated"] == 8 and len(out["batches_compared_after_measurement"]) >= 3      # three measured steps (and what the other legs rotated through)
+
+
+def test_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """`--dump-outputs DIR`: the last timed step's answer, identical for identical arguments (the settle loop's length varies)."""
+    import numpy as np
+
+    lines = []
+    for run in ("a", "b"):
+        proc = subprocess.run(
+            [sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "2000000", "--steps", "5", "--warmup", "1", "--no-cpu-baseline",
+             "--no-extra-legs", "--no-other-configs", "--dump-outputs", str(tmp_path / run)],
+            capture_output=True, text=True, timeout=600, cwd=ROOT,
+        )
+        assert proc.returncode == 0, proc.stderr[-2000:]
+        lines.append(json.loads([l for l in proc.stdout.splitlines() if l.strip()][-1]))
+    for out in lines:
+        assert out["steps"] == 5 and out["ms_per_step"] > 0
+        assert out["dump_outputs"]["batch"] == 4 and out["dump_outputs"]["queries_written"] == 1024
+    for name in ("keys", "hamming", "prefix_bits", "count"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype in (np.float32, np.float64) and a.shape[0] == 1024
+        assert np.array_equal(a, b), name
+    assert np.all(np.load(tmp_path / "a" / "count.npy") == 10)
