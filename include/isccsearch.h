@@ -291,6 +291,37 @@ int isccsearch_simprint_exact(isccsearch_handle* h, uint32_t table, uint32_t n_d
                               uint32_t n_given, const uint32_t* given, uint32_t queried, uint32_t dup_limit, double threshold, uint32_t limit,
                               isccsearch_simprint_result* out_results, isccsearch_simprint_chunk* out_chunks, uint32_t* out_info);
 
+/* Many asset queries in one call, scored on the device: what UsearchIndex.search_assets does for the units of ONE query
+ * (iscc_search/indexes/usearch/index.py:786-839 -- one search per similarity unit, :2024-2045, one prefix match per INSTANCE
+ * unit, :1957-2045; the max per (asset, unit type), the threshold, sum(s ** e) / sum(s) over the confident types, the
+ * self-exclusion, the stable sort by score and the cut to `limit`) for nq <= 1 024 queries at once.  Query q holds the units
+ * units[unit_offsets[q] .. unit_offsets[q + 1]) (at most ISCCSEARCH_MAX_ASSET_UNITS), in the query's order.  The units of
+ * all queries are searched as ONE batch per (table, code length, kind); the lists stay on the device, where one block per
+ * query groups them by asset (asset_score.hip).  INSTANCE units (max_hamming = 0) list instance_first_k rows first; the
+ * lists that came back full are searched again with instance_max_k.
+ *   score_table / pow_table   [(ISCCSEARCH_MAX_BYTES + 1) x 257] host-computed: entry [prefix_bits / 8][hamming] holds the unit
+ *                             score max(0, 1 - float64(float32(h) / float32(prefix_bits))) and its power score ** exponent
+ *   exclude / has_exclude     [nq] per query the asset key left out of its results (an iscc_id query's own asset)
+ *   compensated               0: sums are sequential float64 additions (CPython <= 3.11 sum), 1: Neumaier's compensated form (>= 3.12)
+ * Outputs: out_keys[nq*limit], out_scores[nq*limit] (min(1, total)), out_count[nq]; per result its unit types in insertion
+ * order out_types[nq*limit*n_types] (type index, 0xFF past the last) with their scores out_type_scores[nq*limit*n_types];
+ * out_unit_count[total units] the final length of every unit's list (an INSTANCE list that reaches instance_max_k was cut). */
+#define ISCCSEARCH_MAX_ASSET_UNITS 64
+#define ISCCSEARCH_MAX_UNIT_TYPES  16
+typedef struct isccsearch_asset_unit {
+    uint32_t table;       /* NPHD table of the unit's type, 64-bit keys */
+    uint32_t type;        /* index of the unit type (< n_types) */
+    int32_t max_hamming;  /* < 0: similarity unit (k = limit); 0: INSTANCE prefix match */
+    uint32_t nbytes;      /* code length in bytes */
+    uint64_t words[4];    /* the code, packed as for isccsearch_search */
+} isccsearch_asset_unit;
+int isccsearch_match_assets(isccsearch_handle* h, uint32_t nq, const uint32_t* unit_offsets, const isccsearch_asset_unit* units,
+                            uint32_t limit, uint32_t instance_first_k, uint32_t instance_max_k,
+                            const uint64_t* exclude, const uint8_t* has_exclude,
+                            const double* score_table, const double* pow_table, double threshold, int compensated, uint32_t n_types,
+                            uint64_t* out_keys, double* out_scores, uint32_t* out_count, uint8_t* out_types, double* out_type_scores,
+                            uint32_t* out_unit_count);
+
 /* Multi-GPU building blocks (row-range shards, one process per GPU).
  * search_device: same search, results left in caller-provided DEVICE memory
  *   d_records[nq*k] (isccsearch_record), d_counts[nq]; queries must share one byte length.

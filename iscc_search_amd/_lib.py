@@ -29,7 +29,7 @@ EXPORTS = (
     "isccsearch_size", "isccsearch_add", "isccsearch_remove", "isccsearch_contains", "isccsearch_get",
     "isccsearch_segments", "isccsearch_export", "isccsearch_add_columns",
     "isccsearch_add_synthetic", "isccsearch_search", "isccsearch_search_within", "isccsearch_search_many", "isccsearch_doc_freq", "isccsearch_doc_freq_counted", "isccsearch_get_freq",
-    "isccsearch_simprint_score", "isccsearch_simprint_exact",
+    "isccsearch_simprint_score", "isccsearch_simprint_exact", "isccsearch_match_assets",
     "isccsearch_search_device", "isccsearch_search_within_device", "isccsearch_merge_device",
     "isccsearch_search_device_async", "isccsearch_merge_device_after", "isccsearch_merge_many_after", "isccsearch_stream",
 )
@@ -42,6 +42,12 @@ assert RECORD_DTYPE.itemsize == 24
 SIMPRINT_RESULT_DTYPE = np.dtype([("asset", "<u8"), ("score", "<f8"), ("matches", "<u4"), ("first_chunk", "<u4")])
 SIMPRINT_CHUNK_DTYPE = np.dtype([("key_lo", "<u8"), ("query", "<u4"), ("hamming", "<u4"), ("freq", "<u4"), ("reserved", "<u4")])
 assert SIMPRINT_RESULT_DTYPE.itemsize == 24 and SIMPRINT_CHUNK_DTYPE.itemsize == 24
+# isccsearch_asset_unit (isccsearch_match_assets): one unit of one asset query
+MAX_ASSET_UNITS = 64          # ISCCSEARCH_MAX_ASSET_UNITS: units per asset query
+MAX_UNIT_TYPES = 16           # ISCCSEARCH_MAX_UNIT_TYPES: unit types per call
+ASSET_QUERIES_MAX = 1024      # asset queries per isccsearch_match_assets call (QB_MAX)
+ASSET_UNIT_DTYPE = np.dtype([("table", "<u4"), ("type", "<u4"), ("max_hamming", "<i4"), ("nbytes", "<u4"), ("words", "<u8", (4,))])
+assert ASSET_UNIT_DTYPE.itemsize == 48
 
 
 class Stats(ctypes.Structure):
@@ -176,6 +182,8 @@ def load_library():
         "isccsearch_get_freq": (i, [vp, u32, u64, u64p, u32, u32p]),
         "isccsearch_simprint_score": (i, [vp, u32, u32, u64p, u32, ctypes.c_int32, ctypes.c_double, u32, ctypes.c_int64, u32, vp, vp, vp, u32p]),
         "isccsearch_simprint_exact": (i, [vp, u32, u32, u64p, u32, u32p, u32, u32, ctypes.c_double, u32, vp, vp, u32p]),
+        "isccsearch_match_assets": (i, [vp, u32, u32p, vp, u32, u32, u32, u64p, u8p, vp, vp, ctypes.c_double, i, u32,
+                                        u64p, vp, u32p, u8p, vp, u32p]),
         "isccsearch_search_device": (i, [vp, u32, u32, u64p, u8p, u32, vp, vp]),
         "isccsearch_search_within_device": (i, [vp, u32, u32, u64p, u8p, u32, u32, vp, vp]),
         "isccsearch_merge_device": (i, [vp, u32, u32, u32, i, vp, vp, u64, u64, u64p, u32p, u16p, u32p]),

@@ -160,6 +160,37 @@ class HipEngine:
         _lib.check(self._lib.isccsearch_search_many(self.handle, n, arr))
         return outs
 
+    def match_assets(self, units, offsets, limit, instance_first_k, instance_max_k, exclude, has_exclude, score_table, pow_table,
+                     threshold, compensated, n_types):
+        # type: (np.ndarray, np.ndarray, int, int, int, np.ndarray, np.ndarray, np.ndarray, np.ndarray, float, bool, int) -> tuple
+        """
+        The unit searches of up to ``_lib.ASSET_QUERIES_MAX`` asset queries and their per-asset scoring on the device
+        (``isccsearch_match_assets``).  ``units`` is an ``_lib.ASSET_UNIT_DTYPE`` array, query q holding
+        ``units[offsets[q]:offsets[q + 1]]``.  Returns (keys u64 [nq, limit], scores f64 [nq, limit], counts u32 [nq],
+        types u8 [nq, limit, n_types] (type index in insertion order, 255 past the last), type scores f64 [nq, limit, n_types],
+        unit counts u32 [len(units)]).
+        """
+        nq = len(offsets) - 1
+        units = np.ascontiguousarray(units, dtype=_lib.ASSET_UNIT_DTYPE)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
+        exclude = np.ascontiguousarray(exclude, dtype=np.uint64)
+        has_exclude = np.ascontiguousarray(has_exclude, dtype=np.uint8)
+        score_table = np.ascontiguousarray(score_table, dtype=np.float64)
+        pow_table = np.ascontiguousarray(pow_table, dtype=np.float64)
+        if score_table.size != pow_table.size or score_table.size != (_lib.MAX_BYTES + 1) * 257:
+            raise ValueError("score tables must hold (MAX_BYTES + 1) x 257 entries")
+        keys = np.zeros((nq, limit), dtype=np.uint64)
+        scores = np.zeros((nq, limit), dtype=np.float64)
+        counts = np.zeros(nq, dtype=np.uint32)
+        types = np.zeros((nq, limit, n_types), dtype=np.uint8)
+        type_scores = np.zeros((nq, limit, n_types), dtype=np.float64)
+        unit_counts = np.zeros(max(1, len(units)), dtype=np.uint32)
+        _lib.check(self._lib.isccsearch_match_assets(
+            self.handle, nq, _lib.ptr(offsets), _lib.ptr(units), limit, instance_first_k, instance_max_k, _lib.ptr(exclude),
+            _lib.ptr(has_exclude), _lib.ptr(score_table), _lib.ptr(pow_table), float(threshold), 1 if compensated else 0, n_types,
+            _lib.ptr(keys), _lib.ptr(scores), _lib.ptr(counts), _lib.ptr(types), _lib.ptr(type_scores), _lib.ptr(unit_counts)))
+        return keys, scores, counts, types, type_scores, unit_counts[: len(units)]
+
     def close(self):
         # type: () -> None
         """Idempotent (``protocols/index.py:167-172``)."""

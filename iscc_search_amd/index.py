@@ -16,6 +16,7 @@ import json
 import os
 import re
 import shutil
+import sys
 import threading
 from dataclasses import dataclass
 from typing import Dict, List, Optional
@@ -24,6 +25,7 @@ from urllib.parse import parse_qs, urlparse
 import numpy as np
 
 from iscc_search_amd import codec
+from iscc_search_amd import _lib
 from iscc_search_amd._lib import MAX_K
 
 INSTANCE_FIRST_K = 64   # records per query an INSTANCE prefix match asks for first (a full list is asked again up to MAX_K)
@@ -96,6 +98,84 @@ def _check_instance_hits(count, unit_type):
     """An identity (INSTANCE) match list that fills the engine's cap would be cut silently: refuse instead."""
     if count >= MAX_K:
         raise ValueError(f"more than {MAX_K - 1} assets share the queried {unit_type} prefix; refine the query (longer code)")
+
+
+@dataclass
+class UnitMatches:
+    """
+    Raw answer of ``HipIndex.match_units_many``: per query the first ``counts[q]`` entries of every row are its assets in
+    ``search_assets`` order.  ``type_index[q, r]`` lists the unit types of result r (indices into ``types``) in the insertion
+    order of ``IsccGlobalMatch.types``, 255 past the last; ``type_scores`` holds their scores.
+    """
+
+    keys: np.ndarray          # u64 [nq, limit]
+    scores: np.ndarray        # f64 [nq, limit], min(1.0, total)
+    counts: np.ndarray        # u32 [nq]
+    types: tuple              # unit type names
+    type_index: np.ndarray    # u8 [nq, limit, len(types)]
+    type_scores: np.ndarray   # f64 [nq, limit, len(types)]
+
+
+_SCORE_TABLES = {}
+
+
+def _unit_score_tables(exponent):
+    """
+    [prefix bytes 0..32][hamming 0..256]: the unit score ``max(0, 1 - float64(float32(h) / float32(bits)))`` exactly as
+    ``_search_units`` computes it, and ``score ** exponent`` as CPython computes it (None when Python would raise).
+    """
+    tabs = _SCORE_TABLES.get(exponent)
+    if tabs is None:
+        bits = (np.arange(_lib.MAX_BYTES + 1) * 8).astype(np.float32)
+        ham = np.arange(257).astype(np.float32)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            dist = ham[None, :] / bits[:, None]
+        score = np.maximum(0.0, 1.0 - dist.astype(np.float64))
+        score[0, :] = 0.0                                # (no code is 0 bytes long)
+        try:
+            pows = np.array([s**exponent for s in score.ravel().tolist()], dtype=np.float64)
+        except (ZeroDivisionError, OverflowError, TypeError):
+            pows = None
+        tabs = _SCORE_TABLES[exponent] = (score.ravel().copy(), pows)
+    return tabs
+
+
+def _merge_instance(aggregated, unit_type, keys):
+    # type: (Dict[int, Dict[str, float]], str, list) -> None
+    """An INSTANCE prefix match list into the per-asset scores: every hit scores 1.0 (``usearch/index.py:2010``)."""
+    for key in keys:
+        aggregated.setdefault(key, {})[unit_type] = 1.0
+
+
+def _merge_similarity(aggregated, unit_type, keys, scores):
+    # type: (Dict[int, Dict[str, float]], str, list, list) -> None
+    """A similarity unit's list into the per-asset scores: max per (key, unit_type), first appearance keeps its place (:806)."""
+    for key, score in zip(keys, scores):
+        slot = aggregated.get(key)
+        if slot is None:
+            aggregated[key] = {unit_type: score}
+        elif score > slot.get(unit_type, 0.0):          # max per (key, unit_type), :806; scores are >= 0.0
+            slot[unit_type] = score
+        else:
+            slot.setdefault(unit_type, 0.0)
+
+
+def _rank_aggregated(aggregated, thr, exp, query_iscc_id, limit):
+    # type: (Dict[int, Dict[str, float]], float, int, Optional[str], int) -> list
+    """``usearch/index.py:808-839``: threshold, confidence-weighted total, self-exclusion, stable sort, cut: [(key, total, unit_scores)]."""
+    scored = []
+    for key, unit_scores in aggregated.items():
+        confident = {t: s for t, s in unit_scores.items() if s >= thr}
+        if not confident:
+            continue
+        weight_sum = sum(confident.values())
+        total = sum(s**exp for s in confident.values()) / weight_sum if weight_sum > 0 else 0.0
+        scored.append((key, total, unit_scores))
+    if query_iscc_id:
+        qkey = codec.iscc_id_to_int(query_iscc_id)
+        scored = [r for r in scored if r[0] != qkey]
+    scored.sort(key=lambda r: r[1], reverse=True)   # stable, as the reference (:836)
+    return scored[:limit]
 
 
 class HipIndex:
@@ -335,21 +415,13 @@ class HipIndex:
                     keys, ham, pbits, cnt = self._engine.search_many([request[:3] + (MAX_K, 0)])[0]
                     c = int(cnt[0])
                 _check_instance_hits(c, unit_type)
-                for key in keys[0, :c].tolist():
-                    aggregated.setdefault(key, {})[unit_type] = 1.0
+                _merge_instance(aggregated, unit_type, keys[0, :c].tolist())
                 continue
             # float32 NPHD as HipNphdIndex.search hands it out, then the reference's float64 `1.0 - d` clamp (:2041-2043) -- the same
             # IEEE operations on the whole list at once (a float32 widens to float64 exactly), then plain Python numbers
             dist = ham[0, :c].astype(np.float32) / pbits[0, :c].astype(np.float32)
             scores = np.maximum(0.0, 1.0 - dist.astype(np.float64)).tolist()
-            for key, score in zip(keys[0, :c].tolist(), scores):
-                slot = aggregated.get(key)
-                if slot is None:
-                    aggregated[key] = {unit_type: score}
-                elif score > slot.get(unit_type, 0.0):          # max per (key, unit_type), :806; scores are >= 0.0
-                    slot[unit_type] = score
-                else:
-                    slot.setdefault(unit_type, 0.0)
+            _merge_similarity(aggregated, unit_type, keys[0, :c].tolist(), scores)
         return aggregated
 
     def search_assets(self, query, limit=100, exact=False):
@@ -370,20 +442,8 @@ class HipIndex:
         matches = []
         if query.units:
             aggregated = self._search_units(query.units, limit)
-            scored = []
-            thr, exp = self._opts.match_threshold_units, self._opts.confidence_exponent
-            for key, unit_scores in aggregated.items():
-                confident = {t: s for t, s in unit_scores.items() if s >= thr}
-                if not confident:
-                    continue
-                weight_sum = sum(confident.values())
-                total = sum(s**exp for s in confident.values()) / weight_sum if weight_sum > 0 else 0.0
-                scored.append((key, total, unit_scores))
-            if query_iscc_id:
-                qkey = codec.iscc_id_to_int(query_iscc_id)
-                scored = [r for r in scored if r[0] != qkey]
-            scored.sort(key=lambda r: r[1], reverse=True)   # stable, as the reference (:836)
-            for key, total, unit_scores in scored[:limit]:
+            scored = _rank_aggregated(aggregated, self._opts.match_threshold_units, self._opts.confidence_exponent, query_iscc_id, limit)
+            for key, total, unit_scores in scored:
                 asset = self._assets.get(key)
                 source = metadata = None
                 if asset is not None and asset.metadata:
@@ -396,6 +456,225 @@ class HipIndex:
         if query_iscc_id:
             chunk_matches = [m for m in chunk_matches if m.iscc_id != query_iscc_id]
         return IsccSearchResult(query=query, global_matches=matches, chunk_matches=chunk_matches)
+
+    # -- bulk search -------------------------------------------------------------------------------
+    def _prepare_many(self, queries):
+        # type: (List[IsccQuery]) -> list
+        """
+        Every query as ``search_assets`` sees it -- (normalised query, query iscc_id or None, [(unit_type, body)] of the indexed
+        unit types in query order) -- or the exception ``search_assets`` would raise, naming the query's index in ``queries``.
+        """
+        prepared = []
+        for i, query in enumerate(queries):
+            try:
+                query_iscc_id = None
+                if query.iscc_id:
+                    query_iscc_id = query.iscc_id
+                    asset = self.get_asset(query.iscc_id)
+                    query = IsccQuery(iscc_code=asset.iscc_code, units=asset.units, simprints=None)
+                query = normalize_query(query)
+                units = []
+                for unit_str in query.units or []:
+                    unit = codec.parse(unit_str)
+                    if unit.unit_type in self._unit_tables:
+                        units.append((unit.unit_type, unit.body))
+                if self._sp_tables and query.simprints:
+                    for simprint_objs in query.simprints.values():
+                        for sp in simprint_objs:
+                            codec.decode_base64(_sp_string(sp))
+            except (ValueError, FileNotFoundError) as e:
+                raise type(e)(f"queries[{i}]: {e}") from e
+            prepared.append((query, query_iscc_id, units))
+        return prepared
+
+    def match_units_many(self, queries, limit=100):
+        # type: (List[IsccQuery], int) -> UnitMatches
+        """
+        The unit part of ``search_assets`` for many queries at once, as NumPy arrays (no pydantic objects): per query its
+        assets, scores and per-unit-type scores in ``search_assets`` order.  On a single-GPU engine every unit type (and code
+        length) is ONE batched search over all queries and the per-asset aggregation runs on the device
+        (``isccsearch_match_assets``); other engines run one batched ``search_many`` request per unit type and the
+        aggregation of ``search_assets`` on the host.  Simprints are not looked at.
+        """
+        if not 1 <= limit <= MAX_K:
+            _checked_limit(limit)
+            raise ValueError(f"limit {limit} must be >= 1")
+        prepared = self._prepare_many(queries)
+        return self._match_prepared(prepared, limit)
+
+    def _match_prepared(self, prepared, limit):
+        types = []
+        for _, _, units in prepared:
+            for unit_type, _ in units:
+                if unit_type not in types:
+                    types.append(unit_type)
+        types = tuple(types)
+        nq, nt = len(prepared), max(1, len(types))
+        out = UnitMatches(np.zeros((nq, limit), dtype=np.uint64), np.zeros((nq, limit), dtype=np.float64), np.zeros(nq, dtype=np.uint32),
+                          types, np.full((nq, limit, nt), 255, dtype=np.uint8), np.zeros((nq, limit, nt), dtype=np.float64))
+        score_tab, pow_tab = _unit_score_tables(self._opts.confidence_exponent)
+        device = (hasattr(self._engine, "match_assets") and pow_tab is not None and len(types) <= _lib.MAX_UNIT_TYPES
+                  and all(len(units) <= _lib.MAX_ASSET_UNITS for _, _, units in prepared))
+        step = _lib.ASSET_QUERIES_MAX
+        for first in range(0, nq, step):
+            part = prepared[first:first + step]
+            if device:
+                self._match_device(part, first, limit, types, score_tab, pow_tab, out)
+            else:
+                self._match_host(part, first, limit, types, out)
+        return out
+
+    def _match_device(self, part, first, limit, types, score_tab, pow_tab, out):
+        # the unit records as columns: one join of the zero-padded codes instead of one pack_bytes and record write per unit
+        offsets = np.zeros(len(part) + 1, dtype=np.uint32)
+        exclude = np.zeros(len(part), dtype=np.uint64)
+        has_exclude = np.zeros(len(part), dtype=np.uint8)
+        table_of = {t: self._unit_tables[t]._table.id for t in types}
+        type_of = {t: i for i, t in enumerate(types)}
+        inst_of = {t: t.startswith("INSTANCE_") for t in types}
+        tids, tys, bodies, instances = [], [], [], []   # instances: (query, unit position, unit type) of the INSTANCE units
+        u = 0
+        for q, (_, query_iscc_id, units) in enumerate(part):
+            if query_iscc_id:
+                exclude[q] = codec.iscc_id_to_int(query_iscc_id)
+                has_exclude[q] = 1
+            for unit_type, body in units:
+                if not 1 <= len(body) <= _lib.MAX_BYTES:
+                    raise ValueError(f"code length {len(body)} bytes outside 1..{_lib.MAX_BYTES}")
+                tids.append(table_of[unit_type])
+                tys.append(type_of[unit_type])
+                bodies.append(body)
+                if inst_of[unit_type]:
+                    instances.append((q, u, unit_type))
+                u += 1
+            offsets[q + 1] = u
+        arr = np.zeros(u, dtype=_lib.ASSET_UNIT_DTYPE)
+        if u:
+            arr["table"] = tids
+            arr["type"] = tys
+            arr["nbytes"] = [len(b) for b in bodies]
+            arr["max_hamming"] = [0 if inst_of[types[t]] else -1 for t in tys]
+            arr["words"] = np.frombuffer(b"".join(b.ljust(_lib.MAX_BYTES, b"\0") for b in bodies), dtype=">u8").reshape(u, 4)
+        keys, scores, counts, tidx, tsc, unit_counts = self._engine.match_assets(
+            arr, offsets, limit, INSTANCE_FIRST_K, MAX_K, exclude, has_exclude, score_tab, pow_tab,
+            self._opts.match_threshold_units, sys.version_info >= (3, 12), max(1, len(types)))
+        for q, u, unit_type in instances:
+            try:
+                _check_instance_hits(int(unit_counts[u]), unit_type)
+            except ValueError as e:
+                raise ValueError(f"queries[{first + q}]: {e}") from e
+        n = len(part)
+        out.keys[first:first + n] = keys
+        out.scores[first:first + n] = scores
+        out.counts[first:first + n] = counts
+        out.type_index[first:first + n] = tidx
+        out.type_scores[first:first + n] = tsc
+
+    def _match_host(self, part, first, limit, types, out):
+        """Engines without ``match_assets``: one ``search_many`` request per (unit type, code length), the host aggregation."""
+        groups = {}  # type: Dict[tuple, list]          (unit_type, nbytes) -> [(query, slot, body)]
+        for q, (_, _, units) in enumerate(part):
+            for j, (unit_type, body) in enumerate(units):
+                groups.setdefault((unit_type, len(body)), []).append((q, j, body))
+        results = {}  # (query, slot) -> keys (list) or (keys, scores)
+        requests, plan = [], []
+        for (unit_type, _), items in groups.items():
+            index = self._unit_tables[unit_type]
+            words, nbytes = pack_bytes([body for _, _, body in items], index._table.max_words)
+            inst = unit_type.startswith("INSTANCE_")
+            requests.append((index._table, words, nbytes, INSTANCE_FIRST_K if inst else limit, 0 if inst else None))
+            plan.append((unit_type, items))
+        again_req, again_plan = [], []
+        for (unit_type, items), request, (keys, ham, pbits, cnt) in zip(plan, requests, self._engine.search_many(requests) if requests else []):
+            full = []
+            for r, (q, j, _) in enumerate(items):
+                c = int(cnt[r])
+                if unit_type.startswith("INSTANCE_"):
+                    if c == INSTANCE_FIRST_K:
+                        full.append(r)
+                    results[(q, j)] = keys[r, :c].tolist()
+                    continue
+                dist = ham[r, :c].astype(np.float32) / pbits[r, :c].astype(np.float32)
+                results[(q, j)] = (keys[r, :c].tolist(), np.maximum(0.0, 1.0 - dist.astype(np.float64)).tolist())
+            if full:
+                again_req.append((request[0], request[1][full], request[2][full], MAX_K, 0))
+                again_plan.append([items[r] for r in full])
+        for items, (keys, ham, pbits, cnt) in zip(again_plan, self._engine.search_many(again_req) if again_req else []):
+            for r, (q, j, _) in enumerate(items):
+                results[(q, j)] = keys[r, : int(cnt[r])].tolist()
+        type_of = {t: i for i, t in enumerate(types)}
+        thr, exp = self._opts.match_threshold_units, self._opts.confidence_exponent
+        for q, (_, query_iscc_id, units) in enumerate(part):
+            aggregated = {}  # type: Dict[int, Dict[str, float]]
+            for j, (unit_type, _) in enumerate(units):
+                res = results[(q, j)]
+                if unit_type.startswith("INSTANCE_"):
+                    try:
+                        _check_instance_hits(len(res), unit_type)
+                    except ValueError as e:
+                        raise ValueError(f"queries[{first + q}]: {e}") from e
+                    _merge_instance(aggregated, unit_type, res)
+                    continue
+                _merge_similarity(aggregated, unit_type, *res)
+            scored = _rank_aggregated(aggregated, thr, exp, query_iscc_id, limit)
+            out.counts[first + q] = len(scored)
+            for r, (key, total, unit_scores) in enumerate(scored):
+                out.keys[first + q, r] = key
+                out.scores[first + q, r] = min(1.0, total)
+                for t, (unit_type, score) in enumerate(unit_scores.items()):
+                    out.type_index[first + q, r, t] = type_of[unit_type]
+                    out.type_scores[first + q, r, t] = score
+
+    def search_assets_many(self, queries, limit=100, exact=False):
+        # type: (List[IsccQuery], int, bool) -> List[IsccSearchResult]
+        """
+        ``search_assets`` for many queries: result i equals ``search_assets(queries[i], limit, exact)`` on the same index
+        state.  Every query is validated first; one that ``search_assets`` would reject fails the whole call, before anything
+        is searched, with the same exception naming its index in ``queries``.  The unit part runs as ``match_units_many``
+        (batches of up to 1 024 queries).  The ``chunk_matches`` of queries with simprints are answered per query by the
+        simprint search of ``search_assets``: batching simprint scoring across queries is not done here.
+        """
+        if not 1 <= limit <= MAX_K:
+            # outside the engine's range search_assets itself decides (its limit checks depend on the query's units)
+            out = []
+            for i, query in enumerate(queries):
+                try:
+                    out.append(self.search_assets(query, limit, exact=exact))
+                except (ValueError, FileNotFoundError) as e:
+                    raise type(e)(f"queries[{i}]: {e}") from e
+            return out
+        prepared = self._prepare_many(queries)
+        unit_idx = [i for i, (query, _, _) in enumerate(prepared) if query.units]
+        m = self._match_prepared([prepared[i] for i in unit_idx], limit) if unit_idx else None
+        row_of = {i: r for r, i in enumerate(unit_idx)}
+        results = []
+        for i, (query, query_iscc_id, _) in enumerate(prepared):
+            chunk_matches = []
+            if self._sp_tables and query.simprints:
+                chunk_matches = self._search_simprints(query, limit, exact=exact)
+            matches = []
+            r = row_of.get(i)
+            if r is not None:
+                c = int(m.counts[r])
+                keys = m.keys[r, :c].tolist()
+                scores = m.scores[r, :c].tolist()
+                tidx = m.type_index[r, :c].tolist()
+                tsc = m.type_scores[r, :c].tolist()
+                for key, score, ti, ts in zip(keys, scores, tidx, tsc):
+                    asset = self._assets.get(key)
+                    source = metadata = None
+                    if asset is not None and asset.metadata:
+                        source = asset.metadata.get("source")
+                        metadata = asset.metadata
+                    types = {m.types[t]: s for t, s in zip(ti, ts) if t != 255}
+                    matches.append(IsccGlobalMatch(
+                        iscc_id=codec.iscc_id_from_int(key, self._realm_id or 0), score=score,
+                        types=types, source=source, metadata=metadata,
+                    ))
+            if query_iscc_id:
+                chunk_matches = [cm for cm in chunk_matches if cm.iscc_id != query_iscc_id]
+            results.append(IsccSearchResult(query=query, global_matches=matches, chunk_matches=chunk_matches))
+        return results
 
     def _search_simprints(self, query, limit, exact=False):
         # type: (IsccQuery, int, bool) -> List[IsccChunkMatch]
@@ -771,6 +1050,23 @@ class HipIndexManager:
             return idx.search_assets(query, limit)
         except FileNotFoundError:
             raise FileNotFoundError(f"Asset '{query.iscc_id}' not found in index '{index_name}'")
+
+    def search_assets_many(self, index_name, queries, limit=100):
+        # type: (str, List[IsccQuery], int) -> List[IsccSearchResult]
+        """Many ``search_assets`` queries in one call (``HipIndex.search_assets_many``): result i equals ``search_assets(index_name, queries[i], limit)``."""
+        return self._guarded("search_assets_many", self._search_assets_many, index_name, queries, limit)
+
+    def _search_assets_many(self, index_name, queries, limit=100):
+        with self._lock:
+            idx = self._index(index_name)
+        try:
+            return idx.search_assets_many(queries, limit)
+        except FileNotFoundError as e:
+            m = re.match(r"queries\[(\d+)\]: ", str(e))
+            if m is None:
+                raise
+            i = int(m.group(1))
+            raise FileNotFoundError(f"queries[{i}]: Asset '{queries[i].iscc_id}' not found in index '{index_name}'") from e
 
     def close(self):
         # type: () -> None

@@ -324,8 +324,8 @@ class ShardedTable:
         import torch
 
         first = items[0][0]
-        if first.world_size == 1 or len(items) < 2 or len({(id(t.ops), q.shape[0], k) for t, q, _, k, _ in items}) != len(items):
-            return None            # (two items on one table with one block size would share that table's block buffer)
+        if first.world_size == 1 or len(items) < 2 or len({(id(t.ops), block_bytes(q.shape[0], k)[1]) for t, q, _, k, _ in items}) != len(items):
+            return None            # (two items on one table with one block size -- (3, 4) and (4, 3) alike -- would share that table's block buffer, HipShardOps.buffer)
         if any(t.world_size != first.world_size or t.group is not first.group for t, *_ in items):
             return None
         with _exchange_scope(first.ops):
