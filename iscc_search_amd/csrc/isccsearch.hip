@@ -223,6 +223,7 @@ struct isccsearch_handle {
     int speculate = 1;                // small batches: try one range-limited pass under the previous search's k-th distance first
     uint32_t spec_max_queries = 128;   // ... batches of up to this many queries
     int mfma_pack = 1;                // 64-bit codes on the matrix cores: two row tiles per accumulator, packed f16 fold (mfma_pack_kernel)
+    int mfma_pack3 = 1;               // ... chunks of more than four query groups: three row tiles per accumulator, OR fold (mfma_pack3_kernel); 0: mfma_pack_kernel
     uint64_t mfma_min_rows = 65536;   // launches over fewer rows do not amortise the per-block query expansion
     // k <= self_max_k on the matrix cores: ONE pass whose thresholds tighten themselves (MODE_SELF) instead of levels + picks --
     // every launch of that chain costs ~35 us of ramp, prologue and tail, and a step of 100 M rows had seven of them
@@ -619,11 +620,12 @@ struct Batch {
         if (use_mfma(j, rows) || mode == isk::MODE_SELF) {
             const uint32_t g = isk::mfma_groups_per_chunk((int)j.W, nq_pad, j.pack);
             const uint32_t chunks = (nq_pad + g * 32 - 1) / (g * 32);
-            const uint64_t rps = isk::mfma_rows_per_wave_step((int)j.W, j.pack);
+            const bool pack3 = j.pack && h->mfma_pack3 && isk::mfma_pack3_fits(g);
+            const uint64_t rps = isk::mfma_rows_per_wave_step((int)j.W, j.pack, pack3);
             const uint64_t steps = (rows + rps - 1) / rps;
             const uint64_t wpb = isk::mfma_waves_per_block();
             const uint64_t bx = std::max<uint64_t>(1, std::min<uint64_t>((steps + wpb - 1) / wpb, std::max<uint32_t>(1, (uint32_t)h->cus * isk::mfma_blocks_per_cu((int)j.W, g, j.pack) / chunks)));
-            const int e = isk::launch_mfma_scan((int)j.W, mode, j.pack, (uint32_t)bx, g, h->stream, sp);
+            const int e = isk::launch_mfma_scan((int)j.W, mode, j.pack, (uint32_t)bx, g, h->stream, sp, pack3);
             if (e) return fail(-EIO, "mfma scan: chunk of %u query groups does not fit the LDS budget (%s)", g, hipGetErrorString((hipError_t)e));
             h->stats.mfma_launches += 1;
             if (j.pack) h->stats.mfma_pack_launches += 1;
@@ -1304,6 +1306,7 @@ int isccsearch_set_option(isccsearch_handle* h, const char* name, int64_t value)
     if (!strcmp(name, "self_boot_rows")) { if (value < 256 || value > (1 << 20)) return fail(-EINVAL, "self_boot_rows must be 256..1048576"); h->self_boot_rows = (uint64_t)value; return 0; }
     if (!strcmp(name, "mfma_level_growth")) { if (value < 2 || value > 1024) return fail(-EINVAL, "mfma_level_growth must be 2..1024"); h->mfma_level_growth = (uint64_t)value; return 0; }
     if (!strcmp(name, "mfma_pack")) { h->mfma_pack = value != 0; return 0; }
+    if (!strcmp(name, "mfma_pack3")) { h->mfma_pack3 = value != 0; return 0; }
     if (!strcmp(name, "tiny_rows")) { if (value < 0 || value > (1 << 20)) return fail(-EINVAL, "tiny_rows must be 0..1048576"); h->tiny_rows = (uint32_t)value; return 0; }
     if (!strcmp(name, "select_wide_from")) { if (value < 0) return fail(-EINVAL, "select_wide_from must be >= 0"); h->select_wide_from = (uint32_t)std::min<int64_t>(value, 0xFFFFFFFFll); return 0; }
     if (!strcmp(name, "speculate")) { h->speculate = value != 0; return 0; }

@@ -15,7 +15,7 @@ an asm statement (cdna_hip_programming.md section 5.7), so three invariants are 
   3. every such load group opens with ``s_nop 4`` (the scalar bases may come straight from v_readfirstlane / v_readlane: a
      VALU-written SGPR needs 5 wait states before a VMEM instruction reads it).
 
-The packed matrix-core scan (``mfma_pack_kernel`` in csrc/mfma_scan.hip) issues its MFMAs and the fold of their results
+The packed matrix-core scans (``mfma_pack_kernel`` and ``mfma_pack3_kernel`` in csrc/mfma_scan.hip) issue their MFMAs and the fold of their results
 from inline asm in a fixed order; hipcc places no hazard nops for asm, so two more invariants are checked on the assembly:
 
   4. along EVERY control-flow path, an instruction that reads or writes a VGPR written by a ``v_mfma*`` comes at least
@@ -31,7 +31,7 @@ import sys
 KERNEL_RE = re.compile(r"^(_ZN3isk\w+):\s*(;.*)?$")
 LABEL_RE = re.compile(r"^(\.LBB\d+_\d+):")
 VREG_RE = re.compile(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]")
-AUDITED = ("scan_kernel", "scan_adapt_kernel", "mfma_scan_kernel", "mfma_pack_kernel")
+AUDITED = ("scan_kernel", "scan_adapt_kernel", "mfma_scan_kernel", "mfma_pack_kernel", "mfma_pack3_kernel")
 # an 8-pass MFMA (v_mfma_f32_32x32x64_f8f6f4 with FP4 operands) may be read by the VALU 11 wait states after it was issued
 # (LLVM: passes + 3); one more for margin
 MFMA_WAIT_STATES = 12
@@ -294,7 +294,7 @@ def main():
                 n_groups += n
     n_pack = n_mfma = 0
     for name, ins in kernels.items():
-        if "mfma_pack_kernel" in name or "mfma_scan_kernel" in name:     # every matrix-core kernel: their stages are inline asm
+        if "mfma_pack_kernel" in name or "mfma_pack3_kernel" in name or "mfma_scan_kernel" in name:     # every matrix-core kernel: their stages are inline asm
             b, n = audit_mfma_distances(name, ins)
             bad += b
             n_pack += 1
