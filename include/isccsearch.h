@@ -276,6 +276,23 @@ int isccsearch_simprint_score(isccsearch_handle* h, uint32_t table, uint32_t nq,
                               isccsearch_simprint_result* out_results, isccsearch_simprint_chunk* out_chunks,
                               uint64_t* out_chunk_words, uint32_t* out_info);
 
+/* Many simprint requests against ONE table in one call, each scored on its own: what isccsearch_simprint_score returns for
+ * every request alone, bit for bit -- UsearchSimprintIndex.search_raw once per simprint type and asset query
+ * (iscc_search/indexes/usearch/index.py:1357-1469 -> usearch_core.py:137-269).  Request r holds the query simprints
+ * q_words[req_offsets[r] .. req_offsets[r + 1]) (req_offsets[n_req + 1], non-decreasing; empty requests are allowed), at most
+ * ISCCSEARCH_MAX_SCORED_SIMPRINTS each (-E2BIG).  count, max_hamming, threshold, limit, total_assets and dup_limit are shared.
+ * The library cuts the requests into rounds of at most ISCCSEARCH_MAX_SCORED_SIMPRINTS query simprints (never splitting a
+ * request); a round is ONE batched search of its simprints and one scoring pipeline that keeps the requests apart.
+ * Outputs per request r: out_results[r * limit ..] (its first min(limit, assets) results); out_info[4 r .. 4 r + 4) = {results
+ * written, assets matched, longest neighbour list OF THIS REQUEST, chunks written}; out_chunks / out_chunk_words (both or
+ * neither) laid out as isccsearch_simprint_score's, request r's starting at limit * req_offsets[r] (out_chunks[limit * total],
+ * total = req_offsets[n_req]), first_chunk and the chunks' `query` relative to the request.  128-bit-key Hamming tables only. */
+int isccsearch_simprint_score_many(isccsearch_handle* h, uint32_t table, uint32_t n_req, const uint32_t* req_offsets, const uint64_t* q_words,
+                                   uint32_t count, int32_t max_hamming, double threshold, uint32_t limit,
+                                   int64_t total_assets, uint32_t dup_limit,
+                                   isccsearch_simprint_result* out_results, isccsearch_simprint_chunk* out_chunks,
+                                   uint64_t* out_chunk_words, uint32_t* out_info);
+
 /* Hard-boundary simprint search WITH its scoring, on the device: search_simprints_exact (iscc_search/indexes/simprint/lmdb_ops.py:169-301,
  * called with exact=True from iscc_search/indexes/usearch/index.py:1261-1304).  q_words[n_distinct * max_words] are the DISTINCT query
  * simprints; given[n_given] names, for every query simprint of valid length AS GIVEN (repeats included: a repeated simprint is matched

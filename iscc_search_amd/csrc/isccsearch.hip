@@ -262,6 +262,8 @@ struct isccsearch_handle {
     DevBuf<unsigned char> d_sp_best, d_sp_temp;
     DevBuf<uint64_t> d_sp_asset[2];
     DevBuf<double> d_sp_score[2], d_sp_tab, d_sp_ws, d_sp_idfq;
+    // isccsearch_simprint_score_many: request keys / sort payloads per entry, per-request offsets and counts, chunks per result
+    DevBuf<uint32_t> d_spm_req[2], d_spm_idx[2], d_spm_qbeg, d_spm_nassets, d_spm_astart, d_spm_estart, d_spm_cnt, d_spm_cpos;
     PinBuf<double> p_sp_tab;
     PinBuf<unsigned char> p_sp_out;
     // the similarity / IDF tables on the device are those of (bits, total_assets, dup_limit):
@@ -1251,6 +1253,9 @@ int isccsearch_destroy(isccsearch_handle* h) {
         h->d_sp_cnt.release(); h->d_sp_dofg.release();
         for (int i = 0; i < 2; ++i) { h->d_sp_entry[i].release(); h->d_sp_order[i].release(); h->d_sp_asset[i].release(); h->d_sp_score[i].release(); }
         h->d_sp_tab.release(); h->p_sp_tab.release(); h->p_sp_out.release(); h->d_sp_ws.release(); h->d_sp_idfq.release();
+        for (int i = 0; i < 2; ++i) { h->d_spm_req[i].release(); h->d_spm_idx[i].release(); }
+        h->d_spm_qbeg.release(); h->d_spm_nassets.release(); h->d_spm_astart.release(); h->d_spm_estart.release();
+        h->d_spm_cnt.release(); h->d_spm_cpos.release();
         h->d_am_rec.release(); h->d_am_rec2.release(); h->d_am_cnt.release(); h->d_am_cnt2.release(); h->d_am_off.release();
         h->d_am_slots.release(); h->d_am_ex.release(); h->d_am_hasex.release(); h->d_am_tab.release(); h->d_am_scratch.release();
         h->p_am_out.release();
@@ -1770,6 +1775,7 @@ struct ScoreSink {
     const uint32_t* d_of_g = nullptr;
     uint32_t nd = 0, ng = 0;
     bool prepared = false;
+    uint32_t* q_count = nullptr;    // when set: [nq] length of every query's neighbour list (capped at k)
 };
 
 // The search itself; h->mu is held by the caller.
@@ -2045,6 +2051,7 @@ static int search_locked(isccsearch_handle* h, uint32_t table, uint32_t nq, cons
                     sink->prepared = true;
                 }
                 for (uint32_t i = 0; i < m; ++i) sink->max_count = std::max(sink->max_count, std::min(p_cnt[i], k));
+                if (sink->q_count) for (uint32_t i = 0; i < m; ++i) sink->q_count[pos + i] = std::min(p_cnt[i], k);
             }
             pos = end;
             continue;
@@ -2356,6 +2363,97 @@ int isccsearch_doc_freq_counted(isccsearch_handle* h, uint32_t table, uint32_t n
     return search_locked(h, table, nq, q_words, q_nbytes, dup_limit, nullptr, nullptr, nullptr, nullptr, 0, out_freq, out_collisions);
 }
 
+// The match threshold on the integer distance, the table's frequency column and the similarity / IDF tables of one scoring call
+// (isccsearch_simprint_score and _many); h->mu is held.
+static int simprint_setup(H* h, Table& t, Segment& s, double threshold, int64_t total_assets, uint32_t dup_limit, int& h_max) {
+    int rc;
+    const uint32_t bits = 8 * (uint32_t)t.max_bytes;
+    // the match threshold on the integer distance: score = 1.0 - distance / ndim (usearch_core.py:182) falls with the distance, so
+    // the largest distance whose score -- in this very arithmetic -- still passes is found once
+    h_max = -1;
+    for (uint32_t d = 0; d <= bits; ++d) {
+        if (1.0 - (double)d / (double)bits >= threshold) h_max = (int)d;
+        else break;
+    }
+    if (dup_limit && (rc = ensure_freq_column(h, t, s, dup_limit))) return rc;
+    // similarity and IDF values come from the HOST's arithmetic (log() of libm is what CPython's math.log calls; lmdb_ops.py:67-81)
+    const uint32_t n_idf = dup_limit + 1;
+    if (h->sp_tab_bits != bits || h->sp_tab_dup != dup_limit || h->sp_tab_total != total_assets) {
+        const size_t words = (size_t)bits + 1 + n_idf;
+        if ((rc = h->p_sp_tab.ensure(words))) return rc;
+        if ((rc = h->d_sp_tab.ensure(words))) return rc;
+        HIPOK(hipStreamSynchronize(h->stream));      // (a previous upload may still be reading the staging block)
+        double* tab = h->p_sp_tab.p;
+        for (uint32_t d = 0; d <= bits; ++d) tab[d] = 1.0 - (double)d / (double)bits;
+        auto idf = [&](uint32_t freq) { return total_assets <= 0 ? 0.0 : std::log(1.0 + (double)total_assets / (double)(1 + (uint64_t)freq)); };
+        if (dup_limit) for (uint32_t f = 0; f <= dup_limit; ++f) tab[bits + 1 + f] = idf(f);
+        else tab[bits + 1] = idf(1);
+        HIPOK(hipMemcpyAsync(h->d_sp_tab.p, tab, words * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        h->sp_tab_bits = bits; h->sp_tab_dup = dup_limit; h->sp_tab_total = total_assets;
+    }
+    return 0;
+}
+
+// device buffers of a scoring call over nq query simprints with k neighbours each (entries == 0: the search's; else the scoring's)
+static int simprint_buffers(H* h, uint32_t nq, uint32_t k, uint32_t entries) {
+    int rc;
+    if (entries == 0) {
+        const size_t slots = (size_t)nq * k;
+        if ((rc = h->d_sp_rec.ensure(slots))) return rc;
+        if ((rc = h->d_sp_rows.ensure(slots))) return rc;
+        if ((rc = h->d_sp_best.ensure(slots))) return rc;
+        if ((rc = h->d_sp_nbest.ensure(nq))) return rc;
+        if ((rc = h->d_sp_offs.ensure(nq))) return rc;
+        if ((rc = h->d_sp_freqq.ensure(nq))) return rc;
+        if ((rc = h->d_sp_unknown.ensure(nq))) return rc;
+        if ((rc = h->d_sp_nassets.ensure(1))) return rc;
+        for (int i = 0; i < 2; ++i) {
+            if ((rc = h->d_sp_asset[i].ensure(slots))) return rc;
+            if ((rc = h->d_sp_entry[i].ensure(slots))) return rc;
+        }
+        return 0;
+    }
+    for (int i = 0; i < 2; ++i) {
+        if ((rc = h->d_sp_score[i].ensure(entries))) return rc;
+        if ((rc = h->d_sp_order[i].ensure(entries))) return rc;
+    }
+    if ((rc = h->d_sp_matches.ensure(entries))) return rc;
+    if ((rc = h->d_sp_ws.ensure(entries))) return rc;
+    if ((rc = h->d_sp_idfq.ensure(nq))) return rc;
+    return 0;
+}
+
+static void simprint_bind(H* h, isksp::Buffers& b) {
+    b.rec = reinterpret_cast<const isccsearch_record*>(h->d_sp_rec.p);
+    b.rows = h->d_sp_rows.p; b.best = h->d_sp_best.p; b.nbest = h->d_sp_nbest.p; b.offs = h->d_sp_offs.p;
+    b.freq_q = h->d_sp_freqq.p; b.unknown = h->d_sp_unknown.p; b.n_assets = h->d_sp_nassets.p;
+    for (int i = 0; i < 2; ++i) {
+        b.c_asset[i] = h->d_sp_asset[i].p; b.c_entry[i] = h->d_sp_entry[i].p;
+        b.score[i] = h->d_sp_score[i].p; b.order[i] = h->d_sp_order[i].p;
+    }
+    b.matches = h->d_sp_matches.p; b.ws = h->d_sp_ws.p; b.idf_q = h->d_sp_idfq.p;
+    b.temp = h->d_sp_temp.p; b.temp_bytes = h->d_sp_temp.n;
+}
+
+// rare: a query simprint with k equal stored rows and k < dup_limit -- its document frequency needs the collision scan
+static int simprint_unknown_freq(H* h, uint32_t table, Table& t, uint32_t nq, const uint64_t* q_words, uint32_t dup_limit) {
+    int rc;
+    std::vector<uint32_t> unk(nq), fq(nq);
+    HIPOK(hipMemcpyAsync(unk.data(), h->d_sp_unknown.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPOK(hipMemcpyAsync(fq.data(), h->d_sp_freqq.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPOK(hipStreamSynchronize(h->stream));
+    std::vector<uint32_t> which;
+    for (uint32_t q = 0; q < nq; ++q) if (unk[q]) which.push_back(q);
+    std::vector<uint64_t> qw(which.size() * (size_t)t.max_words);
+    for (size_t i = 0; i < which.size(); ++i) memcpy(&qw[i * t.max_words], q_words + (size_t)which[i] * t.max_words, (size_t)t.max_words * 8);
+    std::vector<uint32_t> freq(which.size());
+    if ((rc = search_locked(h, table, (uint32_t)which.size(), qw.data(), nullptr, dup_limit, nullptr, nullptr, nullptr, nullptr, 0, freq.data()))) return rc;
+    for (size_t i = 0; i < which.size(); ++i) fq[which[i]] = freq[i];
+    HIPOK(hipMemcpyAsync(h->d_sp_freqq.p, fq.data(), (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPOK(hipStreamSynchronize(h->stream));       // (fq leaves scope)
+    return 0;
+}
+
 // Search + asset scoring with the neighbour lists kept on the device (usearch_core.py:137-269); see include/isccsearch.h.
 int isccsearch_simprint_score(isccsearch_handle* h, uint32_t table, uint32_t nq, const uint64_t* q_words,
                               uint32_t count, int32_t max_hamming, double threshold, uint32_t limit,
@@ -2387,87 +2485,21 @@ int isccsearch_simprint_score(isccsearch_handle* h, uint32_t table, uint32_t nq,
     HIPOK(hipSetDevice(h->device));
     h->stats.searches += 1;
     const uint32_t k = count, bits = 8 * (uint32_t)t.max_bytes;
-    // the match threshold on the integer distance: score = 1.0 - distance / ndim (usearch_core.py:182) falls with the distance, so
-    // the largest distance whose score -- in this very arithmetic -- still passes is found once
     int h_max = -1;
-    for (uint32_t d = 0; d <= bits; ++d) {
-        if (1.0 - (double)d / (double)bits >= threshold) h_max = (int)d;
-        else break;
-    }
-    if (dup_limit && (rc = ensure_freq_column(h, t, s, dup_limit))) return rc;
-    // similarity and IDF values come from the HOST's arithmetic (log() of libm is what CPython's math.log calls; lmdb_ops.py:67-81)
-    const uint32_t n_idf = dup_limit + 1;
-    if (h->sp_tab_bits != bits || h->sp_tab_dup != dup_limit || h->sp_tab_total != total_assets) {
-        const size_t words = (size_t)bits + 1 + n_idf;
-        if ((rc = h->p_sp_tab.ensure(words))) return rc;
-        if ((rc = h->d_sp_tab.ensure(words))) return rc;
-        HIPOK(hipStreamSynchronize(h->stream));      // (a previous upload may still be reading the staging block)
-        double* tab = h->p_sp_tab.p;
-        for (uint32_t d = 0; d <= bits; ++d) tab[d] = 1.0 - (double)d / (double)bits;
-        auto idf = [&](uint32_t freq) { return total_assets <= 0 ? 0.0 : std::log(1.0 + (double)total_assets / (double)(1 + (uint64_t)freq)); };
-        if (dup_limit) for (uint32_t f = 0; f <= dup_limit; ++f) tab[bits + 1 + f] = idf(f);
-        else tab[bits + 1] = idf(1);
-        HIPOK(hipMemcpyAsync(h->d_sp_tab.p, tab, words * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        h->sp_tab_bits = bits; h->sp_tab_dup = dup_limit; h->sp_tab_total = total_assets;
-    }
-    const size_t slots = (size_t)nq * k;
-    if ((rc = h->d_sp_rec.ensure(slots))) return rc;
-    if ((rc = h->d_sp_rows.ensure(slots))) return rc;
-    if ((rc = h->d_sp_best.ensure(slots))) return rc;
-    if ((rc = h->d_sp_nbest.ensure(nq))) return rc;
-    if ((rc = h->d_sp_offs.ensure(nq))) return rc;
-    if ((rc = h->d_sp_freqq.ensure(nq))) return rc;
-    if ((rc = h->d_sp_unknown.ensure(nq))) return rc;
-    if ((rc = h->d_sp_nassets.ensure(1))) return rc;
-    for (int i = 0; i < 2; ++i) {
-        if ((rc = h->d_sp_asset[i].ensure(slots))) return rc;
-        if ((rc = h->d_sp_entry[i].ensure(slots))) return rc;
-    }
+    if ((rc = simprint_setup(h, t, s, threshold, total_assets, dup_limit, h_max))) return rc;
+    if ((rc = simprint_buffers(h, nq, k, 0))) return rc;
     ScoreSink sink;
     sink.h_max = h_max;
     sink.dup_limit = dup_limit;
-    auto bind = [&]() {
-        isksp::Buffers& b = sink.buf;
-        b.rec = reinterpret_cast<const isccsearch_record*>(h->d_sp_rec.p);
-        b.rows = h->d_sp_rows.p; b.best = h->d_sp_best.p; b.nbest = h->d_sp_nbest.p; b.offs = h->d_sp_offs.p;
-        b.freq_q = h->d_sp_freqq.p; b.unknown = h->d_sp_unknown.p; b.n_assets = h->d_sp_nassets.p;
-        for (int i = 0; i < 2; ++i) {
-            b.c_asset[i] = h->d_sp_asset[i].p; b.c_entry[i] = h->d_sp_entry[i].p;
-            b.score[i] = h->d_sp_score[i].p; b.order[i] = h->d_sp_order[i].p;
-        }
-        b.matches = h->d_sp_matches.p; b.ws = h->d_sp_ws.p; b.idf_q = h->d_sp_idfq.p;
-        b.temp = h->d_sp_temp.p; b.temp_bytes = h->d_sp_temp.n;
-    };
-    bind();
+    simprint_bind(h, sink.buf);
     if ((rc = search_locked(h, table, nq, q_words, nullptr, k, nullptr, nullptr, nullptr, nullptr, max_hamming < 0 ? -1 : max_hamming, nullptr, nullptr, &sink))) return rc;
     out_info[2] = sink.max_count;
     const uint32_t entries = sink.entries;
     if (entries == 0) return 0;
-    if (sink.unknown_any) {
-        // rare: a query simprint with k equal stored rows and k < dup_limit -- its document frequency needs the collision scan
-        std::vector<uint32_t> unk(nq), fq(nq);
-        HIPOK(hipMemcpyAsync(unk.data(), h->d_sp_unknown.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-        HIPOK(hipMemcpyAsync(fq.data(), h->d_sp_freqq.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-        HIPOK(hipStreamSynchronize(h->stream));
-        std::vector<uint32_t> which;
-        for (uint32_t q = 0; q < nq; ++q) if (unk[q]) which.push_back(q);
-        std::vector<uint64_t> qw(which.size() * (size_t)t.max_words);
-        for (size_t i = 0; i < which.size(); ++i) memcpy(&qw[i * t.max_words], q_words + (size_t)which[i] * t.max_words, (size_t)t.max_words * 8);
-        std::vector<uint32_t> freq(which.size());
-        if ((rc = search_locked(h, table, (uint32_t)which.size(), qw.data(), nullptr, dup_limit, nullptr, nullptr, nullptr, nullptr, 0, freq.data()))) return rc;
-        for (size_t i = 0; i < which.size(); ++i) fq[which[i]] = freq[i];
-        HIPOK(hipMemcpyAsync(h->d_sp_freqq.p, fq.data(), (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-        HIPOK(hipStreamSynchronize(h->stream));       // (fq leaves scope)
-    }
-    for (int i = 0; i < 2; ++i) {
-        if ((rc = h->d_sp_score[i].ensure(entries))) return rc;
-        if ((rc = h->d_sp_order[i].ensure(entries))) return rc;
-    }
-    if ((rc = h->d_sp_matches.ensure(entries))) return rc;
-    if ((rc = h->d_sp_ws.ensure(entries))) return rc;
-    if ((rc = h->d_sp_idfq.ensure(nq))) return rc;
+    if (sink.unknown_any && (rc = simprint_unknown_freq(h, table, t, nq, q_words, dup_limit))) return rc;
+    if ((rc = simprint_buffers(h, nq, k, entries))) return rc;
     if ((rc = h->d_sp_temp.ensure(isksp::sort_temp_bytes(entries)))) return rc;
-    bind();
+    simprint_bind(h, sink.buf);
     // outputs in pinned memory, written by the emit kernel itself: {info[4] | results[limit] | chunks | chunk words}
     const uint32_t W = (uint32_t)t.max_words;
     const size_t res_off = 16, chunk_off = res_off + (size_t)limit * sizeof(isccsearch_simprint_result);
@@ -2494,6 +2526,137 @@ int isccsearch_simprint_score(isccsearch_handle* h, uint32_t table, uint32_t nq,
     if (out_chunks) {
         memcpy(out_chunks, po + chunk_off, (size_t)info[3] * sizeof(isccsearch_simprint_chunk));
         memcpy(out_chunk_words, po + words_off, (size_t)info[3] * W * 8);
+    }
+    return 0;
+}
+
+// Many simprint requests against one table, each scored on its own (usearch_core.py:137-269 per request); see include/isccsearch.h.
+int isccsearch_simprint_score_many(isccsearch_handle* h, uint32_t table, uint32_t n_req, const uint32_t* req_offsets, const uint64_t* q_words,
+                                   uint32_t count, int32_t max_hamming, double threshold, uint32_t limit,
+                                   int64_t total_assets, uint32_t dup_limit,
+                                   isccsearch_simprint_result* out_results, isccsearch_simprint_chunk* out_chunks,
+                                   uint64_t* out_chunk_words, uint32_t* out_info) {
+    if (!h) return fail(-EINVAL, "handle is NULL");
+    if (count < 1) return fail(-EINVAL, "`count` must be >= 1");
+    if (count > ISCCSEARCH_MAX_K) return fail(-EINVAL, "count %u exceeds ISCCSEARCH_MAX_K (%d)", count, ISCCSEARCH_MAX_K);
+    if (max_hamming > 256) return fail(-EINVAL, "max_hamming %d exceeds 256", max_hamming);
+    if (dup_limit > ISCCSEARCH_MAX_K) return fail(-EINVAL, "dup_limit %u exceeds ISCCSEARCH_MAX_K (%d)", dup_limit, ISCCSEARCH_MAX_K);
+    if (limit < 1) return fail(-EINVAL, "limit must be >= 1");
+    if (n_req == 0) return 0;
+    if (!out_info || !req_offsets) return fail(-EINVAL, "NULL argument");
+    memset(out_info, 0, (size_t)n_req * 4 * sizeof(uint32_t));
+    for (uint32_t r = 0; r < n_req; ++r) {
+        if (req_offsets[r + 1] < req_offsets[r]) return fail(-EINVAL, "req_offsets must not decrease (request %u)", r);
+        if (req_offsets[r + 1] - req_offsets[r] > isksp::MAX_QUERY_SIMPRINTS)
+            return fail(-E2BIG, "request %u: %u query simprints exceed the %u one scoring call takes", r, req_offsets[r + 1] - req_offsets[r], isksp::MAX_QUERY_SIMPRINTS);
+    }
+    if (req_offsets[n_req] == req_offsets[0]) return 0;
+    if (!q_words || !out_results || (out_chunks == nullptr) != (out_chunk_words == nullptr)) return fail(-EINVAL, "NULL argument");
+    if ((uint64_t)limit * n_req > 0xFFFFFFFFull || (uint64_t)limit * req_offsets[n_req] > 0xFFFFFFFFull)
+        return fail(-E2BIG, "limit %u x %u requests exceeds the 32-bit result addressing", limit, n_req);
+    if (!(threshold == threshold)) return fail(-EINVAL, "threshold is not a number");
+    std::lock_guard<std::mutex> lk(h->mu);
+    Table* tp;
+    int rc = get_table(h, table, tp);
+    if (rc) return rc;
+    Table& t = *tp;
+    if (t.metric != ISCCSEARCH_METRIC_HAMMING || t.key_words != 2)
+        return fail(-EINVAL, "simprint scoring is defined for fixed-length (Hamming) tables with 128-bit chunk-pointer keys");
+    Segment& s = t.seg[t.max_bytes];
+    if (s.n == 0) return 0;
+    if (s.n > 0xFFFFFFFFull) return fail(-E2BIG, "simprint scoring addresses rows with 32 bits; the table holds %llu", (unsigned long long)s.n);
+    HIPOK(hipSetDevice(h->device));
+    const uint32_t k = count, bits = 8 * (uint32_t)t.max_bytes, W = (uint32_t)t.max_words;
+    int h_max = -1;
+    if ((rc = simprint_setup(h, t, s, threshold, total_assets, dup_limit, h_max))) return rc;
+    std::vector<uint32_t> qbeg, q_count;
+    // rounds: consecutive requests of at most MAX_QUERY_SIMPRINTS query simprints together, a request never split
+    for (uint32_t r0 = 0; r0 < n_req;) {
+        const uint32_t base = req_offsets[r0];
+        uint32_t r1 = r0 + 1;
+        while (r1 < n_req && req_offsets[r1 + 1] - base <= isksp::MAX_QUERY_SIMPRINTS) ++r1;
+        const uint32_t nq = req_offsets[r1] - base, nr = r1 - r0;
+        const uint64_t* const qw = q_words + (size_t)base * t.max_words;
+        if (nq == 0) { r0 = r1; continue; }
+        h->stats.searches += 1;
+        if ((rc = simprint_buffers(h, nq, k, 0))) return rc;
+        q_count.assign(nq, 0);
+        ScoreSink sink;
+        sink.h_max = h_max;
+        sink.dup_limit = dup_limit;
+        sink.q_count = q_count.data();
+        simprint_bind(h, sink.buf);
+        if ((rc = search_locked(h, table, nq, qw, nullptr, k, nullptr, nullptr, nullptr, nullptr, max_hamming < 0 ? -1 : max_hamming, nullptr, nullptr, &sink))) return rc;
+        uint32_t words = 0;                // LDS words of the score kernel: the most 64-bit words one request's range touches
+        qbeg.resize(nr + 1);
+        for (uint32_t r = 0; r < nr; ++r) {
+            const uint32_t qb = req_offsets[r0 + r] - base, qe = req_offsets[r0 + r + 1] - base;
+            qbeg[r] = qb;
+            uint32_t longest = 0;
+            for (uint32_t q = qb; q < qe; ++q) longest = std::max(longest, q_count[q]);
+            out_info[4 * (size_t)(r0 + r) + 2] = longest;
+            if (qe > qb) words = std::max(words, ((qe - 1) >> 6) - (qb >> 6) + 1);
+        }
+        qbeg[nr] = nq;
+        const uint32_t entries = sink.entries;
+        if (entries == 0) { r0 = r1; continue; }
+        if (sink.unknown_any && (rc = simprint_unknown_freq(h, table, t, nq, qw, dup_limit))) return rc;
+        const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)nr * limit, entries);
+        if ((rc = simprint_buffers(h, nq, k, entries))) return rc;
+        for (int i = 0; i < 2; ++i) {
+            if ((rc = h->d_spm_req[i].ensure(entries))) return rc;
+            if ((rc = h->d_spm_idx[i].ensure(entries))) return rc;
+        }
+        if ((rc = h->d_spm_qbeg.ensure(nr + 1))) return rc;
+        if ((rc = h->d_spm_nassets.ensure(nr))) return rc;
+        if ((rc = h->d_spm_astart.ensure(nr + 1))) return rc;
+        if ((rc = h->d_spm_estart.ensure(nr + 1))) return rc;
+        if ((rc = h->d_spm_cnt.ensure(cap))) return rc;
+        if ((rc = h->d_spm_cpos.ensure(cap))) return rc;
+        if ((rc = h->d_sp_temp.ensure(isksp::many_temp_bytes(entries, cap)))) return rc;
+        simprint_bind(h, sink.buf);
+        isksp::ManyBuffers mb{};
+        for (int i = 0; i < 2; ++i) { mb.req[i] = h->d_spm_req[i].p; mb.idx[i] = h->d_spm_idx[i].p; }
+        mb.qbeg = h->d_spm_qbeg.p; mb.n_assets = h->d_spm_nassets.p; mb.a_start = h->d_spm_astart.p; mb.e_start = h->d_spm_estart.p;
+        mb.cnt = h->d_spm_cnt.p; mb.c_pos = h->d_spm_cpos.p;
+        HIPOK(hipMemcpyAsync(mb.qbeg, qbeg.data(), (size_t)(nr + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        // outputs in pinned memory, compact: {info[nr][4] | results[cap] | chunks | chunk words}
+        const size_t res_off = ((size_t)nr * 16 + 15) / 16 * 16, chunk_off = res_off + (size_t)cap * sizeof(isccsearch_simprint_result);
+        const size_t chunk_cap = out_chunks ? (size_t)std::min<uint64_t>((uint64_t)limit * nq, entries) : 0;
+        const size_t words_off = chunk_off + chunk_cap * sizeof(isccsearch_simprint_chunk);
+        if ((rc = h->p_sp_out.ensure(words_off + chunk_cap * W * 8))) return rc;
+        unsigned char* const po = h->p_sp_out.p;
+        isksp::ScoreManyArgs ma{};
+        isksp::ScoreArgs& sa = ma.s;
+        sa.nq = nq; sa.k = k; sa.entries = entries; sa.limit = limit;
+        sa.sim_tab = h->d_sp_tab.p; sa.idf_tab = h->d_sp_tab.p + bits + 1; sa.dup_limit = dup_limit;
+        sa.freq_col = dup_limit ? s.freq : nullptr;
+        for (uint32_t w = 0; w < s.W; ++w) sa.col[w] = s.col[w];
+        sa.W = W;
+        sa.out_info = reinterpret_cast<uint32_t*>(po);
+        sa.out_results = reinterpret_cast<isccsearch_simprint_result*>(po + res_off);
+        sa.out_chunks = out_chunks ? reinterpret_cast<isccsearch_simprint_chunk*>(po + chunk_off) : nullptr;
+        sa.out_chunk_words = out_chunks ? reinterpret_cast<uint64_t*>(po + words_off) : nullptr;
+        ma.n_req = nr; ma.cap = cap; ma.words = words;
+        HIPOK(isksp::queue_score_many(sink.buf, mb, ma, h->stream));
+        HIPOK(hipStreamSynchronize(h->stream));       // (qbeg is read by the kernels until here)
+        // into the caller's regions: request r's results at r x limit, its chunks at limit x req_offsets[r]
+        const uint32_t* info = reinterpret_cast<const uint32_t*>(po);
+        size_t res_at = 0, chunk_at = 0;
+        for (uint32_t r = 0; r < nr; ++r) {
+            const uint32_t n = info[4 * r], c = info[4 * r + 3];
+            uint32_t* oi = out_info + 4 * (size_t)(r0 + r);
+            oi[0] = n; oi[1] = info[4 * r + 1]; oi[3] = c;
+            memcpy(out_results + (size_t)(r0 + r) * limit, po + res_off + res_at * sizeof(isccsearch_simprint_result), (size_t)n * sizeof(isccsearch_simprint_result));
+            if (out_chunks && c) {
+                const size_t dst = (size_t)limit * req_offsets[r0 + r];
+                memcpy(out_chunks + dst, po + chunk_off + chunk_at * sizeof(isccsearch_simprint_chunk), (size_t)c * sizeof(isccsearch_simprint_chunk));
+                memcpy(out_chunk_words + dst * W, po + words_off + chunk_at * W * 8, (size_t)c * W * 8);
+            }
+            res_at += n;
+            chunk_at += c;
+        }
+        r0 = r1;
     }
     return 0;
 }

@@ -84,6 +84,35 @@ struct ScoreArgs {
 // sort by asset -> score -> sort by score -> emit
 hipError_t queue_score(Buffers& b, const ScoreArgs& a, hipStream_t stream);
 
+// Many requests in one call (isccsearch_simprint_score_many): the query simprints of a round are the concatenation of its
+// requests' (request r: queries [qbeg[r], qbeg[r + 1]) of the round), searched, marked and compacted as ONE request by
+// queue_batch -- so the entries are grouped by request already -- then
+//     stable radix sort by asset, stable radix sort by request -> every (request, asset) run adjacent, ascending query
+//     score    as score_kernel, the unmatched sum over the run's own request only; assets counted per request
+//     stable radix sort by score (descending), stable radix sort by request -> every request's assets in (-score, asset) order
+//     emit     one wave per written result (never a block per (request, rank) slot): results, compact, in request order
+// Pinned outputs are staged compactly: request r's results follow those of the requests before it, its chunks likewise;
+// out_info[4 r ..] = {results, assets matched, -, chunks written} -- the host moves them into the caller's per-request regions.
+struct ManyBuffers {
+    uint32_t* req[2];               // [entries] request index per entry (sort keys)
+    uint32_t* idx[2];               // [entries] sort payload: position before the sort
+    uint32_t* qbeg;                 // [n_req + 1] device: first query simprint of every request in the round
+    uint32_t* n_assets;             // [n_req]
+    uint32_t* a_start;              // [n_req + 1] first sorted position of every request's assets
+    uint32_t* e_start;              // [n_req + 1] first written result of every request
+    uint32_t* cnt;                  // [cap] chunks of every written result
+    uint32_t* c_pos;                // [cap] their exclusive prefix: the result's first chunk in the staging block
+};
+size_t many_temp_bytes(size_t entries, size_t cap);
+
+struct ScoreManyArgs {
+    ScoreArgs s;                    // nq = query simprints of the round; out_results [cap]; out_chunks / words [<= entries];
+    uint32_t n_req;                 //   out_info [n_req * 4]
+    uint32_t cap;                   // min(entries, n_req x limit): results the round can write at most
+    uint32_t words;                 // LDS words per thread of the score kernel: the most 64-bit words any request's range touches
+};
+hipError_t queue_score_many(Buffers& b, const ManyBuffers& mb, const ScoreManyArgs& a, hipStream_t stream);
+
 // Hard-boundary requests (search_simprints_exact, lmdb_ops.py:169-301).  Buffers: rec = the collision lists [nd][k] of the DISTINCT
 // query simprints, freq_q [nd] their document frequencies, nbest / unknown / offs sized for the GIVEN simprints [ng].
 hipError_t exact_prepare(const Buffers& b, const uint32_t* cnt, const uint32_t* d_of_g, uint32_t nd, uint32_t ng, uint32_t k, uint32_t* info, hipStream_t stream);

@@ -496,6 +496,218 @@ __global__ void exact_score_kernel(const ExactScoreParams p) {
     if ((tid & 63) == 0 && kept) atomicAdd(p.n_assets, (uint32_t)__popcll(kept));
 }
 
+// =====================================================================================================================
+// Many requests per call (queue_score_many; see simprint_score.h).  A run is a (request, asset) pair; everything a single
+// request computes is computed per request, in the same float64 operations and the same order.
+// =====================================================================================================================
+// last r in [0, n) with starts[r] <= v (starts ascending, starts[0] == 0 <= v)
+__device__ __forceinline__ uint32_t segment_of(const uint32_t* starts, uint32_t n, uint32_t v) {
+    uint32_t lo = 0, hi = n;          // starts[lo] <= v < starts[hi] (starts[n] taken as +inf)
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (starts[mid] <= v) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// after the sort by asset: per entry its request (from the query simprint it belongs to) and its position
+__global__ __launch_bounds__(BLOCK) void req_key_kernel(const uint32_t* entry, const uint32_t* qbeg, uint32_t n_req, uint32_t k,
+                                                        uint32_t* req, uint32_t* idx, uint32_t entries) {
+    const uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
+    if (t < entries) { req[t] = segment_of(qbeg, n_req, entry[t] / k); idx[t] = t; }
+}
+
+// the entries in (request, asset) order
+__global__ __launch_bounds__(BLOCK) void gather_kernel(const uint32_t* idx, const uint64_t* asset_in, const uint32_t* entry_in,
+                                                       uint64_t* asset_out, uint32_t* entry_out, uint32_t entries) {
+    const uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
+    if (t < entries) { const uint32_t i = idx[t]; asset_out[t] = asset_in[i]; entry_out[t] = entry_in[i]; }
+}
+
+// score_kernel with a run = (request, asset): the matched sum is the same walk; the unmatched sum runs over the run's own
+// request [qbeg[r], qbeg[r + 1]) in ascending order.  The wave walks the union of its heads' ranges (the same v_readlane
+// broadcast); a lane skips the query simprints outside its own range like matched ones.  Its LDS row holds the 64-bit words its
+// range touches, relative to the range's first word.
+// dynamic LDS: mask[words][threads] u64
+struct ScoreManyParams {
+    const uint64_t* asset;          // sorted by (request, asset)
+    const uint32_t* req;            // sorted
+    const double* w;
+    const double* ws;
+    const uint32_t* q;
+    const double* idf_q;
+    const uint32_t* qbeg;
+    double* score;
+    uint32_t* order;
+    uint32_t* matches;
+    uint32_t* n_assets;             // [n_req]
+    uint32_t entries, nq, words;
+};
+__global__ void score_many_kernel(const ScoreManyParams p) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned long long* mask = reinterpret_cast<unsigned long long*>(smem);
+    const uint32_t T = blockDim.x, tid = threadIdx.x, lane = tid & 63;
+    const uint32_t e = blockIdx.x * T + tid;
+    const uint64_t a = e < p.entries ? p.asset[e] : 0;
+    const uint32_t r = e < p.entries ? p.req[e] : 0;
+    const bool head = e < p.entries && (e == 0 || p.asset[e - 1] != a || p.req[e - 1] != r);
+    double total = 0.0, weighted = 0.0;
+    uint32_t end = e, qb = 0, qe = 0, wb = 0, we = 0;
+    if (e < p.entries) p.order[e] = e;
+    if (head) {
+        qb = p.qbeg[r]; qe = p.qbeg[r + 1];                   // (qe > qb: the request has entries)
+        wb = qb >> 6; we = ((qe - 1) >> 6) + 1;
+        for (uint32_t w = 0; w < we - wb; ++w) mask[w * T + tid] = 0;
+        constexpr int U = 8;
+        uint32_t j = e;
+        for (bool more = true; more;) {
+            uint64_t aa[U]; double ww[U], ss[U]; uint32_t qq[U], rr[U];
+            for (int u = 0; u < U; ++u) {
+                const uint32_t jj = j + u < p.entries ? j + u : p.entries - 1;
+                aa[u] = p.asset[jj]; rr[u] = p.req[jj]; ww[u] = p.w[jj]; ss[u] = p.ws[jj]; qq[u] = p.q[jj];
+            }
+            int u = 0;
+            for (; u < U; ++u) {
+                if (j + u >= p.entries || aa[u] != a || rr[u] != r) { more = false; break; }
+                total = total + ww[u];
+                weighted = weighted + ss[u];
+                mask[((qq[u] >> 6) - wb) * T + tid] |= 1ull << (qq[u] & 63);
+            }
+            j += u;
+        }
+        end = j;
+    }
+    if (__ballot(head)) {
+        uint32_t lo = head ? wb : 0xFFFFFFFFu, hi = head ? we : 0;
+        for (int off = 32; off > 0; off >>= 1) {
+            const uint32_t l2 = __shfl_xor(lo, off), h2 = __shfl_xor(hi, off);
+            lo = l2 < lo ? l2 : lo;
+            hi = h2 > hi ? h2 : hi;
+        }
+        for (uint32_t w = lo; w < hi; ++w) {
+            const uint32_t q0 = 64 * w, n = p.nq - q0 < 64 ? p.nq - q0 : 64;
+            unsigned long long m = ~0ULL;
+            if (head && w >= wb && w < we) {
+                m = mask[(w - wb) * T + tid];
+                if (q0 < qb) m |= (1ull << (qb - q0)) - 1;     // before the request (w == wb: qb - q0 < 64)
+                if (qe - q0 < 64) m |= ~0ULL << (qe - q0);      // behind it (qe > q0 here)
+            }
+            const double mine = lane < n ? p.idf_q[q0 + lane] : 0.0;
+            const int lo_w = __double2loint(mine), hi_w = __double2hiint(mine);
+#pragma unroll
+            for (uint32_t i = 0; i < 64; ++i) {
+                const double x = __hiloint2double(__builtin_amdgcn_readlane(hi_w, i), __builtin_amdgcn_readlane(lo_w, i));
+                total = (m >> i) & 1 ? total : total + x;
+            }
+        }
+    }
+    if (e < p.entries) {
+        p.score[e] = !head ? -1.0 : (total > 0.0 ? weighted / total : 0.0);
+        p.matches[e] = end - e;
+    }
+    if (head) atomicAdd(&p.n_assets[r], 1u);
+}
+
+// after the sort by score: the request of every run head as the key of the regrouping sort (n_req behind every head: the
+// non-heads, score -1, stay at the end)
+__global__ __launch_bounds__(BLOCK) void head_key_kernel(const double* score, const uint32_t* order, const uint32_t* req, uint32_t n_req,
+                                                         uint32_t* key, uint32_t* idx, uint32_t entries) {
+    const uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
+    if (t < entries) { const uint32_t e = order[t]; key[t] = score[t] >= 0.0 ? req[e] : n_req; idx[t] = e; }
+}
+
+// one block: a_start = exclusive prefix of the assets per request, e_start = of the results written per request; out_info
+__global__ __launch_bounds__(BLOCK) void req_scan_kernel(const uint32_t* n_assets, uint32_t n_req, uint32_t limit, uint32_t* a_start, uint32_t* e_start, uint32_t* out_info) {
+    __shared__ uint32_t wtot[4];
+    const uint32_t tid = threadIdx.x;
+    uint32_t ra = 0, re = 0;
+    for (uint32_t c0 = 0; c0 < n_req; c0 += BLOCK) {
+        const uint32_t r = c0 + tid;
+        const uint32_t na = r < n_req ? n_assets[r] : 0, n = na < limit ? na : limit;
+        uint32_t ta, te;
+        const uint32_t pa = ra + block_exclusive(na, wtot, ta);
+        const uint32_t pe = re + block_exclusive(n, wtot, te);
+        if (r < n_req) {
+            a_start[r] = pa; e_start[r] = pe;
+            out_info[4 * r] = n; out_info[4 * r + 1] = na; out_info[4 * r + 2] = 0; out_info[4 * r + 3] = 0;
+        }
+        ra += ta; re += te;
+    }
+    if (tid == 0) { a_start[n_req] = ra; e_start[n_req] = re; }
+}
+
+// chunks of written result t (0 past the last one)
+__global__ __launch_bounds__(BLOCK) void result_chunks_kernel(const uint32_t* e_start, const uint32_t* a_start, const uint32_t* idx, const uint32_t* matches,
+                                                              uint32_t n_req, uint32_t* cnt, uint32_t cap) {
+    const uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
+    if (t >= cap) return;
+    uint32_t m = 0;
+    if (t < e_start[n_req]) {
+        const uint32_t r = segment_of(e_start, n_req, t);
+        m = matches[idx[a_start[r] + t - e_start[r]]];
+    }
+    cnt[t] = m;
+}
+
+// one wave per written result (grid-stride): result t = rank t - e_start[r] of request r, its chunks behind those of the results
+// before it (first_chunk relative to the request's first chunk)
+struct EmitManyParams {
+    const double* score;            // per run head
+    const uint32_t* idx;            // run head of every sorted position
+    const uint64_t* asset;
+    const uint32_t* entry;
+    const uint32_t* matches;
+    const uint32_t* a_start;
+    const uint32_t* e_start;
+    const uint32_t* c_pos;
+    const uint32_t* qbeg;
+    const isccsearch_record* rec;
+    const uint32_t* rows;
+    const uint32_t* freq_col;
+    const uint64_t* col[4];
+    isccsearch_simprint_result* out_results;
+    isccsearch_simprint_chunk* out_chunks;
+    uint64_t* out_chunk_words;
+    uint32_t* out_info;
+    uint32_t n_req, k, W, dup_limit;
+};
+__global__ __launch_bounds__(BLOCK) void emit_many_kernel(const EmitManyParams p) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t waves = gridDim.x * (BLOCK / 64);
+    const uint32_t total = p.e_start[p.n_req];
+    for (uint32_t t = (blockIdx.x * BLOCK + threadIdx.x) / 64; t < total; t += waves) {
+        const uint32_t r = segment_of(p.e_start, p.n_req, t);
+        const uint32_t first = p.e_start[r], j = t - first, n = p.e_start[r + 1] - first;
+        const uint32_t e = p.idx[p.a_start[r] + j], m = p.matches[e];
+        const uint32_t at = p.c_pos[t], rel = at - p.c_pos[first];
+        if (lane == 0) {
+            isccsearch_simprint_result res;
+            res.asset = p.asset[e];
+            res.score = p.score[e];
+            res.matches = m;
+            res.first_chunk = rel;
+            p.out_results[t] = res;
+            if (j == n - 1) p.out_info[4 * r + 3] = p.out_chunks ? rel + m : 0;
+        }
+        if (!p.out_chunks) continue;
+        const uint32_t q0 = p.qbeg[r];
+        for (uint32_t jj = lane; jj < m; jj += 64) {
+            const uint32_t ent = p.entry[e + jj];
+            const isccsearch_record& rec = p.rec[ent];
+            const uint32_t row = p.rows[ent];
+            isccsearch_simprint_chunk c;
+            c.query = ent / p.k - q0;
+            c.reserved = 0;
+            c.key_lo = rec.key_lo;
+            c.hamming = rec.hamming;
+            c.freq = p.dup_limit ? p.freq_col[row] : 1u;
+            p.out_chunks[at + jj] = c;
+            for (uint32_t w = 0; w < p.W; ++w) p.out_chunk_words[(uint64_t)(at + jj) * p.W + w] = p.col[w][row];
+        }
+    }
+}
+
 
 uint32_t log2_slots(uint32_t k) {   // hash slots of mark_kernel: the power of two >= 2 k (>= 64)
     uint32_t l = 6;
@@ -596,6 +808,66 @@ hipError_t queue_score(Buffers& b, const ScoreArgs& a, hipStream_t stream) {
     ep.out_results = a.out_results; ep.out_chunks = a.out_chunks; ep.out_chunk_words = a.out_chunk_words; ep.out_info = a.out_info;
     ep.limit = a.limit; ep.k = a.k; ep.W = a.W; ep.dup_limit = a.dup_limit;
     hipLaunchKernelGGL(emit_kernel, dim3(a.limit < a.entries ? a.limit : a.entries), dim3(BLOCK), 0, stream, ep);
+    return hipGetLastError();
+}
+
+size_t many_temp_bytes(size_t entries, size_t cap) {
+    size_t a = sort_temp_bytes(entries), b = 0, c = 0;
+    uint32_t* v = nullptr;
+    (void)rocprim::radix_sort_pairs(nullptr, b, v, v, v, v, entries, 0, 32, (hipStream_t) nullptr);
+    (void)rocprim::exclusive_scan(nullptr, c, v, v, 0u, cap, rocprim::plus<uint32_t>(), (hipStream_t) nullptr);
+    return std::max(a, std::max(b, c));
+}
+
+hipError_t queue_score_many(Buffers& b, const ManyBuffers& mb, const ScoreManyArgs& ma, hipStream_t stream) {
+    const ScoreArgs& a = ma.s;
+    hipError_t e;
+    const uint32_t nr = ma.n_req, grid = (a.entries + BLOCK - 1) / BLOCK;
+    uint32_t req_bits = 1;                                   // request keys 0 .. n_req (n_req: the non-heads of the regrouping sort)
+    while ((1u << req_bits) <= nr) ++req_bits;
+    if (ma.words == 0 || ma.words > MAX_QUERY_SIMPRINTS / 64) return hipErrorInvalidValue;
+    // (request, asset) order: stable by asset, then stable by request
+    size_t bytes = b.temp_bytes;
+    e = rocprim::radix_sort_pairs(b.temp, bytes, b.c_asset[0], b.c_asset[1], b.c_entry[0], b.c_entry[1], a.entries, 0, 64, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(req_key_kernel, dim3(grid), dim3(BLOCK), 0, stream, b.c_entry[1], mb.qbeg, nr, a.k, mb.req[0], mb.idx[0], a.entries);
+    bytes = b.temp_bytes;
+    e = rocprim::radix_sort_pairs(b.temp, bytes, mb.req[0], mb.req[1], mb.idx[0], mb.idx[1], a.entries, 0, (int)req_bits, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(gather_kernel, dim3(grid), dim3(BLOCK), 0, stream, mb.idx[1], b.c_asset[1], b.c_entry[1], b.c_asset[0], b.c_entry[0], a.entries);
+    // (weights and query indices in the outputs of the score sort, as queue_score)
+    WeightParams wp{b.c_entry[0], b.rec, b.rows, a.freq_col, b.freq_q, a.sim_tab, a.idf_tab, b.score[1], b.ws, b.order[1], b.idf_q,
+                    b.n_assets, a.entries, a.nq, a.k, a.dup_limit};
+    const uint32_t wn = a.entries > a.nq ? a.entries : a.nq;
+    hipLaunchKernelGGL(weights_kernel, dim3((wn + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, wp);
+    e = hipMemsetAsync(mb.n_assets, 0, (size_t)nr * sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    const uint32_t T = ma.words <= 32 ? 256 : (ma.words <= 64 ? 128 : 64);     // one LDS row of `words` u64 per thread, <= 64 KB per block
+    ScoreManyParams sp{b.c_asset[0], mb.req[1], b.score[1], b.ws, b.order[1], b.idf_q, mb.qbeg, b.score[0], b.order[0], b.matches, mb.n_assets,
+                       a.entries, a.nq, ma.words};
+    hipLaunchKernelGGL(score_many_kernel, dim3((a.entries + T - 1) / T), dim3(T), (size_t)ma.words * T * 8, stream, sp);
+    // every request's assets in (-score, asset) order: stable by score (descending), then stable by request
+    bytes = b.temp_bytes;
+    e = rocprim::radix_sort_pairs_desc(b.temp, bytes, b.score[0], b.score[1], b.order[0], b.order[1], a.entries, 0, 64, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(head_key_kernel, dim3(grid), dim3(BLOCK), 0, stream, b.score[1], b.order[1], mb.req[1], nr, mb.req[0], mb.idx[0], a.entries);
+    bytes = b.temp_bytes;
+    e = rocprim::radix_sort_pairs(b.temp, bytes, mb.req[0], mb.req[1], mb.idx[0], mb.idx[1], a.entries, 0, (int)req_bits, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(req_scan_kernel, dim3(1), dim3(BLOCK), 0, stream, mb.n_assets, nr, a.limit, mb.a_start, mb.e_start, a.out_info);
+    hipLaunchKernelGGL(result_chunks_kernel, dim3((ma.cap + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, mb.e_start, mb.a_start, mb.idx[1], b.matches, nr, mb.cnt, ma.cap);
+    bytes = b.temp_bytes;
+    e = rocprim::exclusive_scan(b.temp, bytes, mb.cnt, mb.c_pos, 0u, ma.cap, rocprim::plus<uint32_t>(), stream);
+    if (e != hipSuccess) return e;
+    EmitManyParams ep{};
+    ep.score = b.score[0]; ep.idx = mb.idx[1]; ep.asset = b.c_asset[0]; ep.entry = b.c_entry[0]; ep.matches = b.matches;
+    ep.a_start = mb.a_start; ep.e_start = mb.e_start; ep.c_pos = mb.c_pos; ep.qbeg = mb.qbeg;
+    ep.rec = b.rec; ep.rows = b.rows; ep.freq_col = a.freq_col;
+    for (uint32_t w = 0; w < 4; ++w) ep.col[w] = a.col[w];
+    ep.out_results = a.out_results; ep.out_chunks = a.out_chunks; ep.out_chunk_words = a.out_chunk_words; ep.out_info = a.out_info;
+    ep.n_req = nr; ep.k = a.k; ep.W = a.W; ep.dup_limit = a.dup_limit;
+    const uint32_t waves_wanted = ma.cap, blocks = std::min<uint32_t>((waves_wanted + 3) / 4, 2048);
+    hipLaunchKernelGGL(emit_many_kernel, dim3(blocks ? blocks : 1), dim3(BLOCK), 0, stream, ep);
     return hipGetLastError();
 }
 

@@ -453,6 +453,37 @@ class HipTable:
         n, c = int(info[0]), int(info[3])
         return results[:n], (chunks[:c] if detailed else None), (words[:c] if detailed else None), tuple(int(x) for x in info)
 
+    def simprint_score_many(self, q_words, offsets, count, max_hamming, threshold, limit, total_assets, dup_limit, detailed):
+        # type: (np.ndarray, np.ndarray, int, int | None, float, int, int, int, bool) -> tuple
+        """
+        ``simprint_score`` for many requests in one call (``isccsearch_simprint_score_many``): request r holds the query simprints
+        ``q_words[offsets[r]:offsets[r + 1]]``.  Returns (results [n_req, limit] ``SIMPRINT_RESULT_DTYPE``, chunks [limit x simprints]
+        ``SIMPRINT_CHUNK_DTYPE`` or None, chunk words uint64 [limit x simprints, max_words] or None, info uint32 [n_req, 4]):
+        request r's results are ``results[r, :info[r, 0]]``, its chunks ``chunks[limit * offsets[r]:][:info[r, 3]]``.
+        """
+        q_words = self._words(q_words)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
+        n_req = offsets.shape[0] - 1
+        nq = q_words.shape[0]
+        if n_req < 0 or (n_req and int(offsets[-1]) > nq):
+            raise ValueError("offsets must hold n_req + 1 entries within the query simprints")
+        if count < 1:
+            raise ValueError("`count` must be >= 1")
+        limit = int(limit)
+        results = np.empty((max(n_req, 0), limit), dtype=_lib.SIMPRINT_RESULT_DTYPE)
+        info = np.zeros((max(n_req, 0), 4), dtype=np.uint32)
+        chunks = words = None
+        if detailed:
+            cap = limit * nq
+            chunks = np.empty(cap, dtype=_lib.SIMPRINT_CHUNK_DTYPE)
+            words = np.empty((cap, self.max_words), dtype=np.uint64)
+        if n_req > 0 and nq:
+            _lib.check(self.engine._lib.isccsearch_simprint_score_many(
+                self.engine.handle, self.id, n_req, _lib.ptr(offsets), _lib.ptr(q_words), int(count),
+                -1 if max_hamming is None else int(max_hamming), float(threshold), limit, int(total_assets), int(dup_limit),
+                _lib.ptr(results), _lib.ptr(chunks), _lib.ptr(words), _lib.ptr(info)))
+        return results, chunks, words, info
+
     def simprint_exact(self, q_words, given, queried, dup_limit, threshold, limit, detailed):
         # type: (np.ndarray, np.ndarray, int, int, float, int, bool) -> tuple
         """

@@ -631,8 +631,10 @@ class HipIndex:
         ``search_assets`` for many queries: result i equals ``search_assets(queries[i], limit, exact)`` on the same index
         state.  Every query is validated first; one that ``search_assets`` would reject fails the whole call, before anything
         is searched, with the same exception naming its index in ``queries``.  The unit part runs as ``match_units_many``
-        (batches of up to 1 024 queries).  The ``chunk_matches`` of queries with simprints are answered per query by the
-        simprint search of ``search_assets``: batching simprint scoring across queries is not done here.
+        (batches of up to 1 024 queries).  The ``chunk_matches`` of queries with simprints: per simprint type ONE
+        ``search_raw_many`` over every query that carries it (on a single-GPU engine one library call, scored per query on the
+        device), then the ranking of ``search_assets`` per query.  With ``exact=True`` they are answered per query by the
+        collision search of ``search_assets``.
         """
         if not 1 <= limit <= MAX_K:
             # outside the engine's range search_assets itself decides (its limit checks depend on the query's units)
@@ -647,11 +649,15 @@ class HipIndex:
         unit_idx = [i for i, (query, _, _) in enumerate(prepared) if query.units]
         m = self._match_prepared([prepared[i] for i in unit_idx], limit) if unit_idx else None
         row_of = {i: r for r, i in enumerate(unit_idx)}
+        sp_raw = {} if exact else self._search_simprints_many(prepared, limit)
         results = []
         for i, (query, query_iscc_id, _) in enumerate(prepared):
             chunk_matches = []
             if self._sp_tables and query.simprints:
-                chunk_matches = self._search_simprints(query, limit, exact=exact)
+                if exact:
+                    chunk_matches = self._search_simprints(query, limit, exact=True)
+                else:
+                    chunk_matches = self._rank_simprint_matches(sp_raw.get(i, []), limit)
             matches = []
             r = row_of.get(i)
             if r is not None:
@@ -676,6 +682,36 @@ class HipIndex:
             results.append(IsccSearchResult(query=query, global_matches=matches, chunk_matches=chunk_matches))
         return results
 
+    def _search_simprints_many(self, prepared, limit):
+        # type: (list, int) -> Dict[int, list]
+        """
+        The approximate simprint searches of ``_search_simprints`` for every prepared query: per simprint type one
+        ``search_raw_many`` over the queries that carry it, with ``_search_simprints``' arguments.  Returns query index ->
+        [(simprint type, SimprintMatchRaw list)] in each query's type order.
+        """
+        if not self._sp_tables:
+            return {}
+        total_assets = len(self._assets)
+        requests = {}  # type: Dict[str, list]          simprint type -> [(query index, query simprints)]
+        for i, (query, _, _) in enumerate(prepared):
+            for sp_type, simprint_objs in (query.simprints or {}).items():
+                if sp_type in self._sp_tables:
+                    requests.setdefault(sp_type, []).append((i, [codec.decode_base64(_sp_string(s)) for s in simprint_objs]))
+        found = {}  # type: Dict[tuple, list]
+        for sp_type, items in requests.items():
+            raws = self._sp_tables[sp_type].search_raw_many(
+                [q_bytes for _, q_bytes in items], limit=limit * 2, threshold=self._opts.match_threshold_simprints, detailed=True,
+                total_assets=total_assets, device_doc_freq=True,
+            )
+            for (i, _), raw in zip(items, raws):
+                found[(i, sp_type)] = raw
+        out = {}  # type: Dict[int, list]
+        for i, (query, _, _) in enumerate(prepared):
+            for sp_type in (query.simprints or {}):
+                if (i, sp_type) in found:
+                    out.setdefault(i, []).append((sp_type, found[(i, sp_type)]))
+        return out
+
     def _search_simprints(self, query, limit, exact=False):
         # type: (IsccQuery, int, bool) -> List[IsccChunkMatch]
         """
@@ -683,7 +719,7 @@ class HipIndex:
         ``usearch/index.py:1357-1469``, or with ``exact`` the hard-boundary collision search of ``:1261-1355``.
         """
         total_assets = len(self._assets)
-        per_asset = {}  # type: Dict[bytes, Dict[str, object]]
+        per_type = []
         for sp_type, simprint_objs in query.simprints.items():
             table = self._sp_tables.get(sp_type)
             if table is None:
@@ -696,6 +732,14 @@ class HipIndex:
                     simprints=q_bytes, limit=limit * 2, threshold=self._opts.match_threshold_simprints, detailed=True,
                     total_assets=total_assets, device_doc_freq=True,   # lmdb_ops.count_doc_freq, on the device
                 )
+            per_type.append((sp_type, raw))
+        return self._rank_simprint_matches(per_type, limit)
+
+    def _rank_simprint_matches(self, per_type, limit):
+        # type: (list, int) -> List[IsccChunkMatch]
+        """The chunk matches of one query from its per-type ``SimprintMatchRaw`` lists (in the query's type order): mean over types, order (-score, iscc_id)."""
+        per_asset = {}  # type: Dict[bytes, Dict[str, object]]
+        for sp_type, raw in per_type:
             for r in raw:
                 per_asset.setdefault(r.iscc_id_body, {})[sp_type] = r
         if not per_asset:

@@ -410,6 +410,12 @@ class HipIndex128:
         return hasattr(self._table, "simprint_score")
 
     @property
+    def scores_many_on_device(self):
+        # type: () -> bool
+        """Whether the table scores many simprint requests in one call (``isccsearch_simprint_score_many``)."""
+        return hasattr(self._table, "simprint_score_many")
+
+    @property
     def scores_exact_on_device(self):
         # type: () -> bool
         """Whether the table scores hard-boundary (collision) searches itself (``isccsearch_simprint_exact``)."""
@@ -420,6 +426,12 @@ class HipIndex128:
         """``HipTable.simprint_score`` for byte vectors: search + scoring of ``usearch_core.py:137-269`` in one device round trip."""
         q_words, _ = pack_bytes(self._vectors(vectors), self._table.max_words)
         return self._table.simprint_score(q_words, count, max_hamming, threshold, limit, total_assets, dup_limit, detailed)
+
+    def score_assets_many(self, vectors, offsets, count, max_hamming, threshold, limit, total_assets, dup_limit, detailed):
+        # type: (np.ndarray, np.ndarray, int, int | None, float, int, int, int, bool) -> tuple
+        """``HipTable.simprint_score_many`` for byte vectors: request r holds ``vectors[offsets[r]:offsets[r + 1]]``."""
+        q_words, _ = pack_bytes(self._vectors(vectors), self._table.max_words)
+        return self._table.simprint_score_many(q_words, offsets, count, max_hamming, threshold, limit, total_assets, dup_limit, detailed)
 
     def exact_assets(self, vectors, given, queried, dup_limit, threshold, limit, detailed):
         # type: (np.ndarray, np.ndarray, int, int, float, int, bool) -> tuple

@@ -158,6 +158,54 @@ class HipSimprintIndex:
             return self._search_raw_device(simprints, limit, threshold, detailed, total_assets, DOC_FREQ_DUP_LIMIT if device_doc_freq else 0)
         return self._search_raw_host(simprints, limit, threshold, detailed, doc_freq_fn, total_assets, device_doc_freq)
 
+    def search_raw_many(self, requests, limit=10, threshold=0.0, detailed=False, total_assets=0, device_doc_freq=False):
+        # type: (list[list[bytes]], int, float, bool, int, bool) -> list[list[SimprintMatchRaw]]
+        """
+        ``search_raw`` for many requests: result i equals ``search_raw(requests[i], limit, threshold, detailed,
+        total_assets=total_assets, device_doc_freq=device_doc_freq)``, an exception included (the first request in order that
+        raises decides it).  On a table that scores many requests itself (``isccsearch_simprint_score_many``) every request of
+        up to ``MAX_SCORED_SIMPRINTS`` simprints is searched and scored in ONE library call, in rounds of at most that many
+        simprints; the others -- and every request on other tables (sharded, the CPU oracle) -- run through ``search_raw``.
+        """
+        requests = [list(r) for r in requests]
+        one = lambda r: self.search_raw(r, limit=limit, threshold=threshold, detailed=detailed, total_assets=total_assets, device_doc_freq=device_doc_freq)
+        if len(self._index) == 0 or not self._index.scores_many_on_device or limit < 1:
+            return [one(r) for r in requests]
+        nbytes = self.ndim // 8
+        batched = [i for i, r in enumerate(requests) if r and len(r) <= MAX_SCORED_SIMPRINTS]
+        if any(len(sp) != nbytes for i in batched for sp in requests[i]):
+            return [one(r) for r in requests]        # (search_raw's own error, in request order)
+        out = [None] * len(requests)  # type: list
+        if batched:
+            flat = [bytes(sp) for i in batched for sp in requests[i]]
+            offsets = np.zeros(len(batched) + 1, dtype=np.uint32)
+            offsets[1:] = np.cumsum([len(requests[i]) for i in batched])
+            count = max(1, limit * self.oversampling_factor)
+            radius = None
+            if count > MAX_K:
+                radius, count = self._radius_for(threshold), MAX_K
+            dup_limit = DOC_FREQ_DUP_LIMIT if device_doc_freq else 0
+            results, chunks, words, info = self._index.score_assets_many(_pack_simprints(flat), offsets, count, radius, threshold, limit,
+                                                                         total_assets, dup_limit, detailed)
+            for j, i in enumerate(batched):
+                out[i] = (results[j, : int(info[j, 0])], int(offsets[j]), int(info[j, 2]), int(info[j, 3]))
+        for i, r in enumerate(requests):
+            if out[i] is None:
+                out[i] = one(r)
+                continue
+            res, first, longest, c = out[i]
+            if radius is not None and longest >= MAX_K:
+                raise ValueError(
+                    f"limit {limit} x oversampling {self.oversampling_factor} = {limit * self.oversampling_factor} neighbours per simprint exceeds the "
+                    f"{MAX_K} this backend returns, and a query simprint has that many stored chunks within the match threshold"
+                )
+            at = limit * first
+            if detailed:
+                out[i] = self._unpack_device(r, res, chunks[at : at + c], words[at : at + c].astype(">u8").tobytes(), detailed)
+            else:
+                out[i] = self._unpack_device(r, res, None, b"", detailed)
+        return out
+
     def _radius_for(self, threshold):
         # type: (float) -> int
         """Largest distance whose score ``1 - d / ndim`` still passes ``threshold`` (0 when none does)."""
@@ -187,6 +235,11 @@ class HipSimprintIndex:
                 f"limit {limit} x oversampling {self.oversampling_factor} = {limit * self.oversampling_factor} neighbours per simprint exceeds the "
                 f"{MAX_K} this backend returns, and a query simprint has that many stored chunks within the match threshold"
             )
+        return self._unpack_device(simprints, results, chunks, np.ascontiguousarray(words).astype(">u8").tobytes() if detailed else b"", detailed)
+
+    def _unpack_device(self, simprints, results, chunks, raw, detailed):
+        # type: (list[bytes], np.ndarray, np.ndarray | None, bytes, bool) -> list[SimprintMatchRaw]
+        """One request's device results as ``SimprintMatchRaw``: ``chunks`` are the request's, ``raw`` the big-endian bytes of their words."""
         # (columns as lists and positional construction: 520 chunk objects -- 13 assets x 40 matched simprints -- cost 0.67 ms built
         #  field by field from structured rows, 0.28 ms this way)
         body = [a.to_bytes(8, "big") for a in results["asset"].tolist()]
@@ -194,7 +247,6 @@ class HipSimprintIndex:
             return [SimprintMatchRaw(b, s, len(simprints), m, None) for b, s, m in zip(body, results["score"].tolist(), results["matches"].tolist())]
         nbytes = self.ndim // 8
         stride = (nbytes + 7) // 8 * 8
-        raw = np.ascontiguousarray(words).astype(">u8").tobytes()
         sim = [1.0 - h / self.ndim for h in range(self.ndim + 1)]
         key_lo = chunks["key_lo"]
         cols = zip(chunks["query"].tolist(), chunks["hamming"].tolist(), (key_lo >> np.uint64(32)).tolist(),
