@@ -264,6 +264,7 @@ struct isccsearch_handle {
     DevBuf<double> d_sp_score[2], d_sp_tab, d_sp_ws, d_sp_idfq;
     // isccsearch_simprint_score_many: request keys / sort payloads per entry, per-request offsets and counts, chunks per result
     DevBuf<uint32_t> d_spm_req[2], d_spm_idx[2], d_spm_qbeg, d_spm_nassets, d_spm_astart, d_spm_estart, d_spm_cnt, d_spm_cpos;
+    std::vector<uint32_t> h_sp_qbeg, h_sp_qcount;     // (host side of a round: kept, so that a scoring call allocates nothing here)
     PinBuf<double> p_sp_tab;
     PinBuf<unsigned char> p_sp_out;
     // the similarity / IDF tables on the device are those of (bits, total_assets, dup_limit):
@@ -2454,107 +2455,15 @@ static int simprint_unknown_freq(H* h, uint32_t table, Table& t, uint32_t nq, co
     return 0;
 }
 
-// Search + asset scoring with the neighbour lists kept on the device (usearch_core.py:137-269); see include/isccsearch.h.
-int isccsearch_simprint_score(isccsearch_handle* h, uint32_t table, uint32_t nq, const uint64_t* q_words,
-                              uint32_t count, int32_t max_hamming, double threshold, uint32_t limit,
-                              int64_t total_assets, uint32_t dup_limit,
-                              isccsearch_simprint_result* out_results, isccsearch_simprint_chunk* out_chunks,
-                              uint64_t* out_chunk_words, uint32_t* out_info) {
-    if (!h) return fail(-EINVAL, "handle is NULL");
-    if (count < 1) return fail(-EINVAL, "`count` must be >= 1");
-    if (count > ISCCSEARCH_MAX_K) return fail(-EINVAL, "count %u exceeds ISCCSEARCH_MAX_K (%d)", count, ISCCSEARCH_MAX_K);
-    if (max_hamming > 256) return fail(-EINVAL, "max_hamming %d exceeds 256", max_hamming);
-    if (dup_limit > ISCCSEARCH_MAX_K) return fail(-EINVAL, "dup_limit %u exceeds ISCCSEARCH_MAX_K (%d)", dup_limit, ISCCSEARCH_MAX_K);
-    if (limit < 1) return fail(-EINVAL, "limit must be >= 1");
-    if (!out_info) return fail(-EINVAL, "NULL argument");
-    out_info[0] = out_info[1] = out_info[2] = out_info[3] = 0;
-    if (nq == 0) return 0;
-    if (!q_words || !out_results || (out_chunks == nullptr) != (out_chunk_words == nullptr)) return fail(-EINVAL, "NULL argument");
-    if (nq > isksp::MAX_QUERY_SIMPRINTS) return fail(-E2BIG, "%u query simprints exceed the %u one scoring call takes", nq, isksp::MAX_QUERY_SIMPRINTS);
-    if (!(threshold == threshold)) return fail(-EINVAL, "threshold is not a number");
-    std::lock_guard<std::mutex> lk(h->mu);
-    Table* tp;
-    int rc = get_table(h, table, tp);
-    if (rc) return rc;
-    Table& t = *tp;
-    if (t.metric != ISCCSEARCH_METRIC_HAMMING || t.key_words != 2)
-        return fail(-EINVAL, "simprint scoring is defined for fixed-length (Hamming) tables with 128-bit chunk-pointer keys");
-    Segment& s = t.seg[t.max_bytes];
-    if (s.n == 0) return 0;
-    if (s.n > 0xFFFFFFFFull) return fail(-E2BIG, "simprint scoring addresses rows with 32 bits; the table holds %llu", (unsigned long long)s.n);
-    HIPOK(hipSetDevice(h->device));
-    h->stats.searches += 1;
-    const uint32_t k = count, bits = 8 * (uint32_t)t.max_bytes;
-    int h_max = -1;
-    if ((rc = simprint_setup(h, t, s, threshold, total_assets, dup_limit, h_max))) return rc;
-    if ((rc = simprint_buffers(h, nq, k, 0))) return rc;
-    ScoreSink sink;
-    sink.h_max = h_max;
-    sink.dup_limit = dup_limit;
-    simprint_bind(h, sink.buf);
-    if ((rc = search_locked(h, table, nq, q_words, nullptr, k, nullptr, nullptr, nullptr, nullptr, max_hamming < 0 ? -1 : max_hamming, nullptr, nullptr, &sink))) return rc;
-    out_info[2] = sink.max_count;
-    const uint32_t entries = sink.entries;
-    if (entries == 0) return 0;
-    if (sink.unknown_any && (rc = simprint_unknown_freq(h, table, t, nq, q_words, dup_limit))) return rc;
-    if ((rc = simprint_buffers(h, nq, k, entries))) return rc;
-    if ((rc = h->d_sp_temp.ensure(isksp::sort_temp_bytes(entries)))) return rc;
-    simprint_bind(h, sink.buf);
-    // outputs in pinned memory, written by the emit kernel itself: {info[4] | results[limit] | chunks | chunk words}
-    const uint32_t W = (uint32_t)t.max_words;
-    const size_t res_off = 16, chunk_off = res_off + (size_t)limit * sizeof(isccsearch_simprint_result);
-    const size_t chunk_cap = out_chunks ? (size_t)std::min<uint64_t>((uint64_t)limit * nq, entries) : 0;
-    const size_t words_off = chunk_off + chunk_cap * sizeof(isccsearch_simprint_chunk);
-    if ((rc = h->p_sp_out.ensure(words_off + chunk_cap * W * 8))) return rc;
-    unsigned char* const po = h->p_sp_out.p;
-    isksp::ScoreArgs sa{};
-    sa.nq = nq; sa.k = k; sa.entries = entries; sa.limit = limit;
-    sa.sim_tab = h->d_sp_tab.p; sa.idf_tab = h->d_sp_tab.p + bits + 1; sa.dup_limit = dup_limit;
-    sa.freq_col = dup_limit ? s.freq : nullptr;
-    for (uint32_t w = 0; w < s.W; ++w) sa.col[w] = s.col[w];
-    sa.W = W;
-    sa.out_info = reinterpret_cast<uint32_t*>(po);
-    sa.out_results = reinterpret_cast<isccsearch_simprint_result*>(po + res_off);
-    sa.out_chunks = out_chunks ? reinterpret_cast<isccsearch_simprint_chunk*>(po + chunk_off) : nullptr;
-    sa.out_chunk_words = out_chunks ? reinterpret_cast<uint64_t*>(po + words_off) : nullptr;
-    HIPOK(isksp::queue_score(sink.buf, sa, h->stream));
-    HIPOK(hipStreamSynchronize(h->stream));
-    const uint32_t* info = reinterpret_cast<const uint32_t*>(po);
-    const uint32_t n = info[0];
-    out_info[0] = n; out_info[1] = info[1]; out_info[3] = info[3];
-    memcpy(out_results, po + res_off, (size_t)n * sizeof(isccsearch_simprint_result));
-    if (out_chunks) {
-        memcpy(out_chunks, po + chunk_off, (size_t)info[3] * sizeof(isccsearch_simprint_chunk));
-        memcpy(out_chunk_words, po + words_off, (size_t)info[3] * W * 8);
-    }
-    return 0;
-}
-
-// Many simprint requests against one table, each scored on its own (usearch_core.py:137-269 per request); see include/isccsearch.h.
-int isccsearch_simprint_score_many(isccsearch_handle* h, uint32_t table, uint32_t n_req, const uint32_t* req_offsets, const uint64_t* q_words,
-                                   uint32_t count, int32_t max_hamming, double threshold, uint32_t limit,
-                                   int64_t total_assets, uint32_t dup_limit,
-                                   isccsearch_simprint_result* out_results, isccsearch_simprint_chunk* out_chunks,
-                                   uint64_t* out_chunk_words, uint32_t* out_info) {
-    if (!h) return fail(-EINVAL, "handle is NULL");
-    if (count < 1) return fail(-EINVAL, "`count` must be >= 1");
-    if (count > ISCCSEARCH_MAX_K) return fail(-EINVAL, "count %u exceeds ISCCSEARCH_MAX_K (%d)", count, ISCCSEARCH_MAX_K);
-    if (max_hamming > 256) return fail(-EINVAL, "max_hamming %d exceeds 256", max_hamming);
-    if (dup_limit > ISCCSEARCH_MAX_K) return fail(-EINVAL, "dup_limit %u exceeds ISCCSEARCH_MAX_K (%d)", dup_limit, ISCCSEARCH_MAX_K);
-    if (limit < 1) return fail(-EINVAL, "limit must be >= 1");
-    if (n_req == 0) return 0;
-    if (!out_info || !req_offsets) return fail(-EINVAL, "NULL argument");
-    memset(out_info, 0, (size_t)n_req * 4 * sizeof(uint32_t));
-    for (uint32_t r = 0; r < n_req; ++r) {
-        if (req_offsets[r + 1] < req_offsets[r]) return fail(-EINVAL, "req_offsets must not decrease (request %u)", r);
-        if (req_offsets[r + 1] - req_offsets[r] > isksp::MAX_QUERY_SIMPRINTS)
-            return fail(-E2BIG, "request %u: %u query simprints exceed the %u one scoring call takes", r, req_offsets[r + 1] - req_offsets[r], isksp::MAX_QUERY_SIMPRINTS);
-    }
-    if (req_offsets[n_req] == req_offsets[0]) return 0;
-    if (!q_words || !out_results || (out_chunks == nullptr) != (out_chunk_words == nullptr)) return fail(-EINVAL, "NULL argument");
-    if ((uint64_t)limit * n_req > 0xFFFFFFFFull || (uint64_t)limit * req_offsets[n_req] > 0xFFFFFFFFull)
-        return fail(-E2BIG, "limit %u x %u requests exceeds the 32-bit result addressing", limit, n_req);
-    if (!(threshold == threshold)) return fail(-EINVAL, "threshold is not a number");
+// The scoring of isccsearch_simprint_score and _many once their arguments are checked (out_info zeroed; request r = query simprints
+// [req_offsets[r], req_offsets[r + 1]), at most MAX_QUERY_SIMPRINTS each): consecutive requests of at most MAX_QUERY_SIMPRINTS query
+// simprints form a round, a request is never split.  A round is ONE search with the lists left on the device and one scoring: a round
+// of one request takes queue_score's pipeline, a round of several queue_score_many's (which returns per request what queue_score would).
+static int simprint_score_rounds(H* h, uint32_t table, uint32_t n_req, const uint32_t* req_offsets, const uint64_t* q_words,
+                                 uint32_t count, int32_t max_hamming, double threshold, uint32_t limit,
+                                 int64_t total_assets, uint32_t dup_limit,
+                                 isccsearch_simprint_result* out_results, isccsearch_simprint_chunk* out_chunks,
+                                 uint64_t* out_chunk_words, uint32_t* out_info) {
     std::lock_guard<std::mutex> lk(h->mu);
     Table* tp;
     int rc = get_table(h, table, tp);
@@ -2569,8 +2478,8 @@ int isccsearch_simprint_score_many(isccsearch_handle* h, uint32_t table, uint32_
     const uint32_t k = count, bits = 8 * (uint32_t)t.max_bytes, W = (uint32_t)t.max_words;
     int h_max = -1;
     if ((rc = simprint_setup(h, t, s, threshold, total_assets, dup_limit, h_max))) return rc;
-    std::vector<uint32_t> qbeg, q_count;
-    // rounds: consecutive requests of at most MAX_QUERY_SIMPRINTS query simprints together, a request never split
+    std::vector<uint32_t>& qbeg = h->h_sp_qbeg;
+    std::vector<uint32_t>& q_count = h->h_sp_qcount;
     for (uint32_t r0 = 0; r0 < n_req;) {
         const uint32_t base = req_offsets[r0];
         uint32_t r1 = r0 + 1;
@@ -2603,31 +2512,29 @@ int isccsearch_simprint_score_many(isccsearch_handle* h, uint32_t table, uint32_
         if (sink.unknown_any && (rc = simprint_unknown_freq(h, table, t, nq, qw, dup_limit))) return rc;
         const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)nr * limit, entries);
         if ((rc = simprint_buffers(h, nq, k, entries))) return rc;
-        for (int i = 0; i < 2; ++i) {
-            if ((rc = h->d_spm_req[i].ensure(entries))) return rc;
-            if ((rc = h->d_spm_idx[i].ensure(entries))) return rc;
+        if (nr == 1) {
+            if ((rc = h->d_sp_temp.ensure(isksp::sort_temp_bytes(entries)))) return rc;
+        } else {
+            for (int i = 0; i < 2; ++i) {
+                if ((rc = h->d_spm_req[i].ensure(entries))) return rc;
+                if ((rc = h->d_spm_idx[i].ensure(entries))) return rc;
+            }
+            if ((rc = h->d_spm_qbeg.ensure(nr + 1))) return rc;
+            if ((rc = h->d_spm_nassets.ensure(nr))) return rc;
+            if ((rc = h->d_spm_astart.ensure(nr + 1))) return rc;
+            if ((rc = h->d_spm_estart.ensure(nr + 1))) return rc;
+            if ((rc = h->d_spm_cnt.ensure(cap))) return rc;
+            if ((rc = h->d_spm_cpos.ensure(cap))) return rc;
+            if ((rc = h->d_sp_temp.ensure(isksp::many_temp_bytes(entries, cap)))) return rc;
         }
-        if ((rc = h->d_spm_qbeg.ensure(nr + 1))) return rc;
-        if ((rc = h->d_spm_nassets.ensure(nr))) return rc;
-        if ((rc = h->d_spm_astart.ensure(nr + 1))) return rc;
-        if ((rc = h->d_spm_estart.ensure(nr + 1))) return rc;
-        if ((rc = h->d_spm_cnt.ensure(cap))) return rc;
-        if ((rc = h->d_spm_cpos.ensure(cap))) return rc;
-        if ((rc = h->d_sp_temp.ensure(isksp::many_temp_bytes(entries, cap)))) return rc;
         simprint_bind(h, sink.buf);
-        isksp::ManyBuffers mb{};
-        for (int i = 0; i < 2; ++i) { mb.req[i] = h->d_spm_req[i].p; mb.idx[i] = h->d_spm_idx[i].p; }
-        mb.qbeg = h->d_spm_qbeg.p; mb.n_assets = h->d_spm_nassets.p; mb.a_start = h->d_spm_astart.p; mb.e_start = h->d_spm_estart.p;
-        mb.cnt = h->d_spm_cnt.p; mb.c_pos = h->d_spm_cpos.p;
-        HIPOK(hipMemcpyAsync(mb.qbeg, qbeg.data(), (size_t)(nr + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-        // outputs in pinned memory, compact: {info[nr][4] | results[cap] | chunks | chunk words}
+        // outputs in pinned memory, written by the emit kernels themselves, compact: {info[nr][4] | results[cap] | chunks | chunk words}
         const size_t res_off = ((size_t)nr * 16 + 15) / 16 * 16, chunk_off = res_off + (size_t)cap * sizeof(isccsearch_simprint_result);
         const size_t chunk_cap = out_chunks ? (size_t)std::min<uint64_t>((uint64_t)limit * nq, entries) : 0;
         const size_t words_off = chunk_off + chunk_cap * sizeof(isccsearch_simprint_chunk);
         if ((rc = h->p_sp_out.ensure(words_off + chunk_cap * W * 8))) return rc;
         unsigned char* const po = h->p_sp_out.p;
-        isksp::ScoreManyArgs ma{};
-        isksp::ScoreArgs& sa = ma.s;
+        isksp::ScoreArgs sa{};
         sa.nq = nq; sa.k = k; sa.entries = entries; sa.limit = limit;
         sa.sim_tab = h->d_sp_tab.p; sa.idf_tab = h->d_sp_tab.p + bits + 1; sa.dup_limit = dup_limit;
         sa.freq_col = dup_limit ? s.freq : nullptr;
@@ -2637,8 +2544,17 @@ int isccsearch_simprint_score_many(isccsearch_handle* h, uint32_t table, uint32_
         sa.out_results = reinterpret_cast<isccsearch_simprint_result*>(po + res_off);
         sa.out_chunks = out_chunks ? reinterpret_cast<isccsearch_simprint_chunk*>(po + chunk_off) : nullptr;
         sa.out_chunk_words = out_chunks ? reinterpret_cast<uint64_t*>(po + words_off) : nullptr;
-        ma.n_req = nr; ma.cap = cap; ma.words = words;
-        HIPOK(isksp::queue_score_many(sink.buf, mb, ma, h->stream));
+        if (nr == 1) {
+            HIPOK(isksp::queue_score(sink.buf, sa, h->stream));
+        } else {
+            isksp::ManyBuffers mb{};
+            for (int i = 0; i < 2; ++i) { mb.req[i] = h->d_spm_req[i].p; mb.idx[i] = h->d_spm_idx[i].p; }
+            mb.qbeg = h->d_spm_qbeg.p; mb.n_assets = h->d_spm_nassets.p; mb.a_start = h->d_spm_astart.p; mb.e_start = h->d_spm_estart.p;
+            mb.cnt = h->d_spm_cnt.p; mb.c_pos = h->d_spm_cpos.p;
+            HIPOK(hipMemcpyAsync(mb.qbeg, qbeg.data(), (size_t)(nr + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+            isksp::ScoreManyArgs ma{sa, nr, cap, words};
+            HIPOK(isksp::queue_score_many(sink.buf, mb, ma, h->stream));
+        }
         HIPOK(hipStreamSynchronize(h->stream));       // (qbeg is read by the kernels until here)
         // into the caller's regions: request r's results at r x limit, its chunks at limit x req_offsets[r]
         const uint32_t* info = reinterpret_cast<const uint32_t*>(po);
@@ -2659,6 +2575,58 @@ int isccsearch_simprint_score_many(isccsearch_handle* h, uint32_t table, uint32_
         r0 = r1;
     }
     return 0;
+}
+
+// Search + asset scoring with the neighbour lists kept on the device (usearch_core.py:137-269); see include/isccsearch.h.
+int isccsearch_simprint_score(isccsearch_handle* h, uint32_t table, uint32_t nq, const uint64_t* q_words,
+                              uint32_t count, int32_t max_hamming, double threshold, uint32_t limit,
+                              int64_t total_assets, uint32_t dup_limit,
+                              isccsearch_simprint_result* out_results, isccsearch_simprint_chunk* out_chunks,
+                              uint64_t* out_chunk_words, uint32_t* out_info) {
+    if (!h) return fail(-EINVAL, "handle is NULL");
+    if (count < 1) return fail(-EINVAL, "`count` must be >= 1");
+    if (count > ISCCSEARCH_MAX_K) return fail(-EINVAL, "count %u exceeds ISCCSEARCH_MAX_K (%d)", count, ISCCSEARCH_MAX_K);
+    if (max_hamming > 256) return fail(-EINVAL, "max_hamming %d exceeds 256", max_hamming);
+    if (dup_limit > ISCCSEARCH_MAX_K) return fail(-EINVAL, "dup_limit %u exceeds ISCCSEARCH_MAX_K (%d)", dup_limit, ISCCSEARCH_MAX_K);
+    if (limit < 1) return fail(-EINVAL, "limit must be >= 1");
+    if (!out_info) return fail(-EINVAL, "NULL argument");
+    out_info[0] = out_info[1] = out_info[2] = out_info[3] = 0;
+    if (nq == 0) return 0;
+    if (!q_words || !out_results || (out_chunks == nullptr) != (out_chunk_words == nullptr)) return fail(-EINVAL, "NULL argument");
+    if (nq > isksp::MAX_QUERY_SIMPRINTS) return fail(-E2BIG, "%u query simprints exceed the %u one scoring call takes", nq, isksp::MAX_QUERY_SIMPRINTS);
+    if (!(threshold == threshold)) return fail(-EINVAL, "threshold is not a number");
+    const uint32_t req_offsets[2] = {0, nq};
+    return simprint_score_rounds(h, table, 1, req_offsets, q_words, count, max_hamming, threshold, limit, total_assets, dup_limit,
+                                 out_results, out_chunks, out_chunk_words, out_info);
+}
+
+// Many simprint requests against one table, each scored on its own (usearch_core.py:137-269 per request); see include/isccsearch.h.
+int isccsearch_simprint_score_many(isccsearch_handle* h, uint32_t table, uint32_t n_req, const uint32_t* req_offsets, const uint64_t* q_words,
+                                   uint32_t count, int32_t max_hamming, double threshold, uint32_t limit,
+                                   int64_t total_assets, uint32_t dup_limit,
+                                   isccsearch_simprint_result* out_results, isccsearch_simprint_chunk* out_chunks,
+                                   uint64_t* out_chunk_words, uint32_t* out_info) {
+    if (!h) return fail(-EINVAL, "handle is NULL");
+    if (count < 1) return fail(-EINVAL, "`count` must be >= 1");
+    if (count > ISCCSEARCH_MAX_K) return fail(-EINVAL, "count %u exceeds ISCCSEARCH_MAX_K (%d)", count, ISCCSEARCH_MAX_K);
+    if (max_hamming > 256) return fail(-EINVAL, "max_hamming %d exceeds 256", max_hamming);
+    if (dup_limit > ISCCSEARCH_MAX_K) return fail(-EINVAL, "dup_limit %u exceeds ISCCSEARCH_MAX_K (%d)", dup_limit, ISCCSEARCH_MAX_K);
+    if (limit < 1) return fail(-EINVAL, "limit must be >= 1");
+    if (n_req == 0) return 0;
+    if (!out_info || !req_offsets) return fail(-EINVAL, "NULL argument");
+    memset(out_info, 0, (size_t)n_req * 4 * sizeof(uint32_t));
+    for (uint32_t r = 0; r < n_req; ++r) {
+        if (req_offsets[r + 1] < req_offsets[r]) return fail(-EINVAL, "req_offsets must not decrease (request %u)", r);
+        if (req_offsets[r + 1] - req_offsets[r] > isksp::MAX_QUERY_SIMPRINTS)
+            return fail(-E2BIG, "request %u: %u query simprints exceed the %u one scoring call takes", r, req_offsets[r + 1] - req_offsets[r], isksp::MAX_QUERY_SIMPRINTS);
+    }
+    if (req_offsets[n_req] == req_offsets[0]) return 0;
+    if (!q_words || !out_results || (out_chunks == nullptr) != (out_chunk_words == nullptr)) return fail(-EINVAL, "NULL argument");
+    if ((uint64_t)limit * n_req > 0xFFFFFFFFull || (uint64_t)limit * req_offsets[n_req] > 0xFFFFFFFFull)
+        return fail(-E2BIG, "limit %u x %u requests exceeds the 32-bit result addressing", limit, n_req);
+    if (!(threshold == threshold)) return fail(-EINVAL, "threshold is not a number");
+    return simprint_score_rounds(h, table, n_req, req_offsets, q_words, count, max_hamming, threshold, limit, total_assets, dup_limit,
+                                 out_results, out_chunks, out_chunk_words, out_info);
 }
 
 // Hard-boundary simprint search with its scoring on the device (lmdb_ops.py:169-301); see include/isccsearch.h.
@@ -2700,19 +2668,7 @@ int isccsearch_simprint_exact(isccsearch_handle* h, uint32_t table, uint32_t n_d
     if ((rc = h->d_sp_nassets.ensure(1))) return rc;
     ScoreSink sink;
     sink.exact = true;
-    auto bind = [&]() {
-        isksp::Buffers& b = sink.buf;
-        b.rec = reinterpret_cast<const isccsearch_record*>(h->d_sp_rec.p);
-        b.rows = nullptr; b.best = nullptr; b.nbest = h->d_sp_nbest.p; b.offs = h->d_sp_offs.p;
-        b.freq_q = h->d_sp_freqq.p; b.unknown = h->d_sp_unknown.p; b.n_assets = h->d_sp_nassets.p;
-        for (int i = 0; i < 2; ++i) {
-            b.c_asset[i] = h->d_sp_asset[i].p; b.c_entry[i] = h->d_sp_entry[i].p;
-            b.score[i] = h->d_sp_score[i].p; b.order[i] = h->d_sp_order[i].p;
-        }
-        b.matches = h->d_sp_matches.p; b.ws = nullptr; b.idf_q = nullptr;
-        b.temp = h->d_sp_temp.p; b.temp_bytes = h->d_sp_temp.n;
-    };
-    bind();
+    simprint_bind(h, sink.buf);
     // (the lookup of every given simprint goes up first: when one batch holds all lookups, hits and offsets are prepared behind its
     //  select and the number of entries arrives with the batch's own synchronisation)
     HIPOK(hipMemcpyAsync(h->d_sp_dofg.p, given, (size_t)ng * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
@@ -2741,7 +2697,7 @@ int isccsearch_simprint_exact(isccsearch_handle* h, uint32_t table, uint32_t n_d
     }
     if ((rc = h->d_sp_matches.ensure(entries))) return rc;
     if ((rc = h->d_sp_temp.ensure(isksp::sort_temp_bytes(entries)))) return rc;
-    bind();
+    simprint_bind(h, sink.buf);
     const size_t res_off = 16, chunk_off = res_off + (size_t)limit * sizeof(isccsearch_simprint_result);
     const size_t chunk_cap = out_chunks ? entries : 0;
     if ((rc = h->p_sp_out.ensure(chunk_off + chunk_cap * sizeof(isccsearch_simprint_chunk)))) return rc;

@@ -12,7 +12,7 @@
 //              frequency from its hamming-0 prefix
 //     offsets  exclusive scan of the per-query best counts (one block)
 //     compact  the best entries of the batch, in (query, rank) order, appended to (asset[], entry[])
-//   once per request:
+//   once per request (queue_score; a round of isccsearch_simprint_score_many that holds one request takes it too):
 //     stable radix sort by asset (rocPRIM) -> every asset's entries adjacent, ascending query
 //     score    one thread per asset run, sequential float64 sums in the reference's order (no contraction into fused
 //              multiply-adds: -ffp-contract=off; IEEE rounding); IDF and similarity values come from host-computed tables
@@ -84,11 +84,12 @@ struct ScoreArgs {
 // sort by asset -> score -> sort by score -> emit
 hipError_t queue_score(Buffers& b, const ScoreArgs& a, hipStream_t stream);
 
-// Many requests in one call (isccsearch_simprint_score_many): the query simprints of a round are the concatenation of its
-// requests' (request r: queries [qbeg[r], qbeg[r + 1]) of the round), searched, marked and compacted as ONE request by
-// queue_batch -- so the entries are grouped by request already -- then
+// Many requests in one call (a round of two or more requests of isccsearch_simprint_score_many): the query simprints of a round
+// are the concatenation of its requests' (request r: queries [qbeg[r], qbeg[r + 1]) of the round), searched, marked and compacted
+// as ONE request by queue_batch -- so the entries are grouped by request already -- then
 //     stable radix sort by asset, stable radix sort by request -> every (request, asset) run adjacent, ascending query
-//     score    as score_kernel, the unmatched sum over the run's own request only; assets counted per request
+//     score    the same score_kernel with a run = (request, asset): the unmatched sum over the run's own request only; assets
+//              counted per request
 //     stable radix sort by score (descending), stable radix sort by request -> every request's assets in (-score, asset) order
 //     emit     one wave per written result (never a block per (request, rank) slot): results, compact, in request order
 // Pinned outputs are staged compactly: request r's results follow those of the requests before it, its chunks likewise;

@@ -1,6 +1,7 @@
 // Simprint asset scoring on the device: see simprint_score.h for the pipeline and the reference lines it restates
 // (iscc_search/indexes/simprint/usearch_core.py:171-269).  Built for gfx950 only.
 #include <cstring>   // rocPRIM's texture iterator calls memset without including it
+#include <type_traits>
 
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
@@ -205,13 +206,16 @@ __global__ __launch_bounds__(BLOCK) void weights_kernel(const WeightParams p) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// score_kernel: one thread per sorted entry; the thread at the head of an asset's run scores the asset.
+// score_kernel: one thread per sorted entry; the thread at the head of a run scores it.  A run is an asset's entries (ScoreParams,
+// queue_score) or a (request, asset) pair's (ScoreManyParams, queue_score_many: entries sorted by request, then asset).
 //   usearch_core.py:215-236 -- total_idf and weighted_sim over the matched query simprints in ascending query order (the
 //   insertion order of best_per_query), then total_idf over every unmatched query simprint in ascending order; score =
 //   weighted / total when total > 0.  Sequential float64 operations with IEEE rounding, none contracted.
-//   The run is walked four entries at a time (its loads do not depend on the sums), and leaves a bit per matched query in the
+//   The run is walked eight entries at a time (its loads do not depend on the sums), and leaves a bit per matched query in the
 //   thread's LDS row, so that the second sum runs over the query simprints without touching memory it has to wait for.
-// dynamic LDS: mask[words][threads] u64, words = ceil(nq / 64)
+//   With many requests the unmatched sum runs over the run's own request [qbeg[r], qbeg[r + 1]) only, and the LDS row holds the
+//   64-bit words that range touches, relative to its first word.
+// dynamic LDS: mask[words][threads] u64 (ScoreParams: words = ceil(nq / 64))
 // ---------------------------------------------------------------------------------------------
 struct ScoreParams {
     const uint64_t* asset;          // sorted
@@ -225,37 +229,66 @@ struct ScoreParams {
     uint32_t* n_assets;
     uint32_t entries, nq, words;
 };
-__global__ void score_kernel(const ScoreParams p) {
+struct ScoreManyParams {
+    const uint64_t* asset;          // sorted by (request, asset)
+    const uint32_t* req;            // sorted
+    const double* w;
+    const double* ws;
+    const uint32_t* q;
+    const double* idf_q;
+    const uint32_t* qbeg;
+    double* score;
+    uint32_t* order;
+    uint32_t* matches;
+    uint32_t* n_assets;             // [n_req]
+    uint32_t entries, nq, words;
+};
+template <class P>
+__global__ void score_kernel(const P p) {
     // HIP's __dadd_rn / __dmul_rn are plain `+` / `*`, and device code is compiled with -ffp-contract=fast: without this pragma
     // (and the file's -ffp-contract=off) `weighted + idf * sim` becomes ONE fused multiply-add -- a single rounding where the
     // reference's Python does two (found by tests/test_gpu_simprint_score.py: scores one ulp off)
 #pragma clang fp contract(off)
+    constexpr bool MANY = std::is_same<P, ScoreManyParams>::value;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned long long* mask = reinterpret_cast<unsigned long long*>(smem);
     const uint32_t T = blockDim.x, tid = threadIdx.x, lane = tid & 63;
     const uint32_t e = blockIdx.x * T + tid;
     const uint64_t a = e < p.entries ? p.asset[e] : 0;
-    const bool head = e < p.entries && (e == 0 || p.asset[e - 1] != a);
+    uint32_t r = 0;
+    bool head;
+    if constexpr (MANY) {
+        r = e < p.entries ? p.req[e] : 0;
+        head = e < p.entries && (e == 0 || p.asset[e - 1] != a || p.req[e - 1] != r);
+    } else {
+        head = e < p.entries && (e == 0 || p.asset[e - 1] != a);
+    }
     double total = 0.0, weighted = 0.0;
-    uint32_t end = e;
+    uint32_t end = e, qb = 0, qe = 0, wb = 0, we = 0;
     if (e < p.entries) p.order[e] = e;
     if (head) {
         // 1. the matched query simprints, ascending (the run is sorted by asset, stably: by query inside an asset)
-        for (uint32_t w = 0; w < p.words; ++w) mask[w * T + tid] = 0;
+        uint32_t words = p.words;
+        if constexpr (MANY) {
+            qb = p.qbeg[r]; qe = p.qbeg[r + 1];                   // (qe > qb: the request has entries)
+            wb = qb >> 6; we = ((qe - 1) >> 6) + 1;
+            words = we - wb;
+        }
+        for (uint32_t w = 0; w < words; ++w) mask[w * T + tid] = 0;
         constexpr int U = 8;
         uint32_t j = e;
         for (bool more = true; more;) {
-            uint64_t aa[U]; double ww[U], ss[U]; uint32_t qq[U];
+            uint64_t aa[U]; double ww[U], ss[U]; uint32_t qq[U], rr[U];
             for (int u = 0; u < U; ++u) {
                 const uint32_t jj = j + u < p.entries ? j + u : p.entries - 1;
-                aa[u] = p.asset[jj]; ww[u] = p.w[jj]; ss[u] = p.ws[jj]; qq[u] = p.q[jj];
+                aa[u] = p.asset[jj]; if constexpr (MANY) rr[u] = p.req[jj]; ww[u] = p.w[jj]; ss[u] = p.ws[jj]; qq[u] = p.q[jj];
             }
             int u = 0;
             for (; u < U; ++u) {
-                if (j + u >= p.entries || aa[u] != a) { more = false; break; }
+                if (j + u >= p.entries || aa[u] != a || (MANY && rr[u] != r)) { more = false; break; }
                 total = total + ww[u];
                 weighted = weighted + ss[u];
-                mask[(qq[u] >> 6) * T + tid] |= 1ull << (qq[u] & 63);
+                mask[((qq[u] >> 6) - wb) * T + tid] |= 1ull << (qq[u] & 63);
             }
             j += u;
         }
@@ -263,17 +296,37 @@ __global__ void score_kernel(const ScoreParams p) {
     }
     // 2. every unmatched query simprint, ascending.  The whole wave walks the queries together -- lane l holds the IDF of query
     //    64 w + l, each step broadcasts one of them from a register (v_readlane) -- so nothing in a head's chain of additions waits
-    //    for memory; lanes that head no run tag along.
+    //    for memory; lanes that head no run tag along.  With many requests the wave walks the union of its heads' ranges, and a
+    //    lane skips the query simprints outside its own range like matched ones.
     if (__ballot(head)) {
-        for (uint32_t w = 0; w < p.words; ++w) {
+        uint32_t lo = 0, hi = p.words;
+        if constexpr (MANY) {
+            lo = head ? wb : 0xFFFFFFFFu; hi = head ? we : 0;
+            for (int off = 32; off > 0; off >>= 1) {
+                const uint32_t l2 = __shfl_xor(lo, off), h2 = __shfl_xor(hi, off);
+                lo = l2 < lo ? l2 : lo;
+                hi = h2 > hi ? h2 : hi;
+            }
+        }
+        for (uint32_t w = lo; w < hi; ++w) {
             const uint32_t q0 = 64 * w, n = p.nq - q0 < 64 ? p.nq - q0 : 64;
-            // (bits of queries beyond nq are set: skipped like matched ones, so that the loop below has a fixed trip count)
-            const unsigned long long m = (head ? mask[w * T + tid] : ~0ULL) | (n < 64 ? ~0ULL << n : 0ULL);
+            unsigned long long m;
+            if constexpr (MANY) {
+                m = ~0ULL;
+                if (head && w >= wb && w < we) {
+                    m = mask[(w - wb) * T + tid];
+                    if (q0 < qb) m |= (1ull << (qb - q0)) - 1;     // before the request (w == wb: qb - q0 < 64)
+                    if (qe - q0 < 64) m |= ~0ULL << (qe - q0);      // behind it (qe > q0 here)
+                }
+            } else {
+                // (bits of queries beyond nq are set: skipped like matched ones, so that the loop below has a fixed trip count)
+                m = (head ? mask[w * T + tid] : ~0ULL) | (n < 64 ? ~0ULL << n : 0ULL);
+            }
             const double mine = lane < n ? p.idf_q[q0 + lane] : 0.0;
-            const int lo = __double2loint(mine), hi = __double2hiint(mine);
+            const int lo_w = __double2loint(mine), hi_w = __double2hiint(mine);
 #pragma unroll
             for (uint32_t i = 0; i < 64; ++i) {
-                const double x = __hiloint2double(__builtin_amdgcn_readlane(hi, i), __builtin_amdgcn_readlane(lo, i));
+                const double x = __hiloint2double(__builtin_amdgcn_readlane(hi_w, i), __builtin_amdgcn_readlane(lo_w, i));
                 total = (m >> i) & 1 ? total : total + x;
             }
         }
@@ -282,8 +335,12 @@ __global__ void score_kernel(const ScoreParams p) {
         p.score[e] = !head ? -1.0 : (total > 0.0 ? weighted / total : 0.0);       // (f64 division: correctly rounded by default)
         p.matches[e] = end - e;
     }
-    const unsigned long long heads = __ballot(head);
-    if (lane == 0 && heads) atomicAdd(p.n_assets, (uint32_t)__popcll(heads));
+    if constexpr (MANY) {
+        if (head) atomicAdd(&p.n_assets[r], 1u);
+    } else {
+        const unsigned long long heads = __ballot(head);
+        if (lane == 0 && heads) atomicAdd(p.n_assets, (uint32_t)__popcll(heads));
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -524,91 +581,6 @@ __global__ __launch_bounds__(BLOCK) void gather_kernel(const uint32_t* idx, cons
     if (t < entries) { const uint32_t i = idx[t]; asset_out[t] = asset_in[i]; entry_out[t] = entry_in[i]; }
 }
 
-// score_kernel with a run = (request, asset): the matched sum is the same walk; the unmatched sum runs over the run's own
-// request [qbeg[r], qbeg[r + 1]) in ascending order.  The wave walks the union of its heads' ranges (the same v_readlane
-// broadcast); a lane skips the query simprints outside its own range like matched ones.  Its LDS row holds the 64-bit words its
-// range touches, relative to the range's first word.
-// dynamic LDS: mask[words][threads] u64
-struct ScoreManyParams {
-    const uint64_t* asset;          // sorted by (request, asset)
-    const uint32_t* req;            // sorted
-    const double* w;
-    const double* ws;
-    const uint32_t* q;
-    const double* idf_q;
-    const uint32_t* qbeg;
-    double* score;
-    uint32_t* order;
-    uint32_t* matches;
-    uint32_t* n_assets;             // [n_req]
-    uint32_t entries, nq, words;
-};
-__global__ void score_many_kernel(const ScoreManyParams p) {
-#pragma clang fp contract(off)
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned long long* mask = reinterpret_cast<unsigned long long*>(smem);
-    const uint32_t T = blockDim.x, tid = threadIdx.x, lane = tid & 63;
-    const uint32_t e = blockIdx.x * T + tid;
-    const uint64_t a = e < p.entries ? p.asset[e] : 0;
-    const uint32_t r = e < p.entries ? p.req[e] : 0;
-    const bool head = e < p.entries && (e == 0 || p.asset[e - 1] != a || p.req[e - 1] != r);
-    double total = 0.0, weighted = 0.0;
-    uint32_t end = e, qb = 0, qe = 0, wb = 0, we = 0;
-    if (e < p.entries) p.order[e] = e;
-    if (head) {
-        qb = p.qbeg[r]; qe = p.qbeg[r + 1];                   // (qe > qb: the request has entries)
-        wb = qb >> 6; we = ((qe - 1) >> 6) + 1;
-        for (uint32_t w = 0; w < we - wb; ++w) mask[w * T + tid] = 0;
-        constexpr int U = 8;
-        uint32_t j = e;
-        for (bool more = true; more;) {
-            uint64_t aa[U]; double ww[U], ss[U]; uint32_t qq[U], rr[U];
-            for (int u = 0; u < U; ++u) {
-                const uint32_t jj = j + u < p.entries ? j + u : p.entries - 1;
-                aa[u] = p.asset[jj]; rr[u] = p.req[jj]; ww[u] = p.w[jj]; ss[u] = p.ws[jj]; qq[u] = p.q[jj];
-            }
-            int u = 0;
-            for (; u < U; ++u) {
-                if (j + u >= p.entries || aa[u] != a || rr[u] != r) { more = false; break; }
-                total = total + ww[u];
-                weighted = weighted + ss[u];
-                mask[((qq[u] >> 6) - wb) * T + tid] |= 1ull << (qq[u] & 63);
-            }
-            j += u;
-        }
-        end = j;
-    }
-    if (__ballot(head)) {
-        uint32_t lo = head ? wb : 0xFFFFFFFFu, hi = head ? we : 0;
-        for (int off = 32; off > 0; off >>= 1) {
-            const uint32_t l2 = __shfl_xor(lo, off), h2 = __shfl_xor(hi, off);
-            lo = l2 < lo ? l2 : lo;
-            hi = h2 > hi ? h2 : hi;
-        }
-        for (uint32_t w = lo; w < hi; ++w) {
-            const uint32_t q0 = 64 * w, n = p.nq - q0 < 64 ? p.nq - q0 : 64;
-            unsigned long long m = ~0ULL;
-            if (head && w >= wb && w < we) {
-                m = mask[(w - wb) * T + tid];
-                if (q0 < qb) m |= (1ull << (qb - q0)) - 1;     // before the request (w == wb: qb - q0 < 64)
-                if (qe - q0 < 64) m |= ~0ULL << (qe - q0);      // behind it (qe > q0 here)
-            }
-            const double mine = lane < n ? p.idf_q[q0 + lane] : 0.0;
-            const int lo_w = __double2loint(mine), hi_w = __double2hiint(mine);
-#pragma unroll
-            for (uint32_t i = 0; i < 64; ++i) {
-                const double x = __hiloint2double(__builtin_amdgcn_readlane(hi_w, i), __builtin_amdgcn_readlane(lo_w, i));
-                total = (m >> i) & 1 ? total : total + x;
-            }
-        }
-    }
-    if (e < p.entries) {
-        p.score[e] = !head ? -1.0 : (total > 0.0 ? weighted / total : 0.0);
-        p.matches[e] = end - e;
-    }
-    if (head) atomicAdd(&p.n_assets[r], 1u);
-}
-
 // after the sort by score: the request of every run head as the key of the regrouping sort (n_req behind every head: the
 // non-heads, score -1, stay at the end)
 __global__ __launch_bounds__(BLOCK) void head_key_kernel(const double* score, const uint32_t* order, const uint32_t* req, uint32_t n_req,
@@ -797,7 +769,7 @@ hipError_t queue_score(Buffers& b, const ScoreArgs& a, hipStream_t stream) {
     const uint32_t T = words <= 32 ? 256 : (words <= 64 ? 128 : 64);         // one LDS row of `words` u64 per thread, <= 64 KB per block
     if (words > MAX_QUERY_SIMPRINTS / 64) return hipErrorInvalidValue;
     ScoreParams sp{b.c_asset[1], b.score[1], b.ws, b.order[1], b.idf_q, b.score[0], b.order[0], b.matches, b.n_assets, a.entries, a.nq, words};
-    hipLaunchKernelGGL(score_kernel, dim3((a.entries + T - 1) / T), dim3(T), (size_t)words * T * 8, stream, sp);
+    hipLaunchKernelGGL(score_kernel<ScoreParams>, dim3((a.entries + T - 1) / T), dim3(T), (size_t)words * T * 8, stream, sp);
     bytes = b.temp_bytes;
     e = rocprim::radix_sort_pairs_desc(b.temp, bytes, b.score[0], b.score[1], b.order[0], b.order[1], a.entries, 0, 64, stream);
     if (e != hipSuccess) return e;
@@ -845,7 +817,7 @@ hipError_t queue_score_many(Buffers& b, const ManyBuffers& mb, const ScoreManyAr
     const uint32_t T = ma.words <= 32 ? 256 : (ma.words <= 64 ? 128 : 64);     // one LDS row of `words` u64 per thread, <= 64 KB per block
     ScoreManyParams sp{b.c_asset[0], mb.req[1], b.score[1], b.ws, b.order[1], b.idf_q, mb.qbeg, b.score[0], b.order[0], b.matches, mb.n_assets,
                        a.entries, a.nq, ma.words};
-    hipLaunchKernelGGL(score_many_kernel, dim3((a.entries + T - 1) / T), dim3(T), (size_t)ma.words * T * 8, stream, sp);
+    hipLaunchKernelGGL(score_kernel<ScoreManyParams>, dim3((a.entries + T - 1) / T), dim3(T), (size_t)ma.words * T * 8, stream, sp);
     // every request's assets in (-score, asset) order: stable by score (descending), then stable by request
     bytes = b.temp_bytes;
     e = rocprim::radix_sort_pairs_desc(b.temp, bytes, b.score[0], b.score[1], b.order[0], b.order[1], a.entries, 0, 64, stream);

@@ -180,10 +180,7 @@ class HipSimprintIndex:
             flat = [bytes(sp) for i in batched for sp in requests[i]]
             offsets = np.zeros(len(batched) + 1, dtype=np.uint32)
             offsets[1:] = np.cumsum([len(requests[i]) for i in batched])
-            count = max(1, limit * self.oversampling_factor)
-            radius = None
-            if count > MAX_K:
-                radius, count = self._radius_for(threshold), MAX_K
+            count, radius = self._count_radius(limit, threshold)
             dup_limit = DOC_FREQ_DUP_LIMIT if device_doc_freq else 0
             results, chunks, words, info = self._index.score_assets_many(_pack_simprints(flat), offsets, count, radius, threshold, limit,
                                                                          total_assets, dup_limit, detailed)
@@ -195,16 +192,34 @@ class HipSimprintIndex:
                 continue
             res, first, longest, c = out[i]
             if radius is not None and longest >= MAX_K:
-                raise ValueError(
-                    f"limit {limit} x oversampling {self.oversampling_factor} = {limit * self.oversampling_factor} neighbours per simprint exceeds the "
-                    f"{MAX_K} this backend returns, and a query simprint has that many stored chunks within the match threshold"
-                )
+                self._raise_max_k(limit)
             at = limit * first
             if detailed:
                 out[i] = self._unpack_device(r, res, chunks[at : at + c], words[at : at + c].astype(">u8").tobytes(), detailed)
             else:
                 out[i] = self._unpack_device(r, res, None, b"", detailed)
         return out
+
+    def _count_radius(self, limit, threshold):
+        # type: (int, float) -> tuple[int, int | None]
+        """
+        Neighbours to list per query simprint and the radius they lie within (``None``: the nearest ``count``).  The reference asks
+        usearch for ``limit x oversampling`` neighbours unbounded (``usearch_core.py:164``); the engine returns at most ``MAX_K`` per
+        query.  Only neighbours scoring >= threshold survive the filter, i.e. rows within a fixed radius: beyond the cap the request
+        becomes "every row within the match threshold".  A list that still fills the cap cannot be represented -- ``_raise_max_k``,
+        never truncate.
+        """
+        count = max(1, limit * self.oversampling_factor)
+        if count > MAX_K:
+            return MAX_K, self._radius_for(threshold)
+        return count, None
+
+    def _raise_max_k(self, limit):
+        # type: (int) -> None
+        raise ValueError(
+            f"limit {limit} x oversampling {self.oversampling_factor} = {limit * self.oversampling_factor} neighbours per simprint exceeds the "
+            f"{MAX_K} this backend returns, and a query simprint has that many stored chunks within the match threshold"
+        )
 
     def _radius_for(self, threshold):
         # type: (float) -> int
@@ -224,17 +239,10 @@ class HipSimprintIndex:
         (``doc_freq_fn=None``); otherwise the device's own frequencies (``device_doc_freq``).
         """
         queries = _pack_simprints(simprints)
-        count = max(1, limit * self.oversampling_factor)
-        radius = None
-        if count > MAX_K:
-            # (see _search_raw_host: beyond the cap the request becomes "every row within the match threshold")
-            radius, count = self._radius_for(threshold), MAX_K
+        count, radius = self._count_radius(limit, threshold)
         results, chunks, words, info = self._index.score_assets(queries, count, radius, threshold, limit, total_assets, dup_limit, detailed)
         if radius is not None and info[2] >= MAX_K:
-            raise ValueError(
-                f"limit {limit} x oversampling {self.oversampling_factor} = {limit * self.oversampling_factor} neighbours per simprint exceeds the "
-                f"{MAX_K} this backend returns, and a query simprint has that many stored chunks within the match threshold"
-            )
+            self._raise_max_k(limit)
         return self._unpack_device(simprints, results, chunks, np.ascontiguousarray(words).astype(">u8").tobytes() if detailed else b"", detailed)
 
     def _unpack_device(self, simprints, results, chunks, raw, detailed):
@@ -263,20 +271,10 @@ class HipSimprintIndex:
         owning ranks).  The neighbour search is the device's either way.
         """
         queries = _pack_simprints(simprints)
-        count = max(1, limit * self.oversampling_factor)
-        if count <= MAX_K:
-            key_words, ham, cnt = self._index.search_arrays(queries, count=count)
-        else:
-            # The reference asks usearch for `count` neighbours unbounded (usearch_core.py:164); the engine returns at most
-            # MAX_K per query.  Only neighbours scoring >= threshold survive the filter below, i.e. rows within a fixed
-            # radius: list exactly those.  A list that still fills the cap cannot be represented -- refuse, never truncate.
-            radius = self._radius_for(threshold)
-            key_words, ham, cnt = self._index.search_arrays(queries, count=MAX_K, max_hamming=radius)
-            if int(cnt.max(initial=0)) >= MAX_K and count > MAX_K:
-                raise ValueError(
-                    f"limit {limit} x oversampling {self.oversampling_factor} = {count} neighbours per simprint exceeds the "
-                    f"{MAX_K} this backend returns, and a query simprint has that many stored chunks within the match threshold"
-                )
+        count, radius = self._count_radius(limit, threshold)
+        key_words, ham, cnt = self._index.search_arrays(queries, count=count, max_hamming=radius)
+        if radius is not None and int(cnt.max(initial=0)) >= MAX_K:
+            self._raise_max_k(limit)
 
         # Threshold first, on the whole [queries x count] block at once: the reference walks every neighbour in
         # Python (usearch_core.py:175-196); most of an oversampled list fails the threshold.  Same arithmetic
