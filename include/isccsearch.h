@@ -339,6 +339,18 @@ int isccsearch_match_assets(isccsearch_handle* h, uint32_t nq, const uint32_t* u
                             uint64_t* out_keys, double* out_scores, uint32_t* out_count, uint8_t* out_types, double* out_type_scores,
                             uint32_t* out_unit_count);
 
+/* All unordered pairs of distinct rows of ONE table whose Hamming distance over their common prefix of p bytes is
+ * <= max_hamming[p] (p = 1..32; entry 0 unused; a negative entry: no pair with that prefix qualifies).  NPHD tables
+ * compare min(len_a, len_b) bytes, as isccsearch_search does; HAMMING tables compare their one length.
+ * On success (*out_total <= capacity): pairs in out_*[0 .. *out_total), key_a < key_b (128-bit keys compared as
+ * (hi, lo) unsigned), sorted ascending by (key_a, key_b).  out_keys_a / out_keys_b hold key_words words per pair.
+ * If *out_total > capacity: returns -ENOSPC with *out_total set and the outputs unspecified, so the caller can retry
+ * with exactly that capacity.  Device memory for the outputs: capacity x (16 * key_words + 6) bytes.
+ * No reference counterpart (the reference has no index-wide join). */
+int isccsearch_join_within(isccsearch_handle* h, uint32_t table, const int16_t* max_hamming /* [33] */,
+                           uint64_t capacity, uint64_t* out_keys_a, uint64_t* out_keys_b,
+                           uint32_t* out_hamming, uint16_t* out_prefix_bits, uint64_t* out_total);
+
 /* Multi-GPU building blocks (row-range shards, one process per GPU).
  * search_device: same search, results left in caller-provided DEVICE memory
  *   d_records[nq*k] (isccsearch_record), d_counts[nq]; queries must share one byte length.

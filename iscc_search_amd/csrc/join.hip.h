@@ -1,0 +1,223 @@
+// join.hip.h -- gfx950 device code of the index-wide self-join (isccsearch_join_within).
+//
+// Every unordered pair of distinct rows of one table whose Hamming distance over the common prefix is <= tau.  The host
+// launches one join_scan_kernel per pair of segments (one segment per code length); a pair of
+// segments (la <= lb bytes) compares W = ceil(la/8) words, the partial last word masked as the scans mask it.
+//
+// join_scan_kernel<W, MASK>: the XOR + popcount scan of kernels.hip.h with a tile of the table's own rows as its queries.
+//   grid = one block per group of TQ rows of side A (wave-uniform, in SGPRs); every block streams side B once, each lane
+//   holding 2*U rows per slab in VGPRs.  Within one segment (A == B) only pairs row_a < row_b count, and a block starts
+//   streaming at the slab of its first row: no block is launched without a pair to look at.
+//   Per (row, A row): acc = bias + popc(lo ^ a_lo) + popc(hi ^ a_hi) per word, acc < 2^31 <=> hamming <= tau; one v_min3
+//   folds two rows into the lane's minimum.  A wave whose minimum passes anywhere takes the (rare) emit path: it rescores
+//   its rows against the A rows re-read by scalar loads, drops the pairs that are not pairs (row_b <= row_a, rows past the
+//   end), counts the rest, takes ONE atomic slot range for the wave and writes (key_a < key_b, hamming, prefix bits) with
+//   vector stores.  Pairs past `capacity` are counted and not written.
+// Slabs are read up to the next multiple of the slab size: column capacities are multiples of ROW_ALIGN (2 048 rows), which
+// every slab size divides, so those reads stay inside the allocation (rows past n are dropped in the emit path).
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "kernels.hip.h"
+
+namespace isk {
+
+// What only the emit path reads, in device memory: as kernel arguments hipcc keeps them in SGPRs for the whole kernel,
+// next to the A rows, and spills.
+struct JoinEmit {
+    const uint64_t* keys_a;
+    const uint64_t* keys_b;
+    uint64_t n_a;
+    uint64_t capacity;            // pairs the outputs hold
+    unsigned long long* total;    // pairs found (all launches of one call add to it)
+    uint64_t* out_keys_a;         // [capacity * kw]
+    uint64_t* out_keys_b;
+    uint32_t* out_hamming;
+    uint16_t* out_prefix_bits;
+    uint32_t prefix_bits, kw;
+};
+struct JoinParams {
+    const uint64_t* col_a[4];     // side A: rows held in SGPRs, TQ per block
+    const uint64_t* col_b[4];     // side B: streamed
+    const JoinEmit* e;
+    uint64_t n_a, n_b;
+    uint64_t mask;                // of the last compared word
+    uint32_t tau, same;
+};
+
+// A rows per block (2*TQ*W SGPR operands: more spill them into VGPR lanes, read back by v_readlane in the hot loop) and
+// 16-byte loads per lane and column per slab
+template <int W> struct JoinCfg {
+    static constexpr int TQ = W == 1 ? 16 : 8;
+    static constexpr int U = TileCfg<W>::U;
+    static constexpr uint32_t SLAB = BLOCK * 2 * U;
+};
+template <int W> constexpr uint32_t join_rows_per_block() { return JoinCfg<W>::TQ; }
+template <int W> constexpr uint32_t join_slab_rows() { return JoinCfg<W>::SLAB; }
+
+template <int W, bool MASK>
+__global__ __launch_bounds__(BLOCK) void join_scan_kernel(const JoinParams p) {
+    constexpr int TQ = JoinCfg<W>::TQ, U = JoinCfg<W>::U;
+    constexpr uint32_t SLAB = JoinCfg<W>::SLAB;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint64_t a0 = (uint64_t)blockIdx.x * TQ;
+    const uint32_t bias = sgpr(0x7FFFFFFFu - p.tau);
+    const uint32_t mlo = sgpr((uint32_t)p.mask), mhi = sgpr((uint32_t)(p.mask >> 32));
+
+    // the block's A rows as SGPR operands; rows past n_a repeat the last one (the emit path drops their pairs)
+    uint32_t qlo[TQ][W], qhi[TQ][W];
+#pragma unroll
+    for (int q = 0; q < TQ; ++q) {
+        const uint64_t row = a0 + q < p.n_a ? a0 + q : p.n_a - 1;
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            const uint64_t v = p.col_a[w][row];
+            qlo[q][w] = sgpr((uint32_t)v);
+            qhi[q][w] = sgpr((uint32_t)(v >> 32));
+        }
+    }
+
+    // lane rows of slab s: s*SLAB + wave*(U*128) + u*128 + lane*2 + r (the layout of scan_kernel's tiles)
+    const uint32_t lrow = wave * (uint32_t)(U * 128) + lane * 2u;
+    const uint32_t s_begin = p.same ? (uint32_t)(a0 / SLAB) : 0u;
+    const uint32_t s_end = (uint32_t)((p.n_b + SLAB - 1) / SLAB);
+
+    auto load = [&](u32x4 (&v)[U][W], uint32_t s) {
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int w = 0; w < W; ++w)
+                v[u][w] = *reinterpret_cast<const u32x4*>(p.col_b[w] + (uint64_t)s * SLAB + lrow + u * 128);
+    };
+
+    // exact distance of lane row (u, r) to the A row (al, ah)
+    auto dist = [&](const u32x4 (&v)[U][W], int u, int r, const uint32_t (&al)[W], const uint32_t (&ah)[W]) {
+        uint32_t a = 0;
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            uint32_t x = (r ? v[u][w].z : v[u][w].x) ^ al[w], y = (r ? v[u][w].w : v[u][w].y) ^ ah[w];
+            if (MASK && w == W - 1) { x &= mlo; y &= mhi; }
+            a = bcnt(y, bcnt(x, a));
+        }
+        return a;
+    };
+
+    // rare: some pair of this wave is within tau.  Two passes over the A rows (re-read by scalar loads, so the loop need not
+    // be unrolled): count, one atomic per wave, write.
+    auto emit = [&](const u32x4 (&v)[U][W], uint32_t s) {
+        u32x4 r[U][W];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int w = 0; w < W; ++w) { r[u][w] = v[u][w]; asm volatile("" : "+v"(r[u][w])); }
+        const uint64_t base = (uint64_t)s * SLAB + lrow;
+        auto a_row = [&](uint64_t i, uint32_t (&al)[W], uint32_t (&ah)[W]) {
+#pragma unroll
+            for (int w = 0; w < W; ++w) {
+                const uint64_t x = p.col_a[w][i];
+                al[w] = (uint32_t)x; ah[w] = (uint32_t)(x >> 32);
+            }
+        };
+        auto is_pair = [&](uint64_t i, uint64_t j, uint32_t h) { return h <= p.tau && j < p.n_b && (!p.same || j > i); };
+        const JoinEmit& e = *p.e;
+        uint32_t c = 0;
+        const uint64_t a_end = a0 + TQ < p.n_a ? a0 + TQ : p.n_a;
+#pragma unroll 1
+        for (uint64_t i = a0; i < a_end; ++i) {
+            uint32_t al[W], ah[W];
+            a_row(i, al, ah);
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int rr = 0; rr < 2; ++rr) c += is_pair(i, base + u * 128 + rr, dist(r, u, rr, al, ah)) ? 1u : 0u;
+        }
+        // wave-inclusive prefix of the counts; lane 63 holds the wave's total
+        uint32_t incl = c;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t t = (uint32_t)__shfl_up((int)incl, d, 64);
+            if (lane >= (uint32_t)d) incl += t;
+        }
+        const uint32_t wave_total = (uint32_t)__shfl((int)incl, 63, 64);
+        if (wave_total == 0) return;               // only non-pairs passed (the diagonal, rows past the end)
+        uint32_t lo = 0, hi = 0;
+        if (lane == 0) {
+            const unsigned long long b = atomicAdd(e.total, (unsigned long long)wave_total);
+            lo = (uint32_t)b; hi = (uint32_t)(b >> 32);
+        }
+        uint64_t slot = ((uint64_t)(uint32_t)__shfl((int)hi, 0, 64) << 32 | (uint32_t)__shfl((int)lo, 0, 64)) + (incl - c);
+        if (c == 0) return;
+        const uint32_t kw = e.kw;
+#pragma unroll 1
+        for (uint64_t i = a0; i < a_end; ++i) {
+            uint32_t al[W], ah[W];
+            a_row(i, al, ah);
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int rr = 0; rr < 2; ++rr) {
+                    const uint64_t j = base + u * 128 + rr;
+                    const uint32_t h = dist(r, u, rr, al, ah);
+                    if (!is_pair(i, j, h)) continue;
+                    if (slot < e.capacity) {
+                        uint64_t ka_hi = kw == 2 ? e.keys_a[i * 2] : 0, ka_lo = e.keys_a[i * kw + kw - 1];
+                        uint64_t kb_hi = kw == 2 ? e.keys_b[j * 2] : 0, kb_lo = e.keys_b[j * kw + kw - 1];
+                        if (kb_hi < ka_hi || (kb_hi == ka_hi && kb_lo < ka_lo)) {
+                            uint64_t t = ka_hi; ka_hi = kb_hi; kb_hi = t;
+                            t = ka_lo; ka_lo = kb_lo; kb_lo = t;
+                        }
+                        if (kw == 2) { e.out_keys_a[slot * 2] = ka_hi; e.out_keys_b[slot * 2] = kb_hi; }
+                        e.out_keys_a[slot * kw + kw - 1] = ka_lo;
+                        e.out_keys_b[slot * kw + kw - 1] = kb_lo;
+                        e.out_hamming[slot] = h;
+                        e.out_prefix_bits[slot] = (uint16_t)e.prefix_bits;
+                    }
+                    ++slot;
+                }
+        }
+    };
+
+    auto process = [&](const u32x4 (&v)[U][W], uint32_t s) {
+        uint32_t m = 0xFFFFFFFFu;
+#pragma unroll
+        for (int q = 0; q < TQ; ++q) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                uint32_t a0v, a1v;
+#pragma unroll
+                for (int w = 0; w < W; ++w) {
+                    uint32_t x0 = v[u][w].x ^ qlo[q][w], y0 = v[u][w].y ^ qhi[q][w];
+                    uint32_t x1 = v[u][w].z ^ qlo[q][w], y1 = v[u][w].w ^ qhi[q][w];
+                    if (MASK && w == W - 1) { x0 &= mlo; y0 &= mhi; x1 &= mlo; y1 &= mhi; }
+                    if (w == 0) { a0v = bcnt_s(x0, bias); a1v = bcnt_s(x1, bias); }
+                    else { a0v = pin(bcnt_v(x0, a0v)); a1v = pin(bcnt_v(x1, a1v)); }
+                    a0v = bcnt_v(y0, a0v);
+                    a1v = bcnt_v(y1, a1v);
+                    if (W > 1 && w + 1 < W) { a0v = pin(a0v); a1v = pin(a1v); }
+                }
+                m = min3u(m, a0v, a1v);
+            }
+        }
+        if (__ballot((int32_t)m >= 0)) emit(v, s);
+    };
+
+    if (s_begin >= s_end) return;
+    u32x4 va[U][W], vb[U][W];
+    uint32_t s = s_begin;
+    load(va, s);
+    for (;;) {
+        const uint32_t s1 = s + 1;
+        if (s1 < s_end) load(vb, s1);
+        process(va, s);
+        if (s1 >= s_end) break;
+        const uint32_t s2 = s1 + 1;
+        if (s2 < s_end) load(va, s2);
+        process(vb, s1);
+        if (s2 >= s_end) break;
+        s = s2;
+    }
+}
+
+}  // namespace isk

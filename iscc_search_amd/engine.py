@@ -7,6 +7,7 @@ This is the thinnest layer above ``include/isccsearch.h``; the reference-shaped 
 """
 
 import ctypes
+import errno
 import threading
 
 import numpy as np
@@ -376,6 +377,34 @@ class HipTable:
         if nq:
             _lib.check(self.engine._lib.isccsearch_search_within(self.engine.handle, self.id, nq, _lib.ptr(q_words), _lib.ptr(q_nbytes), k, int(max_hamming), *addr))
         return out
+
+    def join_within(self, max_hamming_by_prefix, max_pairs):
+        # type: (object, int) -> tuple
+        """
+        Every unordered pair of distinct rows within ``max_hamming_by_prefix[p]`` bits over their common prefix of p bytes
+        (33 entries, p = 1..32; a negative entry excludes that prefix): ``(keys_a, keys_b, hamming, prefix_bits)``, key_a < key_b,
+        sorted by (key_a, key_b).  One library call with room for ``min(max_pairs, 2^20)`` pairs, retried once with exactly
+        the total when more were found.  More than ``max_pairs`` pairs raise ValueError: the cap is never applied silently.
+        """
+        mh = np.ascontiguousarray(max_hamming_by_prefix, dtype=np.int16)
+        if mh.shape != (_lib.MAX_BYTES + 1,):
+            raise ValueError(f"max_hamming_by_prefix must have {_lib.MAX_BYTES + 1} entries (prefix bytes 0..{_lib.MAX_BYTES})")
+        lib = self.engine._lib
+        total = ctypes.c_uint64()
+        capacity = min(int(max_pairs), 1 << 20)
+        for attempt in range(2):
+            kshape = (capacity, 2) if self.key_words == 2 else (capacity,)
+            out = (np.empty(kshape, np.uint64), np.empty(kshape, np.uint64), np.empty(capacity, np.uint32), np.empty(capacity, np.uint16))
+            rc = lib.isccsearch_join_within(self.engine.handle, self.id, _lib.ptr(mh), capacity, *(_lib.ptr(a) for a in out), ctypes.byref(total))
+            n = int(total.value)
+            if n > max_pairs:
+                raise ValueError(f"{n} pairs exceed max_pairs={max_pairs}")
+            if rc == -errno.ENOSPC and attempt == 0:
+                capacity = n
+                continue
+            _lib.check(rc)
+            return tuple(a[:n] for a in out)
+        raise RuntimeError("isccsearch_join_within: the retry with the reported total did not fit")
 
     def doc_freq(self, q_words, q_nbytes=None, dup_limit=1000):
         # type: (np.ndarray, np.ndarray | None, int) -> np.ndarray

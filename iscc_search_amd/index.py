@@ -160,6 +160,43 @@ def _merge_similarity(aggregated, unit_type, keys, scores):
             slot.setdefault(unit_type, 0.0)
 
 
+def _confidence_total(confident, exp):
+    # type: (Dict[str, float], int) -> float
+    """Confidence-weighted total of the unit scores at or above the threshold (``usearch/index.py:818-826``): sum(s^exp) / sum(s)."""
+    weight_sum = sum(confident.values())
+    return sum(s**exp for s in confident.values()) / weight_sum if weight_sum > 0 else 0.0
+
+
+def _unit_max_hamming(thr, instance=False):
+    # type: (float, bool) -> np.ndarray
+    """
+    max_hamming[p] for p = 1..32 prefix bytes: the largest h whose unit score ``max(0, 1 - float64(float32(h) / float32(8p)))``
+    -- the float operations of ``_search_units`` -- is >= ``thr``; -1 where no h is.  INSTANCE units match by prefix equality,
+    scoring 1.0: 0 everywhere (-1 when even 1.0 is below the threshold).  Entry 0 is unused (-1).
+    """
+    out = np.full(_lib.MAX_BYTES + 1, -1, dtype=np.int16)
+    if instance:
+        out[1:] = 0 if 1.0 >= thr else -1
+        return out
+    score, _ = _unit_score_tables(1)
+    score = score.reshape(_lib.MAX_BYTES + 1, 257)
+    for p in range(1, _lib.MAX_BYTES + 1):
+        ok = np.nonzero(score[p, : 8 * p + 1] >= thr)[0]
+        # the score falls with h: the confident distances are 0..h_max
+        out[p] = int(ok[-1]) if len(ok) else -1
+    return out
+
+
+@dataclass
+class DuplicatePair:
+    """One near-duplicate pair of ``find_duplicates``: ``score`` and ``types`` as ``search_assets`` from either asset lists the other."""
+
+    iscc_id_a: str      # the smaller key
+    iscc_id_b: str
+    score: float
+    types: Dict[str, float]   # the confident unit scores, in the unit order of asset a
+
+
 def _rank_aggregated(aggregated, thr, exp, query_iscc_id, limit):
     # type: (Dict[int, Dict[str, float]], float, int, Optional[str], int) -> list
     """``usearch/index.py:808-839``: threshold, confidence-weighted total, self-exclusion, stable sort, cut: [(key, total, unit_scores)]."""
@@ -168,9 +205,7 @@ def _rank_aggregated(aggregated, thr, exp, query_iscc_id, limit):
         confident = {t: s for t, s in unit_scores.items() if s >= thr}
         if not confident:
             continue
-        weight_sum = sum(confident.values())
-        total = sum(s**exp for s in confident.values()) / weight_sum if weight_sum > 0 else 0.0
-        scored.append((key, total, unit_scores))
+        scored.append((key, _confidence_total(confident, exp), unit_scores))
     if query_iscc_id:
         qkey = codec.iscc_id_to_int(query_iscc_id)
         scored = [r for r in scored if r[0] != qkey]
@@ -456,6 +491,53 @@ class HipIndex:
         if query_iscc_id:
             chunk_matches = [m for m in chunk_matches if m.iscc_id != query_iscc_id]
         return IsccSearchResult(query=query, global_matches=matches, chunk_matches=chunk_matches)
+
+    # -- near-duplicates -------------------------------------------------------------------------
+    def find_duplicates(self, min_score=None, unit_types=None, max_pairs=1_000_000):
+        # type: (Optional[float], Optional[List[str]], int) -> List[DuplicatePair]
+        """
+        Every pair of assets {a, b} that ``search_assets(IsccQuery(iscc_id=a), limit=len(index))`` would list as b's match,
+        with that score and the confident part of b's unit scores -- found by ONE self-join per unit table on the device
+        (``HipTable.join_within``) instead of a search per asset.  Units are compared as they were indexed.  Pairs are
+        aggregated over the unit types both assets carry, kept when one unit is confident (and the score is >= ``min_score``,
+        if given), and ordered by score descending, then (key_a, key_b).  ``unit_types`` restricts the unit tables joined.
+        More than ``max_pairs`` unit pairs in one table raise ValueError.
+        """
+        thr, exp = self._opts.match_threshold_units, self._opts.confidence_exponent
+        with self._lock:
+            tables = {t: idx for t, idx in self._unit_tables.items() if unit_types is None or t in unit_types}
+            asset_units = dict(self._asset_units)
+        pair_scores = {}  # type: Dict[tuple, Dict[str, float]]
+        for unit_type in sorted(tables):
+            table = tables[unit_type]._table
+            if not hasattr(table, "join_within"):
+                raise NotImplementedError("find_duplicates needs a single-GPU engine: pairs across shards need their rows exchanged")
+            instance = unit_type.startswith("INSTANCE_")
+            keys_a, keys_b, ham, pbits = table.join_within(_unit_max_hamming(thr, instance), max_pairs)
+            if instance:
+                scores = [1.0] * len(ham)
+            else:
+                dist = ham.astype(np.float32) / pbits.astype(np.float32)
+                scores = np.maximum(0.0, 1.0 - dist.astype(np.float64)).tolist()
+            for a, b, score in zip(keys_a.tolist(), keys_b.tolist(), scores):
+                ua, ub = asset_units.get(a), asset_units.get(b)
+                # a row an update left behind in a table of a type the asset no longer carries is not compared
+                if ua is None or ub is None or unit_type not in ua or unit_type not in ub:
+                    continue
+                pair_scores.setdefault((a, b), {})[unit_type] = score
+        out = []
+        for (a, b), by_type in pair_scores.items():
+            # the unit order of asset a, as search_assets by a's iscc_id merges them
+            confident = {t: by_type[t] for t in asset_units[a] if t in by_type and by_type[t] >= thr}
+            if not confident:
+                continue
+            score = min(1.0, _confidence_total(confident, exp))
+            if min_score is not None and score < min_score:
+                continue
+            out.append((a, b, score, confident))
+        out.sort(key=lambda r: (-r[2], r[0], r[1]))
+        realm = self._realm_id or 0
+        return [DuplicatePair(codec.iscc_id_from_int(a, realm), codec.iscc_id_from_int(b, realm), score, types) for a, b, score, types in out]
 
     # -- bulk search -------------------------------------------------------------------------------
     def _prepare_many(self, queries):
@@ -1111,6 +1193,21 @@ class HipIndexManager:
                 raise
             i = int(m.group(1))
             raise FileNotFoundError(f"queries[{i}]: Asset '{queries[i].iscc_id}' not found in index '{index_name}'") from e
+
+    def find_duplicates(self, index_name, min_score=None, unit_types=None, max_pairs=1_000_000):
+        # type: (str, Optional[float], Optional[List[str]], int) -> List[DuplicatePair]
+        """Near-duplicate asset pairs of one index (``HipIndex.find_duplicates``).  Not available on a sharded index."""
+        if self.devices > 1:
+            raise NotImplementedError(
+                f"find_duplicates is not available on a sharded index (devices={self.devices}): pairs across shards need the rows "
+                f"exchanged between the GPUs"
+            )
+        return self._guarded("find_duplicates", self._find_duplicates, index_name, min_score, unit_types, max_pairs)
+
+    def _find_duplicates(self, index_name, min_score=None, unit_types=None, max_pairs=1_000_000):
+        with self._lock:
+            idx = self._index(index_name)
+        return idx.find_duplicates(min_score=min_score, unit_types=unit_types, max_pairs=max_pairs)
 
     def close(self):
         # type: () -> None
