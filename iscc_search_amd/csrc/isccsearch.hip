@@ -72,6 +72,18 @@ using iskhost::KeyHash;
 using iskhost::KeyMap;
 using iskhost::Loc;
 
+// the backoff of a speculation hint: the hint serves batches of ONE k, and a miss makes the next `penalty` batches of its class take
+// the ordinary path (1, 3, 7, 15 for misses in a row)
+struct HintBackoff {
+    uint32_t k = 0, skip = 0, penalty = 0;
+    bool ready(uint32_t want_k) {                       // speculate now?
+        if (k != want_k) return false;
+        if (skip) { skip -= 1; return false; }
+        return true;
+    }
+    void miss() { penalty = std::min<uint32_t>(2 * penalty + 1, 15); skip = penalty - 1; }      // (the rerun that follows is the first skipped batch)
+};
+
 struct Segment {
     uint32_t nbytes = 0, W = 0;
     uint64_t n = 0, cap = 0;
@@ -87,21 +99,15 @@ struct Segment {
     // one tries ONE collect pass under it (+ margin) before the bootstrap / level / pick chain (search_locked).  One hint per
     // batch-size class (the worst k-th distance of 100 queries lies a bit or two above that of one); a hint decays by one bit per
     // hit towards what the batches need (a near-duplicate query between two ordinary ones does not pull it down to its own
-    // distance); a miss makes the next `penalty` batches of the class take the ordinary path (1, 3, 7, 15 for misses in a row).
-    struct SpecHint {
-        uint32_t k = 0, tau = 0, skip = 0, penalty = 0;
-        bool ready(uint32_t want_k) {                       // speculate now?
-            if (k != want_k) return false;
-            if (skip) { skip -= 1; return false; }
-            return true;
-        }
+    // distance); a miss backs off (HintBackoff).
+    struct SpecHint : HintBackoff {
+        uint32_t tau = 0;
         // margin above the worst k-th distance the last batch ended at.  The k-th distance of a query concentrates as k grows (it is an
         // order statistic k deep into the distribution), and so does its maximum over a batch: from k = 64 one bit is enough -- and a bit
         // is worth a factor ~2.6 in candidates at these distances (10 M x 64-bit, 512 queries, k = 400: 3 480 candidates per query
         // under + 2, profiles/r04_candidate_path.txt).  Small k keeps two: its k-th distance wanders more and a bit costs little there.
         static uint32_t margin(uint32_t want_k) { return want_k >= 64 ? 1u : 2u; }
         void hit(uint32_t worst) { penalty = 0; tau = std::min<uint32_t>(std::max<uint32_t>(worst + margin(k), tau ? tau - 1 : 0), 8 * ISCCSEARCH_MAX_BYTES); }
-        void miss() { penalty = std::min<uint32_t>(2 * penalty + 1, 15); skip = penalty - 1; }      // (the rerun that follows is the first skipped batch)
         void seed(uint32_t new_k, uint32_t worst) { k = new_k; tau = std::min<uint32_t>(worst + margin(new_k), 8 * ISCCSEARCH_MAX_BYTES); }
     } spec[12][5];
     // one hint per batch-size class (1 | 2-3 | 4-7 | ... | 1024) and per compared PREFIX length (8 / 16 / 24 / 32 bytes and the odd ones:
@@ -115,22 +121,26 @@ struct Table {
     Segment seg[ISCCSEARCH_MAX_BYTES + 1];
     // Tables of SEVERAL code lengths (an ISCC-UNIT index): the hint is the worst k-th NPHD (distance / compared bits) the previous
     // batch of that size and query length ended at; every segment then lists its rows within (ratio + 1/32) x its compared bits.
-    struct RatioHint {
-        uint32_t k = 0, skip = 0, penalty = 0;
+    struct RatioHint : HintBackoff {
         double ratio = 0.0;
-        bool ready(uint32_t want_k) {
-            if (k != want_k) return false;
-            if (skip) { skip -= 1; return false; }
-            return true;
-        }
         void hit(double worst) { penalty = 0; ratio = std::max(worst, ratio - 1.0 / 256.0); }
-        void miss() { penalty = std::min<uint32_t>(2 * penalty + 1, 15); skip = penalty - 1; }
         void seed(uint32_t new_k, double worst) { k = new_k; ratio = worst; }
     } mspec[12][5];
     RatioHint& mhint(uint32_t nq, uint32_t len) { return mspec[nq ? 32 - __builtin_clz(nq) : 0][len % 8 == 0 && len >= 8 && len <= 32 ? len / 8 : 0]; }
     bool indexed = false;
     KeyMap index;
-    uint64_t total = 0;
+    uint64_t total = 0;     // rows over all segments
+    uint32_t segments() const {     // non-empty segments: the jobs of a batch
+        uint32_t n = 0;
+        for (uint32_t b = 1; b <= ISCCSEARCH_MAX_BYTES; ++b) n += seg[b].n ? 1 : 0;
+        return n;
+    }
+    Segment* sole_segment() {       // the only non-empty segment, or nullptr
+        Segment* one = nullptr;
+        for (uint32_t b = 1; b <= ISCCSEARCH_MAX_BYTES; ++b)
+            if (seg[b].n) { if (one) return nullptr; one = &seg[b]; }
+        return one;
+    }
 };
 
 constexpr uint32_t QB_MAX = 1024;        // queries per pipeline run
@@ -536,7 +546,7 @@ struct Batch {
     bool ratio_starts_self = false;   // ... as the START of each segment's single self-tightening pass (large batches) instead of a fixed radius
     size_t pq_off = 0;                  // this batch's slice of the pinned query staging buffer (words)
     uint32_t* d_flags = nullptr;        // overflow flags [jobs][nq_pad]; the caller may place them inside its result block
-    const uint32_t* h_flags = nullptr;  // where the host finds them after the copy (default: h->p_flags)
+    const uint32_t* h_flags = nullptr;  // ... and where the host finds them after ITS copy (nullptr: copy_flags() brings them to h->p_flags)
     uint32_t nq_pad = 0, groups = 0, cap = 0, P = 0;
     size_t sel_lds = 0;
     bool multi = false;
@@ -925,21 +935,29 @@ struct Batch {
         return 0;
     }
 
-    // queue the overflow flags for the host (pinned); valid after the next stream synchronisation
+    // queue the overflow flags for the host (pinned); valid after the next stream synchronisation.  Flags that ride in the
+    // caller's result block (h_flags set) come with its copy instead.
     int copy_flags() {
-        if (jobs.empty()) return 0;
+        if (jobs.empty() || h_flags) return 0;
         int rc;
         if ((rc = h->p_flags.ensure(flag_words()))) return rc;
         HIPOK(hipMemcpyAsync(h->p_flags.p, d_flags, flag_words() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-        h_flags = h->p_flags.p;
         return 0;
     }
     // flags of the padding queries are never written: look at the real ones only
-    bool flagged(size_t ji, uint32_t q) const { return h_flags[ji * nq_pad + q] != 0; }
+    bool flagged(size_t ji, uint32_t q) const { return (h_flags ? h_flags : h->p_flags.p)[ji * nq_pad + q] != 0; }
     bool any_flag() const {
         for (size_t ji = 0; ji < jobs.size(); ++ji)
             for (uint32_t q = 0; q < nq; ++q) if (flagged(ji, q)) return true;
         return false;
+    }
+    // a range-limited or hinted pass over `rows` rows is the exact answer when no list overflowed and every query found
+    // min(k, rows) rows under its threshold (its k nearest are then among them)
+    bool complete(const uint32_t* cnt, uint64_t rows) const {
+        if (any_flag()) return false;
+        const uint32_t need = (uint32_t)std::min<uint64_t>(k, rows);
+        for (uint32_t q = 0; q < nq; ++q) if (cnt[q] < need) return false;
+        return true;
     }
 
     // exact fallback for every flagged (job, query): full histogram -> exact threshold -> collect into
@@ -1051,22 +1069,48 @@ struct Batch {
         return begin(hq);
     }
 
-    // everything up to final device-resident results (used by the device variant and multi-segment tables)
-    int run_to_device(const uint64_t* hq) {
+    // Everything after begin(): the flags (and what `queue_results` queues) reach the host behind one synchronisation, an
+    // overflowed single pass is redone by retry_with_levels(), fix() answers what is still flagged, several lists are merged.
+    // One segment: the results travel with the flags, and again after fix().  Several segments: the lists are complete before
+    // the merge, and the merged results leave after it.  Without `queue_results` (device-resident results) nothing follows the
+    // last step, and a batch without jobs is not synchronised at all.
+    int finish(const uint64_t* hq, const std::function<int()>& queue_results = nullptr) {
+        if (jobs.empty() && !queue_results) return 0;
+        const bool with_flags = queue_results && !multi;
+        auto settle = [&]() -> int {
+            int rs;
+            if ((rs = copy_flags())) return rs;
+            if (with_flags && (rs = queue_results())) return rs;
+            HIPOK(hipStreamSynchronize(h->stream));
+            return 0;
+        };
         int rc;
-        if ((rc = begin(hq))) return rc;
-        if (jobs.empty()) return 0;
-        if ((rc = copy_flags())) return rc;
-        HIPOK(hipStreamSynchronize(h->stream));
+        if ((rc = settle())) return rc;
         if (used_self && any_flag()) {
             if ((rc = retry_with_levels(hq))) return rc;
-            if ((rc = copy_flags())) return rc;
+            if ((rc = settle())) return rc;
+        }
+        const bool fixed = any_flag();
+        if (fixed && (rc = fix())) return rc;
+        if ((rc = merge())) return rc;
+        if (queue_results && (multi || fixed)) {
+            if ((rc = queue_results())) return rc;
             HIPOK(hipStreamSynchronize(h->stream));
         }
-        if (any_flag() && (rc = fix())) return rc;
-        return merge();
+        return 0;
     }
 };
+
+// where a batch's lists ended -- the worst k-th distance, read off the records or off `kth` (the lists' last distances) -- is
+// where the next small batch of the class starts (+ a margin: P(h <= t) grows ~3x per step at these distances, so it costs a
+// handful of candidates and absorbs the spread between queries): hit() after a speculative pass that held, seed() after any other
+void record_hint(Segment::SpecHint& hint, bool spec_ok, uint32_t nq, uint32_t k, const uint32_t* cnt, const isk::Record* rec, const uint32_t* kth) {
+    uint32_t worst = 0;
+    for (uint32_t i = 0; i < nq; ++i)
+        if (cnt[i]) worst = std::max<uint32_t>(worst, kth ? kth[i] : rec[(size_t)i * k + cnt[i] - 1].hamming);
+    if (spec_ok) hint.hit(worst);
+    else hint.seed(k, worst);
+}
 
 void unpack_range(const isk::Record* rec, const uint32_t* cnt, uint32_t q_begin, uint32_t q_end, uint32_t k, int key_words,
                   const uint32_t* dest_index, uint64_t* out_keys, uint32_t* out_h, uint16_t* out_p, uint32_t* out_c);
@@ -1840,8 +1884,7 @@ static int search_locked(isccsearch_handle* h, uint32_t table, uint32_t nq, cons
         if ((rc = h->p_block.ensure(block_bytes))) return rc;
         const isk::Record* const p_rec = reinterpret_cast<const isk::Record*>(h->p_block.p);
         uint32_t* const p_cnt = reinterpret_cast<uint32_t*>(h->p_block.p + rec_bytes);
-        uint32_t segments = 0;
-        for (uint32_t b = 1; b <= ISCCSEARCH_MAX_BYTES; ++b) segments += t.seg[b].n ? 1 : 0;
+        const uint32_t segments = t.segments();
         const bool one_copy = segments == 1 && !out_freq;   // flags ride in the block: results leave in ONE copy
         // ... or in none: select_kernel writes a small block straight into the pinned mirror (page-locked memory is mapped
         // into the device's address space), so the host only synchronises.  A device->host copy costs ~25 us of queue
@@ -1855,23 +1898,41 @@ static int search_locked(isccsearch_handle* h, uint32_t table, uint32_t nq, cons
         batch.radius = radius;
         if (sink) { if (!sink->exact) batch.d_out_rows = h->d_sp_rows.p + (size_t)pos * k; batch.d_out_kth = d_cnt + m + flag_slots; }
         if (one_copy) { batch.d_flags = d_cnt + m; batch.h_flags = p_cnt + m; }
-        // (see the speculative branch below) eligible: an ordinary top-k search of a small batch over ONE segment that has been
-        // searched with this k before
-        Segment* spec_seg = nullptr;
-        if (segments == 1)
-            for (uint32_t b = 1; b <= ISCCSEARCH_MAX_BYTES; ++b) if (t.seg[b].n) spec_seg = &t.seg[b];
+        // Speculation: ONE pass under where an earlier batch of this size and query length ended, verified by one look at its
+        // lists; a miss (a list overflowed, a query came up short) sends the batch through the ordinary path -- nothing is ever
+        // returned unverified.
+        //   radius     SMALL batches over one segment.  One query costs boot + level + pick + collect + select: five launches for
+        //              what is one pass over the rows (0.22 ms against a 0.13 ms pass).  The k-th distance of similar queries over
+        //              the same rows hardly moves, so the pass is first tried as a RANGE-LIMITED search under the distance the
+        //              previous search of this segment ended at (+ 2): radius_init + collect + select.  It is exact whenever every
+        //              query finds k rows within that radius (its k nearest are then among them).
+        //   self_hint  LARGER batches over one segment keep their single self-tightening pass (one radius for hundreds of queries
+        //              admits several times the candidates of per-query thresholds) but START it under the hint instead of a
+        //              bootstrap sample's threshold: no sample kernel, no flood of candidates in the first steps.  Same check.
+        //   ratio      SEVERAL segments (an index of mixed code lengths -- what an ISCC-UNIT index is).  The ordinary path costs
+        //              boot + level + pick + collect + select per segment and two synchronisations (0.62 ms for one 256-bit query
+        //              over 4 x 25 M rows); here every segment lists its rows within (hint + 1/32) x compared bits (radius_init +
+        //              collect + select each), the lists are merged and ONE synchronisation brings results and flags.  The answer
+        //              stands if no list overflowed, every query has k rows and its k-th NPHD is <= hint + 1/32: a row outside a
+        //              segment's radius lies strictly beyond that ratio, a row inside it but not listed has k nearer rows of its own
+        //              segment before it.
+        enum class Spec { none, radius, self_hint, ratio } spec = Spec::none;
+        // radius / self_hint: an ordinary top-k search over ONE segment that has been searched with this k before
+        Segment* const spec_seg = t.sole_segment();
         // (a segment small enough for the one-launch search -- Batch::tiny -- has nothing to gain from a radius: it is exact in that launch either way)
         const bool one_launch = spec_seg && h->tiny_rows && spec_seg->n <= h->tiny_rows && spec_seg->n < h->mfma_min_rows && spec_seg->n <= h->candidate_cap;
         const bool hintable = spec_seg && radius < 0 && !out_freq && one_copy && k <= spec_seg->n && !one_launch;
         const bool small_batch = hintable && m <= h->spec_max_queries;
-        const bool hint_ready = hintable && h->speculate && !h->spec_suppress && (small_batch || h->self_hint) && spec_seg->hint(m, len).ready(k);
-        const bool speculate = hint_ready && small_batch;
-        if (speculate) batch.radius = (int)spec_seg->hint(m, len).tau;
-        // LARGER batches keep their single self-tightening pass (one radius for hundreds of queries admits several times the
-        // candidates of per-query thresholds) but START it under the hint instead of a bootstrap sample's threshold: no sample
-        // kernel, no flood of candidates in the first steps.  Verified the same way (`used_hint`).
-        if (hint_ready && !small_batch) batch.self_hint = (int)spec_seg->hint(m, len).tau;
-        bool spec_ok = false;
+        if (hintable && h->speculate && !h->spec_suppress && (small_batch || h->self_hint) && spec_seg->hint(m, len).ready(k)) {
+            if (small_batch) { spec = Spec::radius; batch.radius = (int)spec_seg->hint(m, len).tau; }
+            else { spec = Spec::self_hint; batch.self_hint = (int)spec_seg->hint(m, len).tau; }
+        }
+        const bool mhintable = segments > 1 && radius < 0 && !out_freq && (m <= h->spec_max_queries || h->self_hint) && k <= t.total;
+        if (mhintable && h->speculate && !h->spec_suppress && t.mhint(m, len).ready(k)) {
+            spec = Spec::ratio;
+            batch.radius_ratio = t.mhint(m, len).ratio + 1.0 / 32.0;      // the margin: 2 bits of 64, 8 of 256
+            batch.ratio_starts_self = m > h->spec_max_queries;             // larger batches: each segment's single pass STARTS under it
+        }
         auto copy_results = [&]() -> int {
             if (out_freq) {
                 // only the distinct-asset count of every list leaves the device
@@ -1904,21 +1965,6 @@ static int search_locked(isccsearch_handle* h, uint32_t table, uint32_t nq, cons
             HIPOK(hipMemcpyAsync(h->p_block.p, h->d_block.p, bytes, hipMemcpyDeviceToHost, h->stream));
             return 0;
         };
-        // SEVERAL segments (an index of mixed code lengths -- what an ISCC-UNIT index is): the same speculation per segment.  The
-        // ordinary path costs boot + level + pick + collect + select per segment and two synchronisations (0.62 ms for one 256-bit
-        // query over 4 x 25 M rows); here every segment lists its rows within (hint + 1/32) x compared bits (radius_init + collect +
-        // select each), the lists are merged and ONE synchronisation brings results and flags.  The answer stands if no list
-        // overflowed, every query has k rows and its k-th NPHD is <= hint + 1/32: a row outside a segment's radius lies strictly
-        // beyond that ratio, a row inside it but not listed has k nearer rows of its own segment before it.
-        uint64_t total_rows = 0;
-        for (uint32_t b = 1; b <= ISCCSEARCH_MAX_BYTES; ++b) total_rows += t.seg[b].n;
-        const bool mhintable = segments > 1 && radius < 0 && !out_freq && (m <= h->spec_max_queries || h->self_hint) && k <= total_rows;
-        bool mspec = mhintable && h->speculate && !h->spec_suppress && t.mhint(m, len).ready(k);
-        bool mspec_ok = false;
-        if (mspec) {
-            batch.radius_ratio = t.mhint(m, len).ratio + 1.0 / 32.0;      // the margin: 2 bits of 64, 8 of 256
-            batch.ratio_starts_self = m > h->spec_max_queries;             // larger batches: per-query thresholds from there on (see `hinted` below)
-        }
         auto worst_ratio = [&]() -> double {                 // worst k-th NPHD of the merged lists; < 0: some query holds fewer than k rows
             double worst = 0.0;
             for (uint32_t i = 0; i < m; ++i) {
@@ -1929,118 +1975,30 @@ static int search_locked(isccsearch_handle* h, uint32_t table, uint32_t nq, cons
             return worst;
         };
         if ((rc = batch.begin(hq.data()))) return rc;
-        if (mspec && !batch.multi) {                        // (every non-empty segment is a job: cannot happen; never answer unverified)
-            mspec = false;
+        if (spec == Spec::ratio && !batch.multi) {          // (every non-empty segment is a job: cannot happen; never answer unverified)
+            spec = Spec::none;
             batch.radius_ratio = -1.0;
             if ((rc = batch.begin(hq.data()))) return rc;
         }
-        if (batch.multi && mspec) {
+        if (spec == Spec::self_hint && !batch.used_hint) spec = Spec::none;     // (no job took the single pass: nothing to verify)
+        bool spec_ok = false;
+        if (spec != Spec::none) {
             if ((rc = batch.merge())) return rc;
             if ((rc = batch.copy_flags())) return rc;
             if ((rc = copy_results())) return rc;
             HIPOK(hipStreamSynchronize(h->stream));
-            const double worst = batch.any_flag() ? -1.0 : worst_ratio();
-            mspec_ok = worst >= 0.0 && worst <= batch.radius_ratio;        // (a row outside a radius lies beyond floor(ratio x bits) + 1 bits: strictly farther)
-            if (mspec_ok) { h->stats.spec_hits += 1; t.mhint(m, len).hit(worst); }
+            // (ratio: a row outside a radius lies beyond floor(ratio x bits) + 1 bits, strictly farther than the worst k-th NPHD)
+            spec_ok = spec == Spec::ratio ? batch.complete(p_cnt, k) && worst_ratio() <= batch.radius_ratio : batch.complete(p_cnt, spec_seg->n);
+            if (spec_ok) h->stats.spec_hits += 1;
             else {
                 h->stats.spec_misses += 1;
-                t.mhint(m, len).miss();
-                batch.radius_ratio = -1.0;
+                if (spec == Spec::ratio) t.mhint(m, len).miss();
+                else spec_seg->hint(m, len).miss();
+                batch.radius = radius; batch.self_hint = -1; batch.used_hint = false; batch.radius_ratio = -1.0;     // the ordinary pass
                 if ((rc = batch.begin(hq.data()))) return rc;
             }
         }
-        if (batch.multi && mspec_ok) {
-            // (answered above)
-        } else if (batch.multi) {
-            // the per-segment lists must be complete before they are merged
-            if ((rc = batch.copy_flags())) return rc;
-            HIPOK(hipStreamSynchronize(h->stream));
-            if (batch.used_self && batch.any_flag()) {
-                if ((rc = batch.retry_with_levels(hq.data()))) return rc;
-                if ((rc = batch.copy_flags())) return rc;
-                HIPOK(hipStreamSynchronize(h->stream));
-            }
-            if (batch.any_flag() && (rc = batch.fix())) return rc;
-            if ((rc = batch.merge())) return rc;
-            if ((rc = copy_results())) return rc;
-            HIPOK(hipStreamSynchronize(h->stream));
-            if (mhintable) {
-                const double worst = worst_ratio();
-                if (worst >= 0.0) t.mhint(m, len).seed(k, worst);
-            }
-        } else if (speculate) {
-            // SPECULATIVE single pass (small batches over one segment).  One query costs boot + level + pick + collect + select:
-            // five launches for what is one pass over the rows (0.22 ms against a 0.13 ms pass).  The k-th distance of similar
-            // queries over the same rows hardly moves, so the pass is first tried as a RANGE-LIMITED search under the distance
-            // the previous search of this segment ended at (+ 2): radius_init + collect + select.  It is exact whenever every
-            // query finds k rows within that radius (its k nearest are then among them); a query that does not, or a list
-            // that overflows, sends the batch through the ordinary path -- nothing is ever returned unverified.
-            bool ok = true;
-            if ((rc = copy_results())) return rc;
-            HIPOK(hipStreamSynchronize(h->stream));
-            if (batch.any_flag()) ok = false;
-            const uint32_t need = (uint32_t)std::min<uint64_t>(k, spec_seg->n);
-            for (uint32_t i = 0; i < m && ok; ++i) ok = p_cnt[i] >= need;
-            spec_ok = ok;
-            if (ok) h->stats.spec_hits += 1;
-            else {
-                h->stats.spec_misses += 1;
-                spec_seg->hint(m, len).miss();
-                batch.radius = -1;
-                if ((rc = batch.begin(hq.data()))) return rc;
-                if ((rc = copy_results())) return rc;
-                HIPOK(hipStreamSynchronize(h->stream));
-                if (!batch.jobs.empty() && batch.used_self && batch.any_flag()) {
-                    if ((rc = batch.retry_with_levels(hq.data()))) return rc;
-                    if ((rc = copy_results())) return rc;
-                    HIPOK(hipStreamSynchronize(h->stream));
-                }
-                if (!batch.jobs.empty() && batch.any_flag()) {
-                    if ((rc = batch.fix())) return rc;
-                    if ((rc = copy_results())) return rc;
-                    HIPOK(hipStreamSynchronize(h->stream));
-                }
-            }
-        } else {
-            // one segment: flags and results travel together, ONE copy and ONE synchronisation per batch
-            auto finish = [&]() -> int {
-                int rf;
-                if (!one_copy && (rf = batch.copy_flags())) return rf;
-                if ((rf = copy_results())) return rf;
-                HIPOK(hipStreamSynchronize(h->stream));
-                if (!batch.jobs.empty() && batch.used_self && batch.any_flag()) {
-                    if ((rf = batch.retry_with_levels(hq.data()))) return rf;
-                    if (!one_copy && (rf = batch.copy_flags())) return rf;
-                    if ((rf = copy_results())) return rf;
-                    HIPOK(hipStreamSynchronize(h->stream));
-                }
-                if (!batch.jobs.empty() && batch.any_flag()) {
-                    if ((rf = batch.fix())) return rf;
-                    if ((rf = copy_results())) return rf;
-                    HIPOK(hipStreamSynchronize(h->stream));
-                }
-                return 0;
-            };
-            if (batch.used_hint) {
-                // the hinted pass holds if no list overflowed and every query found k rows under the hint
-                if (!one_copy && (rc = batch.copy_flags())) return rc;
-                if ((rc = copy_results())) return rc;
-                HIPOK(hipStreamSynchronize(h->stream));
-                bool ok = !batch.any_flag();
-                const uint32_t need = (uint32_t)std::min<uint64_t>(k, spec_seg->n);
-                for (uint32_t i = 0; i < m && ok; ++i) ok = p_cnt[i] >= need;
-                spec_ok = ok;
-                if (ok) h->stats.spec_hits += 1;
-                else {
-                    h->stats.spec_misses += 1;
-                    spec_seg->hint(m, len).miss();
-                    batch.self_hint = -1;
-                    batch.used_hint = false;
-                    if ((rc = batch.begin(hq.data()))) return rc;
-                    if ((rc = finish())) return rc;
-                }
-            } else if ((rc = finish())) return rc;
-        }
+        if (!spec_ok && (rc = batch.finish(hq.data(), copy_results))) return rc;
         if (h->count_candidates && batch.jobs.size() == 1) {
             // accounting (tools/probe_candidate_path.py, option "count_candidates"): how many candidates the scan appended for this batch
             std::vector<uint32_t> hc((size_t)batch.nq_pad * isk::CNT_STRIDE);
@@ -2049,14 +2007,12 @@ static int search_locked(isccsearch_handle* h, uint32_t table, uint32_t nq, cons
             for (uint32_t i = 0; i < m; ++i) h->stats.candidates += hc[(size_t)i * isk::CNT_STRIDE];
             h->stats.candidate_batches += 1;
         }
-        if (hintable && !batch.jobs.empty()) {
-            // where this batch's lists ended: the next small batch of this segment starts there (+ 2: P(h <= t) grows ~3x per
-            // step at these distances, so the margin costs a handful of candidates and absorbs the spread between queries)
-            uint32_t worst = 0;
-            for (uint32_t i = 0; i < m; ++i)
-                if (p_cnt[i]) worst = std::max<uint32_t>(worst, sink ? p_kth[i] : p_rec[(size_t)i * k + p_cnt[i] - 1].hamming);
-            if (spec_ok) spec_seg->hint(m, len).hit(worst);
-            else spec_seg->hint(m, len).seed(k, worst);
+        // where this batch's lists ended: the next batch of its class starts there (+ the hint's margin)
+        if (hintable && !batch.jobs.empty()) record_hint(spec_seg->hint(m, len), spec_ok, m, k, p_cnt, p_rec, sink ? p_kth : nullptr);
+        if (mhintable) {
+            const double worst = worst_ratio();
+            if (spec_ok) t.mhint(m, len).hit(worst);
+            else if (worst >= 0.0) t.mhint(m, len).seed(k, worst);
         }
         if (sink) {
             if (!batch.jobs.empty()) {
@@ -2248,12 +2204,10 @@ int isccsearch_search_many(isccsearch_handle* h, uint32_t n, isccsearch_request*
         if (!rc) rc = check_query_lengths(*tp, r.nq, r.q_nbytes);
         if (rc) { reject(r, rc); continue; }
         const Table& t = *tp;
-        uint32_t segments = 0;
-        for (uint32_t b = 1; b <= ISCCSEARCH_MAX_BYTES; ++b) segments += t.seg[b].n ? 1 : 0;
         bool one_len = true;
         if (t.metric == ISCCSEARCH_METRIC_NPHD)
             for (uint32_t q = 1; q < r.nq; ++q) one_len = one_len && r.q_nbytes[q] == r.q_nbytes[0];
-        if (segments != 1 || !one_len || r.nq > QB_MAX) continue;     // ordinary path below
+        if (t.segments() != 1 || !one_len || r.nq > QB_MAX) continue;     // ordinary path below
         deferred[i] = true;
         Slot& sl = slots[i];
         sl.rec_bytes = (size_t)r.nq * r.k * sizeof(isk::Record);
@@ -2284,7 +2238,7 @@ int isccsearch_search_many(isccsearch_handle* h, uint32_t n, isccsearch_request*
         Batch& b = *sl.batch;
         b.radius = r.max_hamming < 0 ? -1 : r.max_hamming;
         // small top-k batches: the speculative single pass of search_locked (see there), verified in pass 3a
-        for (uint32_t bb = 1; bb <= ISCCSEARCH_MAX_BYTES; ++bb) if (t.seg[bb].n) sl.seg = &t.seg[bb];
+        sl.seg = t.sole_segment();
         sl.small = r.max_hamming < 0 && r.nq <= h->spec_max_queries && sl.seg && r.k <= sl.seg->n;
         sl.len = len;
         sl.spec = sl.small && h->speculate && sl.seg->hint(r.nq, len).ready(r.k);
@@ -2314,21 +2268,11 @@ int isccsearch_search_many(isccsearch_handle* h, uint32_t n, isccsearch_request*
         const uint32_t* p_cnt = reinterpret_cast<const uint32_t*>(h->p_block.p + slots[i].block_off + slots[i].rec_bytes);
         Slot& sl = slots[i];
         if (sl.spec) {
-            // the speculative pass holds only if every query found k rows within the radius and no list overflowed
-            bool ok = b.jobs.empty() || !b.any_flag();
-            const uint32_t need = (uint32_t)std::min<uint64_t>(r.k, sl.seg->n);
-            for (uint32_t q = 0; q < r.nq && ok; ++q) ok = p_cnt[q] >= need;
-            if (ok) h->stats.spec_hits += 1;
+            if (b.complete(p_cnt, sl.seg->n)) h->stats.spec_hits += 1;
             else { h->stats.spec_misses += 1; sl.seg->hint(r.nq, sl.len).miss(); ordinary[i] = true; respec[i] = false; continue; }      // (the ordinary path re-seeds the radius)
         }
-        if (!b.jobs.empty() && b.any_flag()) { ordinary[i] = true; continue; }   // rare: exact fallback through the normal path
-        if (sl.small && !b.jobs.empty()) {
-            uint32_t worst = 0;
-            for (uint32_t q = 0; q < r.nq; ++q)
-                if (p_cnt[q]) worst = std::max<uint32_t>(worst, p_rec[(size_t)q * r.k + p_cnt[q] - 1].hamming);
-            if (sl.spec) sl.seg->hint(r.nq, sl.len).hit(worst);
-            else sl.seg->hint(r.nq, sl.len).seed(r.k, worst);
-        }
+        if (b.any_flag()) { ordinary[i] = true; continue; }   // rare: exact fallback through the normal path
+        if (sl.small && !b.jobs.empty()) record_hint(sl.seg->hint(r.nq, sl.len), sl.spec, r.nq, r.k, p_cnt, p_rec, nullptr);
         unpack_records(p_rec, p_cnt, r.nq, r.k, h->tables[r.table]->key_words, nullptr, r.out_keys, r.out_hamming, r.out_prefix_bits, r.out_count);
     }
     // pass 3b: overflowed and non-deferred requests run the ordinary pipeline
@@ -2855,7 +2799,7 @@ int isccsearch_simprint_exact(isccsearch_handle* h, uint32_t table, uint32_t n_d
 // isccsearch_match_assets: the unit searches of many asset queries as one batch per (table, code length, kind), their lists left
 // on the device, and asset_score.hip's scoring behind them.  One synchronisation for the searches over one-segment tables and the
 // scoring together; tables of several code lengths take the synchronous per-batch path (their per-segment lists are merged with the
-// host's help, Batch::run_to_device) before those are queued; one more round only when an INSTANCE list came back full or a
+// host's help, Batch::finish) before those are queued; one more round only when an INSTANCE list came back full or a
 // candidate list overflowed.
 namespace {
 constexpr uint64_t SCRATCH_BYTES = 256ull << 20;   // isccsearch_match_assets: global sort scratch of the scoring kernel, at most
@@ -2877,12 +2821,6 @@ void am_pack(const Table& t, const isccsearch_asset_unit* units, AmChunk& c) {
     c.hq.assign(c.units.size() * (size_t)t.max_words, 0);
     for (size_t i = 0; i < c.units.size(); ++i)
         for (int w = 0; w < t.max_words; ++w) c.hq[i * t.max_words + w] = units[c.units[i]].words[w];
-}
-
-uint32_t am_segments(const Table& t) {
-    uint32_t segments = 0;
-    for (uint32_t b = 1; b <= ISCCSEARCH_MAX_BYTES; ++b) segments += t.seg[b].n ? 1 : 0;
-    return segments;
 }
 
 // split the listed units into chunks of <= QB_MAX per (table, code length, kind), in first-appearance order
@@ -2952,7 +2890,7 @@ extern "C" int isccsearch_match_assets(isccsearch_handle* h, uint32_t nq, const 
     size_t rec_total = 0, cnt_total = 0, flag_total = 0, pq_words = 0;
     for (AmChunk& c : chunks) {
         const Table& t = *h->tables[c.table];
-        c.deferred = am_segments(t) <= 1;
+        c.deferred = t.segments() <= 1;
         const size_t m = c.units.size();
         rec_total += m * c.k;
         cnt_total += m;
@@ -2981,16 +2919,21 @@ extern "C" int isccsearch_match_assets(isccsearch_handle* h, uint32_t nq, const 
             slots[u].type = units[u].type;
         }
 
-    // (1) tables of several code lengths: the synchronous path, list by list merged on the device
-    for (AmChunk& c : chunks) {
-        if (c.deferred) continue;
-        Table& t = *h->tables[c.table];
-        am_pack(t, units, c);
-        Batch b(h, t, (uint32_t)c.units.size(), c.nbytes, c.k, c.d_rec, c.d_cnt);
+    // a chunk searched on its own (the synchronous path): its lists are final on the device when this returns
+    auto search_now = [&](AmChunk& c) -> int {
+        Batch b(h, *h->tables[c.table], (uint32_t)c.units.size(), c.nbytes, c.k, c.d_rec, c.d_cnt);
         b.radius = c.radius;
         h->stats.searches += 1;
         h->stats.queries += c.units.size();
-        if ((rc = b.run_to_device(c.hq.data()))) return rc;
+        int rs;
+        if ((rs = b.begin(c.hq.data()))) return rs;
+        return b.finish(c.hq.data());
+    };
+    // (1) tables of several code lengths: the synchronous path, list by list merged on the device
+    for (AmChunk& c : chunks) {
+        if (c.deferred) continue;
+        am_pack(*h->tables[c.table], units, c);
+        if ((rc = search_now(c))) return rc;
     }
     // (2) one-segment tables: queued back to back, each with its own slice of the pinned query staging and its own flags
     if (h->ev_staged_pending) { HIPOK(hipEventSynchronize(h->ev_staged)); h->ev_staged_pending = false; }
@@ -3094,12 +3037,7 @@ extern "C" int isccsearch_match_assets(isccsearch_handle* h, uint32_t nq, const 
         bool flagged = false;
         for (size_t i = 0; i < c.units.size() && !flagged; ++i) flagged = p_flags[c.flag_off + i] != 0;     // (one job: one segment)
         if (!flagged) continue;
-        Table& t = *h->tables[c.table];
-        Batch b(h, t, (uint32_t)c.units.size(), c.nbytes, c.k, c.d_rec, c.d_cnt);
-        b.radius = c.radius;
-        h->stats.searches += 1;
-        h->stats.queries += c.units.size();
-        if ((rc = b.run_to_device(c.hq.data()))) return rc;
+        if ((rc = search_now(c))) return rc;
         for (uint32_t u : c.units) redo_q[unit_query[u]] = 1;
         again = true;
     }
@@ -3129,13 +3067,8 @@ extern "C" int isccsearch_match_assets(isccsearch_handle* h, uint32_t nq, const 
             c.d_cnt = h->d_am_cnt2.p + ci;
             r += c.units.size() * (size_t)c.k;
             ci += c.units.size();
-            Table& t = *h->tables[c.table];
-            am_pack(t, units, c);
-            Batch b(h, t, (uint32_t)c.units.size(), c.nbytes, c.k, c.d_rec, c.d_cnt);
-            b.radius = c.radius;
-            h->stats.searches += 1;
-            h->stats.queries += c.units.size();
-            if ((rc = b.run_to_device(c.hq.data()))) return rc;
+            am_pack(*h->tables[c.table], units, c);
+            if ((rc = search_now(c))) return rc;
             for (uint32_t i = 0; i < c.units.size(); ++i) {
                 const uint32_t u = c.units[i];
                 slots[u].rec = reinterpret_cast<const isccsearch_record*>(c.d_rec + (size_t)i * c.k);
@@ -3198,7 +3131,9 @@ static int search_device_impl(isccsearch_handle* h, uint32_t table, uint32_t nq,
         const uint32_t m = std::min<uint32_t>(QB_MAX, nq - pos);
         Batch batch(h, t, m, len, k, out + (size_t)pos * k, d_counts + pos);
         batch.radius = radius;
-        if ((rc = batch.run_to_device(q_words + (size_t)pos * t.max_words))) return rc;
+        const uint64_t* const hq = q_words + (size_t)pos * t.max_words;
+        if ((rc = batch.begin(hq))) return rc;
+        if ((rc = batch.finish(hq))) return rc;
     }
     HIPOK(hipStreamSynchronize(h->stream));
     return 0;
@@ -3346,14 +3281,13 @@ int isccsearch_search_device_async(isccsearch_handle* h, uint32_t table, uint32_
         if (rc) return rc;
         Table& t = *tp;
         if ((rc = check_query_lengths(t, nq, q_nbytes))) return rc;
-        uint32_t len = (uint32_t)t.max_bytes, segments = 0;
-        for (uint32_t b = 1; b <= ISCCSEARCH_MAX_BYTES; ++b) segments += t.seg[b].n ? 1 : 0;
+        uint32_t len = (uint32_t)t.max_bytes;
         if (t.metric == ISCCSEARCH_METRIC_NPHD) {
             len = q_nbytes[0];
             for (uint32_t q = 1; q < nq; ++q)
                 if (q_nbytes[q] != len) return fail(-EINVAL, "search_device needs queries of one byte length (query %u differs)", q);
         }
-        if (segments <= 1) {
+        if (t.segments() <= 1) {
             HIPOK(hipSetDevice(h->device));
             h->stats.searches += 1;
             h->stats.queries += nq;
