@@ -19,7 +19,7 @@ uint32_t mfma_waves_per_block();
 // pack3: 64-bit codes on mfma_pack3_kernel (three row tiles per accumulator, OR fold of indicator bits) -- chunks of more than
 // four groups only (mfma_pack3_fits); smaller chunks keep mfma_pack_kernel
 bool mfma_pack3_fits(uint32_t groups);
-uint32_t mfma_rows_per_wave_step(int W, bool pack, bool pack3 = false);   // rows a wave takes per step (192 pack3, 128 packed, else 64, or 32 when a build runs one tile per wave)
+uint32_t mfma_rows_per_wave_step(int W, bool pack, bool pack3 = false);   // rows a wave takes per step (192 pack3, 128 packed, else 64)
 uint32_t mfma_blocks_per_cu(int W, uint32_t groups, bool pack);   // resident blocks per CU (LDS and register limits)
 // grid = (blocks_x, chunks of groups * 32 queries); returns 0 or a hipError_t when the chunk would not fit (check
 // hipGetLastError() for the launch itself, as with every other kernel)

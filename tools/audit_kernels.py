@@ -15,8 +15,9 @@ an asm statement (cdna_hip_programming.md section 5.7), so three invariants are 
   3. every such load group opens with ``s_nop 4`` (the scalar bases may come straight from v_readfirstlane / v_readlane: a
      VALU-written SGPR needs 5 wait states before a VMEM instruction reads it).
 
-The packed matrix-core scans (``mfma_pack_kernel`` and ``mfma_pack3_kernel`` in csrc/mfma_scan.hip) issue their MFMAs and the fold of their results
-from inline asm in a fixed order; hipcc places no hazard nops for asm, so two more invariants are checked on the assembly:
+The packed matrix-core scans (``mfma_pack_kernel`` and ``mfma_pack3_kernel``, csrc/mfma_pack_kernel.hip.h and
+csrc/mfma_pack3_kernel.hip.h) issue their MFMAs and the fold of their results from inline asm
+in a fixed order; hipcc places no hazard nops for asm, so two more invariants are checked on the assembly:
 
   4. along EVERY control-flow path, an instruction that reads or writes a VGPR written by a ``v_mfma*`` comes at least
      MFMA_WAIT_STATES wait states after it (one per instruction, N + 1 for ``s_nop N`` -- the rule hipcc applies to its
