@@ -1,4 +1,4 @@
-// Asset scoring of unit searches on the device (internal interface between isccsearch.hip and asset_score.hip).
+// Asset scoring of unit searches on the device (internal interface between isccsearch.hip -- assets_api.hip.h -- and asset_score.hip).
 //
 // What UsearchIndex.search_assets does AFTER its per-unit searches (iscc_search/indexes/usearch/index.py:786-839), for many
 // asset queries at once.  Input: every query's unit neighbour lists as select_kernel / merge_kernel left them in device memory

@@ -1,4 +1,4 @@
-// Document-frequency column of one segment (internal interface between isccsearch.hip and docfreq.hip).
+// Document-frequency column of one segment (internal interface between isccsearch.hip -- store.hip.h -- and docfreq.hip).
 //
 // freq[row] = number of DISTINCT assets among the first `dup_limit` rows (ascending key) that hold the same
 // code as `row` -- what the reference computes per matched simprint with an LMDB cursor walk

@@ -1,0 +1,506 @@
+// search_api.hip.h -- search_locked (every host-result search ends there), the combining queue of isccsearch_search, search_many,
+// search_within and the document-frequency calls.  Needs Batch and the query checks of isccsearch.hip, get_table of store.hip.h.
+extern "C" {
+static_assert(isksp::MAX_QUERY_SIMPRINTS == ISCCSEARCH_MAX_SCORED_SIMPRINTS, "header and kernels disagree");
+// isccsearch_simprint_score: where a search leaves its lists for the scoring kernels instead of handing them to the host
+struct ScoreSink {
+    isksp::Buffers buf{};
+    int h_max = -1;
+    uint32_t dup_limit = 0;
+    uint32_t entries = 0;       // best (asset, query) entries appended so far -- known after each batch's synchronisation
+    uint32_t max_count = 0;     // longest neighbour list
+    bool unknown_any = false;   // some query's own document frequency could not be read off its list
+    bool exact = false;         // isccsearch_simprint_exact: the lists are collision lists; only their lengths are kept per batch (no marking)
+    // ... and when ONE batch holds every lookup, its hits / offsets are prepared behind its select, so that the number of entries
+    // arrives with the batch's own synchronisation
+    const uint32_t* d_of_g = nullptr;
+    uint32_t nd = 0, ng = 0;
+    bool prepared = false;
+    uint32_t* q_count = nullptr;    // when set: [nq] length of every query's neighbour list (capped at k)
+};
+
+// What a search_locked call wants back -- ONE of:
+//   lists         keys / hamming / prefix_bits [nq][k] and count [nq] in the caller's arrays
+//   doc_freq      only the number of distinct assets per result list (doc frequency), and the lists' lengths when `collisions` is given
+//   to_sink       (one-segment Hamming tables) records and rows stay in the sink's device buffers, every batch is followed by the marking /
+//                 compaction kernels of simprint_score.hip, and only {counts | flags | k-th distances | info} reach the host
+struct SearchOut {
+    uint64_t* keys = nullptr; uint32_t* hamming = nullptr; uint16_t* prefix_bits = nullptr; uint32_t* count = nullptr;
+    uint32_t* freq = nullptr; uint32_t* collisions = nullptr;
+    ScoreSink* sink = nullptr;
+    static SearchOut lists(uint64_t* k, uint32_t* h, uint16_t* p, uint32_t* c) { SearchOut o; o.keys = k; o.hamming = h; o.prefix_bits = p; o.count = c; return o; }
+    static SearchOut doc_freq(uint32_t* freq, uint32_t* collisions = nullptr) { SearchOut o; o.freq = freq; o.collisions = collisions; return o; }
+    static SearchOut to_sink(ScoreSink* sink) { SearchOut o; o.sink = sink; return o; }
+};
+
+// The search itself; h->mu is held by the caller.  radius >= 0: range-limited search (fixed threshold).
+static int search_locked(isccsearch_handle* h, uint32_t table, uint32_t nq, const uint64_t* q_words, const uint8_t* q_nbytes, uint32_t k,
+                         int radius, const SearchOut& out) {
+    uint32_t* const out_freq = out.freq; uint32_t* const out_collisions = out.collisions; ScoreSink* const sink = out.sink;
+    Table* tp;
+    int rc = get_table(h, table, tp);
+    if (rc) return rc;
+    Table& t = *tp;
+    if ((rc = check_query_lengths(t, nq, q_nbytes))) return rc;
+    HIPOK(hipSetDevice(h->device));
+    h->stats.queries += nq;
+
+    // group queries by byte length (NPHD prefix length differs per class)
+    std::vector<uint32_t> order(nq);
+    for (uint32_t q = 0; q < nq; ++q) order[q] = q;
+    auto qlen = [&](uint32_t q) -> uint32_t { return (t.metric == ISCCSEARCH_METRIC_NPHD) ? q_nbytes[q] : (uint32_t)t.max_bytes; };
+    if (t.metric == ISCCSEARCH_METRIC_NPHD)
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return q_nbytes[a] < q_nbytes[b]; });
+
+    std::vector<uint64_t> hq;
+    uint32_t pos = 0;
+    while (pos < nq) {
+        const uint32_t len = qlen(order[pos]);
+        uint32_t end = pos;
+        while (end < nq && end - pos < QB_MAX && qlen(order[end]) == len) ++end;
+        const uint32_t m = end - pos;
+        hq.resize((size_t)m * t.max_words);
+        for (uint32_t i = 0; i < m; ++i)
+            memcpy(&hq[(size_t)i * t.max_words], q_words + (size_t)order[pos + i] * t.max_words, (size_t)t.max_words * 8);
+        // result block {records [m][k] | counts [m] | flags [<= m + 15]} on the device and, mirrored, in pinned memory
+        const size_t rec_bytes = sink ? 0 : (size_t)m * k * sizeof(isk::Record);     // (a sink keeps the records on the device)
+        const size_t flag_slots = flag_slots_for(m);
+        // (+ m counts behind the flags when a document-frequency call also wants the lists' lengths;
+        //  + m k-th distances and the scoring kernels' info words when the lists stay on the device)
+        const size_t block_bytes = rec_bytes + ((size_t)m + flag_slots + (out_collisions || sink ? m : 0) + (sink ? isksp::INFO_WORDS : 0)) * sizeof(uint32_t);
+        if ((rc = h->d_block.ensure(block_bytes))) return rc;
+        if ((rc = h->p_block.ensure(block_bytes))) return rc;
+        const isk::Record* const p_rec = reinterpret_cast<const isk::Record*>(h->p_block.p);
+        uint32_t* const p_cnt = reinterpret_cast<uint32_t*>(h->p_block.p + rec_bytes);
+        const uint32_t segments = t.segments();
+        const bool one_copy = segments == 1 && !out_freq;   // flags ride in the block: results leave in ONE copy
+        // ... or in none: select_kernel writes a small block straight into the pinned mirror (page-locked memory is mapped
+        // into the device's address space), so the host only synchronises.  A device->host copy costs ~25 us of queue
+        // hand-over after the kernel, more than the 240 bytes per query take to cross PCIe as plain stores.  Large blocks
+        // (big k x many queries) keep the DMA copy.
+        const bool direct = one_copy && block_bytes <= DIRECT_RESULT_BYTES && !sink;
+        isk::Record* const d_rec = sink ? h->d_sp_rec.p + (size_t)pos * k : reinterpret_cast<isk::Record*>(direct ? h->p_block.p : h->d_block.p);
+        uint32_t* const d_cnt = reinterpret_cast<uint32_t*>((direct ? h->p_block.p : h->d_block.p) + rec_bytes);
+        uint32_t* const p_kth = p_cnt + m + flag_slots;                  // (sink) hamming of every query's last result
+        Batch batch(h, t, m, len, k, d_rec, d_cnt);
+        batch.radius = radius;
+        if (sink) { if (!sink->exact) batch.d_out_rows = h->d_sp_rows.p + (size_t)pos * k; batch.d_out_kth = d_cnt + m + flag_slots; }
+        if (one_copy) { batch.d_flags = d_cnt + m; batch.h_flags = p_cnt + m; }
+        // Speculation: ONE pass under where an earlier batch of this size and query length ended, verified by one look at its
+        // lists; a miss (a list overflowed, a query came up short) sends the batch through the ordinary path -- nothing is ever
+        // returned unverified.
+        //   radius     SMALL batches over one segment.  One query costs boot + level + pick + collect + select: five launches for
+        //              what is one pass over the rows (0.22 ms against a 0.13 ms pass).  The k-th distance of similar queries over
+        //              the same rows hardly moves, so the pass is first tried as a RANGE-LIMITED search under the distance the
+        //              previous search of this segment ended at (+ 2): radius_init + collect + select.  It is exact whenever every
+        //              query finds k rows within that radius (its k nearest are then among them).
+        //   self_hint  LARGER batches over one segment keep their single self-tightening pass (one radius for hundreds of queries
+        //              admits several times the candidates of per-query thresholds) but START it under the hint instead of a
+        //              bootstrap sample's threshold: no sample kernel, no flood of candidates in the first steps.  Same check.
+        //   ratio      SEVERAL segments (an index of mixed code lengths -- what an ISCC-UNIT index is).  The ordinary path costs
+        //              boot + level + pick + collect + select per segment and two synchronisations (0.62 ms for one 256-bit query
+        //              over 4 x 25 M rows); here every segment lists its rows within (hint + 1/32) x compared bits (radius_init +
+        //              collect + select each), the lists are merged and ONE synchronisation brings results and flags.  The answer
+        //              stands if no list overflowed, every query has k rows and its k-th NPHD is <= hint + 1/32: a row outside a
+        //              segment's radius lies strictly beyond that ratio, a row inside it but not listed has k nearer rows of its own
+        //              segment before it.
+        enum class Spec { none, radius, self_hint, ratio } spec = Spec::none;
+        // radius / self_hint: an ordinary top-k search over ONE segment that has been searched with this k before
+        Segment* const spec_seg = t.sole_segment();
+        // (a segment small enough for the one-launch search -- Batch::tiny -- has nothing to gain from a radius: it is exact in that launch either way)
+        const bool one_launch = spec_seg && h->tiny_rows && spec_seg->n <= h->tiny_rows && spec_seg->n < h->mfma_min_rows && spec_seg->n <= h->candidate_cap;
+        const bool hintable = spec_seg && radius < 0 && !out_freq && one_copy && k <= spec_seg->n && !one_launch;
+        const bool small_batch = hintable && m <= h->spec_max_queries;
+        if (hintable && h->speculate && !h->spec_suppress && (small_batch || h->self_hint) && spec_seg->hint(m, len).ready(k)) {
+            if (small_batch) { spec = Spec::radius; batch.radius = (int)spec_seg->hint(m, len).tau; }
+            else { spec = Spec::self_hint; batch.self_hint = (int)spec_seg->hint(m, len).tau; }
+        }
+        const bool mhintable = segments > 1 && radius < 0 && !out_freq && (m <= h->spec_max_queries || h->self_hint) && k <= t.total;
+        if (mhintable && h->speculate && !h->spec_suppress && t.mhint(m, len).ready(k)) {
+            spec = Spec::ratio;
+            batch.radius_ratio = t.mhint(m, len).ratio + 1.0 / 32.0;      // the margin: 2 bits of 64, 8 of 256
+            batch.ratio_starts_self = m > h->spec_max_queries;             // larger batches: each segment's single pass STARTS under it
+        }
+        auto copy_results = [&]() -> int {
+            if (out_freq) {
+                // only the distinct-asset count of every list leaves the device
+                int rf;
+                if ((rf = h->d_freq.ensure(m))) return rf;
+                isk::DistinctParams dp{d_rec, d_cnt, h->d_freq.p, k, (uint32_t)t.key_words};
+                hipLaunchKernelGGL(isk::distinct_kernel, dim3(m), dim3(isk::BLOCK), 0, h->stream, dp);
+                HIPOK(hipGetLastError());
+                if (out_collisions) HIPOK(hipMemcpyAsync(p_cnt + m + flag_slots, d_cnt, m * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+                HIPOK(hipMemcpyAsync(p_cnt, h->d_freq.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+                return 0;
+            }
+            if (direct) return 0;                                  // already written where the host reads it
+            if (sink) {
+                // the lists are final on the device (or will be redone and this queued again): mark the best chunk of every
+                // (asset, query), append them to the request's entry list; the host gets counts, flags, k-th distances and info
+                uint32_t* const d_info = d_cnt + m + flag_slots + m;
+                if (sink->exact) {
+                    HIPOK(hipMemcpyAsync(h->d_sp_cnt.p + pos, d_cnt, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
+                    if (pos == 0 && m == sink->nd && sink->d_of_g)
+                        HIPOK(isksp::exact_prepare(sink->buf, d_cnt, sink->d_of_g, sink->nd, sink->ng, k, d_info, h->stream));
+                } else {
+                    isksp::BatchArgs ba{pos, m, k, d_cnt, sink->h_max, sink->dup_limit, sink->entries, d_info};
+                    HIPOK(isksp::queue_batch(sink->buf, ba, h->stream));
+                }
+                HIPOK(hipMemcpyAsync(h->p_block.p, h->d_block.p, block_bytes, hipMemcpyDeviceToHost, h->stream));
+                return 0;
+            }
+            const size_t bytes = rec_bytes + (size_t)m * sizeof(uint32_t) + (one_copy ? batch.flag_words() * sizeof(uint32_t) : 0);
+            HIPOK(hipMemcpyAsync(h->p_block.p, h->d_block.p, bytes, hipMemcpyDeviceToHost, h->stream));
+            return 0;
+        };
+        auto worst_ratio = [&]() -> double {                 // worst k-th NPHD of the merged lists; < 0: some query holds fewer than k rows
+            double worst = 0.0;
+            for (uint32_t i = 0; i < m; ++i) {
+                if (p_cnt[i] < k) return -1.0;
+                const isk::Record& r = p_rec[(size_t)i * k + k - 1];
+                worst = std::max(worst, r.prefix_bits ? (double)r.hamming / (double)r.prefix_bits : 0.0);
+            }
+            return worst;
+        };
+        if ((rc = batch.begin(hq.data()))) return rc;
+        if (spec == Spec::ratio && !batch.multi) {          // (every non-empty segment is a job: cannot happen; never answer unverified)
+            spec = Spec::none;
+            batch.radius_ratio = -1.0;
+            if ((rc = batch.begin(hq.data()))) return rc;
+        }
+        if (spec == Spec::self_hint && !batch.used_hint) spec = Spec::none;     // (no job took the single pass: nothing to verify)
+        bool spec_ok = false;
+        if (spec != Spec::none) {
+            if ((rc = batch.merge())) return rc;
+            if ((rc = batch.copy_flags())) return rc;
+            if ((rc = copy_results())) return rc;
+            HIPOK(hipStreamSynchronize(h->stream));
+            // (ratio: a row outside a radius lies beyond floor(ratio x bits) + 1 bits, strictly farther than the worst k-th NPHD)
+            spec_ok = spec == Spec::ratio ? batch.complete(p_cnt, k) && worst_ratio() <= batch.radius_ratio : batch.complete(p_cnt, spec_seg->n);
+            if (spec_ok) h->stats.spec_hits += 1;
+            else {
+                h->stats.spec_misses += 1;
+                if (spec == Spec::ratio) t.mhint(m, len).miss();
+                else spec_seg->hint(m, len).miss();
+                batch.radius = radius; batch.self_hint = -1; batch.used_hint = false; batch.radius_ratio = -1.0;     // the ordinary pass
+                if ((rc = batch.begin(hq.data()))) return rc;
+            }
+        }
+        if (!spec_ok && (rc = batch.finish(hq.data(), copy_results))) return rc;
+        if (h->count_candidates && batch.jobs.size() == 1) {
+            // accounting (tools/probe_candidate_path.py, option "count_candidates"): how many candidates the scan appended for this batch
+            std::vector<uint32_t> hc((size_t)batch.nq_pad * isk::CNT_STRIDE);
+            HIPOK(hipMemcpyAsync(hc.data(), h->d_cnt.p, hc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+            HIPOK(hipStreamSynchronize(h->stream));
+            for (uint32_t i = 0; i < m; ++i) h->stats.candidates += hc[(size_t)i * isk::CNT_STRIDE];
+            h->stats.candidate_batches += 1;
+        }
+        // where this batch's lists ended: the next batch of its class starts there (+ the hint's margin)
+        if (hintable && !batch.jobs.empty()) record_hint(spec_seg->hint(m, len), spec_ok, m, k, p_cnt, p_rec, sink ? p_kth : nullptr);
+        if (mhintable) {
+            const double worst = worst_ratio();
+            if (spec_ok) t.mhint(m, len).hit(worst);
+            else if (worst >= 0.0) t.mhint(m, len).seed(k, worst);
+        }
+        if (sink) {
+            if (!batch.jobs.empty()) {
+                const uint32_t* p_info = p_kth + m;
+                if (!sink->exact) {
+                    sink->entries = p_info[0];
+                    sink->unknown_any = sink->unknown_any || p_info[1] != 0;
+                } else if (pos == 0 && m == sink->nd && sink->d_of_g) {
+                    sink->entries = p_info[0];
+                    sink->prepared = true;
+                }
+                for (uint32_t i = 0; i < m; ++i) sink->max_count = std::max(sink->max_count, std::min(p_cnt[i], k));
+                if (sink->q_count) for (uint32_t i = 0; i < m; ++i) sink->q_count[pos + i] = std::min(p_cnt[i], k);
+            }
+            pos = end;
+            continue;
+        }
+        if (out_freq) {
+            if (batch.jobs.empty()) for (uint32_t i = 0; i < m; ++i) out_freq[order[pos + i]] = 0;
+            else for (uint32_t i = 0; i < m; ++i) out_freq[order[pos + i]] = p_cnt[i];
+            if (out_collisions)
+                for (uint32_t i = 0; i < m; ++i) out_collisions[order[pos + i]] = batch.jobs.empty() ? 0 : p_cnt[m + flag_slots + i];
+        } else {
+            unpack_records(p_rec, p_cnt, m, k, t.key_words, &order[pos], out.keys, out.hamming, out.prefix_bits, out.count);
+        }
+        pos = end;
+    }
+    return 0;
+}
+
+// Searches arriving from many threads are COMBINED: the reference calls `search` once per query unit from
+// FastAPI's thread pool (usearch/index.py:786-806, docs/explanation/architecture.md:120-126), and a
+// streaming pass costs the same for one query as for T_q.  The first caller becomes the leader, takes every
+// request waiting on the same (table, k) and runs them as ONE batch; the others sleep until their slice of
+// the results has been written.  A single-threaded caller pays nothing for this.
+struct PendingSearch {
+    uint32_t table, nq, k;
+    const uint64_t* q_words;
+    const uint8_t* q_nbytes;
+    SearchOut out;      // (its lists)
+    int rc = 0;
+    bool done = false;
+    std::string err;
+};
+
+namespace {
+void run_combined(isccsearch_handle* h, std::vector<PendingSearch*>& reqs) {
+    std::lock_guard<std::mutex> lk(h->mu);
+    std::vector<bool> handled(reqs.size(), false);
+    for (size_t i = 0; i < reqs.size(); ++i) {
+        if (handled[i]) continue;
+        // requests sharing table and k (and therefore key width / words per query)
+        std::vector<size_t> grp;
+        for (size_t j = i; j < reqs.size(); ++j)
+            if (!handled[j] && reqs[j]->table == reqs[i]->table && reqs[j]->k == reqs[i]->k) { grp.push_back(j); handled[j] = true; }
+        h->stats.searches += grp.size();
+        Table* tp = nullptr;
+        int rc = get_table(h, reqs[i]->table, tp);
+        // validate each request on its own so that one bad caller does not fail the others
+        std::vector<size_t> ok;
+        for (size_t j : grp) {
+            PendingSearch* r = reqs[j];
+            int rj = rc ? rc : check_query_lengths(*tp, r->nq, r->q_nbytes);
+            if (rj) { r->rc = rj; r->err = g_last_error; }
+            else ok.push_back(j);
+        }
+        if (ok.empty()) continue;
+        if (ok.size() == 1) {
+            PendingSearch* r = reqs[ok[0]];
+            r->rc = search_locked(h, r->table, r->nq, r->q_words, r->q_nbytes, r->k, -1, r->out);
+            if (r->rc) r->err = g_last_error;
+            continue;
+        }
+        const Table& t = *tp;
+        const uint32_t k = reqs[i]->k;
+        const int MW = t.max_words, KW = t.key_words;
+        size_t total = 0;
+        for (size_t j : ok) total += reqs[j]->nq;
+        std::vector<uint64_t> qw(total * MW), okeys(total * k * KW);
+        std::vector<uint8_t> qn(t.metric == ISCCSEARCH_METRIC_NPHD ? total : 0);
+        std::vector<uint32_t> oh(total * k), oc(total);
+        std::vector<uint16_t> op(total * k);
+        size_t off = 0;
+        for (size_t j : ok) {
+            PendingSearch* r = reqs[j];
+            memcpy(&qw[off * MW], r->q_words, (size_t)r->nq * MW * 8);
+            if (!qn.empty()) memcpy(&qn[off], r->q_nbytes, r->nq);
+            off += r->nq;
+        }
+        const int rg = search_locked(h, reqs[i]->table, (uint32_t)total, qw.data(), qn.empty() ? nullptr : qn.data(), k, -1,
+                                     SearchOut::lists(okeys.data(), oh.data(), op.data(), oc.data()));
+        const std::string eg = rg ? g_last_error : std::string();
+        off = 0;
+        for (size_t j : ok) {
+            PendingSearch* r = reqs[j];
+            r->rc = rg;
+            r->err = eg;
+            if (!rg) {
+                memcpy(r->out.keys, &okeys[off * k * KW], (size_t)r->nq * k * KW * 8);
+                memcpy(r->out.hamming, &oh[off * k], (size_t)r->nq * k * 4);
+                memcpy(r->out.prefix_bits, &op[off * k], (size_t)r->nq * k * 2);
+                memcpy(r->out.count, &oc[off], (size_t)r->nq * 4);
+            }
+            off += r->nq;
+        }
+    }
+}
+}  // namespace
+
+int isccsearch_search(isccsearch_handle* h, uint32_t table, uint32_t nq, const uint64_t* q_words,
+                      const uint8_t* q_nbytes, uint32_t k,
+                      uint64_t* out_keys, uint32_t* out_hamming, uint16_t* out_prefix_bits, uint32_t* out_count) {
+    if (!h) return fail(-EINVAL, "handle is NULL");
+    if (int rc = check_count(k)) return rc;
+    if (nq == 0) return 0;
+    if (!q_words || !out_keys || !out_hamming || !out_prefix_bits || !out_count) return fail(-EINVAL, "NULL argument");
+    PendingSearch me;
+    me.table = table; me.nq = nq; me.k = k; me.q_words = q_words; me.q_nbytes = q_nbytes;
+    me.out = SearchOut::lists(out_keys, out_hamming, out_prefix_bits, out_count);
+    {
+        std::unique_lock<std::mutex> ql(h->qmu);
+        h->pending.push_back(&me);
+        for (;;) {
+            if (me.done) {
+                if (me.rc) g_last_error = me.err;
+                return me.rc;
+            }
+            if (!h->leader_active) { h->leader_active = true; break; }   // nobody is serving: lead the next round
+            h->qcv.wait(ql);
+        }
+    }
+    // leader of exactly one round (it contains my own request), then hand over to a waiter
+    std::vector<PendingSearch*> round;
+    {
+        std::unique_lock<std::mutex> ql(h->qmu);
+        round.swap(h->pending);
+    }
+    run_combined(h, round);
+    {
+        std::unique_lock<std::mutex> ql(h->qmu);
+        for (PendingSearch* r : round) r->done = true;
+        h->leader_active = false;
+    }
+    h->qcv.notify_all();
+    if (me.rc) g_last_error = me.err;
+    return me.rc;
+}
+
+// Several searches, ONE synchronisation.  Requests over single-segment tables whose queries share one length are
+// enqueued back to back (the device buffers are reused in stream order; only the pinned staging is sliced per
+// request) and their result blocks are read after a single hipStreamSynchronize; everything else -- and any
+// request whose candidate list overflowed -- takes the ordinary path afterwards.
+int isccsearch_search_many(isccsearch_handle* h, uint32_t n, isccsearch_request* reqs) {
+    if (!h) return fail(-EINVAL, "handle is NULL");
+    if (n == 0) return 0;
+    if (!reqs) return fail(-EINVAL, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPOK(hipSetDevice(h->device));
+    struct Slot {
+        std::unique_ptr<Batch> batch;
+        std::vector<uint64_t> hq;
+        size_t block_off = 0, rec_bytes = 0;
+        Segment* seg = nullptr;
+        bool small = false, spec = false;
+        uint32_t len = 0;      // compared prefix length of the request (the hint is kept per length)
+    };
+    std::vector<Slot> slots(n);
+    std::vector<bool> deferred(n, false);
+    int first_error = 0;
+    auto reject = [&](isccsearch_request& r, int rc) { r.status = rc; if (!first_error) first_error = rc; };
+
+    // pass 1: validate, pick the requests that can be deferred, size the pinned staging once (a later ensure()
+    // would move slices that are already referenced by queued copies)
+    size_t pq_words = 0, block_total = 0, block_max = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        isccsearch_request& r = reqs[i];
+        r.status = 0;
+        if (r.nq == 0) continue;
+        if (int rk = check_count(r.k)) { reject(r, rk); continue; }
+        if (r.max_hamming > 256) { reject(r, fail(-EINVAL, "max_hamming %d exceeds 256", r.max_hamming)); continue; }
+        if (!r.q_words || !r.out_keys || !r.out_hamming || !r.out_prefix_bits || !r.out_count) { reject(r, fail(-EINVAL, "NULL argument")); continue; }
+        Table* tp;
+        int rc = get_table(h, r.table, tp);
+        if (!rc) rc = check_query_lengths(*tp, r.nq, r.q_nbytes);
+        if (rc) { reject(r, rc); continue; }
+        const Table& t = *tp;
+        if (t.segments() != 1 || first_other_length(t, r.nq, r.q_nbytes) != r.nq || r.nq > QB_MAX) continue;     // ordinary path below
+        deferred[i] = true;
+        Slot& sl = slots[i];
+        sl.rec_bytes = (size_t)r.nq * r.k * sizeof(isk::Record);
+        const size_t bytes = (sl.rec_bytes + ((size_t)r.nq + flag_slots_for(r.nq)) * sizeof(uint32_t) + 15) & ~(size_t)15;
+        sl.block_off = block_total;
+        block_total += bytes;
+        block_max = std::max(block_max, bytes);
+        pq_words += staged_words_for(r.nq);
+    }
+    int rc;
+    if ((rc = wait_staged(h))) return rc;
+    if ((rc = h->p_queries.ensure(pq_words))) return rc;
+    if ((rc = h->p_block.ensure(block_total))) return rc;
+    if ((rc = h->d_block.ensure(block_max))) return rc;
+
+    // pass 2: enqueue
+    size_t pq_off = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!deferred[i]) continue;
+        isccsearch_request& r = reqs[i];
+        Table& t = *h->tables[r.table];
+        Slot& sl = slots[i];
+        const uint32_t len = t.metric == ISCCSEARCH_METRIC_NPHD ? r.q_nbytes[0] : (uint32_t)t.max_bytes;
+        isk::Record* const d_rec = reinterpret_cast<isk::Record*>(h->d_block.p);
+        uint32_t* const d_cnt = reinterpret_cast<uint32_t*>(h->d_block.p + sl.rec_bytes);
+        uint32_t* const p_cnt = reinterpret_cast<uint32_t*>(h->p_block.p + sl.block_off + sl.rec_bytes);
+        sl.batch.reset(new Batch(h, t, r.nq, len, r.k, d_rec, d_cnt));
+        Batch& b = *sl.batch;
+        b.radius = r.max_hamming < 0 ? -1 : r.max_hamming;
+        // small top-k batches: the speculative single pass of search_locked (see there), verified in pass 3a
+        sl.seg = t.sole_segment();
+        sl.small = r.max_hamming < 0 && r.nq <= h->spec_max_queries && sl.seg && r.k <= sl.seg->n;
+        sl.len = len;
+        sl.spec = sl.small && h->speculate && sl.seg->hint(r.nq, len).ready(r.k);
+        if (sl.spec) b.radius = (int)sl.seg->hint(r.nq, len).tau;
+        b.pq_off = pq_off;
+        b.d_flags = d_cnt + r.nq;
+        b.h_flags = p_cnt + r.nq;
+        pq_off += staged_words_for(r.nq);
+        sl.hq.assign(r.q_words, r.q_words + (size_t)r.nq * t.max_words);
+        h->stats.searches += 1;
+        h->stats.queries += r.nq;
+        if ((rc = b.begin(sl.hq.data()))) return rc;
+        const size_t bytes = sl.rec_bytes + ((size_t)r.nq + b.flag_words()) * sizeof(uint32_t);
+        HIPOK(hipMemcpyAsync(h->p_block.p + sl.block_off, h->d_block.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPOK(hipStreamSynchronize(h->stream));
+
+    // pass 3a: hand out EVERY deferred result first.  The ordinary pipeline below stages its own results in p_block
+    // from offset 0 (and may reallocate it), so no deferred slice may still be unread when it runs.
+    std::vector<bool> ordinary(n, false), respec(n, true);      // respec: the ordinary rerun may itself speculate (not after a miss)
+    for (uint32_t i = 0; i < n; ++i) {
+        isccsearch_request& r = reqs[i];
+        if (r.status || r.nq == 0) continue;
+        if (!deferred[i]) { ordinary[i] = true; continue; }
+        Batch& b = *slots[i].batch;
+        const isk::Record* p_rec = reinterpret_cast<const isk::Record*>(h->p_block.p + slots[i].block_off);
+        const uint32_t* p_cnt = reinterpret_cast<const uint32_t*>(h->p_block.p + slots[i].block_off + slots[i].rec_bytes);
+        Slot& sl = slots[i];
+        if (sl.spec) {
+            if (b.complete(p_cnt, sl.seg->n)) h->stats.spec_hits += 1;
+            else { h->stats.spec_misses += 1; sl.seg->hint(r.nq, sl.len).miss(); ordinary[i] = true; respec[i] = false; continue; }      // (the ordinary path re-seeds the radius)
+        }
+        if (b.any_flag()) { ordinary[i] = true; continue; }   // rare: exact fallback through the normal path
+        if (sl.small && !b.jobs.empty()) record_hint(sl.seg->hint(r.nq, sl.len), sl.spec, r.nq, r.k, p_cnt, p_rec, nullptr);
+        unpack_records(p_rec, p_cnt, r.nq, r.k, h->tables[r.table]->key_words, nullptr, r.out_keys, r.out_hamming, r.out_prefix_bits, r.out_count);
+    }
+    // pass 3b: overflowed and non-deferred requests run the ordinary pipeline
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!ordinary[i]) continue;
+        isccsearch_request& r = reqs[i];
+        if (!deferred[i]) h->stats.searches += 1;
+        h->spec_suppress = !respec[i];
+        rc = search_locked(h, r.table, r.nq, r.q_words, r.q_nbytes, r.k, r.max_hamming < 0 ? -1 : r.max_hamming,
+                           SearchOut::lists(r.out_keys, r.out_hamming, r.out_prefix_bits, r.out_count));
+        h->spec_suppress = false;
+        if (rc) reject(r, rc);
+    }
+    return first_error;
+}
+
+int isccsearch_search_within(isccsearch_handle* h, uint32_t table, uint32_t nq, const uint64_t* q_words,
+                             const uint8_t* q_nbytes, uint32_t k, uint32_t max_hamming,
+                             uint64_t* out_keys, uint32_t* out_hamming, uint16_t* out_prefix_bits, uint32_t* out_count) {
+    if (!h) return fail(-EINVAL, "handle is NULL");
+    if (int rc = check_count(k)) return rc;
+    if (max_hamming > 256) return fail(-EINVAL, "max_hamming %u exceeds 256", max_hamming);
+    if (nq == 0) return 0;
+    if (!q_words || !out_keys || !out_hamming || !out_prefix_bits || !out_count) return fail(-EINVAL, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->stats.searches += 1;
+    return search_locked(h, table, nq, q_words, q_nbytes, k, (int)max_hamming, SearchOut::lists(out_keys, out_hamming, out_prefix_bits, out_count));
+}
+
+int isccsearch_doc_freq(isccsearch_handle* h, uint32_t table, uint32_t nq, const uint64_t* q_words,
+                        const uint8_t* q_nbytes, uint32_t dup_limit, uint32_t* out_freq) {
+    if (!h) return fail(-EINVAL, "handle is NULL");
+    if (dup_limit < 1 || dup_limit > ISCCSEARCH_MAX_K) return fail(-EINVAL, "dup_limit %u outside 1..ISCCSEARCH_MAX_K (%d)", dup_limit, ISCCSEARCH_MAX_K);
+    if (nq == 0) return 0;
+    if (!q_words || !out_freq) return fail(-EINVAL, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->stats.searches += 1;
+    return search_locked(h, table, nq, q_words, q_nbytes, dup_limit, 0, SearchOut::doc_freq(out_freq));
+}
+
+int isccsearch_doc_freq_counted(isccsearch_handle* h, uint32_t table, uint32_t nq, const uint64_t* q_words,
+                                const uint8_t* q_nbytes, uint32_t dup_limit, uint32_t* out_freq, uint32_t* out_collisions) {
+    if (!h) return fail(-EINVAL, "handle is NULL");
+    if (dup_limit < 1 || dup_limit > ISCCSEARCH_MAX_K) return fail(-EINVAL, "dup_limit %u outside 1..ISCCSEARCH_MAX_K (%d)", dup_limit, ISCCSEARCH_MAX_K);
+    if (nq == 0) return 0;
+    if (!q_words || !out_freq || !out_collisions) return fail(-EINVAL, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->stats.searches += 1;
+    return search_locked(h, table, nq, q_words, q_nbytes, dup_limit, 0, SearchOut::doc_freq(out_freq, out_collisions));
+}
+}  // extern "C"

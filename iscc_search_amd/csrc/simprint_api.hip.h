@@ -1,0 +1,356 @@
+// simprint_api.hip.h -- the three simprint entry points: a search whose lists stay on the device (ScoreSink) and the scoring of
+// simprint_score.hip behind it.  Needs search_locked and ScoreSink of search_api.hip.h, ensure_freq_column of store.hip.h.
+namespace {
+// The match threshold on the integer distance, the table's frequency column and the similarity / IDF tables of one scoring call
+// (isccsearch_simprint_score and _many); h->mu is held.
+int simprint_setup(H* h, Table& t, Segment& s, double threshold, int64_t total_assets, uint32_t dup_limit, int& h_max) {
+    int rc;
+    const uint32_t bits = 8 * (uint32_t)t.max_bytes;
+    // the match threshold on the integer distance: score = 1.0 - distance / ndim (usearch_core.py:182) falls with the distance, so
+    // the largest distance whose score -- in this very arithmetic -- still passes is found once
+    h_max = -1;
+    for (uint32_t d = 0; d <= bits; ++d) {
+        if (1.0 - (double)d / (double)bits >= threshold) h_max = (int)d;
+        else break;
+    }
+    if (dup_limit && (rc = ensure_freq_column(h, t, s, dup_limit))) return rc;
+    // similarity and IDF values come from the HOST's arithmetic (log() of libm is what CPython's math.log calls; lmdb_ops.py:67-81)
+    const uint32_t n_idf = dup_limit + 1;
+    if (h->sp_tab_bits != bits || h->sp_tab_dup != dup_limit || h->sp_tab_total != total_assets) {
+        const size_t words = (size_t)bits + 1 + n_idf;
+        if ((rc = h->p_sp_tab.ensure(words))) return rc;
+        if ((rc = h->d_sp_tab.ensure(words))) return rc;
+        HIPOK(hipStreamSynchronize(h->stream));      // (a previous upload may still be reading the staging block)
+        double* tab = h->p_sp_tab.p;
+        for (uint32_t d = 0; d <= bits; ++d) tab[d] = 1.0 - (double)d / (double)bits;
+        auto idf = [&](uint32_t freq) { return total_assets <= 0 ? 0.0 : std::log(1.0 + (double)total_assets / (double)(1 + (uint64_t)freq)); };
+        if (dup_limit) for (uint32_t f = 0; f <= dup_limit; ++f) tab[bits + 1 + f] = idf(f);
+        else tab[bits + 1] = idf(1);
+        HIPOK(hipMemcpyAsync(h->d_sp_tab.p, tab, words * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        h->sp_tab_bits = bits; h->sp_tab_dup = dup_limit; h->sp_tab_total = total_assets;
+    }
+    return 0;
+}
+
+// device buffers of a scoring call over nq query simprints with k neighbours each (entries == 0: the search's; else the scoring's)
+int simprint_buffers(H* h, uint32_t nq, uint32_t k, uint32_t entries) {
+    int rc;
+    if (entries == 0) {
+        const size_t slots = (size_t)nq * k;
+        if ((rc = h->d_sp_rec.ensure(slots))) return rc;
+        if ((rc = h->d_sp_rows.ensure(slots))) return rc;
+        if ((rc = h->d_sp_best.ensure(slots))) return rc;
+        if ((rc = h->d_sp_nbest.ensure(nq))) return rc;
+        if ((rc = h->d_sp_offs.ensure(nq))) return rc;
+        if ((rc = h->d_sp_freqq.ensure(nq))) return rc;
+        if ((rc = h->d_sp_unknown.ensure(nq))) return rc;
+        if ((rc = h->d_sp_nassets.ensure(1))) return rc;
+        for (int i = 0; i < 2; ++i) {
+            if ((rc = h->d_sp_asset[i].ensure(slots))) return rc;
+            if ((rc = h->d_sp_entry[i].ensure(slots))) return rc;
+        }
+        return 0;
+    }
+    for (int i = 0; i < 2; ++i) {
+        if ((rc = h->d_sp_score[i].ensure(entries))) return rc;
+        if ((rc = h->d_sp_order[i].ensure(entries))) return rc;
+    }
+    if ((rc = h->d_sp_matches.ensure(entries))) return rc;
+    if ((rc = h->d_sp_ws.ensure(entries))) return rc;
+    if ((rc = h->d_sp_idfq.ensure(nq))) return rc;
+    return 0;
+}
+
+void simprint_bind(H* h, isksp::Buffers& b) {
+    b.rec = reinterpret_cast<const isccsearch_record*>(h->d_sp_rec.p);
+    b.rows = h->d_sp_rows.p; b.best = h->d_sp_best.p; b.nbest = h->d_sp_nbest.p; b.offs = h->d_sp_offs.p;
+    b.freq_q = h->d_sp_freqq.p; b.unknown = h->d_sp_unknown.p; b.n_assets = h->d_sp_nassets.p;
+    for (int i = 0; i < 2; ++i) {
+        b.c_asset[i] = h->d_sp_asset[i].p; b.c_entry[i] = h->d_sp_entry[i].p;
+        b.score[i] = h->d_sp_score[i].p; b.order[i] = h->d_sp_order[i].p;
+    }
+    b.matches = h->d_sp_matches.p; b.ws = h->d_sp_ws.p; b.idf_q = h->d_sp_idfq.p;
+    b.temp = h->d_sp_temp.p; b.temp_bytes = h->d_sp_temp.n;
+}
+
+// rare: a query simprint with k equal stored rows and k < dup_limit -- its document frequency needs the collision scan
+int simprint_unknown_freq(H* h, uint32_t table, Table& t, uint32_t nq, const uint64_t* q_words, uint32_t dup_limit) {
+    int rc;
+    std::vector<uint32_t> unk(nq), fq(nq);
+    HIPOK(hipMemcpyAsync(unk.data(), h->d_sp_unknown.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPOK(hipMemcpyAsync(fq.data(), h->d_sp_freqq.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPOK(hipStreamSynchronize(h->stream));
+    std::vector<uint32_t> which;
+    for (uint32_t q = 0; q < nq; ++q) if (unk[q]) which.push_back(q);
+    std::vector<uint64_t> qw(which.size() * (size_t)t.max_words);
+    for (size_t i = 0; i < which.size(); ++i) memcpy(&qw[i * t.max_words], q_words + (size_t)which[i] * t.max_words, (size_t)t.max_words * 8);
+    std::vector<uint32_t> freq(which.size());
+    if ((rc = search_locked(h, table, (uint32_t)which.size(), qw.data(), nullptr, dup_limit, 0, SearchOut::doc_freq(freq.data())))) return rc;
+    for (size_t i = 0; i < which.size(); ++i) fq[which[i]] = freq[i];
+    HIPOK(hipMemcpyAsync(h->d_sp_freqq.p, fq.data(), (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPOK(hipStreamSynchronize(h->stream));       // (fq leaves scope)
+    return 0;
+}
+
+// The scoring of isccsearch_simprint_score and _many once their arguments are checked (out_info zeroed; request r = query simprints
+// [req_offsets[r], req_offsets[r + 1]), at most MAX_QUERY_SIMPRINTS each): consecutive requests of at most MAX_QUERY_SIMPRINTS query
+// simprints form a round, a request is never split.  A round is ONE search with the lists left on the device and one scoring: a round
+// of one request takes queue_score's pipeline, a round of several queue_score_many's (which returns per request what queue_score would).
+int simprint_score_rounds(H* h, uint32_t table, uint32_t n_req, const uint32_t* req_offsets, const uint64_t* q_words,
+                          uint32_t count, int32_t max_hamming, double threshold, uint32_t limit,
+                          int64_t total_assets, uint32_t dup_limit,
+                          isccsearch_simprint_result* out_results, isccsearch_simprint_chunk* out_chunks,
+                          uint64_t* out_chunk_words, uint32_t* out_info) {
+    std::lock_guard<std::mutex> lk(h->mu);
+    Table* tp;
+    int rc = get_table(h, table, tp);
+    if (rc) return rc;
+    Table& t = *tp;
+    if (t.metric != ISCCSEARCH_METRIC_HAMMING || t.key_words != 2)
+        return fail(-EINVAL, "simprint scoring is defined for fixed-length (Hamming) tables with 128-bit chunk-pointer keys");
+    Segment& s = t.seg[t.max_bytes];
+    if (s.n == 0) return 0;
+    if (s.n > 0xFFFFFFFFull) return fail(-E2BIG, "simprint scoring addresses rows with 32 bits; the table holds %llu", (unsigned long long)s.n);
+    HIPOK(hipSetDevice(h->device));
+    const uint32_t k = count, bits = 8 * (uint32_t)t.max_bytes, W = (uint32_t)t.max_words;
+    int h_max = -1;
+    if ((rc = simprint_setup(h, t, s, threshold, total_assets, dup_limit, h_max))) return rc;
+    std::vector<uint32_t>& qbeg = h->h_sp_qbeg;
+    std::vector<uint32_t>& q_count = h->h_sp_qcount;
+    for (uint32_t r0 = 0; r0 < n_req;) {
+        const uint32_t base = req_offsets[r0];
+        uint32_t r1 = r0 + 1;
+        while (r1 < n_req && req_offsets[r1 + 1] - base <= isksp::MAX_QUERY_SIMPRINTS) ++r1;
+        const uint32_t nq = req_offsets[r1] - base, nr = r1 - r0;
+        const uint64_t* const qw = q_words + (size_t)base * t.max_words;
+        if (nq == 0) { r0 = r1; continue; }
+        h->stats.searches += 1;
+        if ((rc = simprint_buffers(h, nq, k, 0))) return rc;
+        q_count.assign(nq, 0);
+        ScoreSink sink;
+        sink.h_max = h_max;
+        sink.dup_limit = dup_limit;
+        sink.q_count = q_count.data();
+        simprint_bind(h, sink.buf);
+        if ((rc = search_locked(h, table, nq, qw, nullptr, k, max_hamming < 0 ? -1 : max_hamming, SearchOut::to_sink(&sink)))) return rc;
+        uint32_t words = 0;                // LDS words of the score kernel: the most 64-bit words one request's range touches
+        qbeg.resize(nr + 1);
+        for (uint32_t r = 0; r < nr; ++r) {
+            const uint32_t qb = req_offsets[r0 + r] - base, qe = req_offsets[r0 + r + 1] - base;
+            qbeg[r] = qb;
+            uint32_t longest = 0;
+            for (uint32_t q = qb; q < qe; ++q) longest = std::max(longest, q_count[q]);
+            out_info[4 * (size_t)(r0 + r) + 2] = longest;
+            if (qe > qb) words = std::max(words, ((qe - 1) >> 6) - (qb >> 6) + 1);
+        }
+        qbeg[nr] = nq;
+        const uint32_t entries = sink.entries;
+        if (entries == 0) { r0 = r1; continue; }
+        if (sink.unknown_any && (rc = simprint_unknown_freq(h, table, t, nq, qw, dup_limit))) return rc;
+        const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)nr * limit, entries);
+        if ((rc = simprint_buffers(h, nq, k, entries))) return rc;
+        if (nr == 1) {
+            if ((rc = h->d_sp_temp.ensure(isksp::sort_temp_bytes(entries)))) return rc;
+        } else {
+            for (int i = 0; i < 2; ++i) {
+                if ((rc = h->d_spm_req[i].ensure(entries))) return rc;
+                if ((rc = h->d_spm_idx[i].ensure(entries))) return rc;
+            }
+            if ((rc = h->d_spm_qbeg.ensure(nr + 1))) return rc;
+            if ((rc = h->d_spm_nassets.ensure(nr))) return rc;
+            if ((rc = h->d_spm_astart.ensure(nr + 1))) return rc;
+            if ((rc = h->d_spm_estart.ensure(nr + 1))) return rc;
+            if ((rc = h->d_spm_cnt.ensure(cap))) return rc;
+            if ((rc = h->d_spm_cpos.ensure(cap))) return rc;
+            if ((rc = h->d_sp_temp.ensure(isksp::many_temp_bytes(entries, cap)))) return rc;
+        }
+        simprint_bind(h, sink.buf);
+        // outputs in pinned memory, written by the emit kernels themselves, compact: {info[nr][4] | results[cap] | chunks | chunk words}
+        const size_t res_off = ((size_t)nr * 16 + 15) / 16 * 16, chunk_off = res_off + (size_t)cap * sizeof(isccsearch_simprint_result);
+        const size_t chunk_cap = out_chunks ? (size_t)std::min<uint64_t>((uint64_t)limit * nq, entries) : 0;
+        const size_t words_off = chunk_off + chunk_cap * sizeof(isccsearch_simprint_chunk);
+        if ((rc = h->p_sp_out.ensure(words_off + chunk_cap * W * 8))) return rc;
+        unsigned char* const po = h->p_sp_out.p;
+        isksp::ScoreArgs sa{};
+        sa.nq = nq; sa.k = k; sa.entries = entries; sa.limit = limit;
+        sa.sim_tab = h->d_sp_tab.p; sa.idf_tab = h->d_sp_tab.p + bits + 1; sa.dup_limit = dup_limit;
+        sa.freq_col = dup_limit ? s.freq : nullptr;
+        set_cols(sa.col, s, s.W);
+        sa.W = W;
+        sa.out_info = reinterpret_cast<uint32_t*>(po);
+        sa.out_results = reinterpret_cast<isccsearch_simprint_result*>(po + res_off);
+        sa.out_chunks = out_chunks ? reinterpret_cast<isccsearch_simprint_chunk*>(po + chunk_off) : nullptr;
+        sa.out_chunk_words = out_chunks ? reinterpret_cast<uint64_t*>(po + words_off) : nullptr;
+        if (nr == 1) {
+            HIPOK(isksp::queue_score(sink.buf, sa, h->stream));
+        } else {
+            isksp::ManyBuffers mb{};
+            for (int i = 0; i < 2; ++i) { mb.req[i] = h->d_spm_req[i].p; mb.idx[i] = h->d_spm_idx[i].p; }
+            mb.qbeg = h->d_spm_qbeg.p; mb.n_assets = h->d_spm_nassets.p; mb.a_start = h->d_spm_astart.p; mb.e_start = h->d_spm_estart.p;
+            mb.cnt = h->d_spm_cnt.p; mb.c_pos = h->d_spm_cpos.p;
+            HIPOK(hipMemcpyAsync(mb.qbeg, qbeg.data(), (size_t)(nr + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+            isksp::ScoreManyArgs ma{sa, nr, cap, words};
+            HIPOK(isksp::queue_score_many(sink.buf, mb, ma, h->stream));
+        }
+        HIPOK(hipStreamSynchronize(h->stream));       // (qbeg is read by the kernels until here)
+        // into the caller's regions: request r's results at r x limit, its chunks at limit x req_offsets[r]
+        const uint32_t* info = reinterpret_cast<const uint32_t*>(po);
+        size_t res_at = 0, chunk_at = 0;
+        for (uint32_t r = 0; r < nr; ++r) {
+            const uint32_t n = info[4 * r], c = info[4 * r + 3];
+            uint32_t* oi = out_info + 4 * (size_t)(r0 + r);
+            oi[0] = n; oi[1] = info[4 * r + 1]; oi[3] = c;
+            memcpy(out_results + (size_t)(r0 + r) * limit, po + res_off + res_at * sizeof(isccsearch_simprint_result), (size_t)n * sizeof(isccsearch_simprint_result));
+            if (out_chunks && c) {
+                const size_t dst = (size_t)limit * req_offsets[r0 + r];
+                memcpy(out_chunks + dst, po + chunk_off + chunk_at * sizeof(isccsearch_simprint_chunk), (size_t)c * sizeof(isccsearch_simprint_chunk));
+                memcpy(out_chunk_words + dst * W, po + words_off + chunk_at * W * 8, (size_t)c * W * 8);
+            }
+            res_at += n;
+            chunk_at += c;
+        }
+        r0 = r1;
+    }
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+// Search + asset scoring with the neighbour lists kept on the device (usearch_core.py:137-269); see include/isccsearch.h.
+int isccsearch_simprint_score(isccsearch_handle* h, uint32_t table, uint32_t nq, const uint64_t* q_words,
+                              uint32_t count, int32_t max_hamming, double threshold, uint32_t limit,
+                              int64_t total_assets, uint32_t dup_limit,
+                              isccsearch_simprint_result* out_results, isccsearch_simprint_chunk* out_chunks,
+                              uint64_t* out_chunk_words, uint32_t* out_info) {
+    if (!h) return fail(-EINVAL, "handle is NULL");
+    if (int rc = check_count(count)) return rc;
+    if (max_hamming > 256) return fail(-EINVAL, "max_hamming %d exceeds 256", max_hamming);
+    if (dup_limit > ISCCSEARCH_MAX_K) return fail(-EINVAL, "dup_limit %u exceeds ISCCSEARCH_MAX_K (%d)", dup_limit, ISCCSEARCH_MAX_K);
+    if (limit < 1) return fail(-EINVAL, "limit must be >= 1");
+    if (!out_info) return fail(-EINVAL, "NULL argument");
+    out_info[0] = out_info[1] = out_info[2] = out_info[3] = 0;
+    if (nq == 0) return 0;
+    if (!q_words || !out_results || (out_chunks == nullptr) != (out_chunk_words == nullptr)) return fail(-EINVAL, "NULL argument");
+    if (nq > isksp::MAX_QUERY_SIMPRINTS) return fail(-E2BIG, "%u query simprints exceed the %u one scoring call takes", nq, isksp::MAX_QUERY_SIMPRINTS);
+    if (!(threshold == threshold)) return fail(-EINVAL, "threshold is not a number");
+    const uint32_t req_offsets[2] = {0, nq};
+    return simprint_score_rounds(h, table, 1, req_offsets, q_words, count, max_hamming, threshold, limit, total_assets, dup_limit,
+                                 out_results, out_chunks, out_chunk_words, out_info);
+}
+
+// Many simprint requests against one table, each scored on its own (usearch_core.py:137-269 per request); see include/isccsearch.h.
+int isccsearch_simprint_score_many(isccsearch_handle* h, uint32_t table, uint32_t n_req, const uint32_t* req_offsets, const uint64_t* q_words,
+                                   uint32_t count, int32_t max_hamming, double threshold, uint32_t limit,
+                                   int64_t total_assets, uint32_t dup_limit,
+                                   isccsearch_simprint_result* out_results, isccsearch_simprint_chunk* out_chunks,
+                                   uint64_t* out_chunk_words, uint32_t* out_info) {
+    if (!h) return fail(-EINVAL, "handle is NULL");
+    if (int rc = check_count(count)) return rc;
+    if (max_hamming > 256) return fail(-EINVAL, "max_hamming %d exceeds 256", max_hamming);
+    if (dup_limit > ISCCSEARCH_MAX_K) return fail(-EINVAL, "dup_limit %u exceeds ISCCSEARCH_MAX_K (%d)", dup_limit, ISCCSEARCH_MAX_K);
+    if (limit < 1) return fail(-EINVAL, "limit must be >= 1");
+    if (n_req == 0) return 0;
+    if (!out_info || !req_offsets) return fail(-EINVAL, "NULL argument");
+    memset(out_info, 0, (size_t)n_req * 4 * sizeof(uint32_t));
+    for (uint32_t r = 0; r < n_req; ++r) {
+        if (req_offsets[r + 1] < req_offsets[r]) return fail(-EINVAL, "req_offsets must not decrease (request %u)", r);
+        if (req_offsets[r + 1] - req_offsets[r] > isksp::MAX_QUERY_SIMPRINTS)
+            return fail(-E2BIG, "request %u: %u query simprints exceed the %u one scoring call takes", r, req_offsets[r + 1] - req_offsets[r], isksp::MAX_QUERY_SIMPRINTS);
+    }
+    if (req_offsets[n_req] == req_offsets[0]) return 0;
+    if (!q_words || !out_results || (out_chunks == nullptr) != (out_chunk_words == nullptr)) return fail(-EINVAL, "NULL argument");
+    if ((uint64_t)limit * n_req > 0xFFFFFFFFull || (uint64_t)limit * req_offsets[n_req] > 0xFFFFFFFFull)
+        return fail(-E2BIG, "limit %u x %u requests exceeds the 32-bit result addressing", limit, n_req);
+    if (!(threshold == threshold)) return fail(-EINVAL, "threshold is not a number");
+    return simprint_score_rounds(h, table, n_req, req_offsets, q_words, count, max_hamming, threshold, limit, total_assets, dup_limit,
+                                 out_results, out_chunks, out_chunk_words, out_info);
+}
+
+// Hard-boundary simprint search with its scoring on the device (lmdb_ops.py:169-301); see include/isccsearch.h.
+int isccsearch_simprint_exact(isccsearch_handle* h, uint32_t table, uint32_t n_distinct, const uint64_t* q_words,
+                              uint32_t n_given, const uint32_t* given, uint32_t queried, uint32_t dup_limit, double threshold, uint32_t limit,
+                              isccsearch_simprint_result* out_results, isccsearch_simprint_chunk* out_chunks, uint32_t* out_info) {
+    if (!h) return fail(-EINVAL, "handle is NULL");
+    if (dup_limit < 1) return fail(-EINVAL, "dup_limit must be >= 1");
+    if (limit < 1) return fail(-EINVAL, "limit must be >= 1");
+    if (!out_info) return fail(-EINVAL, "NULL argument");
+    out_info[0] = out_info[1] = out_info[2] = out_info[3] = 0;
+    if (n_distinct == 0 || n_given == 0) return 0;
+    if (!q_words || !given || !out_results) return fail(-EINVAL, "NULL argument");
+    if (n_distinct > isksp::MAX_QUERY_SIMPRINTS || n_given > isksp::MAX_QUERY_SIMPRINTS)
+        return fail(-E2BIG, "%u / %u query simprints exceed the %u one scoring call takes", n_distinct, n_given, isksp::MAX_QUERY_SIMPRINTS);
+    if (queried < n_given) return fail(-EINVAL, "queried (%u) counts every query simprint as given: it cannot be below n_given (%u)", queried, n_given);
+    if (!(threshold == threshold)) return fail(-EINVAL, "threshold is not a number");
+    for (uint32_t g = 0; g < n_given; ++g)
+        if (given[g] >= n_distinct) return fail(-EINVAL, "given[%u] = %u is no index into the %u distinct simprints", g, given[g], n_distinct);
+    std::lock_guard<std::mutex> lk(h->mu);
+    Table* tp;
+    int rc = get_table(h, table, tp);
+    if (rc) return rc;
+    Table& t = *tp;
+    if (t.metric != ISCCSEARCH_METRIC_HAMMING || t.key_words != 2)
+        return fail(-EINVAL, "simprint scoring is defined for fixed-length (Hamming) tables with 128-bit chunk-pointer keys");
+    Segment& s = t.seg[t.max_bytes];
+    if (s.n == 0) return 0;
+    HIPOK(hipSetDevice(h->device));
+    h->stats.searches += 1;
+    const uint32_t k = std::min<uint32_t>(dup_limit, ISCCSEARCH_MAX_K), nd = n_distinct, ng = n_given;
+    if ((rc = h->d_sp_rec.ensure((size_t)nd * k))) return rc;
+    if ((rc = h->d_sp_cnt.ensure(nd))) return rc;
+    if ((rc = h->d_sp_freqq.ensure(nd))) return rc;
+    if ((rc = h->d_sp_dofg.ensure(ng))) return rc;
+    if ((rc = h->d_sp_nbest.ensure(ng))) return rc;
+    if ((rc = h->d_sp_unknown.ensure(ng))) return rc;
+    if ((rc = h->d_sp_offs.ensure(ng))) return rc;
+    if ((rc = h->d_sp_nassets.ensure(1))) return rc;
+    ScoreSink sink;
+    sink.exact = true;
+    simprint_bind(h, sink.buf);
+    // (the lookup of every given simprint goes up first: when one batch holds all lookups, hits and offsets are prepared behind its
+    //  select and the number of entries arrives with the batch's own synchronisation)
+    HIPOK(hipMemcpyAsync(h->d_sp_dofg.p, given, (size_t)ng * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPOK(hipStreamSynchronize(h->stream));           // (`given` is the caller's memory)
+    sink.d_of_g = h->d_sp_dofg.p; sink.nd = nd; sink.ng = ng;
+    // every row equal to a query simprint, ascending key, at most dup_limit per simprint (lmdb_ops.py:197-210): the lists stay on the device
+    if ((rc = search_locked(h, table, nd, q_words, nullptr, k, 0, SearchOut::to_sink(&sink)))) return rc;
+    out_info[2] = sink.max_count;
+    uint32_t entries = sink.entries;
+    if (!sink.prepared) {
+        // several batches of lookups: hits per given simprint and their offsets now; the number of entries comes back with one small copy
+        if ((rc = h->d_block.ensure(isksp::INFO_WORDS * sizeof(uint32_t)))) return rc;
+        if ((rc = h->p_block.ensure(isksp::INFO_WORDS * sizeof(uint32_t)))) return rc;
+        uint32_t* const d_info = reinterpret_cast<uint32_t*>(h->d_block.p);
+        HIPOK(isksp::exact_prepare(sink.buf, h->d_sp_cnt.p, h->d_sp_dofg.p, nd, ng, k, d_info, h->stream));
+        HIPOK(hipMemcpyAsync(h->p_block.p, d_info, isksp::INFO_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPOK(hipStreamSynchronize(h->stream));
+        entries = reinterpret_cast<const uint32_t*>(h->p_block.p)[0];
+    }
+    if (entries == 0) return 0;
+    for (int i = 0; i < 2; ++i) {
+        if ((rc = h->d_sp_asset[i].ensure(entries))) return rc;
+        if ((rc = h->d_sp_entry[i].ensure(entries))) return rc;
+        if ((rc = h->d_sp_score[i].ensure(entries))) return rc;
+        if ((rc = h->d_sp_order[i].ensure(entries))) return rc;
+    }
+    if ((rc = h->d_sp_matches.ensure(entries))) return rc;
+    if ((rc = h->d_sp_temp.ensure(isksp::sort_temp_bytes(entries)))) return rc;
+    simprint_bind(h, sink.buf);
+    const size_t res_off = 16, chunk_off = res_off + (size_t)limit * sizeof(isccsearch_simprint_result);
+    const size_t chunk_cap = out_chunks ? entries : 0;
+    if ((rc = h->p_sp_out.ensure(chunk_off + chunk_cap * sizeof(isccsearch_simprint_chunk)))) return rc;
+    unsigned char* const po = h->p_sp_out.p;
+    isksp::ExactArgs ea{};
+    ea.nd = nd; ea.ng = ng; ea.k = k; ea.entries = entries; ea.limit = limit; ea.queried = queried;
+    ea.d_of_g = h->d_sp_dofg.p; ea.threshold = threshold;
+    ea.out_info = reinterpret_cast<uint32_t*>(po);
+    ea.out_results = reinterpret_cast<isccsearch_simprint_result*>(po + res_off);
+    ea.out_chunks = out_chunks ? reinterpret_cast<isccsearch_simprint_chunk*>(po + chunk_off) : nullptr;
+    HIPOK(isksp::queue_exact(sink.buf, ea, h->stream));
+    HIPOK(hipStreamSynchronize(h->stream));
+    const uint32_t* info = reinterpret_cast<const uint32_t*>(po);
+    out_info[0] = info[0]; out_info[1] = info[1]; out_info[3] = info[3];
+    memcpy(out_results, po + res_off, (size_t)info[0] * sizeof(isccsearch_simprint_result));
+    if (out_chunks) memcpy(out_chunks, po + chunk_off, (size_t)info[3] * sizeof(isccsearch_simprint_chunk));
+    return 0;
+}
+}  // extern "C"

@@ -1,4 +1,4 @@
-// Simprint asset scoring on the device (internal interface between isccsearch.hip and simprint_score.hip).
+// Simprint asset scoring on the device (internal interface between isccsearch.hip -- search_api.hip.h, simprint_api.hip.h -- and simprint_score.hip).
 //
 // What UsearchSimprintIndex.search_raw does AFTER its batched neighbour search
 // (iscc_search/indexes/simprint/usearch_core.py:171-269): threshold on the distance, best chunk per (asset, query
