@@ -336,9 +336,9 @@ using H = isccsearch_handle;
 //  and every extra variant costs build time
 template <int W, bool MASK, int TQ>
 void launch_scan_mode(int mode, dim3 grid, hipStream_t st, const isk::ScanParams& p) {
-    if (mode == isk::MODE_COLLECT) hipLaunchKernelGGL((isk::scan_kernel<W, MASK, TQ, isk::MODE_COLLECT, true>), grid, dim3(isk::BLOCK), 0, st, p);
-    else if (mode == isk::MODE_STRETCH) hipLaunchKernelGGL((isk::scan_kernel<W, MASK, TQ, isk::MODE_STRETCH, true>), grid, dim3(isk::BLOCK), 0, st, p);
-    else hipLaunchKernelGGL((isk::scan_kernel<W, MASK, TQ, isk::MODE_BOTH, true>), grid, dim3(isk::BLOCK), 0, st, p);
+    if (mode == isk::MODE_COLLECT) hipLaunchKernelGGL((isk::scan_kernel<W, MASK, TQ, isk::MODE_COLLECT>), grid, dim3(isk::BLOCK), 0, st, p);
+    else if (mode == isk::MODE_STRETCH) hipLaunchKernelGGL((isk::scan_kernel<W, MASK, TQ, isk::MODE_STRETCH>), grid, dim3(isk::BLOCK), 0, st, p);
+    else hipLaunchKernelGGL((isk::scan_kernel<W, MASK, TQ, isk::MODE_BOTH>), grid, dim3(isk::BLOCK), 0, st, p);
 }
 template <int W, bool MASK>
 void launch_scan_tq(int tq, int mode, dim3 grid, hipStream_t st, const isk::ScanParams& p) {

@@ -4,7 +4,7 @@
 // launches one join_scan_kernel per pair of segments (one segment per code length); a pair of
 // segments (la <= lb bytes) compares W = ceil(la/8) words, the partial last word masked as the scans mask it.
 //
-// join_scan_kernel<W, MASK>: the XOR + popcount scan of kernels.hip.h with a tile of the table's own rows as its queries.
+// join_scan_kernel<W, MASK>: the XOR + popcount scan of valu_scan_kernel.hip.h with a tile of the table's own rows as its queries.
 //   grid = one block per group of TQ rows of side A (wave-uniform, in SGPRs); every block streams side B once, each lane
 //   holding 2*U rows per slab in VGPRs.  Within one segment (A == B) only pairs row_a < row_b count, and a block starts
 //   streaming at the slab of its first row: no block is launched without a pair to look at.
@@ -20,7 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "kernels.hip.h"
+#include "valu_scan_kernel.hip.h"
 
 namespace isk {
 
@@ -108,10 +108,7 @@ __global__ __launch_bounds__(BLOCK) void join_scan_kernel(const JoinParams p) {
     // be unrolled): count, one atomic per wave, write.
     auto emit = [&](const u32x4 (&v)[U][W], uint32_t s) {
         u32x4 r[U][W];
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int w = 0; w < W; ++w) { r[u][w] = v[u][w]; asm volatile("" : "+v"(r[u][w])); }
+        launder_rows(r, v);
         const uint64_t base = (uint64_t)s * SLAB + lrow;
         auto a_row = [&](uint64_t i, uint32_t (&al)[W], uint32_t (&ah)[W]) {
 #pragma unroll

@@ -300,7 +300,7 @@ __global__ __launch_bounds__(MBLOCK, 3) void mfma_pack_kernel(const ScanParams p
     };
     // DEPTH > 1: the loads are issued from inline asm and retired by COUNTED waits, so that DEPTH steps of rows stay in flight.
     // (Left to hipcc, every step began with s_waitcnt vmcnt(0) and a copy of the whole row-register array: nothing was in flight
-    //  while a step computed, and 17..64 queries scanned at 3.4 TB/s.)  Same discipline as load_tile_asm (kernels.hip.h), checked
+    //  while a step computed, and 17..64 queries scanned at 3.4 TB/s.)  Same discipline as load_tile_asm (valu_scan_kernel.hip.h), checked
     // at build time by tools/audit_kernels.py: nothing touches a destination between its load and its wait; `s_nop 4` in front
     // (a VALU-written SGPR base needs 5 wait states before a VMEM instruction reads it); no spills in this kernel.
     const uint32_t lane_bytes = lane * 16;

@@ -1,6 +1,6 @@
 // mfma_scan.hip -- the collect scan for LARGE query batches on the matrix cores of gfx950 (MI355X).
 //
-// Same contract as scan_kernel (kernels.hip.h): for every row of [row_begin, n_rows) and every query, append
+// Same contract as scan_kernel (valu_scan_kernel.hip.h): for every row of [row_begin, n_rows) and every query, append
 // (hamming, row) to the query's candidate list when hamming over the compared prefix <= tau_q
 // (reference call sites: iscc_search/indexes/usearch/index.py:2037, iscc_search/indexes/simprint/usearch_core.py:165;
 // metric: docs/explanation/similarity-search.md:24-29).  What differs is the arithmetic:

@@ -1,0 +1,93 @@
+// table_kernels.hip.h -- upkeep of the column store: synthetic fill, row moves, row gathers, the ingest split, u32 gathers.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "scan_params.hip.h"
+
+namespace isk {
+
+__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ULL;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
+    return x ^ (x >> 31);
+}
+
+struct FillParams {
+    uint64_t* col[4];
+    uint64_t* keys;
+    uint64_t dst_row;      // first destination row in the segment
+    uint64_t n;
+    uint64_t seed, first_row, key_base;
+    uint32_t W, KW;
+    uint64_t mask_last;    // codes shorter than W words keep zero padding
+};
+__global__ __launch_bounds__(BLOCK) void fill_kernel(const FillParams p) {
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < p.n; i += (uint64_t)gridDim.x * BLOCK) {
+        const uint64_t src = p.first_row + i;
+        for (uint32_t w = 0; w < p.W; ++w) {
+            uint64_t v = splitmix64(p.seed + 4 * src + w);
+            if (w == p.W - 1) v &= p.mask_last;
+            p.col[w][p.dst_row + i] = v;
+        }
+        if (p.KW == 2) { p.keys[2 * (p.dst_row + i)] = 0; p.keys[2 * (p.dst_row + i) + 1] = p.key_base + src; }
+        else p.keys[p.dst_row + i] = p.key_base + src;
+    }
+}
+
+// sequential row moves (swap-with-last removal): lane c owns column c for every move, in order
+struct MoveParams {
+    uint64_t* col[4];
+    uint64_t* keys;
+    const uint64_t* moves;   // [n_moves][2] = (dst, src)
+    uint64_t n_moves;
+    uint32_t W, KW;
+};
+__global__ void move_rows_kernel(const MoveParams p) {
+    const uint32_t c = threadIdx.x;
+    if (c < p.W) {
+        uint64_t* col = p.col[c];
+        for (uint64_t m = 0; m < p.n_moves; ++m) col[p.moves[2 * m]] = col[p.moves[2 * m + 1]];
+    } else if (c < p.W + p.KW) {
+        const uint32_t kw = c - p.W;
+        for (uint64_t m = 0; m < p.n_moves; ++m) p.keys[p.moves[2 * m] * p.KW + kw] = p.keys[p.moves[2 * m + 1] * p.KW + kw];
+    }
+}
+
+struct GatherParams {
+    const uint64_t* col[4];
+    const uint64_t* rows;    // [n]
+    uint64_t* out;           // [n][W]
+    uint64_t n;
+    uint32_t W;
+};
+__global__ __launch_bounds__(BLOCK) void gather_rows_kernel(const GatherParams p) {
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < p.n; i += (uint64_t)gridDim.x * BLOCK)
+        for (uint32_t w = 0; w < p.W; ++w) p.out[i * p.W + w] = p.col[w][p.rows[i]];
+}
+
+// ingest: rows handed over row-major [n][MW] -> the segment's word columns (the last kept word masked to the code length)
+struct SplitParams {
+    uint64_t* col[4];
+    const uint64_t* rows;    // [n][MW]
+    uint64_t dst_row, n;
+    uint32_t W, MW;
+    uint64_t mask_last;
+};
+__global__ __launch_bounds__(BLOCK) void split_rows_kernel(const SplitParams p) {
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < p.n; i += (uint64_t)gridDim.x * BLOCK)
+        for (uint32_t w = 0; w < p.W; ++w) {
+            uint64_t v = p.rows[i * p.MW + w];
+            if (w == p.W - 1) v &= p.mask_last;
+            p.col[w][p.dst_row + i] = v;
+        }
+}
+
+// out[i] = src[rows[i]]  (document-frequency column lookups)
+__global__ __launch_bounds__(BLOCK) void gather_u32_kernel(const uint32_t* src, const uint64_t* rows, uint32_t* out, uint64_t n) {
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (uint64_t)gridDim.x * BLOCK) out[i] = src[rows[i]];
+}
+
+}  // namespace isk

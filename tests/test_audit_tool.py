@@ -10,7 +10,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOOL = os.path.join(ROOT, "tools", "audit_kernels.py")
 
-RES = """remark: Function Name: _ZN3isk11scan_kernelILi1ELb0ELi8ELi0ELb1EEEvNS_10ScanParamsE
+RES = """remark: Function Name: _ZN3isk11scan_kernelILi1ELb0ELi8ELi0EEEvNS_10ScanParamsE
 remark:     TotalSGPRs: 96
 remark:     VGPRs: 74
 remark:     AGPRs: 0
@@ -20,7 +20,7 @@ remark:     SGPRs Spill: 4
 remark:     VGPRs Spill: {spill}
 """
 
-ASM = """_ZN3isk11scan_kernelILi1ELb0ELi8ELi0ELb1EEEvNS_10ScanParamsE:
+ASM = """_ZN3isk11scan_kernelILi1ELb0ELi8ELi0EEEvNS_10ScanParamsE:
 	s_load_dwordx2 s[0:1], s[4:5], 0x0
 	;;#ASMSTART
 	{nop}
@@ -88,7 +88,7 @@ def test_rejects_missing_wait_state_pad_scratch_and_spills(tmp_path):
 
 # hipcc merges the loop's `break` exits and its back edge into ONE block steered by an SGPR mask; the address arithmetic of
 # the loop-head group may then sit in registers that group's own loads are about to overwrite
-ASM_MERGED = """_ZN3isk11scan_kernelILi1ELb0ELi8ELi0ELb1EEEvNS_10ScanParamsE:
+ASM_MERGED = """_ZN3isk11scan_kernelILi1ELb0ELi8ELi0EEEvNS_10ScanParamsE:
 	;;#ASMSTART
 	s_nop 4
 	global_load_dwordx4 v[2:5], v1, s[0:1] offset:0 nt

@@ -2,7 +2,7 @@
 """
 Build-time audit of the scan kernels (run by ``make -C iscc_search_amd/csrc audit`` and by ``__graft_entry__.build()``).
 
-The XOR + popcount scan issues its streaming loads from inline asm (``load_tile_asm`` in csrc/kernels.hip.h) so that the
+The XOR + popcount scan issues its streaming loads from inline asm (``load_tile_asm`` in csrc/valu_scan_kernel.hip.h) so that the
 prefetch of the next tile stays in flight while the current one is scored.  hipcc neither counts nor orders what is inside
 an asm statement (cdna_hip_programming.md section 5.7), so three invariants are the kernel author's and are checked here:
 

@@ -13,7 +13,7 @@ occ_key = "Occupancy \\[waves/SIMD\\]"
 scr_key = "ScratchSize \\[bytes/lane\\]"
 for b in re.split(r"Function Name: ", txt)[1:]:
     name = b.split()[0]
-    m = re.match(r"_ZN3isk11scan_kernelILi(\d)ELb(\d)ELi(\d+)ELi(\d)ELb1E", name)
+    m = re.match(r"_ZN3isk11scan_kernelILi(\d)ELb(\d)ELi(\d+)ELi(\d)EE", name)
     if m:
         W, MASK, TQ, MODE = m.groups()
     else:

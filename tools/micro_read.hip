@@ -7,7 +7,7 @@
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-template <bool NT, int U>
+template <bool NONTEMPORAL, int U>
 __global__ __launch_bounds__(256) void rd(const uint64_t* __restrict__ col, uint64_t n_tiles, uint32_t* out) {
     u32x4 acc = {0, 0, 0, 0};
     for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
@@ -15,23 +15,23 @@ __global__ __launch_bounds__(256) void rd(const uint64_t* __restrict__ col, uint
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const u32x4* p = reinterpret_cast<const u32x4*>(tb + threadIdx.x * 16u + u * 4096u);
-            u32x4 v = NT ? __builtin_nontemporal_load(p) : *p;
+            u32x4 v = NONTEMPORAL ? __builtin_nontemporal_load(p) : *p;
             acc ^= v;
         }
     }
     if ((acc.x ^ acc.y ^ acc.z ^ acc.w) == 0x12345678u) out[0] = 1;   // keep the loads alive
 }
 
-template <bool NT, int U>
+template <bool NONTEMPORAL, int U>
 void run(const char* name, const uint64_t* d, uint64_t bytes, int blocks) {
     uint32_t* out; hipMalloc(&out, 4);
     uint64_t n_tiles = bytes / (256 * 16 * U);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-    rd<NT, U><<<blocks, 256>>>(d, n_tiles, out);
+    rd<NONTEMPORAL, U><<<blocks, 256>>>(d, n_tiles, out);
     hipDeviceSynchronize();
     const int reps = 20;
     hipEventRecord(e0);
-    for (int i = 0; i < reps; ++i) rd<NT, U><<<blocks, 256>>>(d, n_tiles, out);
+    for (int i = 0; i < reps; ++i) rd<NONTEMPORAL, U><<<blocks, 256>>>(d, n_tiles, out);
     hipEventRecord(e1); hipEventSynchronize(e1);
     float ms; hipEventElapsedTime(&ms, e0, e1);
     printf("%-28s blocks=%5d  %.1f us/pass  %.0f GB/s\n", name, blocks, ms / reps * 1e3, bytes * (double)reps / (ms * 1e-3) / 1e9);
