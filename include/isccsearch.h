@@ -351,6 +351,20 @@ int isccsearch_join_within(isccsearch_handle* h, uint32_t table, const int16_t* 
                            uint64_t capacity, uint64_t* out_keys_a, uint64_t* out_keys_b,
                            uint32_t* out_hamming, uint16_t* out_prefix_bits, uint64_t* out_total);
 
+/* All pairs (row a of table_a, row b of table_b) of TWO tables of one handle whose Hamming distance over their common
+ * prefix of p = min(len_a, len_b) bytes is <= max_hamming[p]: the prefix rule, the masking of a partial last word and the
+ * meaning of max_hamming are those of isccsearch_join_within.  out_keys_a always holds the key from table_a and
+ * out_keys_b the key from table_b (never swapped; a pair of equal keys -- one asset in both tables -- is a pair like any
+ * other), sorted ascending by (key_a, key_b), 128-bit keys compared as (hi, lo) unsigned.  Capacity protocol and device
+ * memory as for isccsearch_join_within: -ENOSPC with *out_total set, and a retry with exactly that capacity succeeds.
+ * -EINVAL: table_a == table_b (isccsearch_join_within joins a table with itself), tables that differ in metric or
+ * key_words, HAMMING tables that differ in max_bytes (NPHD tables may), NULL arguments as for isccsearch_join_within.
+ * No reference counterpart (the reference has no index-wide join, within one index or between two). */
+int isccsearch_join_between(isccsearch_handle* h, uint32_t table_a, uint32_t table_b,
+                            const int16_t* max_hamming /* [33] */, uint64_t capacity,
+                            uint64_t* out_keys_a, uint64_t* out_keys_b,
+                            uint32_t* out_hamming, uint16_t* out_prefix_bits, uint64_t* out_total);
+
 /* Multi-GPU building blocks (row-range shards, one process per GPU).
  * search_device: same search, results left in caller-provided DEVICE memory
  *   d_records[nq*k] (isccsearch_record), d_counts[nq]; queries must share one byte length.

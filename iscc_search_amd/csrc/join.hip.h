@@ -1,8 +1,10 @@
-// join.hip.h -- gfx950 device code of the index-wide self-join (isccsearch_join_within).
+// join.hip.h -- gfx950 device code of the index-wide joins: the self-join of one table (isccsearch_join_within) and the
+// cross join of two tables (isccsearch_join_between).
 //
-// Every unordered pair of distinct rows of one table whose Hamming distance over the common prefix is <= tau.  The host
-// launches one join_scan_kernel per pair of segments (one segment per code length); a pair of
-// segments (la <= lb bytes) compares W = ceil(la/8) words, the partial last word masked as the scans mask it.
+// Every unordered pair of distinct rows of one table -- or every pair (row of table A, row of table B) -- whose Hamming distance
+// over the common prefix is <= tau.  The host launches one join_scan_kernel per pair of segments (one
+// segment per code length); a pair of segments (la, lb bytes) compares W = ceil(min(la, lb)/8) words, the partial last word
+// masked as the scans mask it.
 //
 // join_scan_kernel<W, MASK>: the XOR + popcount scan of valu_scan_kernel.hip.h with a tile of the table's own rows as its queries.
 //   grid = one block per group of TQ rows of side A (wave-uniform, in SGPRs); every block streams side B once, each lane
@@ -13,6 +15,9 @@
 //   its rows against the A rows re-read by scalar loads, drops the pairs that are not pairs (row_b <= row_a, rows past the
 //   end), counts the rest, takes ONE atomic slot range for the wave and writes (key_a < key_b, hamming, prefix bits) with
 //   vector stores.  Pairs past `capacity` are counted and not written.
+// join_scan_kernel<W, MASK, true>: the same scan over segments of two tables.  Only the emit path differs: every (row_a, row_b)
+//   is a pair, and the keys are not ordered -- the key of the side in SGPRs goes to the output column of the table it came
+//   from (JoinEmit::sgpr_side_is_b).  A template parameter, so that the self-join's code does not change.
 // Slabs are read up to the next multiple of the slab size: column capacities are multiples of ROW_ALIGN (2 048 rows), which
 // every slab size divides, so those reads stay inside the allocation (rows past n are dropped in the emit path).
 #pragma once
@@ -37,6 +42,7 @@ struct JoinEmit {
     uint32_t* out_hamming;
     uint16_t* out_prefix_bits;
     uint32_t prefix_bits, kw;
+    uint32_t sgpr_side_is_b;      // cross join: the side in SGPRs is table B, its keys go to out_keys_b (else to out_keys_a)
 };
 struct JoinParams {
     const uint64_t* col_a[4];     // side A: rows held in SGPRs, TQ per block
@@ -57,7 +63,7 @@ template <int W> struct JoinCfg {
 template <int W> constexpr uint32_t join_rows_per_block() { return JoinCfg<W>::TQ; }
 template <int W> constexpr uint32_t join_slab_rows() { return JoinCfg<W>::SLAB; }
 
-template <int W, bool MASK>
+template <int W, bool MASK, bool CROSS = false>
 __global__ __launch_bounds__(BLOCK) void join_scan_kernel(const JoinParams p) {
     constexpr int TQ = JoinCfg<W>::TQ, U = JoinCfg<W>::U;
     constexpr uint32_t SLAB = JoinCfg<W>::SLAB;
@@ -117,7 +123,7 @@ __global__ __launch_bounds__(BLOCK) void join_scan_kernel(const JoinParams p) {
                 al[w] = (uint32_t)x; ah[w] = (uint32_t)(x >> 32);
             }
         };
-        auto is_pair = [&](uint64_t i, uint64_t j, uint32_t h) { return h <= p.tau && j < p.n_b && (!p.same || j > i); };
+        auto is_pair = [&](uint64_t i, uint64_t j, uint32_t h) { return h <= p.tau && j < p.n_b && (CROSS || !p.same || j > i); };
         const JoinEmit& e = *p.e;
         uint32_t c = 0;
         const uint64_t a_end = a0 + TQ < p.n_a ? a0 + TQ : p.n_a;
@@ -161,7 +167,7 @@ __global__ __launch_bounds__(BLOCK) void join_scan_kernel(const JoinParams p) {
                     if (slot < e.capacity) {
                         uint64_t ka_hi = kw == 2 ? e.keys_a[i * 2] : 0, ka_lo = e.keys_a[i * kw + kw - 1];
                         uint64_t kb_hi = kw == 2 ? e.keys_b[j * 2] : 0, kb_lo = e.keys_b[j * kw + kw - 1];
-                        if (kb_hi < ka_hi || (kb_hi == ka_hi && kb_lo < ka_lo)) {
+                        if (CROSS ? e.sgpr_side_is_b != 0 : kb_hi < ka_hi || (kb_hi == ka_hi && kb_lo < ka_lo)) {
                             uint64_t t = ka_hi; ka_hi = kb_hi; kb_hi = t;
                             t = ka_lo; ka_lo = kb_lo; kb_lo = t;
                         }

@@ -1,94 +1,112 @@
-// join_api.hip.h -- isccsearch_join_within: the self-join of a table by the kernel of join.hip.h.
+// join_api.hip.h -- isccsearch_join_within and isccsearch_join_between: the self-join of a table and the cross join of two
+// tables by the kernel of join.hip.h.
 // Needs the store of isccsearch.hip (Segment, Table; get_table of store.hip.h) and its scratch buffers.
 namespace {
-// isccsearch_join_within: one launch of the self-join kernel (join.hip.h)
-template <int W>
+// one launch of the join kernel (join.hip.h)
+template <int W, bool CROSS>
 void launch_join(const isk::JoinParams& jp, bool mask, uint64_t blocks, hipStream_t stream) {
-    if (mask) hipLaunchKernelGGL((isk::join_scan_kernel<W, true>), dim3((uint32_t)blocks), dim3(isk::BLOCK), 0, stream, jp);
-    else hipLaunchKernelGGL((isk::join_scan_kernel<W, false>), dim3((uint32_t)blocks), dim3(isk::BLOCK), 0, stream, jp);
+    if (mask) hipLaunchKernelGGL((isk::join_scan_kernel<W, true, CROSS>), dim3((uint32_t)blocks), dim3(isk::BLOCK), 0, stream, jp);
+    else hipLaunchKernelGGL((isk::join_scan_kernel<W, false, CROSS>), dim3((uint32_t)blocks), dim3(isk::BLOCK), 0, stream, jp);
+}
+template <bool CROSS>
+void launch_join(uint32_t W, const isk::JoinParams& jp, bool mask, uint64_t blocks, hipStream_t stream) {
+    switch (W) {
+        case 1: launch_join<1, CROSS>(jp, mask, blocks, stream); break;
+        case 2: launch_join<2, CROSS>(jp, mask, blocks, stream); break;
+        case 3: launch_join<3, CROSS>(jp, mask, blocks, stream); break;
+        default: launch_join<4, CROSS>(jp, mask, blocks, stream); break;
+    }
 }
 constexpr uint32_t join_rows_per_block(uint32_t W) {
     return W == 1 ? isk::join_rows_per_block<1>() : W == 2 ? isk::join_rows_per_block<2>() : W == 3 ? isk::join_rows_per_block<3>() : isk::join_rows_per_block<4>();
 }
-}  // namespace
 
-// One join_scan_kernel launch per pair of segments (join.hip.h), all appending to one output; the pairs are sorted on the host.
-extern "C" int isccsearch_join_within(isccsearch_handle* h, uint32_t table, const int16_t* max_hamming, uint64_t capacity,
-                           uint64_t* out_keys_a, uint64_t* out_keys_b, uint32_t* out_hamming, uint16_t* out_prefix_bits,
-                           uint64_t* out_total) {
+// One call's launches: one per pair of segments, all appending to one output.  What only the emit path reads goes to the
+// device as one array of descriptors.
+struct JoinPlan {
+    struct Launch { isk::JoinParams jp; uint32_t W; bool mask; uint64_t blocks; };
+    std::vector<Launch> launches;
+    std::vector<isk::JoinEmit> emits;
+    bool cross = false;
+    uint32_t KW = 1;
+    uint64_t capacity = 0, cap_alloc = 1;
+};
+
+int join_check_args(isccsearch_handle* h, const int16_t* max_hamming, uint64_t capacity, uint64_t* out_keys_a, uint64_t* out_keys_b,
+                    uint32_t* out_hamming, uint16_t* out_prefix_bits, uint64_t* out_total) {
     if (!h) return fail(-EINVAL, "handle is NULL");
     if (!max_hamming || !out_total) return fail(-EINVAL, "NULL argument");
     *out_total = 0;
     if (capacity && (!out_keys_a || !out_keys_b || !out_hamming || !out_prefix_bits))
         return fail(-EINVAL, "NULL output array with capacity %llu", (unsigned long long)capacity);
-    std::lock_guard<std::mutex> lk(h->mu);
-    Table* tp;
-    int rc = get_table(h, table, tp);
-    if (rc) return rc;
-    Table& t = *tp;
-    HIPOK(hipSetDevice(h->device));
-    const uint32_t KW = (uint32_t)t.key_words;
-    const uint64_t cap_alloc = std::max<uint64_t>(capacity, 1);
-    if ((rc = h->d_join_keys.ensure(cap_alloc * 2 * KW))) return rc;
-    if ((rc = h->d_join_ham.ensure(cap_alloc))) return rc;
-    if ((rc = h->d_join_pb.ensure(cap_alloc))) return rc;
+    return 0;
+}
+
+// the output buffers of one call and its pair counter, zeroed
+int join_begin(isccsearch_handle* h, JoinPlan& plan, bool cross, uint32_t KW, uint64_t capacity) {
+    plan.cross = cross;
+    plan.KW = KW;
+    plan.capacity = capacity;
+    plan.cap_alloc = std::max<uint64_t>(capacity, 1);
+    int rc;
+    if ((rc = h->d_join_keys.ensure(plan.cap_alloc * 2 * KW))) return rc;
+    if ((rc = h->d_join_ham.ensure(plan.cap_alloc))) return rc;
+    if ((rc = h->d_join_pb.ensure(plan.cap_alloc))) return rc;
     if ((rc = h->d_join_total.ensure(1))) return rc;
     HIPOK(hipMemsetAsync(h->d_join_total.p, 0, 8, h->stream));
-    // one launch per pair of segments (la <= lb: the pair compares la bytes under max_hamming[la]); what only the emit path
-    // reads goes to the device as one array of descriptors
-    struct Launch { isk::JoinParams jp; uint32_t W; bool mask; uint64_t blocks; };
-    std::vector<Launch> launches;
-    std::vector<isk::JoinEmit> emits;
-    for (uint32_t la = 1; la <= ISCCSEARCH_MAX_BYTES; ++la) {
-        if (!t.seg[la].n || max_hamming[la] < 0) continue;
-        for (uint32_t lb = la; lb <= ISCCSEARCH_MAX_BYTES; ++lb) {
-            const bool same = la == lb;
-            if (!t.seg[lb].n || (same && t.seg[la].n < 2)) continue;
-            // side A (one block per TQ rows) is the segment with more rows; side B is streamed by every block
-            Segment& A = t.seg[lb].n > t.seg[la].n ? t.seg[lb] : t.seg[la];
-            Segment& B = &A == &t.seg[la] ? t.seg[lb] : t.seg[la];
-            const uint32_t W = (la + 7) / 8;
-            Launch L{};
-            set_cols(L.jp.col_a, A, W);
-            set_cols(L.jp.col_b, B, W);
-            L.jp.n_a = A.n; L.jp.n_b = B.n;
-            L.jp.mask = mask_for(la);
-            L.jp.tau = (uint32_t)std::min<int>(max_hamming[la], 8 * ISCCSEARCH_MAX_BYTES);
-            L.jp.same = same ? 1u : 0u;
-            isk::JoinEmit e{};
-            e.keys_a = A.keys; e.keys_b = B.keys;
-            e.n_a = A.n;
-            e.capacity = capacity;
-            e.total = reinterpret_cast<unsigned long long*>(h->d_join_total.p);
-            e.out_keys_a = h->d_join_keys.p;
-            e.out_keys_b = h->d_join_keys.p + cap_alloc * KW;
-            e.out_hamming = h->d_join_ham.p;
-            e.out_prefix_bits = h->d_join_pb.p;
-            e.prefix_bits = 8 * la;
-            e.kw = KW;
-            // within one segment the last row pairs with no later one
-            const uint64_t a_rows = same ? A.n - 1 : A.n;
-            L.W = W;
-            L.mask = la % 8 != 0;
-            L.blocks = (a_rows + join_rows_per_block(W) - 1) / join_rows_per_block(W);
-            if (L.blocks >= (1ull << 31) || B.n >= (1ull << 40))
-                return fail(-E2BIG, "segments of %llu x %llu rows exceed the join kernel's grid", (unsigned long long)A.n, (unsigned long long)B.n);
-            launches.push_back(L);
-            emits.push_back(e);
-        }
-    }
-    if (!launches.empty()) {
-        if ((rc = h->d_join_emit.ensure(emits.size()))) return rc;
-        HIPOK(hipMemcpyAsync(h->d_join_emit.p, emits.data(), emits.size() * sizeof(isk::JoinEmit), hipMemcpyHostToDevice, h->stream));
-        for (size_t i = 0; i < launches.size(); ++i) {
-            Launch& L = launches[i];
+    return 0;
+}
+
+// One launch: segment A (one block per TQ rows, the rows in SGPRs) against segment B (streamed by every block) over a common
+// prefix of pbytes bytes under tau.  `same`: A and B are one segment (the self-join keeps row_a < row_b).  `sgpr_side_is_b`:
+// a cross join whose segment A belongs to the call's table_b.
+int join_add(isccsearch_handle* h, JoinPlan& plan, Segment& A, Segment& B, uint32_t pbytes, int tau, bool same, bool sgpr_side_is_b) {
+    const uint32_t W = (pbytes + 7) / 8;
+    JoinPlan::Launch L{};
+    set_cols(L.jp.col_a, A, W);
+    set_cols(L.jp.col_b, B, W);
+    L.jp.n_a = A.n; L.jp.n_b = B.n;
+    L.jp.mask = mask_for(pbytes);
+    L.jp.tau = (uint32_t)std::min<int>(tau, 8 * ISCCSEARCH_MAX_BYTES);
+    L.jp.same = same ? 1u : 0u;
+    isk::JoinEmit e{};
+    e.keys_a = A.keys; e.keys_b = B.keys;
+    e.n_a = A.n;
+    e.capacity = plan.capacity;
+    e.total = reinterpret_cast<unsigned long long*>(h->d_join_total.p);
+    e.out_keys_a = h->d_join_keys.p;
+    e.out_keys_b = h->d_join_keys.p + plan.cap_alloc * plan.KW;
+    e.out_hamming = h->d_join_ham.p;
+    e.out_prefix_bits = h->d_join_pb.p;
+    e.prefix_bits = 8 * pbytes;
+    e.kw = plan.KW;
+    e.sgpr_side_is_b = sgpr_side_is_b ? 1u : 0u;
+    // within one segment the last row pairs with no later one
+    const uint64_t a_rows = same ? A.n - 1 : A.n;
+    L.W = W;
+    L.mask = pbytes % 8 != 0;
+    L.blocks = (a_rows + join_rows_per_block(W) - 1) / join_rows_per_block(W);
+    if (L.blocks >= (1ull << 31) || B.n >= (1ull << 40))
+        return fail(-E2BIG, "segments of %llu x %llu rows exceed the join kernel's grid", (unsigned long long)A.n, (unsigned long long)B.n);
+    plan.launches.push_back(L);
+    plan.emits.push_back(e);
+    return 0;
+}
+
+// The shared tail of both joins: the launches, the total read back, the pairs copied to the host and sorted by (key_a, key_b).
+int join_finish(isccsearch_handle* h, JoinPlan& plan, uint64_t* out_keys_a, uint64_t* out_keys_b, uint32_t* out_hamming,
+                uint16_t* out_prefix_bits, uint64_t* out_total) {
+    const uint32_t KW = plan.KW;
+    const uint64_t capacity = plan.capacity, cap_alloc = plan.cap_alloc;
+    if (!plan.launches.empty()) {
+        int rc;
+        if ((rc = h->d_join_emit.ensure(plan.emits.size()))) return rc;
+        HIPOK(hipMemcpyAsync(h->d_join_emit.p, plan.emits.data(), plan.emits.size() * sizeof(isk::JoinEmit), hipMemcpyHostToDevice, h->stream));
+        for (size_t i = 0; i < plan.launches.size(); ++i) {
+            JoinPlan::Launch& L = plan.launches[i];
             L.jp.e = h->d_join_emit.p + i;
-            switch (L.W) {
-                case 1: launch_join<1>(L.jp, L.mask, L.blocks, h->stream); break;
-                case 2: launch_join<2>(L.jp, L.mask, L.blocks, h->stream); break;
-                case 3: launch_join<3>(L.jp, L.mask, L.blocks, h->stream); break;
-                default: launch_join<4>(L.jp, L.mask, L.blocks, h->stream); break;
-            }
+            if (plan.cross) launch_join<true>(L.W, L.jp, L.mask, L.blocks, h->stream);
+            else launch_join<false>(L.W, L.jp, L.mask, L.blocks, h->stream);
             HIPOK(hipGetLastError());
         }
     }
@@ -127,4 +145,68 @@ extern "C" int isccsearch_join_within(isccsearch_handle* h, uint32_t table, cons
         out_prefix_bits[i] = pb[o];
     }
     return 0;
+}
+}  // namespace
+
+// One join_scan_kernel launch per pair of segments (join.hip.h), all appending to one output; the pairs are sorted on the host.
+extern "C" int isccsearch_join_within(isccsearch_handle* h, uint32_t table, const int16_t* max_hamming, uint64_t capacity,
+                           uint64_t* out_keys_a, uint64_t* out_keys_b, uint32_t* out_hamming, uint16_t* out_prefix_bits,
+                           uint64_t* out_total) {
+    int rc = join_check_args(h, max_hamming, capacity, out_keys_a, out_keys_b, out_hamming, out_prefix_bits, out_total);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(h->mu);
+    Table* tp;
+    if ((rc = get_table(h, table, tp))) return rc;
+    Table& t = *tp;
+    HIPOK(hipSetDevice(h->device));
+    JoinPlan plan;
+    if ((rc = join_begin(h, plan, false, (uint32_t)t.key_words, capacity))) return rc;
+    // one launch per pair of segments (la <= lb: the pair compares la bytes under max_hamming[la])
+    for (uint32_t la = 1; la <= ISCCSEARCH_MAX_BYTES; ++la) {
+        if (!t.seg[la].n || max_hamming[la] < 0) continue;
+        for (uint32_t lb = la; lb <= ISCCSEARCH_MAX_BYTES; ++lb) {
+            const bool same = la == lb;
+            if (!t.seg[lb].n || (same && t.seg[la].n < 2)) continue;
+            // side A (one block per TQ rows) is the segment with more rows; side B is streamed by every block
+            Segment& A = t.seg[lb].n > t.seg[la].n ? t.seg[lb] : t.seg[la];
+            Segment& B = &A == &t.seg[la] ? t.seg[lb] : t.seg[la];
+            if ((rc = join_add(h, plan, A, B, la, max_hamming[la], same, false))) return rc;
+        }
+    }
+    return join_finish(h, plan, out_keys_a, out_keys_b, out_hamming, out_prefix_bits, out_total);
+}
+
+// One join_scan_kernel<W, MASK, true> launch per pair of non-empty segments (la of table_a, lb of table_b), in either order of
+// lengths: the pair compares min(la, lb) bytes.  Both tables live on this handle, so one lock covers the call.
+extern "C" int isccsearch_join_between(isccsearch_handle* h, uint32_t table_a, uint32_t table_b, const int16_t* max_hamming,
+                            uint64_t capacity, uint64_t* out_keys_a, uint64_t* out_keys_b, uint32_t* out_hamming,
+                            uint16_t* out_prefix_bits, uint64_t* out_total) {
+    int rc = join_check_args(h, max_hamming, capacity, out_keys_a, out_keys_b, out_hamming, out_prefix_bits, out_total);
+    if (rc) return rc;
+    if (table_a == table_b) return fail(-EINVAL, "join_between needs two tables (table %u given twice): isccsearch_join_within joins a table with itself", table_a);
+    std::lock_guard<std::mutex> lk(h->mu);
+    Table *ta, *tb;
+    if ((rc = get_table(h, table_a, ta))) return rc;
+    if ((rc = get_table(h, table_b, tb))) return rc;
+    if (ta->metric != tb->metric) return fail(-EINVAL, "tables %u and %u differ in metric (%d, %d)", table_a, table_b, ta->metric, tb->metric);
+    if (ta->key_words != tb->key_words)
+        return fail(-EINVAL, "tables %u and %u differ in key_words (%d, %d)", table_a, table_b, ta->key_words, tb->key_words);
+    if (ta->metric == ISCCSEARCH_METRIC_HAMMING && ta->max_bytes != tb->max_bytes)
+        return fail(-EINVAL, "Hamming tables %u and %u hold codes of different lengths (%d, %d bytes)", table_a, table_b, ta->max_bytes, tb->max_bytes);
+    HIPOK(hipSetDevice(h->device));
+    JoinPlan plan;
+    if ((rc = join_begin(h, plan, true, (uint32_t)ta->key_words, capacity))) return rc;
+    for (uint32_t la = 1; la <= ISCCSEARCH_MAX_BYTES; ++la) {
+        if (!ta->seg[la].n) continue;
+        for (uint32_t lb = 1; lb <= ISCCSEARCH_MAX_BYTES; ++lb) {
+            const uint32_t p = std::min(la, lb);
+            if (!tb->seg[lb].n || max_hamming[p] < 0) continue;
+            // as in the self-join the segment with more rows goes into SGPRs: that may be table B's
+            const bool b_in_sgprs = tb->seg[lb].n > ta->seg[la].n;
+            Segment& A = b_in_sgprs ? tb->seg[lb] : ta->seg[la];
+            Segment& B = b_in_sgprs ? ta->seg[la] : tb->seg[lb];
+            if ((rc = join_add(h, plan, A, B, p, max_hamming[p], false, b_in_sgprs))) return rc;
+        }
+    }
+    return join_finish(h, plan, out_keys_a, out_keys_b, out_hamming, out_prefix_bits, out_total);
 }

@@ -386,16 +386,33 @@ class HipTable:
         sorted by (key_a, key_b).  One library call with room for ``min(max_pairs, 2^20)`` pairs, retried once with exactly
         the total when more were found.  More than ``max_pairs`` pairs raise ValueError: the cap is never applied silently.
         """
+        return self._join("isccsearch_join_within", (self.id,), max_hamming_by_prefix, max_pairs)
+
+    def join_between(self, other, max_hamming_by_prefix, max_pairs):
+        # type: (HipTable, object, int) -> tuple
+        """
+        Every pair (row a of this table, row b of ``other``) within ``max_hamming_by_prefix[p]`` bits over their common prefix of
+        p bytes, as ``join_within`` defines it: ``(keys_a, keys_b, hamming, prefix_bits)`` with keys_a from this table and keys_b
+        from ``other`` (never swapped; equal keys are a pair like any other), sorted by (key_a, key_b).  Capacity, the one retry
+        and ``max_pairs`` as for ``join_within``.  Both tables must belong to one engine.
+        """
+        if getattr(other, "engine", None) is not self.engine:
+            raise ValueError("join_between needs two tables of one engine: the other table belongs to another engine")
+        return self._join("isccsearch_join_between", (self.id, other.id), max_hamming_by_prefix, max_pairs)
+
+    def _join(self, symbol, tables, max_hamming_by_prefix, max_pairs):
+        # type: (str, tuple, object, int) -> tuple
+        """One join call of the library, retried once with exactly the reported total when that did not fit."""
         mh = np.ascontiguousarray(max_hamming_by_prefix, dtype=np.int16)
         if mh.shape != (_lib.MAX_BYTES + 1,):
             raise ValueError(f"max_hamming_by_prefix must have {_lib.MAX_BYTES + 1} entries (prefix bytes 0..{_lib.MAX_BYTES})")
-        lib = self.engine._lib
+        call = getattr(self.engine._lib, symbol)
         total = ctypes.c_uint64()
         capacity = min(int(max_pairs), 1 << 20)
         for attempt in range(2):
             kshape = (capacity, 2) if self.key_words == 2 else (capacity,)
             out = (np.empty(kshape, np.uint64), np.empty(kshape, np.uint64), np.empty(capacity, np.uint32), np.empty(capacity, np.uint16))
-            rc = lib.isccsearch_join_within(self.engine.handle, self.id, _lib.ptr(mh), capacity, *(_lib.ptr(a) for a in out), ctypes.byref(total))
+            rc = call(self.engine.handle, *tables, _lib.ptr(mh), capacity, *(_lib.ptr(a) for a in out), ctypes.byref(total))
             n = int(total.value)
             if n > max_pairs:
                 raise ValueError(f"{n} pairs exceed max_pairs={max_pairs}")
@@ -404,7 +421,7 @@ class HipTable:
                 continue
             _lib.check(rc)
             return tuple(a[:n] for a in out)
-        raise RuntimeError("isccsearch_join_within: the retry with the reported total did not fit")
+        raise RuntimeError(f"{symbol}: the retry with the reported total did not fit")
 
     def doc_freq(self, q_words, q_nbytes=None, dup_limit=1000):
         # type: (np.ndarray, np.ndarray | None, int) -> np.ndarray

@@ -197,6 +197,54 @@ class DuplicatePair:
     types: Dict[str, float]   # the confident unit scores, in the unit order of asset a
 
 
+@dataclass
+class IndexMatch:
+    """One pair of ``find_matches``: ``score`` and ``types`` as ``search_assets`` on the other index by asset a's units lists asset b."""
+
+    iscc_id_a: str      # the asset of the index find_matches was called on
+    iscc_id_b: str      # the asset of the other index
+    score: float
+    types: Dict[str, float]   # the confident unit scores, in the unit order of asset a
+
+
+def _join_unit_scores(ham, pbits, instance):
+    # type: (np.ndarray, np.ndarray, bool) -> list
+    """Unit scores of a join's row pairs with the float operations of ``_search_units``; INSTANCE pairs score 1.0."""
+    if instance:
+        return [1.0] * len(ham)
+    dist = ham.astype(np.float32) / pbits.astype(np.float32)
+    return np.maximum(0.0, 1.0 - dist.astype(np.float64)).tolist()
+
+
+def _merge_join(pair_scores, unit_type, join, instance, units_a, units_b):
+    # type: (Dict[tuple, Dict[str, float]], str, tuple, bool, Dict[int, Dict[str, bytes]], Dict[int, Dict[str, bytes]]) -> None
+    """One unit table's join result into the per-pair unit scores; ``units_a`` / ``units_b``: each side's units as indexed."""
+    keys_a, keys_b, ham, pbits = join
+    for a, b, score in zip(keys_a.tolist(), keys_b.tolist(), _join_unit_scores(ham, pbits, instance)):
+        ua, ub = units_a.get(a), units_b.get(b)
+        # a row an update left behind in a table of a type the asset no longer carries is not compared
+        if ua is None or ub is None or unit_type not in ua or unit_type not in ub:
+            continue
+        pair_scores.setdefault((a, b), {})[unit_type] = score
+
+
+def _rank_pairs(pair_scores, units_a, thr, exp, min_score):
+    # type: (Dict[tuple, Dict[str, float]], Dict[int, Dict[str, bytes]], float, int, Optional[float]) -> list
+    """[(key_a, key_b, score, confident unit scores)] of the pairs with a confident unit, score descending, then (key_a, key_b)."""
+    out = []
+    for (a, b), by_type in pair_scores.items():
+        # the unit order of asset a, as search_assets by a's units merges them
+        confident = {t: by_type[t] for t in units_a[a] if t in by_type and by_type[t] >= thr}
+        if not confident:
+            continue
+        score = min(1.0, _confidence_total(confident, exp))
+        if min_score is not None and score < min_score:
+            continue
+        out.append((a, b, score, confident))
+    out.sort(key=lambda r: (-r[2], r[0], r[1]))
+    return out
+
+
 def _rank_aggregated(aggregated, thr, exp, query_iscc_id, limit):
     # type: (Dict[int, Dict[str, float]], float, int, Optional[str], int) -> list
     """``usearch/index.py:808-839``: threshold, confidence-weighted total, self-exclusion, stable sort, cut: [(key, total, unit_scores)]."""
@@ -513,31 +561,46 @@ class HipIndex:
             if not hasattr(table, "join_within"):
                 raise NotImplementedError("find_duplicates needs a single-GPU engine: pairs across shards need their rows exchanged")
             instance = unit_type.startswith("INSTANCE_")
-            keys_a, keys_b, ham, pbits = table.join_within(_unit_max_hamming(thr, instance), max_pairs)
-            if instance:
-                scores = [1.0] * len(ham)
-            else:
-                dist = ham.astype(np.float32) / pbits.astype(np.float32)
-                scores = np.maximum(0.0, 1.0 - dist.astype(np.float64)).tolist()
-            for a, b, score in zip(keys_a.tolist(), keys_b.tolist(), scores):
-                ua, ub = asset_units.get(a), asset_units.get(b)
-                # a row an update left behind in a table of a type the asset no longer carries is not compared
-                if ua is None or ub is None or unit_type not in ua or unit_type not in ub:
-                    continue
-                pair_scores.setdefault((a, b), {})[unit_type] = score
-        out = []
-        for (a, b), by_type in pair_scores.items():
-            # the unit order of asset a, as search_assets by a's iscc_id merges them
-            confident = {t: by_type[t] for t in asset_units[a] if t in by_type and by_type[t] >= thr}
-            if not confident:
-                continue
-            score = min(1.0, _confidence_total(confident, exp))
-            if min_score is not None and score < min_score:
-                continue
-            out.append((a, b, score, confident))
-        out.sort(key=lambda r: (-r[2], r[0], r[1]))
+            join = table.join_within(_unit_max_hamming(thr, instance), max_pairs)
+            _merge_join(pair_scores, unit_type, join, instance, asset_units, asset_units)
         realm = self._realm_id or 0
-        return [DuplicatePair(codec.iscc_id_from_int(a, realm), codec.iscc_id_from_int(b, realm), score, types) for a, b, score, types in out]
+        return [DuplicatePair(codec.iscc_id_from_int(a, realm), codec.iscc_id_from_int(b, realm), score, types)
+                for a, b, score, types in _rank_pairs(pair_scores, asset_units, thr, exp, min_score)]
+
+    def find_matches(self, other, min_score=None, unit_types=None, max_pairs=1_000_000):
+        # type: (HipIndex, Optional[float], Optional[List[str]], int) -> List[IndexMatch]
+        """
+        Every pair (asset a of this index, asset b of ``other``) that ``other.search_assets(IsccQuery(units=<a's units as
+        indexed>), limit=len(other))`` would list as b, with that score and the confident part of that match's unit scores in
+        a's unit order -- found by ONE cross join per unit type both indexes have a table for (``HipTable.join_between``)
+        instead of a search per asset.  The other index's threshold and exponent score the pairs, as its ``search_assets`` would.  An asset present in both
+        indexes pairs with itself.  Kept, filtered (``min_score``, ``unit_types``) and capped (``max_pairs`` unit pairs per
+        table, else ValueError) as ``find_duplicates`` does; ordered by score descending, then (key_a, key_b).  Both indexes
+        must live on one engine.
+        """
+        if other is self:
+            raise ValueError("find_matches compares two indexes: find_duplicates lists the pairs within one")
+        if other._engine is not self._engine:
+            raise ValueError("find_matches needs both indexes on one engine: their tables must share the device's memory")
+        thr, exp = other._opts.match_threshold_units, other._opts.confidence_exponent
+        with self._lock:
+            tables_a = {t: idx for t, idx in self._unit_tables.items() if unit_types is None or t in unit_types}
+            units_a = dict(self._asset_units)
+            realm_a = self._realm_id or 0
+        with other._lock:
+            tables_b = dict(other._unit_tables)
+            units_b = dict(other._asset_units)
+            realm_b = other._realm_id or 0
+        pair_scores = {}  # type: Dict[tuple, Dict[str, float]]
+        for unit_type in sorted(set(tables_a) & set(tables_b)):
+            table_a, table_b = tables_a[unit_type]._table, tables_b[unit_type]._table
+            if not hasattr(table_a, "join_between"):
+                raise NotImplementedError("find_matches needs a single-GPU engine: pairs across shards need their rows exchanged")
+            instance = unit_type.startswith("INSTANCE_")
+            join = table_a.join_between(table_b, _unit_max_hamming(thr, instance), max_pairs)
+            _merge_join(pair_scores, unit_type, join, instance, units_a, units_b)
+        return [IndexMatch(codec.iscc_id_from_int(a, realm_a), codec.iscc_id_from_int(b, realm_b), score, types)
+                for a, b, score, types in _rank_pairs(pair_scores, units_a, thr, exp, min_score)]
 
     # -- bulk search -------------------------------------------------------------------------------
     def _prepare_many(self, queries):
@@ -1208,6 +1271,24 @@ class HipIndexManager:
         with self._lock:
             idx = self._index(index_name)
         return idx.find_duplicates(min_score=min_score, unit_types=unit_types, max_pairs=max_pairs)
+
+    def find_matches(self, index_a, index_b, min_score=None, unit_types=None, max_pairs=1_000_000):
+        # type: (str, str, Optional[float], Optional[List[str]], int) -> List[IndexMatch]
+        """Asset pairs (a of ``index_a``, b of ``index_b``) that match (``HipIndex.find_matches``).  Not available on a sharded index."""
+        if self.devices > 1:
+            raise NotImplementedError(
+                f"find_matches is not available on a sharded index (devices={self.devices}): pairs across shards need the rows "
+                f"exchanged between the GPUs"
+            )
+        return self._guarded("find_matches", self._find_matches, index_a, index_b, min_score, unit_types, max_pairs)
+
+    def _find_matches(self, index_a, index_b, min_score=None, unit_types=None, max_pairs=1_000_000):
+        if index_a == index_b:
+            raise ValueError(f"find_matches compares two indexes, got '{index_a}' twice: find_duplicates lists the pairs within one index")
+        with self._lock:
+            idx_a = self._index(index_a)
+            idx_b = self._index(index_b)
+        return idx_a.find_matches(idx_b, min_score=min_score, unit_types=unit_types, max_pairs=max_pairs)
 
     def close(self):
         # type: () -> None
