@@ -225,7 +225,7 @@ def clean(iscc):
 
 
 # ISCC strings this process produced or parsed recently -> their decoded form.  A request normalised from an ISCC-CODE derives its
-# unit strings (code_units -> str) and searches each of them a moment later (HipIndex._search_units): four decodes saved per request.
+# unit strings (code_units -> str) and searches each of them a moment later (HipIndex._prepare): four decodes saved per request.
 # Iscc objects never change after construction; the memo is bounded and dropped whole when full.
 _PARSED = {}
 _PARSED_MAX = 8192

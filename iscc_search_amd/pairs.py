@@ -1,0 +1,82 @@
+"""
+Asset pairs by device joins: the host side of ``HipIndex.find_duplicates`` (``HipTable.join_within``) and ``find_matches``
+(``HipTable.join_between``), scored as ``search_assets`` scores (``unit_match``).  A *side* of a join is ``(tables, asset_units)``:
+unit type -> ``HipNphdIndex``, and asset key -> {unit_type: body} as indexed.
+"""
+
+from dataclasses import dataclass
+from typing import Dict, Optional
+
+from iscc_search_amd.unit_match import _confidence_total, _is_instance, _unit_max_hamming, _unit_scores
+
+
+@dataclass
+class DuplicatePair:
+    """One near-duplicate pair of ``find_duplicates``: ``score`` and ``types`` as ``search_assets`` from either asset lists the other."""
+
+    iscc_id_a: str      # the smaller key
+    iscc_id_b: str
+    score: float
+    types: Dict[str, float]   # the confident unit scores, in the unit order of asset a
+
+
+@dataclass
+class IndexMatch:
+    """One pair of ``find_matches``: ``score`` and ``types`` as ``search_assets`` on the other index by asset a's units lists asset b."""
+
+    iscc_id_a: str      # the asset of the index find_matches was called on
+    iscc_id_b: str      # the asset of the other index
+    score: float
+    types: Dict[str, float]   # the confident unit scores, in the unit order of asset a
+
+
+def _merge_join(pair_scores, unit_type, join, instance, units_a, units_b):
+    # type: (Dict[tuple, Dict[str, float]], str, tuple, bool, Dict[int, Dict[str, bytes]], Dict[int, Dict[str, bytes]]) -> None
+    """One unit table's join result into the per-pair unit scores; ``units_a`` / ``units_b``: each side's units as indexed."""
+    keys_a, keys_b, ham, pbits = join
+    scores = [1.0] * len(ham) if instance else _unit_scores(ham, pbits).tolist()     # INSTANCE pairs score 1.0
+    for a, b, score in zip(keys_a.tolist(), keys_b.tolist(), scores):
+        ua, ub = units_a.get(a), units_b.get(b)
+        # a row an update left behind in a table of a type the asset no longer carries is not compared
+        if ua is None or ub is None or unit_type not in ua or unit_type not in ub:
+            continue
+        pair_scores.setdefault((a, b), {})[unit_type] = score
+
+
+def _rank_pairs(pair_scores, units_a, thr, exp, min_score):
+    # type: (Dict[tuple, Dict[str, float]], Dict[int, Dict[str, bytes]], float, int, Optional[float]) -> list
+    """[(key_a, key_b, score, confident unit scores)] of the pairs with a confident unit, score descending, then (key_a, key_b)."""
+    out = []
+    for (a, b), by_type in pair_scores.items():
+        # the unit order of asset a, as search_assets by a's units merges them
+        confident = {t: by_type[t] for t in units_a[a] if t in by_type and by_type[t] >= thr}
+        if not confident:
+            continue
+        score = min(1.0, _confidence_total(confident, exp))
+        if min_score is not None and score < min_score:
+            continue
+        out.append((a, b, score, confident))
+    out.sort(key=lambda r: (-r[2], r[0], r[1]))
+    return out
+
+
+def join_sides(caller, side_a, side_b, opts, min_score, max_pairs):
+    # type: (str, tuple, tuple, object, Optional[float], int) -> list
+    """
+    The ranked pairs (``_rank_pairs``) of side a's assets with side b's: ONE join per unit type both sides have a table for --
+    a self-join where ``side_b`` is ``side_a`` -- at the largest distance per code length that ``opts``' threshold still calls
+    confident, aggregated over the unit types both assets carry.  More than ``max_pairs`` unit pairs in one table raise
+    ValueError; tables without the join (a sharded engine's) raise NotImplementedError naming ``caller``.
+    """
+    (tables_a, units_a), (tables_b, units_b) = side_a, side_b
+    thr, exp = opts.match_threshold_units, opts.confidence_exponent
+    pair_scores = {}  # type: Dict[tuple, Dict[str, float]]
+    for unit_type in sorted(set(tables_a) & set(tables_b)):
+        table_a, table_b = tables_a[unit_type]._table, tables_b[unit_type]._table
+        if not hasattr(table_a, "join_within" if side_b is side_a else "join_between"):
+            raise NotImplementedError(f"{caller} needs a single-GPU engine: pairs across shards need their rows exchanged")
+        instance = _is_instance(unit_type)
+        max_hamming = _unit_max_hamming(thr, instance)
+        join = table_a.join_within(max_hamming, max_pairs) if side_b is side_a else table_a.join_between(table_b, max_hamming, max_pairs)
+        _merge_join(pair_scores, unit_type, join, instance, units_a, units_b)
+    return _rank_pairs(pair_scores, units_a, thr, exp, min_score)

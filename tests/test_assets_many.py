@@ -181,13 +181,13 @@ def test_rejections_name_the_query(clustered):
 
 
 def test_instance_cap_names_the_query(manager, monkeypatch):
-    from iscc_search_amd import index as index_mod
+    from iscc_search_amd import unit_match
 
     rng = np.random.default_rng(5)
     inst = rng.integers(0, 256, size=8, dtype=np.uint8).tobytes()
     manager.create_index(IsccIndex(name="cap"))
     manager.add_assets("cap", [IsccEntry(iscc_id=make_iscc_id(i), units=[codec.encode_unit(codec.MT_DATA, 0, 0, bytes(8)), codec.encode_unit(codec.MT_INSTANCE, 0, 0, inst)]) for i in range(80)])
-    monkeypatch.setattr(index_mod, "_check_instance_hits", lambda count, unit_type: (_ for _ in ()).throw(ValueError(f"cap {unit_type}")) if count >= 70 else None)
+    monkeypatch.setattr(unit_match, "_check_instance_hits", lambda count, unit_type: (_ for _ in ()).throw(ValueError(f"cap {unit_type}")) if count >= 70 else None)
     with pytest.raises(ValueError, match=r"queries\[1\]: cap INSTANCE_NONE_V0"):
         manager.search_assets_many("cap", [IsccQuery(units=[codec.encode_unit(codec.MT_DATA, 0, 0, bytes(8))]),
                                            IsccQuery(units=[codec.encode_unit(codec.MT_INSTANCE, 0, 0, inst)])])

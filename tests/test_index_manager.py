@@ -16,8 +16,9 @@ import inspect
 import numpy as np
 import pytest
 
+import unit_match_reference
 from helpers import flip_bits, make_asset, make_iscc_id, rnd_unit
-from iscc_search_amd import codec
+from iscc_search_amd import codec, unit_match
 from iscc_search_amd.index import HipIndexManager, HipOptions, get_index, normalize_query
 from iscc_search_amd.schema import IsccEntry, IsccIndex, IsccQuery, Status
 from oracle_engine import OracleEngine
@@ -239,24 +240,21 @@ def test_more_instance_matches_than_the_first_short_list(manager, rng):
     res = manager.search_assets("t", IsccQuery(units=[codec.encode_unit(codec.MT_INSTANCE, 0, 0, inst)]), limit=1000)
     assert {m.iscc_id for m in res.global_matches} == {make_iscc_id(i) for i in range(n)}
     idx = manager._indexes["t"]
-    assert len(idx._search_instance_unit("INSTANCE_NONE_V0", inst)) == n
+    assert len(unit_match_reference.search_unit(idx, "INSTANCE_NONE_V0", inst, 1000)) == n
 
 
 def test_single_unit_helpers_agree_with_the_batched_path(manager, rng):
-    """``_search_similarity_unit`` / ``_search_instance_unit`` (the reference's per-unit methods, usearch/index.py:2024-2045,
-    :1957-2022) return what ``_search_units`` (one engine call for all units of a request) merges."""
+    """One search per unit (``unit_match_reference.search_unit``: the reference's per-unit methods, usearch/index.py:2024-2045,
+    :1957-2022) returns what ``unit_match.search_units`` (one engine call for all units of a request) merges."""
     manager.create_index(IsccIndex(name="t"))
     assets = [make_asset(rng, i, bits=128) for i in range(30)]
     manager.add_assets("t", assets)
     idx = manager._index("t")
     units = assets[3].units
-    merged = idx._search_units(units, 10)
+    merged = unit_match.search_units(idx._engine, idx._unit_tables, [idx._prepare(IsccQuery(units=units))], 10)[0]
     for unit_str in units:
         unit = codec.Iscc(unit_str)
-        if unit.unit_type.startswith("INSTANCE_"):
-            single = idx._search_instance_unit(unit.unit_type, unit.body)
-        else:
-            single = idx._search_similarity_unit(unit.unit_type, unit.body, 10)
+        single = unit_match_reference.search_unit(idx, unit.unit_type, unit.body, 10)
         assert single == {key: types[unit.unit_type] for key, types in merged.items() if unit.unit_type in types}
 
 
