@@ -294,12 +294,20 @@ extern "C" int isccsearch_match_assets(isccsearch_handle* h, uint32_t nq, const 
         HIPOK(hipStreamSynchronize(h->stream));
     }
 
-    // (5) the caller's arrays
-    memcpy(out_keys, po + o_keys, nr * 8);
-    memcpy(out_scores, po + o_scores, nr * 8);
+    // (5) the caller's arrays.  The kernel writes a query's listed results only: past its count the staging area still holds what an
+    // earlier call left there, and the caller gets zeros (types 0xFF), as the host path pads them
     memcpy(out_count, po + o_count, (size_t)nq * 4);
-    memcpy(out_types, po + o_types, nr * n_types);
-    memcpy(out_type_scores, po + o_types_sc, nr * n_types * 8);
+    for (uint32_t q = 0; q < nq; ++q) {
+        const size_t at = (size_t)q * limit, c = std::min<uint32_t>(out_count[q], limit), rest = limit - c;
+        memcpy(out_keys + at, po + o_keys + at * 8, c * 8);
+        memset(out_keys + at + c, 0, rest * 8);
+        memcpy(out_scores + at, po + o_scores + at * 8, c * 8);
+        memset(out_scores + at + c, 0, rest * 8);
+        memcpy(out_types + at * n_types, po + o_types + at * n_types, c * n_types);
+        memset(out_types + (at + c) * n_types, 0xFF, rest * n_types);
+        memcpy(out_type_scores + at * n_types, po + o_types_sc + at * n_types * 8, c * n_types * 8);
+        memset(out_type_scores + (at + c) * n_types, 0, rest * n_types * 8);
+    }
     memcpy(out_unit_count, po + o_ucnt, (size_t)n_units * 4);
     return 0;
 }
