@@ -152,7 +152,9 @@ uint64_t isccsearch_size(isccsearch_handle* h, uint32_t table);
 
 /* Rows.  keys[n*key_words], code_words[n*max_words], nbytes[n] (NULL for Hamming tables).
  * A key that is already present (or repeated in the batch) fails the whole call with -EEXIST
- * unless ISCCSEARCH_ADD_TRUSTED_UNIQUE is set. */
+ * unless ISCCSEARCH_ADD_TRUSTED_UNIQUE is set.
+ * Bits past a code's length -- in its last word and in the words behind it -- are ignored on input and
+ * stored as zero: isccsearch_get and isccsearch_export return them as zero whatever the caller left there. */
 int isccsearch_add(isccsearch_handle* h, uint32_t table, uint64_t n, const uint64_t* keys,
                    const uint64_t* code_words, const uint8_t* nbytes, uint32_t flags);
 int isccsearch_remove(isccsearch_handle* h, uint32_t table, uint64_t n, const uint64_t* keys, uint64_t* n_removed);
@@ -166,7 +168,8 @@ int isccsearch_get(isccsearch_handle* h, uint32_t table, uint64_t n, const uint6
  *   segments:    out_rows[ISCCSEARCH_MAX_BYTES + 1], out_rows[b] = rows whose codes are b bytes long
  *   export:      rows [first_row, first_row+n) of one segment: out_keys[n*key_words] and out_cols laid out
  *                COLUMN-major [W][n] (W = ceil(nbytes/8)), i.e. exactly the device layout
- *   add_columns: append n rows of one length from column-major words (no host transposition) */
+ *   add_columns: append n rows of one length from column-major words (no host transposition); bits past
+ *                nbytes in the last column are ignored on input and stored as zero, as isccsearch_add does */
 int isccsearch_segments(isccsearch_handle* h, uint32_t table, uint64_t* out_rows);
 int isccsearch_export(isccsearch_handle* h, uint32_t table, int nbytes, uint64_t first_row, uint64_t n,
                       uint64_t* out_keys, uint64_t* out_cols);

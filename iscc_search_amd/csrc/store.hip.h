@@ -340,12 +340,14 @@ int isccsearch_add(isccsearch_handle* h, uint32_t table, uint64_t n, const uint6
         const uint64_t m = per_seg[b];
         if (!m) continue;
         Segment& s = t.seg[b];
-        const bool direct = (m == n && MW == 1);   // single segment, one word: the caller's buffers are already column-shaped
+        // single segment, one whole word: the caller's buffers are already column-shaped (shorter one-word codes take the split below,
+        // which masks the bits past their length)
+        const bool direct = (m == n && MW == 1 && b == 8);
         const uint64_t* kp = keys;
         if (direct) {
             HIPOK(hipMemcpyAsync(s.col[0] + s.n, code_words, m * 8, hipMemcpyHostToDevice, h->stream));
         } else if (m == n) {
-            // one code length, several words: ship the caller's row-major block as it is and split it into the
+            // one code length, several words or a masked one: ship the caller's row-major block as it is and split it into the
             // word columns on the device (a host-side transposition capped 256-bit ingest at 80 M rows/s)
             if ((rc = h->d_misc2.ensure((size_t)n * MW))) return rc;
             HIPOK(hipMemcpyAsync(h->d_misc2.p, code_words, (size_t)n * MW * 8, hipMemcpyHostToDevice, h->stream));
@@ -439,6 +441,12 @@ int isccsearch_add_columns(isccsearch_handle* h, uint32_t table, int nbytes, uin
     if ((rc = seg_reserve(h, t, s, s.n + n))) return rc;
     for (uint32_t w = 0; w < s.W; ++w)
         HIPOK(hipMemcpyAsync(s.col[w] + s.n, cols + (size_t)w * n, n * 8, hipMemcpyHostToDevice, h->stream));
+    if (nbytes & 7) {
+        // bits past the code length are stored as zero whatever the caller left there (whole-word codes have none)
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((n + isk::BLOCK - 1) / isk::BLOCK, (uint64_t)h->cus * 8);
+        hipLaunchKernelGGL(isk::mask_column_kernel, dim3(grid), dim3(isk::BLOCK), 0, h->stream, s.col[s.W - 1] + s.n, n, mask_for((uint32_t)nbytes));
+        HIPOK(hipGetLastError());
+    }
     HIPOK(hipMemcpyAsync(s.keys + s.n * KW, keys, n * 8 * KW, hipMemcpyHostToDevice, h->stream));
     HIPOK(hipStreamSynchronize(h->stream));
     commit_rows(t, s, keys, n);

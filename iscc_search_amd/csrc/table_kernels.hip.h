@@ -1,4 +1,4 @@
-// table_kernels.hip.h -- upkeep of the column store: synthetic fill, row moves, row gathers, the ingest split, u32 gathers.
+// table_kernels.hip.h -- upkeep of the column store: synthetic fill, row moves, row gathers, the ingest split and mask, u32 gathers.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -83,6 +83,11 @@ __global__ __launch_bounds__(BLOCK) void split_rows_kernel(const SplitParams p) 
             if (w == p.W - 1) v &= p.mask_last;
             p.col[w][p.dst_row + i] = v;
         }
+}
+
+// add_columns: the last word column of rows handed over word-major, masked to the code length where it lies
+__global__ __launch_bounds__(BLOCK) void mask_column_kernel(uint64_t* col, uint64_t n, uint64_t mask) {
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (uint64_t)gridDim.x * BLOCK) col[i] &= mask;
 }
 
 // out[i] = src[rows[i]]  (document-frequency column lookups)

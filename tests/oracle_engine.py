@@ -35,16 +35,27 @@ class OracleTable:
     def _kt(k):
         return tuple(int(x) for x in np.atleast_1d(k))
 
+    @staticmethod
+    def _kts(keys):
+        """``_kt`` of every key of an array."""
+        return [tuple(k) for k in keys.tolist()] if keys.ndim == 2 else [(k,) for k in keys.tolist()]
+
     def add(self, keys, words, nbytes=None, trusted_unique=False):
         keys = np.asarray(keys, dtype=np.uint64)
         words = np.asarray(words, dtype=np.uint64)
         n = keys.shape[0]
-        kts = [self._kt(keys[i]) for i in range(n)]
+        kts = self._kts(keys)
         if not trusted_unique:
             if len(set(kts)) != n or any(k in self._rows for k in kts):
                 raise KeyError("key already present")
+        # bits past the code length are ignored on input and stored as zero (include/isccsearch.h, isccsearch_add)
+        lens = np.full(n, self.max_bytes, dtype=np.int64) if nbytes is None else np.asarray(nbytes, dtype=np.int64)
+        words = words.reshape(n, self.max_words).copy()
+        for w in range(self.max_words):
+            inside = np.clip(lens - 8 * w, 0, 8).astype(np.uint64)
+            words[:, w] &= np.where(inside == 0, np.uint64(0), ~np.uint64(0) << ((np.uint64(8) - inside) * np.uint64(8) % np.uint64(64)))
         for i, k in enumerate(kts):
-            nb = int(nbytes[i]) if nbytes is not None else self.max_bytes
+            nb = int(lens[i])
             if self.metric == 0 and nb != self.max_bytes:
                 raise ValueError("Hamming table holds fixed-length codes")
             self._rows[k] = (words[i].copy(), nb)
@@ -52,22 +63,22 @@ class OracleTable:
     def remove(self, keys):
         keys = np.asarray(keys, dtype=np.uint64)
         removed = 0
-        for i in range(keys.shape[0]):
-            if self._rows.pop(self._kt(keys[i]), None) is not None:
+        for k in self._kts(keys):
+            if self._rows.pop(k, None) is not None:
                 removed += 1
         return removed
 
     def contains(self, keys):
         keys = np.asarray(keys, dtype=np.uint64)
-        return np.array([self._kt(keys[i]) in self._rows for i in range(keys.shape[0])], dtype=bool)
+        return np.array([k in self._rows for k in self._kts(keys)], dtype=bool)
 
     def get(self, keys):
         keys = np.asarray(keys, dtype=np.uint64)
         n = keys.shape[0]
         words = np.zeros((n, self.max_words), dtype=np.uint64)
         nb = np.zeros(n, dtype=np.uint8)
-        for i in range(n):
-            row = self._rows.get(self._kt(keys[i]))
+        for i, k in enumerate(self._kts(keys)):
+            row = self._rows.get(k)
             if row is not None:
                 words[i], nb[i] = row
         return words, nb
