@@ -13,6 +13,7 @@ import threading
 import numpy as np
 
 from iscc_search_amd import _lib
+from iscc_search_amd.table_checks import TableChecks
 
 
 def pack_bytes(codes, max_words):
@@ -232,7 +233,7 @@ def _alloc_out(nq, k, key_words):
     return out, (base + pad, base + pad + o_ham, base + pad + o_pre, base + pad + o_cnt)
 
 
-class HipTable:
+class HipTable(TableChecks):
     """A table of (key, code) rows resident in HBM."""
 
     def __init__(self, engine, table_id, metric, key_words, max_bytes):
@@ -244,36 +245,6 @@ class HipTable:
         self.max_bytes = max_bytes
         self.max_words = (max_bytes + 7) // 8
         self._open = True
-
-    # -- helpers -----------------------------------------------------------------------------
-    def _keys(self, keys):
-        keys = np.ascontiguousarray(keys, dtype=np.uint64)
-        if self.key_words == 2:
-            if keys.ndim != 2 or keys.shape[1] != 2:
-                raise ValueError("128-bit keys must be shaped [n, 2] (hi, lo)")
-        elif keys.ndim != 1:
-            raise ValueError("64-bit keys must be shaped [n]")
-        return keys
-
-    def _words(self, words, n=None):
-        words = np.ascontiguousarray(words, dtype=np.uint64)
-        if words.ndim != 2 or words.shape[1] != self.max_words:
-            raise ValueError(f"code words must be shaped [n, {self.max_words}]")
-        if n is not None and words.shape[0] != n:
-            raise ValueError("keys and codes differ in length")
-        return words
-
-    def _nbytes(self, nbytes, n):
-        if self.metric == _lib.METRIC_HAMMING:
-            if nbytes is not None and np.any(np.asarray(nbytes) != self.max_bytes):
-                raise ValueError(f"Hamming table holds {self.max_bytes}-byte codes only")
-            return None
-        if nbytes is None:
-            raise ValueError("nbytes is required for NPHD tables")
-        nbytes = np.ascontiguousarray(nbytes, dtype=np.uint8)
-        if nbytes.shape != (n,):
-            raise ValueError("nbytes must be shaped [n]")
-        return nbytes
 
     # -- C-ABI calls -------------------------------------------------------------------------
     def add(self, keys, words, nbytes=None, trusted_unique=False):

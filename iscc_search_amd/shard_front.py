@@ -49,6 +49,9 @@ import time
 
 import numpy as np
 
+from iscc_search_amd._lib import MAX_BYTES, MAX_K, METRIC_HAMMING, METRIC_NPHD
+from iscc_search_amd.table_checks import TableChecks
+
 ENV_FACTORY = "ISCC_HIP_SHARD_ENGINE_FACTORY"     # "module:callable" -> callable(local_rank) = (local engine, ops factory | None, device | None)
 ENV_BACKEND = "ISCC_HIP_SHARD_BACKEND"
 ENV_SAME_GPU = "ISCC_HIP_SHARD_SAME_GPU"          # "1": every rank uses GPU 0 (rehearsal on a one-GPU box, backend gloo)
@@ -66,12 +69,7 @@ ERROR_CODES = {ValueError: 1, FileNotFoundError: 2, FileExistsError: 3, KeyError
 
 
 def error_code(exc):
-    if exc is None:
-        return 0
-    for cls, code in ERROR_CODES.items():
-        if type(exc) is cls:
-            return code
-    return 99
+    return 0 if exc is None else ERROR_CODES.get(type(exc), 99)
 
 
 def free_port():
@@ -233,7 +231,41 @@ def run_table_op(engine, tables, op, table_id, n, a, b, c, payload):
     raise RuntimeError(f"unknown table operation {op}")
 
 
-class LeaderTable:
+DONE, REFUSED, FAULT = "done", "refused", "fault"      # how a rank's part of a table operation ended
+
+
+def rank_table_op(engine, channel, tables, op, table_id, n, a, b, c, payload):
+    """
+    ONE rank's part of a table operation, the same on the leader and on every worker -- every rank takes the same collectives
+    in the same order: the local part (``run_table_op``), for ``STATUS_OPS`` the exchange of outcomes, for a ``remove`` that
+    succeeded everywhere the all-reduce of its count.  Returns (``DONE``, the result), (``REFUSED``, the exception every
+    rank raised alike) or (``FAULT``, why this rank cannot go on: the outcomes differ, the transport failed, or a read
+    operation -- which exchanges nothing -- raised).
+    """
+    error = result = None
+    try:
+        result = run_table_op(engine, tables, op, table_id, n, a, b, c, payload)
+    except BaseException as exc:                  # noqa: BLE001
+        error = exc
+    if op not in STATUS_OPS:
+        return (DONE, result) if error is None else (FAULT, error)
+    try:
+        same, worst = channel.outcomes_agree(error_code(error))
+        if not same:
+            exc = RuntimeError(f"the ranks disagree about the outcome of table operation {op} "
+                               f"(here: {type(error).__name__ if error else 'ok'}; worst code {worst})")
+            exc.__cause__ = error
+            return FAULT, exc
+        if error is not None:
+            return REFUSED, error
+        if op == OP_REMOVE:                       # the local parts are done everywhere: now the count (one small all-reduce)
+            result = int(engine.all_reduce(np.array([result], dtype=np.int64))[0])
+    except BaseException as exc:                  # noqa: BLE001
+        return FAULT, exc
+    return DONE, result
+
+
+class LeaderTable(TableChecks):
     """One logical table of the sharded index, as the leader's host classes see it: the duck type of ``HipTable``."""
 
     def __init__(self, engine, table_id, metric, key_words, max_bytes):
@@ -241,44 +273,11 @@ class LeaderTable:
         self.metric, self.key_words, self.max_bytes = metric, key_words, max_bytes
         self.max_words = (max_bytes + 7) // 8
 
-    # -- argument checks (nothing invalid is ever broadcast) ---------------------------------------------------------
-    def _keys(self, keys):
-        keys = np.ascontiguousarray(keys, dtype=np.uint64)
-        if self.key_words == 2:
-            if keys.ndim != 2 or keys.shape[1] != 2:
-                raise ValueError("128-bit keys must be shaped [n, 2] (hi, lo)")
-        elif keys.ndim != 1:
-            raise ValueError("64-bit keys must be shaped [n]")
-        return keys
-
-    def _words(self, words, n=None):
-        words = np.ascontiguousarray(words, dtype=np.uint64)
-        if words.ndim != 2 or words.shape[1] != self.max_words:
-            raise ValueError(f"code words must be shaped [n, {self.max_words}]")
-        if n is not None and words.shape[0] != n:
-            raise ValueError("keys and codes differ in length")
-        return words
-
-    def _nbytes(self, nbytes, n):
-        from iscc_search_amd._lib import METRIC_HAMMING
-
-        if self.metric == METRIC_HAMMING:
-            if nbytes is not None and np.any(np.asarray(nbytes) != self.max_bytes):
-                raise ValueError(f"Hamming table holds {self.max_bytes}-byte codes only")
-            return None
-        if nbytes is None:
-            raise ValueError("nbytes is required for NPHD tables")
-        nbytes = np.ascontiguousarray(nbytes, dtype=np.uint8)
-        if nbytes.shape != (n,):
-            raise ValueError("nbytes must be shaped [n]")
-        if n and (int(nbytes.min()) < 1 or int(nbytes.max()) > self.max_bytes):
-            raise ValueError(f"code length outside 1..{self.max_bytes} bytes")
-        return nbytes
+    # -- argument checks (nothing invalid is ever broadcast): those of TableChecks, the code lengths' range among them, and `_k`
+    checks_length_range = True
 
     @staticmethod
     def _k(k):
-        from iscc_search_amd._lib import MAX_K
-
         if k < 1:
             raise ValueError("`count` must be >= 1")
         if k > MAX_K:
@@ -325,8 +324,6 @@ class LeaderTable:
         return self.engine.run(OP_SIZE, self.id)
 
     def get_freq(self, keys, dup_limit=1000):
-        from iscc_search_amd._lib import METRIC_HAMMING
-
         if self.metric != METRIC_HAMMING:
             raise ValueError("get_freq is defined for fixed-length (Hamming) tables")
         keys = self._keys(keys)
@@ -488,45 +485,23 @@ class LeaderEngine:
         self._stop_workers()
         return RuntimeError(f"the sharded index is down: {self._broken}")
 
-    def _send(self, op, *args, **kw):
-        self.channel.send(op, *args, **kw)
-
     # -- one table operation, in the leader's order -------------------------------------------------------------------
     def run(self, op, table=0, n=0, a=0, b=0, c=0, payload=b""):
         with self._lock:
             self.check()
             try:
-                self._send(op, table, n, a, b, c, payload)
+                self.channel.send(op, table, n, a, b, c, payload)
             except BaseException as exc:          # noqa: BLE001 -- the frame did not reach everybody: nothing sane can follow
                 raise self._fault(exc) from exc
-            error = None
-            try:
-                result = run_table_op(self.engine, self._tables, op, table, n, a, b, c, payload)
-            except BaseException as exc:          # noqa: BLE001
-                error, result = exc, None
-            if op in STATUS_OPS:
-                try:
-                    same, worst = self.channel.outcomes_agree(error_code(error))
-                except BaseException as exc:      # noqa: BLE001
-                    raise self._fault(exc) from exc
-                if not same:
-                    raise self._fault(RuntimeError(f"the ranks disagree about the outcome of table operation {op} "
-                                                   f"(here: {type(error).__name__ if error else 'ok'}; worst code {worst})"))
-                if error is not None:
-                    raise error                   # every rank failed alike: the caller's problem, the front stays up
-                if op == OP_REMOVE:               # the local parts are done everywhere: now the count (one small all-reduce)
-                    try:
-                        result = int(self.engine.all_reduce(np.array([result], dtype=np.int64))[0])
-                    except BaseException as exc:  # noqa: BLE001
-                        raise self._fault(exc) from exc
-            elif error is not None:
-                raise self._fault(error) from error
-            return result
+            outcome, value = rank_table_op(self.engine, self.channel, self._tables, op, table, n, a, b, c, payload)
+            if outcome == DONE:
+                return value
+            if outcome == REFUSED:
+                raise value                       # every rank failed alike: the caller's problem, the front stays up
+            raise self._fault(value) from value
 
     # -- HipEngine duck type ------------------------------------------------------------------------------------------
     def open_table(self, metric, key_words, max_bytes):
-        from iscc_search_amd._lib import MAX_BYTES, METRIC_HAMMING, METRIC_NPHD
-
         if metric not in (METRIC_HAMMING, METRIC_NPHD) or key_words not in (1, 2) or not 1 <= max_bytes <= MAX_BYTES:
             raise ValueError("bad table shape")
         with self._lock:
@@ -585,7 +560,6 @@ class LeaderEngine:
                 groups.setdefault((r.table.id, r.k, r.radius), []).append(r)
             for (tid, kk, rad), reqs in groups.items():
                 try:
-                    t = reqs[0].table
                     qw = reqs[0].q_words if len(reqs) == 1 else np.concatenate([r.q_words for r in reqs])
                     qn = None
                     if reqs[0].q_nbytes is not None:
@@ -596,7 +570,6 @@ class LeaderEngine:
                         m = r.q_words.shape[0]
                         r.result = out if len(reqs) == 1 else tuple(np.ascontiguousarray(x[off : off + m]) for x in out)
                         off += m
-                    del t
                 except BaseException as exc:      # noqa: BLE001 -- every caller of the group learns why
                     for r in reqs:
                         r.error = exc
@@ -625,7 +598,7 @@ class LeaderEngine:
                 return
             if self._broken is None:
                 try:
-                    self._send(OP_SHUTDOWN)
+                    self.channel.send(OP_SHUTDOWN)
                     self.engine.close()
                 except BaseException as exc:      # noqa: BLE001 -- closing must not hang on a dead peer
                     self._broken = f"{type(exc).__name__}: {exc}"

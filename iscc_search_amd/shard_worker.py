@@ -2,10 +2,9 @@
 One shard worker of ``hip:///path?devices=N`` (rank 1 .. N-1): started by ``shard_front.LeaderEngine`` as a fresh interpreter.
 
 It holds NO host state of the index -- no assets, no chunk lists, no scoring: it builds a ``ShardedEngine`` over its local
-engine and serves the TABLE operations the leader broadcasts (``shard_front.run_table_op``: the very function the leader runs
-on its own rank), joining the collectives of each, until told to shut down.  It never returns anything to anybody.  Operations
-whose local part can fail on one rank alone end that part with the exchange of outcomes described in ``shard_front``; any
-other failure makes the worker exit, which the leader's watchdog notices.
+engine and serves the TABLE operations the leader broadcasts (``shard_front.rank_table_op``: the very function the leader runs
+on its own rank, the exchange of outcomes described in ``shard_front`` included), joining the collectives of each, until told to
+shut down.  It never returns anything to anybody.  A fault makes the worker exit, which the leader's watchdog notices.
 """
 
 import datetime
@@ -15,7 +14,6 @@ import traceback
 
 
 def main():
-    import numpy as np
     import torch.distributed as dist
 
     from iscc_search_amd import shard_front as front
@@ -46,19 +44,9 @@ def main():
                 continue
             if op == front.OP_SHUTDOWN:
                 break
-            error = result = None
-            try:
-                result = front.run_table_op(engine, tables, op, table, n, a, b, c, payload)
-            except BaseException as exc:  # noqa: BLE001
-                error = exc
-            if op in front.STATUS_OPS:
-                same, _ = channel.outcomes_agree(front.error_code(error))
-                if not same:
-                    raise RuntimeError(f"the ranks disagree about the outcome of table operation {op}") from error
-                if error is None and op == front.OP_REMOVE:
-                    engine.all_reduce(np.array([result], dtype=np.int64))
-            elif error is not None:
-                raise error
+            outcome, value = front.rank_table_op(engine, channel, tables, op, table, n, a, b, c, payload)
+            if outcome == front.FAULT:
+                raise value
             if trace:
                 print(f"[shard worker {os.environ['RANK']}] op {op} n {n}: waited {(t_op - t_wait) * 1e3:.3f} ms, ran {(time.perf_counter() - t_op) * 1e3:.3f} ms", file=sys.stderr)
     except BaseException:                # noqa: BLE001 -- this shard is gone, and says so by exiting

@@ -13,13 +13,15 @@ second collective: at 160 KB per rank for 1 024 queries the exchange is latency 
 C-ABI); tests drive the same class over gloo with an oracle-backed ops object.
 """
 
+import collections
 import contextlib
 import os
 
 import numpy as np
 
+from iscc_search_amd._lib import COUNT_OVERFLOW
+
 RECORD_BYTES = 24
-COUNT_OVERFLOW = 0xFFFFFFFF   # _lib.COUNT_OVERFLOW (kept here so that this module imports without the HIP library)
 
 
 def shard_range(n_rows, rank, world_size):
@@ -48,6 +50,46 @@ def block_bytes(nq, k):
     """Per-rank exchange block {records [nq][k] | counts [nq] | pad}: (record bytes, block bytes)."""
     rec = nq * k * RECORD_BYTES
     return rec, rec + (nq * 4 + 7) // 8 * 8
+
+
+def worst_if_full(result, k):
+    """The largest k-th distance of merged lists that are FULL -- no overflow marker, k rows in each -- else None."""
+    count = result[3]
+    if np.any(count == COUNT_OVERFLOW) or int(count.min()) < k:
+        return None
+    return int(result[1][:, k - 1].max())
+
+
+class ShardHint:
+    """
+    What the shards of one table start a step of one shape under: the GLOBAL k-th distance the previous step of that shape ended
+    at + ``hint_margin``.  Every shard takes one pass within it (no bootstrap sample), and the step stands if the merged lists are
+    full: their rows all lie within the hint, so nothing nearer was left out.  The merged lists are the same on every rank, hence
+    so is every transition taken from them.
+    """
+
+    value = None            # the distance the next hinted step starts under
+    skip = penalty = 0      # steps still to run without a hint after a miss; what the next miss doubles
+
+    def start(self):
+        """The hint this step runs under, or None (which counts one pending skip down)."""
+        if self.skip:
+            self.skip -= 1
+            return None
+        return self.value
+
+    def held(self, worst, k):
+        """The hinted step stood: the hint decays by one bit per step towards what the batches need."""
+        self.value, self.penalty = max(worst + hint_margin(k), self.value - 1), 0
+
+    def missed(self):
+        """The hinted step came up short: 0, 2, 6, 14 steps without a hint for 1, 2, 3, 4 misses in a row."""
+        self.penalty = min(2 * self.penalty + 1, 15)
+        self.skip = self.penalty - 1
+
+    def reseed(self, worst, k):
+        """After an unhinted or a repeated step; ``worst`` None: its lists were not full (a table with fewer than k rows never gets a hint)."""
+        self.value = None if worst is None else worst + hint_margin(k)
 
 
 def _exchange_scope(ops):
@@ -205,12 +247,8 @@ class ShardedTable:
         self.assets_share_a_rank = assets_share_a_rank
         self.world_size = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
-        # (batch-size class, k, query lengths) -> [hint, batches still to skip, penalty]: the GLOBAL k-th distance the previous step of that shape
-        # ended at + 2.  Every shard starts its pass under it (no bootstrap sample; the lists hold the shard's rows within the hint),
-        # and the step stands if every merged list holds k rows -- they all lie within the hint, so nothing nearer was left out.
-        # The merged lists are the same on every rank, hence so is every decision taken from them.
         self.use_hints = bool(getattr(ops, "supports_hint", False)) and not os.environ.get("ISCC_NO_SHARD_HINT")
-        self._hints = {}
+        self._hints = collections.defaultdict(ShardHint)      # by (batch-size class, k, query lengths)
         self.hint_hits = self.hint_misses = 0
         self._stages_on_host = None
 
@@ -281,36 +319,18 @@ class ShardedTable:
         self.dist.all_reduce(t, group=self.group)
         return t.cpu().numpy()
 
+    def _alone(self):
+        """One rank and no forced collective: nothing to exchange."""
+        return self.world_size == 1 and not (self.always_gather and self.dist.is_initialized())
+
+    def hint(self, q_words, q_nbytes, k):
+        # type: (np.ndarray, np.ndarray | None, int) -> ShardHint
+        """The hint of top-k searches of this shape."""
+        qlen = None if q_nbytes is None else tuple(sorted(set(int(b) for b in np.asarray(q_nbytes))))      # (a prefix length has its own distances)
+        return self._hints[(int(q_words.shape[0]).bit_length(), int(k), qlen)]
+
     def _search(self, q_words, q_nbytes, k, max_hamming):
-        nq = q_words.shape[0]
-        alone = self.world_size == 1 and not (self.always_gather and self.dist.is_initialized())
-        state = None
-        if self.use_hints and max_hamming is None and nq and not alone:
-            qlen = None if q_nbytes is None else tuple(sorted(set(int(b) for b in np.asarray(q_nbytes))))      # (a prefix length has its own distances)
-            state = self._hints.setdefault((int(nq).bit_length(), int(k), qlen), [None, 0, 0])
-            if state[0] is not None and state[1] == 0:
-                out = self._exchange(q_words, q_nbytes, k, None, {"hint": state[0]})
-                cnt = out[3]
-                if not np.any(cnt == COUNT_OVERFLOW) and int(cnt.min()) >= k:
-                    worst = int(out[1][:, k - 1].max())
-                    state[0], state[2] = max(worst + hint_margin(k), state[0] - 1), 0          # decays by one bit per step towards what the batches need
-                    self.hint_hits += 1
-                    return out
-                self.hint_misses += 1
-                state[2] = min(2 * state[2] + 1, 15)                             # a miss: 0, 2, 6, 14 steps without a hint for 1, 2, 3, 4 in a row
-                state[1] = state[2] - 1
-            elif state[1]:
-                state[1] -= 1
-        out = self._exchange(q_words, q_nbytes, k, max_hamming, {})
-        if np.any(out[3] == COUNT_OVERFLOW):
-            # some shard's candidate list overflowed and the asynchronous search could only mark it; the merged counts are
-            # the same on every rank, so every rank repeats the step through the synchronous path (exact fallback) together
-            out = self._exchange(q_words, q_nbytes, k, max_hamming, {"synchronous": True})
-        if state is not None:
-            cnt = out[3]
-            full = not np.any(cnt == COUNT_OVERFLOW) and int(cnt.min()) >= k
-            state[0] = int(out[1][:, k - 1].max()) + hint_margin(k) if full else None       # (a table with fewer than k rows never gets a hint)
-        return out
+        return ShardedTable._step([(self, q_words, q_nbytes, k, max_hamming)])[0]
 
     @staticmethod
     def search_many(items):
@@ -321,105 +341,102 @@ class ShardedTable:
         per item; returns the results in order, or None when the items cannot share an exchange (the caller then runs them one
         by one).
         """
-        import torch
-
         first = items[0][0]
         if first.world_size == 1 or len(items) < 2 or len({(id(t.ops), block_bytes(q.shape[0], k)[1]) for t, q, _, k, _ in items}) != len(items):
             return None            # (two items on one table with one block size -- (3, 4) and (4, 3) alike -- would share that table's block buffer, HipShardOps.buffer)
         if any(t.world_size != first.world_size or t.group is not first.group for t, *_ in items):
             return None
-        with _exchange_scope(first.ops):
-            # every item's shards start under the GLOBAL k-th distance its table's previous search of this shape ended at (as `_search`):
-            # the per-unit searches of a request then cost each shard one range-limited pass instead of bootstrap + levels
-            blocks, states = [], []
-            for t, q_words, q_nbytes, k, max_hamming in items:
-                state, how = None, {}
-                if t.use_hints and max_hamming is None:
-                    qlen = None if q_nbytes is None else tuple(sorted(set(int(b) for b in np.asarray(q_nbytes))))
-                    state = t._hints.setdefault((int(q_words.shape[0]).bit_length(), int(k), qlen), [None, 0, 0])
-                    if state[0] is not None and state[1] == 0:
-                        how = {"hint": state[0]}
-                    elif state[1]:
-                        state[1] -= 1
-                states.append((state, bool(how)))
-                blocks.append(t.ops.local_search(q_words, q_nbytes, k, **how) if max_hamming is None else t.ops.local_search(q_words, q_nbytes, k, max_hamming))
-            share = torch.cat(blocks)
-            total = share.numel()
-            if share.is_cuda and first._staged():
-                host = torch.empty(first.world_size * total, dtype=share.dtype)      # rehearsal transport: staged through the host
-                first.dist.all_gather_into_tensor(host, share.cpu(), group=first.group)
-                gathered = host.to(share.device)
-            else:
-                make = getattr(first.ops, "buffer", None)
-                gathered = make("gathered", first.world_size * total) if make else torch.empty(first.world_size * total, dtype=share.dtype, device=share.device)
-                first.dist.all_gather_into_tensor(gathered, share, group=first.group)
-            # the merges: queued back to back behind ONE synchronisation when the ops share an engine that can (HipShardOps.merge_many)
-            merged = None
-            many = getattr(first.ops, "merge_many", None)
-            if many is not None and all(getattr(t.ops, "engine", None) is first.ops.engine for t, *_ in items):
-                parts, offset = [], 0
-                for (t, q_words, _, k, _), block in zip(items, blocks):
-                    parts.append((offset, t.world_size, q_words.shape[0], k, t.ops.key_words))
-                    offset += block.numel()
-                merged = many(gathered, total, parts)
-            out, offset = [], 0
-            for (t, q_words, q_nbytes, k, max_hamming), block in zip(items, blocks):
-                nq = q_words.shape[0]
-                strided = getattr(t.ops, "merge_strided", None)
-                if merged is not None:
-                    res = merged[len(out)]
-                elif strided is not None:
-                    res = strided(gathered, offset, total, t.world_size, nq, k)
-                else:
-                    part = gathered.view(t.world_size, total)[:, offset : offset + block.numel()].contiguous().view(-1)
-                    res = t.ops.merge(part, t.world_size, nq, k)
-                state, hinted = states[len(out)]
-                cnt = res[3]
-                full = not np.any(cnt == COUNT_OVERFLOW) and int(cnt.min()) >= k
-                if hinted and not full:
-                    # the hint was too tight for some query (or a list overflowed under it): the merged lists are the same on every rank, so
-                    # every rank repeats THIS item without it together
-                    t.hint_misses += 1
-                    state[2] = min(2 * state[2] + 1, 15)
-                    state[1] = state[2] - 1
-                    res = t._exchange(q_words, q_nbytes, k, max_hamming, {})
-                    cnt = res[3]
-                    hinted = False
-                if np.any(cnt == COUNT_OVERFLOW):
-                    # a shard could only mark an overflowed candidate list: every rank repeats THIS item through the synchronous path together
-                    res = t._exchange(q_words, q_nbytes, k, max_hamming, {"synchronous": True})
-                    cnt = res[3]
-                if state is not None:
-                    full = not np.any(cnt == COUNT_OVERFLOW) and int(cnt.min()) >= k
-                    if hinted:
-                        t.hint_hits += 1
-                        state[0], state[2] = max(int(res[1][:, k - 1].max()) + hint_margin(k), state[0] - 1), 0
-                    else:
-                        state[0] = int(res[1][:, k - 1].max()) + hint_margin(k) if full else None
-                out.append(res)
-                offset += block.numel()
+        return ShardedTable._step(items)
+
+    @staticmethod
+    def _step(items):
+        """
+        One step for ``items`` (as ``search_many``): the exchange, every top-k item under its table's hint, then one verdict per item
+        from its merged lists -- the same on every rank, so every rank repeats the same items together.
+        """
+        alone = items[0][0]._alone()
+        hints, hows = [], []
+        for t, q_words, q_nbytes, k, max_hamming in items:
+            hint = t.hint(q_words, q_nbytes, k) if t.use_hints and max_hamming is None and q_words.shape[0] and not alone else None
+            start = None if hint is None else hint.start()
+            hints.append(hint)
+            hows.append({} if start is None else {"hint": start})
+        out = ShardedTable._exchange(items, hows, alone)
+        for i, item in enumerate(items):
+            t, k, hint = item[0], item[3], hints[i]
+            if hows[i]:              # (hinted)
+                worst = worst_if_full(out[i], k)
+                if worst is not None:
+                    t.hint_hits += 1
+                    hint.held(worst, k)
+                    continue
+                # the hint was too tight for some query (or a list overflowed under it): THIS item again without it
+                t.hint_misses += 1
+                hint.missed()
+                out[i] = ShardedTable._exchange([item], [{}], alone)[0]
+            if np.any(out[i][3] == COUNT_OVERFLOW):
+                # some shard's candidate list overflowed and the asynchronous search could only mark it: THIS item again
+                # through the synchronous path (exact fallback)
+                out[i] = ShardedTable._exchange([item], [{"synchronous": True}], alone)[0]
+            if hint is not None:
+                hint.reseed(worst_if_full(out[i], k), k)
         return out
 
-    def _exchange(self, q_words, q_nbytes, k, max_hamming, how):
-        nq = q_words.shape[0]
-        alone = self.world_size == 1 and not (self.always_gather and self.dist.is_initialized())
-        single = getattr(self.ops, "search_single", None)
+    @staticmethod
+    def _exchange(items, hows, alone):
+        """Every item's local search (``hows``: its extra arguments), ONE gather of the ranks' shares, the merges: one result per item."""
+        first, q_words, q_nbytes, k, max_hamming = items[0]
+        single = getattr(first.ops, "search_single", None)
         if alone and single is not None:
-            return single(q_words, q_nbytes, k, max_hamming)
-        with _exchange_scope(self.ops):
-            block = self.ops.local_search(q_words, q_nbytes, k, **how) if max_hamming is None else self.ops.local_search(q_words, q_nbytes, k, max_hamming, **how)
-            if alone:
-                return self.ops.merge(block, 1, nq, k)
+            return [single(q_words, q_nbytes, k, max_hamming)]
+        with _exchange_scope(first.ops):
+            blocks = []
+            for (t, qw, qn, kk, radius), how in zip(items, hows):
+                blocks.append(t.ops.local_search(qw, qn, kk, **how) if radius is None else t.ops.local_search(qw, qn, kk, radius, **how))
+            if len(items) == 1:          # (no concatenation, no copy; alone: this rank's block is the one list)
+                gathered = blocks[0] if alone else first._gather(blocks[0])
+                return [first.ops.merge(gathered, 1 if alone else first.world_size, q_words.shape[0], k)]
             import torch
 
-            if block.is_cuda and self._staged():
-                # rehearsal transport (several ranks sharing one GPU cannot use RCCL): stage the blocks through the host
-                host = torch.empty(self.world_size * block.numel(), dtype=block.dtype)
-                self.dist.all_gather_into_tensor(host, block.cpu(), group=self.group)
-                gathered = host.to(block.device)
+            share = torch.cat(blocks)
+            return ShardedTable._merge_parts(items, blocks, first._gather(share), share.numel())
+
+    def _gather(self, share):
+        """The one exchange step of the path: [world] x this rank's share, a share = {records [nq][k] | counts [nq]} per item."""
+        import torch
+
+        total = self.world_size * share.numel()
+        staged = share.is_cuda and self._staged()
+        if staged:
+            # rehearsal transport (several ranks sharing one GPU cannot use RCCL): the blocks are staged through the host
+            gathered, mine = torch.empty(total, dtype=share.dtype), share.cpu()
+        else:
+            make = getattr(self.ops, "buffer", None)
+            gathered, mine = make("gathered", total) if make else torch.empty(total, dtype=share.dtype, device=share.device), share
+        self.dist.all_gather_into_tensor(gathered, mine, group=self.group)
+        return gathered.to(share.device) if staged else gathered
+
+    @staticmethod
+    def _merge_parts(items, blocks, gathered, stride):
+        """
+        The merges of a fused exchange (a part's lists lie ``stride`` bytes apart): queued back to back behind ONE synchronisation
+        when the ops share an engine that can (``HipShardOps.merge_many``), else a strided merge each, else a contiguous copy each.
+        """
+        first = items[0][0]
+        parts, offset = [], 0
+        for (t, q_words, _, k, _), block in zip(items, blocks):
+            parts.append((offset, t.world_size, q_words.shape[0], k, t.ops.key_words))
+            offset += block.numel()
+        many = getattr(first.ops, "merge_many", None)
+        if many is not None and all(getattr(t.ops, "engine", None) is first.ops.engine for t, *_ in items):
+            merged = many(gathered, stride, parts)
+            if merged is not None:
+                return merged
+        out = []
+        for (t, *_), block, (offset, n_lists, nq, k, _) in zip(items, blocks, parts):
+            strided = getattr(t.ops, "merge_strided", None)
+            if strided is not None:
+                out.append(strided(gathered, offset, stride, n_lists, nq, k))
             else:
-                make = getattr(self.ops, "buffer", None)
-                gathered = make("gathered", self.world_size * block.numel()) if make else torch.empty(self.world_size * block.numel(), dtype=block.dtype, device=block.device)
-                # the one exchange step of the path: [world] x {records [nq][k] | counts [nq]}
-                self.dist.all_gather_into_tensor(gathered, block, group=self.group)
-            return self.ops.merge(gathered, self.world_size, nq, k)
+                out.append(t.ops.merge(gathered.view(n_lists, stride)[:, offset : offset + block.numel()].contiguous().view(-1), n_lists, nq, k))
+        return out

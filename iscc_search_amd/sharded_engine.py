@@ -38,6 +38,7 @@ import os
 import numpy as np
 
 from iscc_search_amd.sharded import ShardedTable
+from iscc_search_amd.table_checks import TableChecks
 
 _GOLDEN = np.uint64(0x9E3779B97F4A7C15)
 
@@ -116,8 +117,8 @@ class ShardedEngine:
         for table, q_words, q_nbytes, k, max_hamming in requests:
             if k < 1:
                 raise ValueError("`count` must be >= 1")
-            q_words = np.ascontiguousarray(q_words, dtype=np.uint64).reshape(-1, table.max_words)
-            q_nbytes = None if q_nbytes is None else np.ascontiguousarray(q_nbytes, dtype=np.uint8)
+            q_words = table._words(q_words)
+            q_nbytes = table._nbytes(q_nbytes, q_words.shape[0])
             items.append((table._sharded, q_words, q_nbytes, k, None if max_hamming is None else int(max_hamming)))
         if all(qn is None or len(np.unique(qn)) <= 1 for _, _, qn, _, _ in items) and all(q.shape[0] for _, q, _, _, _ in items):
             fused = ShardedTable.search_many(items)
@@ -132,7 +133,7 @@ class ShardedEngine:
         self.local.close()
 
 
-class ShardedHipTable:
+class ShardedHipTable(TableChecks):
     """One logical table; this rank holds the rows whose key hashes to it."""
 
     def __init__(self, engine, local_table):
@@ -198,10 +199,10 @@ class ShardedHipTable:
     # -- the data path -----------------------------------------------------------------------------------------
     def _by_length(self, q_words, q_nbytes, run):
         """The device search takes queries of ONE byte length per call (one compared prefix per segment)."""
-        q_words = np.ascontiguousarray(q_words, dtype=np.uint64).reshape(-1, self.max_words)
+        q_words = self._words(q_words)
+        q_nbytes = self._nbytes(q_nbytes, q_words.shape[0])
         if q_nbytes is None or len(np.unique(q_nbytes)) <= 1:
-            return run(q_words, None if q_nbytes is None else np.ascontiguousarray(q_nbytes, dtype=np.uint8))
-        q_nbytes = np.asarray(q_nbytes, dtype=np.uint8)
+            return run(q_words, q_nbytes)
         out = None
         for length in np.unique(q_nbytes):
             sel = np.nonzero(q_nbytes == length)[0]

@@ -15,8 +15,8 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-from iscc_search_amd.sharded import RECORD_BYTES, ShardedTable, block_bytes, shard_of_key, shard_range
-from oracle import oracle_topk
+from iscc_search_amd.sharded import RECORD_BYTES, ShardedTable, ShardHint, block_bytes, hint_margin, shard_of_key, shard_range
+from oracle import np_within, oracle_topk
 from oracle_engine import RECORD_DTYPE, OracleTable
 
 
@@ -265,7 +265,7 @@ def _hint_worker(rank, world, port, out_dir):
         ask(random_q[nq : 2 * nq])    # 1: every shard starts under it; the merged lists hold k rows: stands
         ask(near_q)                   # 1: far inside the hint (which decays by one bit)
         ask(random_q[2 * nq : 3 * nq])   # 1
-        sharded._hints[(int(nq).bit_length(), k, None)][0] = 3    # a hint that is too tight for random queries ...
+        sharded.hint(random_q[:nq], None, k).value = 3    # a hint that is too tight for random queries ...
         ask(random_q[3 * nq :])       # 1: ... the merged lists come up short: the step is repeated without it (and re-seeds)
         ask(random_q[:nq])            # 1: one miss does not back off
         assert log == [0, 1, 1, 1, 1, 1], log
@@ -282,4 +282,116 @@ def test_shards_start_under_the_global_kth_distance_of_the_previous_step(tmp_pat
         sock.bind(("127.0.0.1", 0))
         port = sock.getsockname()[1]
     mp.spawn(_hint_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    assert sorted(os.listdir(tmp_path)) == ["ok0.npy", "ok1.npy"]
+
+
+def test_shard_hint_transitions():
+    """The hint policy on its own: seed, decay, the back-off series of consecutive misses, no hint from lists that were not full."""
+    assert [hint_margin(k) for k in (1, 8, 63, 64, 4096)] == [2, 2, 2, 1, 1]
+    hint = ShardHint()
+    assert hint.start() is None                       # a fresh object runs unhinted
+    for k, margin in ((8, 2), (63, 2), (64, 1), (100, 1)):
+        hint.reseed(20, k)
+        assert hint.start() == 20 + margin
+    # held: at most one bit down per step, never below worst + margin
+    hint.reseed(30, 8)
+    assert hint.start() == 32
+    seen = []
+    for worst in (10, 10, 10, 29, 10, 10):
+        hint.held(worst, 8)
+        seen.append(hint.start())
+    assert seen == [31, 30, 29, 31, 30, 29]
+    for _ in range(40):
+        hint.held(10, 8)
+    assert hint.start() == 12
+    hint.held(50, 64)
+    assert hint.start() == 51
+
+    def unhinted_steps_after_a_miss(hint, k=8):
+        """A hinted step misses and is repeated (which re-seeds); then the steps that run unhinted before the next hinted one."""
+        assert hint.start() is not None
+        hint.missed()
+        hint.reseed(20, k)
+        steps = 0
+        while hint.start() is None:
+            hint.reseed(20, k)
+            steps += 1
+            assert steps < 100
+        return steps
+
+    hint = ShardHint()
+    hint.reseed(20, 8)
+    assert [unhinted_steps_after_a_miss(hint) for _ in range(5)] == [0, 2, 6, 14, 14]
+    assert hint.start() == 22
+    hint.held(20, 8)                                  # one step that stands resets the series
+    assert [unhinted_steps_after_a_miss(hint) for _ in range(5)] == [0, 2, 6, 14, 14]
+    # lists that were not full leave no hint, whatever was there before
+    hint = ShardHint()
+    hint.reseed(20, 8)
+    hint.reseed(None, 8)
+    assert hint.start() is None and hint.value is None
+
+
+def _fused_worker(rank, world, port, out_dir):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        rng = np.random.default_rng(815)
+        n, k = 3000, 8
+        data, tables = [], []
+        for _ in range(2):
+            words = rng.integers(0, 2**64, size=(n, 1), dtype=np.uint64)
+            keys = rng.permutation(n).astype(np.uint64) + np.uint64(3)
+            lo, hi = shard_range(n, rank, world)
+            table = OracleTable(0, 1, 8)
+            table.add(keys[lo:hi], words[lo:hi])
+            data.append((keys, words))
+            tables.append(ShardedTable(HintedOracleShardOps(table)))
+        a, b = tables
+        assert a.use_hints and b.use_hints
+        q = rng.integers(0, 2**64, size=(30, 1), dtype=np.uint64)
+        radius = 24
+        log = []
+
+        def ask(qa, qb, qw):
+            """Two top-k items on different tables (1 and 5 queries) and a range-limited item of another block size, ONE exchange."""
+            before = HintedOracleShardOps.hinted_calls, a.hint_hits + b.hint_hits, a.hint_misses, b.hint_misses
+            got = ShardedTable.search_many([(a, qa, None, k, None), (b, qb, None, k, None), (b, qw, None, 3, radius)])
+            assert got is not None and len(got) == 3
+            for (keys, words), qq, res in ((data[0], qa, got[0]), (data[1], qb, got[1])):
+                for g, e in zip(res, oracle_topk(0, keys, words, None, qq, None, k, fixed_nbytes=8)):
+                    np.testing.assert_array_equal(g, e)
+            keys, words = data[1]
+            assert got[2][0].shape == (len(qw), 3)
+            for i in range(len(qw)):
+                kk, h, p = np_within(words, 8, keys, qw[i], 8, 3, radius)
+                c = len(h)
+                assert int(got[2][3][i]) == c
+                np.testing.assert_array_equal(got[2][0][i, :c], kk)
+                np.testing.assert_array_equal(got[2][1][i, :c], h)
+                np.testing.assert_array_equal(got[2][2][i, :c], p)
+                assert not got[2][0][i, c:].any() and not got[2][1][i, c:].any() and not got[2][2][i, c:].any()
+            log.append((HintedOracleShardOps.hinted_calls - before[0], a.hint_hits + b.hint_hits - before[1],
+                        a.hint_misses - before[2], b.hint_misses - before[3]))
+
+        HintedOracleShardOps.hinted_calls = 0
+        ask(q[0:1], q[1:6], q[6:8])             # nothing to go by: no hinted search, both top-k items seed their hints
+        ask(q[8:9], q[9:14], q[14:16])          # both top-k items start under the first call's hints and stand; the range item never has one
+        assert log == [(0, 0, 0, 0), (2, 2, 0, 0)], log
+        assert a.hint(q[0:1], None, k).value is not None and b.hint(q[1:6], None, k).value is not None
+        assert len(a._hints) == 1 and len(b._hints) == 1          # (none for the range-limited item)
+        b.hint(q[1:6], None, k).value = 3       # too tight for random queries, on ONE item ...
+        ask(q[16:17], q[17:22], q[22:24])       # ... which alone is repeated without it; the other hinted item stands
+        assert log[-1] == (2, 1, 0, 1), log
+        ask(q[24:25], q[25:30], q[6:8])         # the repeated item re-seeded its hint: one miss does not back off
+        assert log[-1] == (2, 2, 0, 0), log
+        np.save(os.path.join(out_dir, f"ok{rank}.npy"), np.array(log))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_fused_searches_share_one_exchange_and_keep_their_own_hints(tmp_path):
+    """``ShardedTable.search_many`` over gloo with hints: three items, one exchange, a miss repeats its item alone; all against the oracle."""
+    mp.spawn(_fused_worker, args=(2, _free_port(), str(tmp_path)), nprocs=2, join=True)
     assert sorted(os.listdir(tmp_path)) == ["ok0.npy", "ok1.npy"]
