@@ -112,35 +112,30 @@ int isccsearch_create(int device_id, isccsearch_handle** out);
 int isccsearch_destroy(isccsearch_handle* h);
 const char* isccsearch_last_error(void);
 
-/* Options: "mfma" (0|1, default 1: batches of >= "mfma_min_queries" (17) queries over >= "mfma_min_rows" (65 536) rows are
- * scanned on the matrix cores -- bits as FP4 0/+-1, exact f32 sums, csrc/mfma_scan.hip -- instead of XOR + popcount; 64-bit codes,
- * whose packed form of that kernel is cheaper, from "mfma_pack_min_queries" (9) queries -- as do longer codes over segments of at
- * most "mfma_few_rows" (12 Mi) rows (at 25 M rows one pass of 16 on the XOR + popcount kernel is ahead again);
- * "self_tighten" (0|1, default 1): for k <= "self_max_k" (4 096: every k) that scan is ONE pass whose thresholds tighten themselves,
- * bootstrapped from max("self_boot_rows" (65 536), "self_boot_per_k" (1 024) x k) rows and looking at the live thresholds every "self_refresh_steps" (1) steps,
- * instead of threshold levels growing by "mfma_level_growth" (4)); "mfma_pack" (0|1, default 1: 64-bit codes run the packed
- * form of that kernel -- two row tiles per accumulator, v_pk_minimum3_f16 fold -- unless the batch holds an all-zero query);
- * "speculate" (0|1, default 1: a batch of up to "spec_max_queries" (128) queries over a one-segment table is first tried as ONE
- * range-limited pass under the k-th distance the previous such search ended at + 2, and verified: exact either way; larger
- * batches START their single pass under that hint instead of a bootstrap sample's threshold, "self_hint" (0|1, default 1), verified
- * the same way; "device_search_hint" (-1 | 0..256, one-shot): the next isccsearch_search_device_async starts under THIS distance and
- * its lists hold the table's nearest rows within it -- fewer than k if it was too tight, which the caller must check (sharded.py));
- * "candidate_cap" (16 384: floor of the per-query candidate
- * buffer, in entries); "queries_per_pass" (8|16, XOR + popcount kernel), "profile"
- * (0|1: time every collect-scan launch with HIP events, read back through isccsearch_stats_get), "stretch_mb" (XOR + popcount
- * kernel: rows per collect launch, in MB of codes, when several query groups share a launch: they then read the stretch from the
- * caches instead of HBM; default 128, 0 = one streaming pass per group; matrix-core launches whose query chunks share the rows take
- * "mfma_stretch_factor" (3) times that), "fold_tau" (whole 64-bit codes: query groups whose
- * thresholds are all <= this take the folded 3.5-op fast path; default 11, 0 = never); tuning: "blocks_per_cu", "boot_rows",
- * "level_growth", "repick"; "count_candidates" (0|1: after every batch read back how many candidates its scan appended --
- * statistics `candidates` / `candidate_batches`; one more copy and synchronisation per batch, for accounting runs);
- * "tiny_rows" (16 384: a segment of at most this many rows is answered by ONE launch, one block per query -- distances of every row,
- * candidate list, select; 0: never.  Tables the caller sends to the matrix cores by lowering "mfma_min_rows" keep that path);
- * "select_wide_from" (2 048: selects whose LDS sort buffer has at least this many slots -- k > 256 -- run 1 024-thread blocks
- * instead of 256-thread ones when the batch has fewer queries than half the CUs, and whatever the batch from twice that many
- * slots; a larger value than any buffer turns that off).
- * "nontemporal" accepts only 1 (the only variant built). */
+/* Options, by name: range, default, meaning (the measurements behind them: struct Options in csrc/isccsearch.hip).
+ *   queries_per_pass    8|16      8      queries per streaming pass of the XOR + popcount kernel
+ *   profile             0|1       0      time every scan launch with HIP events (read back through isccsearch_stats_get)
+ *   count_candidates    0|1       0      read back how many candidates each batch's scan appended (stats candidates / candidate_batches)
+ *   tiny_rows           0..2^20   16384  segments of at most this many rows are answered by ONE launch; 0: never
+ *   select_wide_from    0..2^32-1 2048   selects whose sort buffer has at least this many slots run 1 024-thread blocks
+ *   stretch_mb          0..65536  128    MB of rows per collect launch when several query groups share them; 0: one streaming pass
+ *   mfma_stretch_factor 1..64     3      matrix-core launches whose query chunks share the rows take this many times stretch_mb
+ *   mfma                0|1       1      large batches scan on the matrix cores (FP4 MFMA, exact sums) instead of XOR + popcount
+ *   mfma_min_queries    1..1024   17     ... from this many queries (64-bit codes and segments of up to 12 Mi rows: from 9)
+ *   mfma_min_rows       >= 1      65536  ... over at least this many rows
+ *   mfma_pack           0|1       1      64-bit codes: the packed kernel (two row tiles per accumulator) unless a query is all zero
+ *   mfma_pack3          0|1       1      ... three row tiles per accumulator for chunks of more than four query groups
+ *   self_tighten        0|1       1      the matrix-core scan is ONE pass with self-tightening thresholds instead of threshold levels
+ *   self_boot_rows      256..2^20 65536  ... bootstrapped from at least this many rows
+ *   self_boot_per_k     0..2^20   1024   ... and this many per wanted neighbour
+ *   speculate           0|1       1      small batches first try ONE range-limited pass under the previous k-th distance, verified
+ *   spec_max_queries    0..1024   128    ... batches of up to this many queries
+ *   self_hint           0|1       1      larger batches START their single pass under that hint instead of a sample, verified
+ *   device_search_hint  -1..256   -1     one-shot: the next isccsearch_search_device_async starts under this distance (the caller verifies)
+ *   candidate_cap       64..2^22  16384  floor of the per-query candidate buffer, in entries
+ * An unknown name, a NULL argument or a value outside the range fails with -EINVAL and changes nothing. */
 int isccsearch_set_option(isccsearch_handle* h, const char* name, int64_t value);
+int isccsearch_get_option(isccsearch_handle* h, const char* name, int64_t* value);
 int isccsearch_stats_get(isccsearch_handle* h, isccsearch_stats* out, int reset);
 
 /* Tables.  max_bytes = longest code in bytes (1..32); for Hamming tables every code has exactly

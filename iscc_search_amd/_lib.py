@@ -24,7 +24,7 @@ MAX_SCORED_SIMPRINTS = 8192   # ISCCSEARCH_MAX_SCORED_SIMPRINTS: query simprints
 
 # every symbol include/isccsearch.h declares
 EXPORTS = (
-    "isccsearch_create", "isccsearch_destroy", "isccsearch_last_error", "isccsearch_set_option",
+    "isccsearch_create", "isccsearch_destroy", "isccsearch_last_error", "isccsearch_set_option", "isccsearch_get_option",
     "isccsearch_stats_get", "isccsearch_table_open", "isccsearch_table_drop", "isccsearch_reserve",
     "isccsearch_size", "isccsearch_add", "isccsearch_remove", "isccsearch_contains", "isccsearch_get",
     "isccsearch_segments", "isccsearch_export", "isccsearch_add_columns",
@@ -162,6 +162,7 @@ def load_library():
         "isccsearch_destroy": (i, [vp]),
         "isccsearch_last_error": (ctypes.c_char_p, []),
         "isccsearch_set_option": (i, [vp, ctypes.c_char_p, ctypes.c_int64]),
+        "isccsearch_get_option": (i, [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]),
         "isccsearch_stats_get": (i, [vp, ctypes.POINTER(Stats), i]),
         "isccsearch_table_open": (i, [vp, i, i, i, ctypes.POINTER(ctypes.c_uint32)]),
         "isccsearch_table_drop": (i, [vp, u32]),

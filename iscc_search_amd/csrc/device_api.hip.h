@@ -174,8 +174,8 @@ int isccsearch_search_device_async(isccsearch_handle* h, uint32_t table, uint32_
     int hint;
     {
         std::lock_guard<std::mutex> lk(h->mu);
-        hint = h->device_search_hint;
-        h->device_search_hint = -1;
+        hint = (int)h->opt.device_search_hint;
+        h->opt.device_search_hint = -1;
     }
     if (async) {
         std::lock_guard<std::mutex> lk(h->mu);
@@ -198,7 +198,7 @@ int isccsearch_search_device_async(isccsearch_handle* h, uint32_t table, uint32_
             // pass -- radius_init + collect + select instead of bootstrap + levels + picks + collect -- as search_locked's speculative
             // pass does on one GPU; same contract: the table's nearest rows within the hint, fewer than k if it was too tight
             if (radius < 0 && hint >= 0) {
-                if (h->speculate && nq <= h->spec_max_queries) batch.radius = hint;
+                if (h->opt.speculate && nq <= (uint32_t)h->opt.spec_max_queries) batch.radius = hint;
                 else batch.self_hint = hint;
             }
             if ((rc = batch.begin(q_words))) return rc;

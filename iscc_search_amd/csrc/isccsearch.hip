@@ -196,6 +196,86 @@ void seg_free(Segment& s) {
     s.hkeys.shrink_to_fit();
 }
 
+// ------------------------------------------------------------------------------------------
+// options
+// ------------------------------------------------------------------------------------------
+// Selections whose A/B is settled and that no workload sets: constants at the value they were measured to
+constexpr uint32_t BLOCKS_PER_CU = 8;      // scan grid = CUs x this (per query group)
+constexpr uint64_t BOOT_ROWS = 65536;      // rows of the threshold bootstrap of the level design (4 096 exact + the rest counted under that
+                                           // cut; wide blocks for small batches): one level launch + pick less than with 4 096 rows
+                                           // (100 M x 64-bit: 8 queries 0.231 against 0.252 ms, 4 queries at k = 100 0.286 against 0.354)
+constexpr uint64_t LEVEL_GROWTH = 8;       // each threshold level streams this many times the rows seen so far
+constexpr uint64_t MFMA_LEVEL_GROWTH = 4;  // ... when the scan runs on the matrix cores (k <= 64): 4 / 6 / 8 measured 295.5 / 295.9 / 290.4 k q/s at 100 M rows and 1.35 / 1.28 / 1.27 M at 12.5 M
+constexpr uint32_t FOLD_TAU = 11;          // 64-bit codes: groups whose thresholds are all <= this take the folded fast path of scan_adapt_kernel
+constexpr uint32_t MFMA_PACK_MIN_QUERIES = 9;    // 64-bit codes (packed matrix-core kernel): from this many queries (see use_mfma)
+constexpr uint64_t MFMA_FEW_ROWS = 12ull << 20;  // longer codes: segments up to this many rows take the matrix cores from MFMA_PACK_MIN_QUERIES queries too
+constexpr uint32_t SELF_REFRESH_STEPS = 1;       // the single pass: steps of a full chunk between two looks at the live thresholds (power of two)
+// Every k takes the single self-tightening pass (it stopped at 512 until the pass was measured beyond it: k = 1 000 / 2 000 over 100 M rows
+// 6.0 / 9.0 ms against 8.5 / 14.0 of the level design, 4.2 / 6.6 under a hint; the unpruned lists hold ~k ln(n / sample) entries + the
+// first steps' flood: see the cap in Batch::begin.  100 M rows, k = 100 / 256 / 512: 3.80 / 4.52 / 6.04 ms against 4.60 / 5.35 / 7.37 with levels).
+// The collect pass re-derives the threshold after every stretch but the last, and large batches bootstrap with boot_multi_kernel
+// (four queries per block share the sample's row loads).
+
+// What a caller can set and read by name; every value an int64_t, the defaults here
+struct Options {
+    int64_t queries_per_pass = 8;     // queries per streaming pass: 8 keeps the scan HBM-bound
+    int64_t profile = 0;
+    int64_t count_candidates = 0;     // read the candidate counters back after every batch (one more copy + synchronisation: accounting runs only)
+    int64_t tiny_rows = 16384;        // segments of at most this many rows are answered by ONE launch (tiny_search_kernel); 0: never
+    int64_t select_wide_from = 2048;  // sort buffers of at least this many slots are selected by 1 024-thread blocks (0xFFFFFFFF: never)
+    int64_t stretch_mb = CACHE_STRETCH_BYTES >> 20;   // MB of rows per collect launch when several query groups share them (0: one pass)
+    int64_t mfma_stretch_factor = 3;  // ... times this on the matrix cores, when several CHUNKS of queries share them
+    // large batches: the scan as an FP4 matrix-core contraction (mfma_scan.hip) instead of XOR + popcount on the VALU
+    int64_t mfma = 1;
+    int64_t mfma_min_queries = 17;    // batches below this stay on the XOR + popcount kernel, HBM-bound up to ~11 queries per pass
+                                      // (100 M x 64-bit: 32 queries 0.49 ms against 0.71 ms, 24 queries 0.48 against 0.63; at 16 both take 0.47 ms)
+    int64_t mfma_min_rows = 65536;    // launches over fewer rows do not amortise the per-block query expansion
+    int64_t mfma_pack = 1;            // 64-bit codes on the matrix cores: two row tiles per accumulator, packed f16 fold (mfma_pack_kernel)
+    int64_t mfma_pack3 = 1;           // ... chunks of more than four query groups: three row tiles per accumulator, OR fold (mfma_pack3_kernel); 0: mfma_pack_kernel
+    // on the matrix cores: ONE pass whose thresholds tighten themselves (MODE_SELF) instead of levels + picks --
+    // every launch of that chain costs ~35 us of ramp, prologue and tail, and a step of 100 M rows had seven of them
+    int64_t self_tighten = 1;
+    int64_t self_boot_rows = 65536;   // its bootstrap sample: all waves start under the sample's threshold at once, so a
+                                      // short sample floods the first steps with candidates (4 096 rows: ~860 per query)
+    int64_t self_boot_per_k = 1024;   // ... and at least this many rows per wanted neighbour
+    int64_t self_hint = 1;            // batches above spec_max_queries: start the single self-tightening pass under the hint (no bootstrap sample)
+    int64_t speculate = 1;            // small batches: try one range-limited pass under the previous search's k-th distance first
+    int64_t spec_max_queries = 128;   // ... batches of up to this many queries
+    int64_t device_search_hint = -1;  // one-shot: the next isccsearch_search_device_async starts its single pass under this threshold (the caller verifies)
+    int64_t candidate_cap = 16384;    // floor of the per-query candidate buffer (entries); tests shrink it to reach the overflow paths
+};
+
+// name -> field and the values it takes (queries_per_pass: 8 or 16 only, see isccsearch_set_option)
+struct OptionDesc { const char* name; int64_t Options::* field; int64_t min, max; };
+constexpr int64_t NO_MAX = INT64_MAX;
+const OptionDesc OPTIONS[] = {
+    {"queries_per_pass", &Options::queries_per_pass, 8, 16},
+    {"profile", &Options::profile, 0, 1},
+    {"count_candidates", &Options::count_candidates, 0, 1},
+    {"tiny_rows", &Options::tiny_rows, 0, 1 << 20},
+    {"select_wide_from", &Options::select_wide_from, 0, 0xFFFFFFFFll},
+    {"stretch_mb", &Options::stretch_mb, 0, 65536},
+    {"mfma_stretch_factor", &Options::mfma_stretch_factor, 1, 64},
+    {"mfma", &Options::mfma, 0, 1},
+    {"mfma_min_queries", &Options::mfma_min_queries, 1, 1024},
+    {"mfma_min_rows", &Options::mfma_min_rows, 1, NO_MAX},
+    {"mfma_pack", &Options::mfma_pack, 0, 1},
+    {"mfma_pack3", &Options::mfma_pack3, 0, 1},
+    {"self_tighten", &Options::self_tighten, 0, 1},
+    {"self_boot_rows", &Options::self_boot_rows, 256, 1 << 20},
+    {"self_boot_per_k", &Options::self_boot_per_k, 0, 1 << 20},
+    {"self_hint", &Options::self_hint, 0, 1},
+    {"speculate", &Options::speculate, 0, 1},
+    {"spec_max_queries", &Options::spec_max_queries, 0, 1024},
+    {"device_search_hint", &Options::device_search_hint, -1, 8 * ISCCSEARCH_MAX_BYTES},
+    {"candidate_cap", &Options::candidate_cap, 64, 1 << 22},
+};
+const OptionDesc* find_option(const char* name) {
+    for (const OptionDesc& d : OPTIONS)
+        if (!strcmp(d.name, name)) return &d;
+    return nullptr;
+}
+
 }  // namespace
 
 struct PendingSearch;
@@ -210,49 +290,8 @@ struct isccsearch_handle {
     int cus = 256;
     hipStream_t stream = nullptr;
     std::vector<std::unique_ptr<Table>> tables;
-    // options
-    int tq = 8;   // queries per streaming pass: 8 keeps the scan HBM-bound
-    bool profile = false;
-    bool count_candidates = false;   // read the candidate counters back after every batch (one more copy + synchronisation: accounting runs only)
-    uint32_t blocks_per_cu = 8;    // scan grid = CUs x this (per query group)
-    uint64_t boot_rows = 65536;    // rows of the threshold bootstrap of the level design (4 096 exact + the rest counted under that
-                                   // cut; wide blocks for small batches): one level launch + pick less than with 4 096 rows
-                                   // (100 M x 64-bit: 8 queries 0.231 against 0.252 ms, 4 queries at k = 100 0.286 against 0.354)
-    uint64_t level_growth = 8;     // each threshold level streams this many times the rows seen so far
-    bool repick = true;            // re-derive the threshold after every collect stretch but the last
-    uint32_t tiny_rows = 16384;       // segments of at most this many rows are answered by ONE launch (tiny_search_kernel); 0: never
-    uint32_t select_wide_from = 2048; // sort buffers of at least this many slots are selected by 1 024-thread blocks (option; 0xFFFFFFFF: never)
-    uint32_t fold_tau = 11;        // 64-bit codes: groups whose thresholds are all <= this take the folded fast path (0: off)
-    uint64_t stretch_bytes = CACHE_STRETCH_BYTES;   // rows per collect launch when several query groups share them (0: one pass)
-    uint64_t mfma_stretch_factor = 3;               // ... times this on the matrix cores, when several CHUNKS of queries share them
-    // large batches: the scan as an FP4 matrix-core contraction (mfma_scan.hip) instead of XOR + popcount on the VALU
-    bool mfma = true;
-    uint32_t mfma_pack_min_queries = 9;   // 64-bit codes (packed matrix-core kernel): from this many queries (see use_mfma)
-    uint64_t mfma_few_rows = 12ull << 20;   // longer codes: segments up to this many rows take the matrix cores from mfma_pack_min_queries queries too
-    uint32_t mfma_min_queries = 17;   // batches below this stay on the XOR + popcount kernel, HBM-bound up to ~11 queries per pass
-                                      // (100 M x 64-bit: 32 queries 0.49 ms against 0.71 ms, 24 queries 0.48 against 0.63; at 16 both take 0.47 ms)
-    uint32_t self_boot_per_k = 1024;  // the single pass's bootstrap sample is at least this many rows per wanted neighbour (and self_boot_rows)
+    Options opt;                      // what isccsearch_set_option / isccsearch_get_option reach (OPTIONS)
     bool spec_suppress = false;       // (isccsearch_search_many: the ordinary rerun of a request whose speculative pass just missed)
-    int device_search_hint = -1;      // one-shot: the next isccsearch_search_device_async starts its single pass under this threshold (the caller verifies)
-    int self_hint = 1;                // batches above spec_max_queries: start the single self-tightening pass under the hint (no bootstrap sample)
-    int speculate = 1;                // small batches: try one range-limited pass under the previous search's k-th distance first
-    uint32_t spec_max_queries = 128;   // ... batches of up to this many queries
-    int mfma_pack = 1;                // 64-bit codes on the matrix cores: two row tiles per accumulator, packed f16 fold (mfma_pack_kernel)
-    int mfma_pack3 = 1;               // ... chunks of more than four query groups: three row tiles per accumulator, OR fold (mfma_pack3_kernel); 0: mfma_pack_kernel
-    uint64_t mfma_min_rows = 65536;   // launches over fewer rows do not amortise the per-block query expansion
-    // k <= self_max_k on the matrix cores: ONE pass whose thresholds tighten themselves (MODE_SELF) instead of levels + picks --
-    // every launch of that chain costs ~35 us of ramp, prologue and tail, and a step of 100 M rows had seven of them
-    bool self_tighten = true;
-    bool boot_multi = true;           // large batches: boot_multi_kernel (four queries per block share the sample's row loads)
-    uint32_t candidate_cap = 16384;   // floor of the per-query candidate buffer (entries); tests shrink it to reach the overflow paths
-    uint32_t self_refresh_steps = 1;  // steps of a full chunk between two looks at the live thresholds (power of two)
-    uint32_t self_max_k = ISCCSEARCH_MAX_K;   // (512 until the single pass was measured beyond it: k = 1 000 / 2 000 over 100 M rows 6.0 / 9.0 ms against
-                                      //  8.5 / 14.0 of the level design, 4.2 / 6.6 under a hint -- tools/ab_self_max_k.sh; the unpruned lists hold
-                                      //  ~k ln(n / sample) entries + the first steps' flood: see the cap in Batch::begin)
-                                      // (100 M rows, k = 100 / 256 / 512: 3.80 / 4.52 / 6.04 ms against 4.60 / 5.35 / 7.37 with levels)
-    uint64_t self_boot_rows = 65536;  // its bootstrap sample: all waves start under the sample's threshold at once, so a
-                                      // short sample floods the first steps with candidates (4 096 rows: ~860 per query)
-    uint64_t mfma_level_growth = 4;   // threshold levels when the scan runs on the matrix cores (k <= 64): 4 / 6 / 8 measured 295.5 / 295.9 / 290.4 k q/s at 100 M rows and 1.35 / 1.28 / 1.27 M at 12.5 M
     // NPHD distance ranks: rank[p_bytes][h] (u16), row 0 = identity (Hamming tables)
     uint16_t* d_rank = nullptr;
     // scratch
@@ -360,14 +399,14 @@ void launch_scan_adapt(int tq, dim3 grid, hipStream_t st, const isk::ScanParams&
     }
 }
 void launch_scan(int W, bool mask, int tq, int mode, dim3 grid, hipStream_t st, const isk::ScanParams& p) {
-    if (W == 1 && !mask && p.fold_tau) {   // whole 64-bit codes: the kernel picks its fast path per query group
+    if (W == 1 && !mask) {   // whole 64-bit codes: the kernel picks its fast path per query group (ScanParams::fold_tau)
         if (mode == isk::MODE_COLLECT) launch_scan_adapt<isk::MODE_COLLECT>(tq, grid, st, p);
         else if (mode == isk::MODE_STRETCH) launch_scan_adapt<isk::MODE_STRETCH>(tq, grid, st, p);
         else launch_scan_adapt<isk::MODE_BOTH>(tq, grid, st, p);
         return;
     }
     switch (W) {
-        case 1: launch_scan_mask<1>(mask, tq, mode, grid, st, p); break;
+        case 1: launch_scan_tq<1, true>(tq, mode, grid, st, p); break;   // (shorter than 64 bits: whole words went above)
         case 2: launch_scan_mask<2>(mask, tq, mode, grid, st, p); break;
         case 3: launch_scan_mask<3>(mask, tq, mode, grid, st, p); break;
         default: launch_scan_mask<4>(mask, tq, mode, grid, st, p); break;
@@ -385,7 +424,7 @@ int tile_rows_for(int W) { return W == 1 ? isk::tile_rows<1>() : W == 2 ? isk::t
 constexpr uint64_t CACHE_RESIDENT_BYTES = 128ull << 20;   // half of the 256 MiB Infinity Cache
 uint32_t scan_grid_x(H* h, int W, uint64_t rows, uint32_t groups = 1, bool sample = false) {
     const uint64_t tiles = rows / (uint64_t)tile_rows_for(W);
-    uint64_t maxb = (uint64_t)h->cus * h->blocks_per_cu;
+    uint64_t maxb = (uint64_t)h->cus * BLOCKS_PER_CU;
     if (sample || rows * 8 * (uint64_t)W <= CACHE_RESIDENT_BYTES)
         maxb = std::max<uint64_t>(8, maxb / std::max<uint32_t>(1, groups));
     // (the rows behind the last whole tile are scanned one slice of BLOCK rows per block: at least that many blocks)
@@ -409,7 +448,7 @@ int drain_events(H* h) {
 // The profile bracket of one launch (option "profile"; a no-op without it): profile_begin() takes an event pair from the pool, records its
 // first event and hands back the second, which profile_end() records behind the launch (level: a threshold-level launch, not a collect launch)
 int profile_begin(H* h, hipEvent_t& end, bool level = false) {
-    if (!h->profile) return 0;
+    if (!h->opt.profile) return 0;
     // a caller that profiles for a long time without reading the statistics must not grow the pool without bound
     if (h->ev_used >= 4096) { int rc = drain_events(h); if (rc) return rc; }
     if (h->ev_used == h->ev_pool.size()) {
@@ -427,7 +466,7 @@ int profile_begin(H* h, hipEvent_t& end, bool level = false) {
     return 0;
 }
 int profile_end(H* h, hipEvent_t end) {
-    if (h->profile) HIPOK(hipEventRecord(end, h->stream));
+    if (h->opt.profile) HIPOK(hipEventRecord(end, h->stream));
     return 0;
 }
 
@@ -497,10 +536,10 @@ struct Batch {
         Ctx c{};
         set_cols(c.sp.col, s, j.W);
         c.sp.queries = h->d_queries.p; c.sp.bias = h->d_bias.p; c.sp.cnt = h->d_cnt.p; c.sp.cand = h->d_cand.p;
-        c.sp.ghist = h->d_ghist.p; c.sp.cap = cap; c.sp.k = k; c.sp.fold_tau = h->fold_tau; c.sp.nq_pad = nq_pad;
+        c.sp.ghist = h->d_ghist.p; c.sp.cap = cap; c.sp.k = k; c.sp.fold_tau = FOLD_TAU; c.sp.nq_pad = nq_pad;
         c.sp.mask_lo = (uint32_t)j.mask_last; c.sp.mask_hi = (uint32_t)(j.mask_last >> 32);
         c.sp.thr_live = h->d_thr.p;
-        c.sp.refresh_steps = h->self_refresh_steps;
+        c.sp.refresh_steps = SELF_REFRESH_STEPS;
         c.sl.cnt = h->d_cnt.p; c.sl.cand = h->d_cand.p; c.sl.cap = cap; c.sl.keys = s.keys;
         c.sl.rank = h->d_rank + (t.metric == ISCCSEARCH_METRIC_NPHD ? j.pbytes * 257 : 0);
         c.sl.out = multi ? h->d_lists.p + ji * (size_t)nq * k : d_out;
@@ -525,12 +564,13 @@ struct Batch {
     // than half the CUs: 10 M x 128-bit, 16 queries, k = 400: 0.148 -> 0.138 ms per call) and for the largest buffers (k = 2 000 over
     // 100 M rows x 1 024 queries: 6.06 -> 5.4 - 5.6 ms); many queries at k = 400 are no faster that way (0.59 -> 0.61 - 0.63 ms), they keep 256.
     void launch_select(const isk::SelectParams& sl, uint32_t blocks) const {
-        const bool wide = sl.P >= h->select_wide_from && (sl.P >= 2 * h->select_wide_from || blocks <= (uint32_t)h->cus / 2);
+        const uint64_t wide_from = (uint64_t)h->opt.select_wide_from;
+        const bool wide = sl.P >= wide_from && (sl.P >= 2 * wide_from || blocks <= (uint32_t)h->cus / 2);
         if (wide) launch_select_nt<1024>(sl, blocks);
         else launch_select_nt<isk::BLOCK>(sl, blocks);
     }
     // (a caller that sends small tables to the matrix cores -- mfma_min_rows lowered: the parity tests of those kernels -- gets them)
-    bool tiny(const Job& j) const { return h->tiny_rows && j.seg->n <= h->tiny_rows && j.seg->n <= cap && j.seg->n < h->mfma_min_rows; }
+    bool tiny(const Job& j) const { return j.seg->n <= (uint64_t)h->opt.tiny_rows && j.seg->n <= cap && j.seg->n < (uint64_t)h->opt.mfma_min_rows; }
     template <int NT>
     void launch_tiny_nt(const isk::TinyParams& tp, const isk::SelectParams& sl, const isk::InlineQueries& iq) const {
         if (sl.out_rows) {
@@ -549,10 +589,11 @@ struct Batch {
     //  XOR + popcount kernel -- one pass of 16 -- against 0.206 / 0.203 / 0.197; 8 queries 0.168 against 0.208; longer codes tie at 16)
     // (... at 100 M rows.  Over a SMALL segment -- config 5's 10 M chunks -- the longer codes win there from 9 queries as well: one pass of 16
     //  on the XOR + popcount kernel streams 10 M x 128-bit rows at 2.1 TB/s, 16 queries x k = 400 per call 0.132 ms against 0.110 on the
-    //  matrix cores, 256-bit 0.170 against 0.148; at 25 M rows 0.144 against 0.153, at 100 M 0.45 against 0.49: option "mfma_few_rows" (12 Mi), the segment size up to which)
+    //  matrix cores, 256-bit 0.170 against 0.148; at 25 M rows 0.144 against 0.153, at 100 M 0.45 against 0.49: MFMA_FEW_ROWS (12 Mi), the segment size up to which)
     bool use_mfma(const Job& j, uint64_t rows) const {
-        const bool from_nine = j.pack || j.seg->n <= h->mfma_few_rows;
-        return h->mfma && nq_pad >= (from_nine ? std::min(h->mfma_min_queries, h->mfma_pack_min_queries) : h->mfma_min_queries) && rows >= h->mfma_min_rows;
+        const bool from_nine = j.pack || j.seg->n <= MFMA_FEW_ROWS;
+        const uint32_t min_queries = (uint32_t)h->opt.mfma_min_queries;
+        return h->opt.mfma && nq_pad >= (from_nine ? std::min(min_queries, MFMA_PACK_MIN_QUERIES) : min_queries) && rows >= (uint64_t)h->opt.mfma_min_rows;
     }
     int scan(const Job& j, const isk::ScanParams& sp, int mode, bool sample) {
         const uint64_t rows = sp.n_rows - sp.row_begin;
@@ -561,7 +602,7 @@ struct Batch {
         if (use_mfma(j, rows) || mode == isk::MODE_SELF) {
             const uint32_t g = isk::mfma_groups_per_chunk((int)j.W, nq_pad, j.pack);
             const uint32_t chunks = (nq_pad + g * 32 - 1) / (g * 32);
-            const bool pack3 = j.pack && h->mfma_pack3 && isk::mfma_pack3_fits(g);
+            const bool pack3 = j.pack && h->opt.mfma_pack3 && isk::mfma_pack3_fits(g);
             const uint64_t rps = isk::mfma_rows_per_wave_step((int)j.W, j.pack, pack3);
             const uint64_t steps = (rows + rps - 1) / rps;
             const uint64_t wpb = isk::mfma_waves_per_block();
@@ -583,7 +624,7 @@ struct Batch {
     int begin(const uint64_t* hq) {
         jobs.clear();
         used_self = false;
-        tq = h->tq;
+        tq = (int)h->opt.queries_per_pass;
         // 9..16 queries: ONE pass of 16 instead of two passes of 8 -- the pass is VALU-bound then, but the rows cross the memory
         // system once and half the launches go (100 M x 64-bit: 0.31 against 0.41 ms; 256-bit: 0.87 against 1.48; no loss at 10 M)
         if (tq == 8 && nq > 8 && nq <= 16) tq = 16;
@@ -600,7 +641,7 @@ struct Batch {
             j.mask_last = mask_for(j.pbytes);
             // the packed fold of mfma_pack_kernel holds a dot product in 7 bits + sign: -64 .. 63.  +64 takes an all-zero query
             // of 64 compared bits (against a row of all ones): such a batch stays on the unpacked kernel
-            j.pack = h->mfma_pack && j.W == 1;
+            j.pack = h->opt.mfma_pack && j.W == 1;
             if (j.pack && j.pbytes == 8)
                 for (uint32_t q = 0; q < nq && j.pack; ++q) j.pack = hq[(size_t)q * t.max_words] != 0;
             jobs.push_back(j);
@@ -609,9 +650,9 @@ struct Batch {
             HIPOK(hipMemsetAsync(d_out_cnt, 0, nq * sizeof(uint32_t), h->stream));
             return 0;
         }
-        cap = std::max<uint32_t>(h->candidate_cap, 16 * k);
+        cap = std::max<uint32_t>((uint32_t)h->opt.candidate_cap, 16 * k);
         // the self-tightening pass never prunes: ~17 k entries per query over 100 M rows (+ the flood of the first steps)
-        if (h->self_tighten && h->mfma && k <= h->self_max_k && radius < 0 && radius_ratio < 0) cap = std::max<uint32_t>(cap, 64 * k);
+        if (h->opt.self_tighten && h->opt.mfma && radius < 0 && radius_ratio < 0) cap = std::max<uint32_t>(cap, 64 * k);
         multi = jobs.size() > 1;
         // select's LDS sort buffer: room for the k winners AND the tie class at the cut -- with 65 distinct distances the class is
         // ~1.5-2.5 k rows at simprint-sized k, and a list that does not fit takes up to 8 / 16 radix passes over its gathered keys first
@@ -669,7 +710,7 @@ struct Batch {
                 hipEvent_t e1 = nullptr;
                 if ((rc = profile_begin(h, e1))) return rc;
                 // (a block walks ALL rows: 1 024 threads whenever the batch leaves the chip room for them, and for the sort buffers select_kernel gives them)
-                const bool wide = (s.n > 2048 && nq <= (uint32_t)h->cus / 2) || c.sl.P >= 2 * h->select_wide_from || (c.sl.P >= h->select_wide_from && nq <= (uint32_t)h->cus / 2);
+                const bool wide = (s.n > 2048 && nq <= (uint32_t)h->cus / 2) || c.sl.P >= 2 * (uint64_t)h->opt.select_wide_from || (c.sl.P >= (uint64_t)h->opt.select_wide_from && nq <= (uint32_t)h->cus / 2);
                 if (wide) launch_tiny_nt<1024>(tp, c.sl, iq);
                 else launch_tiny_nt<isk::BLOCK>(tp, c.sl, iq);
                 HIPOK(hipGetLastError());
@@ -694,7 +735,7 @@ struct Batch {
                 // (matrix-core launches: the chunks' blocks are all resident and walk a stretch in step, so three times the size
                 //  still shares it in the caches and every launch saved is ~30 us of ramp and tail.  Same box, factor 1 / 2 / 3 / 4:
                 //  256-bit 9.31 / 8.90 / 8.79 / 8.72 ms, 128-bit 4.67 / 4.55 / 4.53 / 4.52, 192-bit 7.88 / 7.74 / 7.67 / 7.99)
-                const uint64_t stretch_bytes = use_mfma(j, s.n - from) ? h->stretch_bytes * h->mfma_stretch_factor : h->stretch_bytes;
+                const uint64_t stretch_bytes = ((uint64_t)h->opt.stretch_mb << 20) * (use_mfma(j, s.n - from) ? (uint64_t)h->opt.mfma_stretch_factor : 1);
                 if (shared && stretch_bytes) stretch = std::max<uint64_t>(tile_rows, stretch_bytes / (8 * j.W) / tile_rows * tile_rows);
                 for (uint64_t a = from; a < s.n;) {
                     const uint64_t b = s.n - a <= stretch + stretch / 4 ? s.n : a + stretch;     // no sliver at the end
@@ -709,7 +750,7 @@ struct Batch {
                     // folded fast path of scan_adapt_kernel switch on as the pass advances)
                     // (the last stretch keeps the histogram too -- a handful of atomics -- so that the whole pass is ONE
                     // kernel instantiation, MODE_STRETCH; it just is not followed by a pick)
-                    const bool hist_too = h->repick && jr < 0;
+                    const bool hist_too = jr < 0;
                     const bool repick = hist_too && b < s.n && !self;
                     if (self) {
                         if ((rcl = scan(j, sp, isk::MODE_SELF, false))) return rcl;
@@ -751,18 +792,18 @@ struct Batch {
             }
 
             // 1. bootstrap threshold from the first s0 rows
-            //    Large batches with k <= self_max_k take ONE pass on the matrix cores with self-tightening thresholds (MODE_SELF).
+            //    Large batches take ONE pass on the matrix cores with self-tightening thresholds (MODE_SELF).
             //    (The XOR + popcount kernels keep the levels: their resident blocks cover ~4 M rows -- 16 M by the time a second
             //    tile could see a new threshold -- before any update reaches them, and fresh thresholds must be read past the
             //    per-XCD L2s (sc1 / glc), where 8 192 waves hammering one line serialise: measured 0.24-0.53 ms for 1-8
             //    queries over 100 M rows against 0.10 ms for the collect pass of the level design.)
-            const bool self = allow_self && h->self_tighten && k <= h->self_max_k && use_mfma(j, s.n);
+            const bool self = allow_self && h->opt.self_tighten && use_mfma(j, s.n);
             used_self = used_self || self;
             // (the single pass appends everything within the bootstrap threshold until the first update arrives -- 3 072 waves x
             //  128 rows at once -- so its sample grows with k (1 024 k rows): 512 k measured 4.39 -> 3.80 ms at k = 256 and 11.9 (list
             //  overflow, retry) -> 5.07 ms at k = 512 against the fixed 65 536, profiles/r03_ab_large_k.txt)
-            const uint64_t s0 = std::min<uint64_t>(s.n, self ? std::max<uint64_t>(h->self_boot_rows, std::min<uint64_t>((uint64_t)h->self_boot_per_k * k, s.n / 8))
-                                                             : std::max<uint64_t>(h->boot_rows, std::min<uint64_t>(65536, 64ull * k)));
+            const uint64_t s0 = std::min<uint64_t>(s.n, self ? std::max<uint64_t>((uint64_t)h->opt.self_boot_rows, std::min<uint64_t>((uint64_t)h->opt.self_boot_per_k * k, s.n / 8))
+                                                             : std::max<uint64_t>(BOOT_ROWS, std::min<uint64_t>(65536, 64ull * k)));
             isk::BootParams bp{};
             set_cols(bp.col, s, j.W);
             bp.queries = h->d_queries.p; bp.bias = h->d_bias.p; bp.cnt = h->d_cnt.p; bp.s0 = s0; bp.nq = nq; bp.k = k; bp.W = j.W; bp.mask_last = j.mask_last;
@@ -778,7 +819,7 @@ struct Batch {
                 bp.hint = (uint32_t)job_hint;
                 used_hint = true;
                 hipLaunchKernelGGL(isk::boot_kernel, dim3(nq_pad), dim3(64), 0, h->stream, bp);
-            } else if (nq_pad > 64 && h->boot_multi) {
+            } else if (nq_pad > 64) {
                 // large batches: four queries per 1 024-thread block share every row load of the sample
                 const dim3 bgrid(nq_pad / isk::BOOT_QB), bblock(1024);
                 switch (j.W) {
@@ -788,8 +829,8 @@ struct Batch {
                     default: hipLaunchKernelGGL(isk::boot_multi_kernel<4>, bgrid, bblock, 0, h->stream, bp); break;
                 }
             } else {
-                // one block per query: a handful of queries get wide blocks, or a 65 536-row sample is one block's latency-bound walk
-                hipLaunchKernelGGL(isk::boot_kernel, dim3(nq_pad), dim3(nq_pad <= 64 ? 1024 : isk::BLOCK), 0, h->stream, bp);
+                // one block per query, and wide ones: a 65 536-row sample is otherwise one block's latency-bound walk
+                hipLaunchKernelGGL(isk::boot_kernel, dim3(nq_pad), dim3(1024), 0, h->stream, bp);
             }
 
             if (self) {
@@ -810,8 +851,8 @@ struct Batch {
             //    it.  A level meets ~k * growth candidates per query, so the stretches grow geometrically (8x;
             //    64x when there are so few query groups that launch gaps outweigh candidate handling; less
             //    when k * growth would not fit the candidate buffer).  No row is read twice.
-            uint64_t growth = (groups <= 2 && k <= 64) ? std::max<uint64_t>(64, h->level_growth) : h->level_growth;
-            if (use_mfma(j, s.n) && k <= 64) growth = h->mfma_level_growth;   // matrix-core launches: see the option's comment
+            uint64_t growth = (groups <= 2 && k <= 64) ? 64 : LEVEL_GROWTH;
+            if (use_mfma(j, s.n) && k <= 64) growth = MFMA_LEVEL_GROWTH;   // matrix-core launches: see the constant's comment
             if (k >= 256) growth = std::min<uint64_t>(growth, 2);   // simprint-sized k: candidate handling dominates, +10 % with short levels
             // a stretch `growth` times the rows seen so far brings ~growth * (rows at or under tau) candidates, and the
             // tie class at tau can make that 2.3x k (ratio of consecutive binomial tails): keep it inside the buffer

@@ -108,18 +108,18 @@ static int search_locked(isccsearch_handle* h, uint32_t table, uint32_t nq, cons
         // radius / self_hint: an ordinary top-k search over ONE segment that has been searched with this k before
         Segment* const spec_seg = t.sole_segment();
         // (a segment small enough for the one-launch search -- Batch::tiny -- has nothing to gain from a radius: it is exact in that launch either way)
-        const bool one_launch = spec_seg && h->tiny_rows && spec_seg->n <= h->tiny_rows && spec_seg->n < h->mfma_min_rows && spec_seg->n <= h->candidate_cap;
+        const bool one_launch = spec_seg && spec_seg->n <= (uint64_t)h->opt.tiny_rows && spec_seg->n < (uint64_t)h->opt.mfma_min_rows && spec_seg->n <= (uint64_t)h->opt.candidate_cap;
         const bool hintable = spec_seg && radius < 0 && !out_freq && one_copy && k <= spec_seg->n && !one_launch;
-        const bool small_batch = hintable && m <= h->spec_max_queries;
-        if (hintable && h->speculate && !h->spec_suppress && (small_batch || h->self_hint) && spec_seg->hint(m, len).ready(k)) {
+        const bool small_batch = hintable && m <= (uint32_t)h->opt.spec_max_queries;
+        if (hintable && h->opt.speculate && !h->spec_suppress && (small_batch || h->opt.self_hint) && spec_seg->hint(m, len).ready(k)) {
             if (small_batch) { spec = Spec::radius; batch.radius = (int)spec_seg->hint(m, len).tau; }
             else { spec = Spec::self_hint; batch.self_hint = (int)spec_seg->hint(m, len).tau; }
         }
-        const bool mhintable = segments > 1 && radius < 0 && !out_freq && (m <= h->spec_max_queries || h->self_hint) && k <= t.total;
-        if (mhintable && h->speculate && !h->spec_suppress && t.mhint(m, len).ready(k)) {
+        const bool mhintable = segments > 1 && radius < 0 && !out_freq && (m <= (uint32_t)h->opt.spec_max_queries || h->opt.self_hint) && k <= t.total;
+        if (mhintable && h->opt.speculate && !h->spec_suppress && t.mhint(m, len).ready(k)) {
             spec = Spec::ratio;
             batch.radius_ratio = t.mhint(m, len).ratio + 1.0 / 32.0;      // the margin: 2 bits of 64, 8 of 256
-            batch.ratio_starts_self = m > h->spec_max_queries;             // larger batches: each segment's single pass STARTS under it
+            batch.ratio_starts_self = m > (uint32_t)h->opt.spec_max_queries;             // larger batches: each segment's single pass STARTS under it
         }
         auto copy_results = [&]() -> int {
             if (out_freq) {
@@ -187,7 +187,7 @@ static int search_locked(isccsearch_handle* h, uint32_t table, uint32_t nq, cons
             }
         }
         if (!spec_ok && (rc = batch.finish(hq.data(), copy_results))) return rc;
-        if (h->count_candidates && batch.jobs.size() == 1) {
+        if (h->opt.count_candidates && batch.jobs.size() == 1) {
             // accounting (tools/probe_candidate_path.py, option "count_candidates"): how many candidates the scan appended for this batch
             std::vector<uint32_t> hc((size_t)batch.nq_pad * isk::CNT_STRIDE);
             HIPOK(hipMemcpyAsync(hc.data(), h->d_cnt.p, hc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
@@ -419,9 +419,9 @@ int isccsearch_search_many(isccsearch_handle* h, uint32_t n, isccsearch_request*
         b.radius = r.max_hamming < 0 ? -1 : r.max_hamming;
         // small top-k batches: the speculative single pass of search_locked (see there), verified in pass 3a
         sl.seg = t.sole_segment();
-        sl.small = r.max_hamming < 0 && r.nq <= h->spec_max_queries && sl.seg && r.k <= sl.seg->n;
+        sl.small = r.max_hamming < 0 && r.nq <= (uint32_t)h->opt.spec_max_queries && sl.seg && r.k <= sl.seg->n;
         sl.len = len;
-        sl.spec = sl.small && h->speculate && sl.seg->hint(r.nq, len).ready(r.k);
+        sl.spec = sl.small && h->opt.speculate && sl.seg->hint(r.nq, len).ready(r.k);
         if (sl.spec) b.radius = (int)sl.seg->hint(r.nq, len).tau;
         b.pq_off = pq_off;
         b.d_flags = d_cnt + r.nq;

@@ -169,7 +169,7 @@ int isccsearch_create(int device_id, isccsearch_handle** out) {
     HIPOK(hipFuncSetAttribute(reinterpret_cast<const void*>(&isk::select_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     HIPOK(hipFuncSetAttribute(reinterpret_cast<const void*>(&isk::select_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     HIPOK(hipFuncSetAttribute(reinterpret_cast<const void*>(&isk::select_kernel<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-    h->stats.queries_per_pass = h->tq;
+    h->stats.queries_per_pass = (uint32_t)h->opt.queries_per_pass;
     h->stats.compute_units = h->cus;
     *out = h.release();
     return 0;
@@ -187,58 +187,29 @@ int isccsearch_destroy(isccsearch_handle* h) {
     return 0;
 }
 
+// (both walk OPTIONS, the one list of what can be set and read)
 int isccsearch_set_option(isccsearch_handle* h, const char* name, int64_t value) {
     if (!h || !name) return fail(-EINVAL, "bad arguments");
     std::lock_guard<std::mutex> lk(h->mu);
-    if (!strcmp(name, "queries_per_pass")) {
-        // 32 is not offered: its query registers spill to scratch, which the asm-issued loads forbid
-        if (value != 8 && value != 16) return fail(-EINVAL, "queries_per_pass must be 8 or 16");
-        h->tq = (int)value;
-        h->stats.queries_per_pass = (uint32_t)value;
-        return 0;
-    }
-    if (!strcmp(name, "profile")) { h->profile = value != 0; return 0; }
-    if (!strcmp(name, "count_candidates")) { h->count_candidates = value != 0; return 0; }
-    if (!strcmp(name, "nontemporal")) {
-        // only the non-temporal variant of the scan kernels is built (plain loads measured no faster):
-        // asking for the other one is refused rather than silently ignored
-        if (value == 0) return fail(-EINVAL, "nontemporal=0 is not available: the scan kernels are built with non-temporal loads only");
-        return 0;
-    }
-    if (!strcmp(name, "fold")) { h->fold_tau = value ? 11 : 0; return 0; }   // shorthand kept from the experiments
-    if (!strcmp(name, "blocks_per_cu")) { if (value < 1 || value > 64) return fail(-EINVAL, "blocks_per_cu must be 1..64"); h->blocks_per_cu = (uint32_t)value; return 0; }
-    if (!strcmp(name, "boot_rows")) { if (value < 256 || value > 65536) return fail(-EINVAL, "boot_rows must be 256..65536"); h->boot_rows = (uint64_t)value; return 0; }
-    if (!strcmp(name, "mfma_stretch_factor")) { if (value < 1 || value > 64) return fail(-EINVAL, "mfma_stretch_factor must be 1..64"); h->mfma_stretch_factor = (uint64_t)value; return 0; }
-    if (!strcmp(name, "stretch_mb")) { if (value < 0 || value > 65536) return fail(-EINVAL, "stretch_mb must be 0..65536"); h->stretch_bytes = (uint64_t)value << 20; return 0; }
-    if (!strcmp(name, "repick")) { h->repick = value != 0; return 0; }
-    if (!strcmp(name, "fold_tau")) { if (value < 0 || value > 32) return fail(-EINVAL, "fold_tau must be 0..32"); h->fold_tau = (uint32_t)value; return 0; }
-    if (!strcmp(name, "level_growth")) { if (value < 2 || value > 1024) return fail(-EINVAL, "level_growth must be 2..1024"); h->level_growth = (uint64_t)value; return 0; }
-    if (!strcmp(name, "mfma")) { h->mfma = value != 0; return 0; }
-    if (!strcmp(name, "device_search_hint")) { if (value < -1 || value > 8 * ISCCSEARCH_MAX_BYTES) return fail(-EINVAL, "device_search_hint must be -1..256"); h->device_search_hint = (int)value; return 0; }
-    if (!strcmp(name, "self_hint")) { h->self_hint = value != 0; return 0; }
-    if (!strcmp(name, "mfma_few_rows")) { if (value < 0) return fail(-EINVAL, "mfma_few_rows must be >= 0"); h->mfma_few_rows = (uint64_t)value; return 0; }
-    if (!strcmp(name, "mfma_pack_min_queries")) { if (value < 1 || value > 1024) return fail(-EINVAL, "mfma_pack_min_queries must be 1..1024"); h->mfma_pack_min_queries = (uint32_t)value; return 0; }
-    if (!strcmp(name, "mfma_min_queries")) { if (value < 1 || value > 1024) return fail(-EINVAL, "mfma_min_queries must be 1..1024"); h->mfma_min_queries = (uint32_t)value; return 0; }
-    if (!strcmp(name, "self_tighten")) { h->self_tighten = value != 0; return 0; }
-    if (!strcmp(name, "boot_multi")) { h->boot_multi = value != 0; return 0; }
-    if (!strcmp(name, "self_refresh_steps")) {
-        if (value < 1 || value > 64 || (value & (value - 1))) return fail(-EINVAL, "self_refresh_steps must be a power of two in 1..64");
-        h->self_refresh_steps = (uint32_t)value; return 0;
-    }
-    if (!strcmp(name, "candidate_cap")) { if (value < 64 || value > (1 << 22)) return fail(-EINVAL, "candidate_cap must be 64..4194304"); h->candidate_cap = (uint32_t)value; return 0; }
-    if (!strcmp(name, "self_max_k")) { if (value < 1 || value > ISCCSEARCH_MAX_K) return fail(-EINVAL, "self_max_k must be 1..%d", ISCCSEARCH_MAX_K); h->self_max_k = (uint32_t)value; return 0; }
-    if (!strcmp(name, "self_boot_rows")) { if (value < 256 || value > (1 << 20)) return fail(-EINVAL, "self_boot_rows must be 256..1048576"); h->self_boot_rows = (uint64_t)value; return 0; }
-    if (!strcmp(name, "mfma_level_growth")) { if (value < 2 || value > 1024) return fail(-EINVAL, "mfma_level_growth must be 2..1024"); h->mfma_level_growth = (uint64_t)value; return 0; }
-    if (!strcmp(name, "mfma_pack")) { h->mfma_pack = value != 0; return 0; }
-    if (!strcmp(name, "mfma_pack3")) { h->mfma_pack3 = value != 0; return 0; }
-    if (!strcmp(name, "tiny_rows")) { if (value < 0 || value > (1 << 20)) return fail(-EINVAL, "tiny_rows must be 0..1048576"); h->tiny_rows = (uint32_t)value; return 0; }
-    if (!strcmp(name, "select_wide_from")) { if (value < 0) return fail(-EINVAL, "select_wide_from must be >= 0"); h->select_wide_from = (uint32_t)std::min<int64_t>(value, 0xFFFFFFFFll); return 0; }
-    if (!strcmp(name, "speculate")) { h->speculate = value != 0; return 0; }
-    if (!strcmp(name, "spec_max_queries")) { if (value < 0 || value > 1024) return fail(-EINVAL, "spec_max_queries must be 0..1024"); h->spec_max_queries = (uint32_t)value; return 0; }
-    if (!strcmp(name, "self_boot_per_k")) { if (value < 0 || value > (1 << 20)) return fail(-EINVAL, "self_boot_per_k must be 0..2^20"); h->self_boot_per_k = (uint32_t)value; return 0; }
-    if (!strcmp(name, "mfma_min_rows")) { if (value < 1) return fail(-EINVAL, "mfma_min_rows must be >= 1"); h->mfma_min_rows = (uint64_t)value; return 0; }
-    if (!strcmp(name, "sample_cost")) return 0;   // accepted for compatibility: the levels no longer re-read rows, nothing to balance
-    return fail(-EINVAL, "unknown option '%s'", name);
+    const OptionDesc* d = find_option(name);
+    if (!d) return fail(-EINVAL, "unknown option '%s'", name);
+    // queries_per_pass: 32 is not offered (its query registers spill to scratch, which the asm-issued loads forbid), nor anything between
+    if (d->field == &Options::queries_per_pass && value != 8 && value != 16) return fail(-EINVAL, "queries_per_pass must be 8 or 16");
+    if (value < d->min || value > d->max)
+        return d->max == NO_MAX ? fail(-EINVAL, "%s must be >= %lld", name, (long long)d->min)
+                                : fail(-EINVAL, "%s must be %lld..%lld", name, (long long)d->min, (long long)d->max);
+    h->opt.*(d->field) = value;
+    h->stats.queries_per_pass = (uint32_t)h->opt.queries_per_pass;
+    return 0;
+}
+
+int isccsearch_get_option(isccsearch_handle* h, const char* name, int64_t* value) {
+    if (!h || !name || !value) return fail(-EINVAL, "bad arguments");
+    std::lock_guard<std::mutex> lk(h->mu);
+    const OptionDesc* d = find_option(name);
+    if (!d) return fail(-EINVAL, "unknown option '%s'", name);
+    *value = h->opt.*(d->field);
+    return 0;
 }
 
 int isccsearch_stats_get(isccsearch_handle* h, isccsearch_stats* out, int reset) {

@@ -6,6 +6,7 @@ This is the thinnest layer above ``include/isccsearch.h``; the reference-shaped 
 ``iscc_search_amd/nphd.py``.  Nothing here computes distances on the CPU.
 """
 
+import contextlib
 import ctypes
 import errno
 import threading
@@ -87,6 +88,25 @@ class HipEngine:
     def set_option(self, name, value):
         # type: (str, int) -> None
         _lib.check(self._lib.isccsearch_set_option(self.handle, name.encode(), int(value)))
+
+    def get_option(self, name):
+        # type: (str) -> int
+        value = ctypes.c_int64()
+        _lib.check(self._lib.isccsearch_get_option(self.handle, name.encode(), ctypes.byref(value)))
+        return value.value
+
+    @contextlib.contextmanager
+    def options(self, **values):
+        # type: (int) -> contextlib.AbstractContextManager
+        """Engine options for one block: sets ``values``; on leaving it, also by an exception, the values read before are set again."""
+        before = {name: self.get_option(name) for name in values}
+        try:
+            for name, value in values.items():
+                self.set_option(name, value)
+            yield
+        finally:
+            for name, value in before.items():
+                self.set_option(name, value)
 
     def stats(self, reset=False):
         # type: (bool) -> dict

@@ -103,6 +103,9 @@ class ShardedEngine:
     def set_option(self, name, value):
         self.local.set_option(name, value)
 
+    def get_option(self, name):
+        return self.local.get_option(name)
+
     def stats(self, reset=False):
         return self.local.stats(reset)
 

@@ -1,9 +1,28 @@
 """Deterministic ISCC sample data for the host-logic tests (built with this repo's own codec)."""
 
+import os
+
 import numpy as np
 
 from iscc_search_amd import codec
 from iscc_search_amd.schema import IsccEntry, IsccSimprint
+
+
+def session_options():
+    # type: () -> dict[str, int]
+    """The engine options of an ISCC_HIP_OPTS="name=value,..." rerun of the GPU tier (what conftest's hip_engine fixture sets)."""
+    items = (item.split("=") for item in filter(None, os.environ.get("ISCC_HIP_OPTS", "").split(",")))
+    return {name.strip(): int(value) for name, value in items}
+
+
+def hip_manager():
+    """A manager on a HIP engine of its own, under the session's engine options."""
+    from iscc_search_amd.index import HipIndexManager
+
+    m = HipIndexManager("hip:///")
+    for name, value in session_options().items():
+        m._get_engine().set_option(name, value)
+    return m
 
 
 def make_iscc_id(i, realm=0):

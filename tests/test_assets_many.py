@@ -7,12 +7,10 @@ flipped), so that keys turn up in several unit lists and scores tie; INSTANCE co
 use) and, marked gpu, through the HIP engine (isccsearch_match_assets).
 """
 
-import os
-
 import numpy as np
 import pytest
 
-from helpers import make_iscc_id, sp
+from helpers import hip_manager, make_iscc_id, sp
 from iscc_search_amd import codec
 from iscc_search_amd.index import HipIndexManager, INSTANCE_FIRST_K
 from iscc_search_amd.schema import IsccEntry, IsccIndex, IsccQuery
@@ -95,11 +93,7 @@ def manager(request):
     if request.param == "oracle":
         m = HipIndexManager("hip:///", engine=OracleEngine())
     else:
-        m = HipIndexManager("hip:///")
-        eng = m._get_engine()
-        for item in filter(None, os.environ.get("ISCC_HIP_OPTS", "").split(",")):    # the engine options of a rerun (conftest.hip_engine)
-            name, value = item.split("=")
-            eng.set_option(name.strip(), int(value))
+        m = hip_manager()
     yield m
     m.close()
 

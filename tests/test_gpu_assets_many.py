@@ -7,28 +7,16 @@ searches per batch, and the kernel's two summation rules against Python restatem
 import numpy as np
 import pytest
 
-from helpers import make_iscc_id
+from helpers import hip_manager, make_iscc_id
 from iscc_search_amd import _lib, codec
 from iscc_search_amd.engine import pack_bytes
-from iscc_search_amd.index import HipIndex, HipIndexManager
+from iscc_search_amd.index import HipIndex
 from iscc_search_amd.schema import IsccEntry, IsccIndex, IsccQuery
 from test_assets_many import _flip, assert_same
 
 pytestmark = pytest.mark.gpu
 
 N_BIG = 70_000          # rows per unit type: above mfma_min_rows (65 536), so batches take the matrix cores
-
-
-def hip_manager():
-    """A manager on its own engine, under the engine options of an ISCC_HIP_OPTS rerun (as the hip_engine fixture)."""
-    import os
-
-    m = HipIndexManager("hip:///")
-    eng = m._get_engine()
-    for item in filter(None, os.environ.get("ISCC_HIP_OPTS", "").split(",")):
-        name, value = item.split("=")
-        eng.set_option(name.strip(), int(value))
-    return m
 
 
 @pytest.fixture(scope="module")

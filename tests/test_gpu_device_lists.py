@@ -454,31 +454,28 @@ def test_search_device_async_with_a_hint(hip_engine, n, self_hint_path):
         side.synchronize()
         return blk.read()
 
+    # a hint of every bit lists the whole table per query: room for it, so that no list is handed back as overflowed
+    opts = dict(candidate_cap=32768)
+    if self_hint_path:
+        opts.update(spec_max_queries=0, mfma_min_rows=4096)
     try:
         t.add(keys, words)
-        if self_hint_path:
-            hip_engine.set_option("spec_max_queries", 0)
-            hip_engine.set_option("mfma_min_rows", 4096)
-        # a hint of every bit lists the whole table per query: room for it, so that no list is handed back as overflowed
-        hip_engine.set_option("candidate_cap", 32768)
-        before = hip_engine.stats()["mfma_launches"]
-        _assert_records(*run(None), exp, 1, "no hint:")
-        _assert_records(*run(64), exp, 1, "hint 64:")
-        rec, cnt = run(tight)
-        assert not (cnt == _lib.COUNT_OVERFLOW).any()
-        _assert_records(rec, cnt, exp, 1, f"hint {tight}:", prefix_only=True)
-        for i in range(q.shape[0]):
-            assert int(cnt[i]) >= int((exp[1][i, :k] < tight).sum()), f"query {i}: rows strictly within the hint are missing"
-            if kth[i] < tight:
-                assert int(cnt[i]) == k, f"query {i}: k-th distance {kth[i]} < hint {tight}, count {int(cnt[i])}"
-        if not self_hint_path:
-            assert (cnt < k).any()
-        if self_hint_path and n > TINY_ROWS and not os.environ.get("ISCC_HIP_OPTS"):
-            assert hip_engine.stats()["mfma_launches"] > before
+        with hip_engine.options(**opts):
+            before = hip_engine.stats()["mfma_launches"]
+            _assert_records(*run(None), exp, 1, "no hint:")
+            _assert_records(*run(64), exp, 1, "hint 64:")
+            rec, cnt = run(tight)
+            assert not (cnt == _lib.COUNT_OVERFLOW).any()
+            _assert_records(rec, cnt, exp, 1, f"hint {tight}:", prefix_only=True)
+            for i in range(q.shape[0]):
+                assert int(cnt[i]) >= int((exp[1][i, :k] < tight).sum()), f"query {i}: rows strictly within the hint are missing"
+                if kth[i] < tight:
+                    assert int(cnt[i]) == k, f"query {i}: k-th distance {kth[i]} < hint {tight}, count {int(cnt[i])}"
+            if not self_hint_path:
+                assert (cnt < k).any()
+            if self_hint_path and n > TINY_ROWS and not os.environ.get("ISCC_HIP_OPTS"):
+                assert hip_engine.stats()["mfma_launches"] > before
     finally:
-        hip_engine.set_option("spec_max_queries", 128)
-        hip_engine.set_option("mfma_min_rows", 65536)
-        hip_engine.set_option("candidate_cap", 16384)
         t.drop()
 
 

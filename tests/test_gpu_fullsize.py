@@ -107,16 +107,11 @@ def test_fullsize_properties_and_oracle_spot_check(hip_engine, big):
     # 64 queries over 100 M rows run on the matrix cores by default; the XOR + popcount kernel (T_q = 8 and the
     # VALU-bound T_q = 16) returns the same bits
     assert hip_engine.stats()["mfma_launches"] > 0 or not MFMA_ON
-    hip_engine.set_option("mfma", 0)
-    try:
-        for tq in (16, 8):
-            hip_engine.set_option("queries_per_pass", tq)
+    for tq in (16, 8):
+        with hip_engine.options(mfma=0, queries_per_pass=tq):
             other = big.search(q, None, K)
-            for a, b in zip((keys, ham, pbits, cnt), other):
-                np.testing.assert_array_equal(a, b)
-    finally:
-        hip_engine.set_option("queries_per_pass", 8)
-        hip_engine.set_option("mfma", 1 if MFMA_ON else 0)
+        for a, b in zip((keys, ham, pbits, cnt), other):
+            np.testing.assert_array_equal(a, b)
     # bit-exact against the oracle over all 100 M rows for a few queries (one planted, rest random)
     words = oracle_splitmix64_fill(ROWS, SEED, stride=4).reshape(ROWS, 1)
     row_keys = np.arange(ROWS, dtype=np.uint64)
@@ -298,11 +293,8 @@ def test_config3_100m_x_256bit_nphd_1024_queries(hip_engine):
             assert int(ham[j, 0]) == f and int(keys[j, 0]) == r, (j, ham[j, :3], keys[j, :3])
         # idempotent, and the XOR + popcount kernel (W = 4, queries in LDS, several stretches of 4 M rows) agrees for every query
         again = t.search(q, qn, K)
-        hip_engine.set_option("mfma", 0)
-        try:
+        with hip_engine.options(mfma=0):
             valu = t.search(q, qn, K)
-        finally:
-            hip_engine.set_option("mfma", 1 if MFMA_ON else 0)
         for a, b, c in zip((keys, ham, pbits, cnt), again, valu):
             np.testing.assert_array_equal(a, b)
             np.testing.assert_array_equal(a, c)
@@ -329,11 +321,8 @@ def test_config5_10m_simprint_tables_128bit_keys_k400(hip_engine, nbytes):
         assert np.all(keys[..., 0] == 0)
         for j, (r, f) in planted.items():
             assert int(ham[j, 0]) == f and int(keys[j, 0, 1]) == r, (j, ham[j, :3], keys[j, :3])
-        hip_engine.set_option("mfma", 0)
-        try:
+        with hip_engine.options(mfma=0):
             valu = t.search(q, None, k)
-        finally:
-            hip_engine.set_option("mfma", 1 if MFMA_ON else 0)
         for a, b in zip((keys, ham, pbits, cnt), valu):
             np.testing.assert_array_equal(a, b)
         pick = [0, 1, 2, 3, 100, 257, 510, 511]

@@ -195,11 +195,8 @@ def test_small_batches_speculate_on_the_previous_k_th_distance_and_stay_exact(hi
         assert ask_many(r[4:8]) == (0, 0)                            # ... six batches of back-off, four of them here
         assert ask_many(r[8:10]) == (0, 0)
         assert ask_many(r[10:12]) == (2, 0)
-        hip_engine.set_option("speculate", 0)
-        try:
+        with hip_engine.options(speculate=0):
             assert ask(r[:3])[:2] == (0, 0)
-        finally:
-            hip_engine.set_option("speculate", 1)
     finally:
         t.drop()
 
@@ -249,14 +246,10 @@ def test_matrix_core_batches_speculate_too(hip_engine, nq):
         mixed[nq // 2] = centre                                      # 30 000 rows within the radius of one query: its list overflows
         assert ask(mixed)[:2] == (0, 1)
         assert ask(random_q[2 * nq : 3 * nq])[:2] == (1, 0)          # the ordinary rerun re-seeded the radius; one miss does not back off
-        hip_engine.set_option("spec_max_queries", nq - 1)            # one above the limit: the single pass, started under the hint
-        try:
+        with hip_engine.options(spec_max_queries=nq - 1):            # one above the limit: the single pass, started under the hint
             assert ask(random_q[:nq])[:2] == (1, 0)
-            hip_engine.set_option("self_hint", 0)
-            assert ask(random_q[:nq])[:2] == (0, 0)                  # ... or under its bootstrap sample
-        finally:
-            hip_engine.set_option("spec_max_queries", 128)
-            hip_engine.set_option("self_hint", 1)
+            with hip_engine.options(self_hint=0):
+                assert ask(random_q[:nq])[:2] == (0, 0)              # ... or under its bootstrap sample
     finally:
         t.drop()
 
@@ -306,11 +299,9 @@ def test_large_batches_start_their_single_pass_under_the_hint(hip_engine, nq, k)
         assert ask(with_centre) == (0, 1)                            # a list overflows under the hint -> ordinary pass (whose own retry repairs it)
         assert ask(r[:nq]) == (1, 0)                                 # (one miss does not back off)
         assert ask(near) == (1, 0)                                   # near-duplicates: far inside the hint, which decays by one bit
-        hip_engine.set_option("self_hint", 0)
-        assert ask(near) == (0, 0)
-        hip_engine.set_option("self_hint", 1)
+        with hip_engine.options(self_hint=0):
+            assert ask(near) == (0, 0)
     finally:
-        hip_engine.set_option("self_hint", 1)
         t.drop()
 
 
@@ -350,7 +341,7 @@ def test_a_hint_that_is_too_tight_is_noticed(hip_engine):
 @needs_matrix_cores
 @pytest.mark.parametrize("nbytes,n,nq,k", [(8, 150_000, 150, 700), (8, 120_000, 40, 4096), (16, 100_000, 150, 2048), (32, 80_000, 64, 1000)])
 def test_the_single_pass_serves_every_k(hip_engine, nbytes, n, nq, k):
-    """``self_max_k`` = 4 096: large k takes the single self-tightening pass too (bootstrap sample, then under the hint); both against the oracle."""
+    """Up to the largest k, 4 096: large k takes the single self-tightening pass too (bootstrap sample, then under the hint); both against the oracle."""
     from oracle import oracle_topk
 
     rng = np.random.default_rng(31 + nbytes + k)
@@ -464,10 +455,7 @@ def test_tables_of_several_code_lengths_speculate_per_segment(hip_engine):
         q[2] = centre
         assert ask(q, 32) == (0, 1)                                    # the 256-bit segment's list overflows: ordinary path
         assert ask(rnd(5), 32) == (1, 0)
-        hip_engine.set_option("speculate", 0)
-        try:
+        with hip_engine.options(speculate=0):
             assert ask(rnd(5), 32) == (0, 0)
-        finally:
-            hip_engine.set_option("speculate", 1)
     finally:
         t.drop()

@@ -23,14 +23,10 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture
 def forced(hip_engine):
     """Every scan launch on the matrix cores; restored afterwards."""
-    hip_engine.set_option("mfma", 1)
-    hip_engine.set_option("mfma_min_queries", 1)
-    hip_engine.set_option("mfma_min_rows", 1)
-    before = hip_engine.stats()["mfma_launches"]
-    yield hip_engine
-    ran = hip_engine.stats()["mfma_launches"] - before
-    hip_engine.set_option("mfma_min_queries", 17)
-    hip_engine.set_option("mfma_min_rows", 65536)
+    with hip_engine.options(mfma=1, mfma_min_queries=1, mfma_min_rows=1):
+        before = hip_engine.stats()["mfma_launches"]
+        yield hip_engine
+        ran = hip_engine.stats()["mfma_launches"] - before
     assert ran > 0, "the case never reached the MFMA kernel"
 
 
@@ -128,11 +124,8 @@ def test_large_batch_under_default_thresholds(hip_engine, nbytes, metric):
         for g, e, name in zip(got, exp, ("keys", "hamming", "prefix_bits", "count")):
             np.testing.assert_array_equal(g, e, err_msg=name)
         # the XOR + popcount kernel returns the same bits
-        hip_engine.set_option("mfma", 0)
-        try:
+        with hip_engine.options(mfma=0):
             other = t.search(q, qlens, k)
-        finally:
-            hip_engine.set_option("mfma", 1)
         for g, e, name in zip(other, exp, ("keys", "hamming", "prefix_bits", "count")):
             np.testing.assert_array_equal(g, e, err_msg="valu " + name)
     finally:
@@ -147,9 +140,8 @@ def test_large_batch_under_default_thresholds(hip_engine, nbytes, metric):
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.fixture
 def forced_levels(forced):
-    forced.set_option("self_tighten", 0)
-    yield forced
-    forced.set_option("self_tighten", 1)
+    with forced.options(self_tighten=0):
+        yield forced
 
 
 @pytest.mark.parametrize("n,k,nq", [(70000, 10, 40), (300000, 100, 17)])
@@ -190,12 +182,9 @@ def test_self_tightening_pass_equals_levels_and_oracle(hip_engine, nbytes, k):
         single_pass = t.search(q, None, k)
         after = hip_engine.stats()
         assert after["mfma_launches"] > before["mfma_launches"] and after["level_launches"] == before["level_launches"], "not the single pass"
-        hip_engine.set_option("self_tighten", 0)
-        try:
+        with hip_engine.options(self_tighten=0):
             levels = t.search(q, None, k)
             assert hip_engine.stats()["level_launches"] > after["level_launches"], "not the level design"
-        finally:
-            hip_engine.set_option("self_tighten", 1)
         exp = oracle_topk(0, keys, words, None, q, None, k, fixed_nbytes=nbytes)
         for g, l, e, name in zip(single_pass, levels, exp, ("keys", "hamming", "prefix_bits", "count")):
             np.testing.assert_array_equal(g, e, err_msg="single pass: " + name)
@@ -219,17 +208,10 @@ def test_an_overflowed_single_pass_is_answered_again_by_the_levels(hip_engine):
     t = hip_engine.open_table(0, 1, 8)
     try:
         t.add(keys, words)
-        hip_engine.set_option("candidate_cap", 256)
-        hip_engine.set_option("self_boot_rows", 256)
-        hip_engine.set_option("self_boot_per_k", 0)         # (the sample otherwise grows with k)
-        try:
+        with hip_engine.options(candidate_cap=256, self_boot_rows=256, self_boot_per_k=0):      # (the sample otherwise grows with k)
             before = hip_engine.stats()
             got = t.search(q, None, k)
             after = hip_engine.stats()
-        finally:
-            hip_engine.set_option("candidate_cap", 16384)
-            hip_engine.set_option("self_boot_rows", 65536)
-            hip_engine.set_option("self_boot_per_k", 1024)
         delta = {x: after[x] - before[x] for x in ("self_retries", "fallback_queries", "mfma_launches", "mfma_pack_launches", "level_launches", "scan_launches")}
         assert after["self_retries"] == before["self_retries"] + 1, f"the single pass was expected to overflow its lists: {delta}"
         assert after["fallback_queries"] == before["fallback_queries"], "the level design was expected to fit its lists"

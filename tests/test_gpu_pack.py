@@ -58,13 +58,8 @@ def _assert_equal(got, exp, what):
 
 @pytest.fixture
 def forced(hip_engine):
-    hip_engine.set_option("mfma", 1)
-    hip_engine.set_option("mfma_pack", 1)
-    hip_engine.set_option("mfma_min_queries", 1)
-    hip_engine.set_option("mfma_min_rows", 1)
-    yield hip_engine
-    hip_engine.set_option("mfma_min_queries", 17)
-    hip_engine.set_option("mfma_min_rows", 65536)
+    with hip_engine.options(mfma=1, mfma_pack=1, mfma_min_queries=1, mfma_min_rows=1):
+        yield hip_engine
 
 
 # (65..128 queries: chunks of three and four groups, their own instantiations; 160: five groups, the general loop with an odd count;
@@ -83,19 +78,13 @@ def test_packed_kernel_vs_oracle_and_unpacked(forced, n, k, nq, nbytes):
         after = forced.stats()
         assert after["mfma_pack_launches"] > before["mfma_pack_launches"], "the batch did not run on the packed kernel"
         _assert_equal(got, _expect(keys, words, q, k, nbytes), "packed")
-        forced.set_option("mfma_pack", 0)
-        try:
+        with forced.options(mfma_pack=0):
             again = t.search(q, None, k)
             assert forced.stats()["mfma_pack_launches"] == after["mfma_pack_launches"]
-        finally:
-            forced.set_option("mfma_pack", 1)
         _assert_equal(again, got, "unpacked against packed")
         # the level design on the packed kernel
-        forced.set_option("self_tighten", 0)
-        try:
+        with forced.options(self_tighten=0):
             levels = t.search(q, None, k)
-        finally:
-            forced.set_option("self_tighten", 1)
         _assert_equal(levels, got, "levels against the single pass")
     finally:
         t.drop()
@@ -160,15 +149,10 @@ def test_self_pass_in_stretches_with_a_short_last_one(hip_engine):
     t = hip_engine.open_table(0, 1, nbytes)
     try:
         t.add(keys, words)
-        hip_engine.set_option("stretch_mb", 1)
-        hip_engine.set_option("mfma_stretch_factor", 1)
-        try:
+        with hip_engine.options(stretch_mb=1, mfma_stretch_factor=1):
             before = hip_engine.stats()
             got = t.search(q, None, k)
             after = hip_engine.stats()
-        finally:
-            hip_engine.set_option("stretch_mb", 128)
-            hip_engine.set_option("mfma_stretch_factor", 3)
         launches = after["scan_launches"] - before["scan_launches"]
         assert launches > 2, "the pass was expected to run in several stretches"
         assert after["scan_mfma_launches"] - before["scan_mfma_launches"] == launches, "a stretch of the single pass left the matrix cores"

@@ -8,7 +8,7 @@ The kernel takes chunks of more than four query groups (> 128 queries).  Exercis
   * planted near-duplicates: the thresholds of one chunk spread over 0..14, so the block threshold is loose for most queries
     and the candidate path's per-query test decides;
   * range-limited searches up to the radius that admits every row (the block threshold's "every row" mode);
-  * several chunks walking stretches of rows (scans that start at row_begin > 0), k up to ``self_max_k``.
+  * several chunks walking stretches of rows (scans that start at row_begin > 0), k up to the largest (4 096).
 """
 
 import numpy as np
@@ -50,25 +50,15 @@ def _assert_equal(got, exp, what):
 
 @pytest.fixture
 def forced(hip_engine):
-    hip_engine.set_option("mfma", 1)
-    hip_engine.set_option("mfma_pack", 1)
-    hip_engine.set_option("mfma_pack3", 1)
-    hip_engine.set_option("mfma_min_queries", 1)
-    hip_engine.set_option("mfma_min_rows", 1)
-    yield hip_engine
-    hip_engine.set_option("mfma_pack3", 1)
-    hip_engine.set_option("mfma_min_queries", 17)
-    hip_engine.set_option("mfma_min_rows", 65536)
+    with hip_engine.options(mfma=1, mfma_pack=1, mfma_pack3=1, mfma_min_queries=1, mfma_min_rows=1):
+        yield hip_engine
 
 
 def _both(engine, fn):
-    engine.set_option("mfma_pack3", 1)
-    a = fn()
-    engine.set_option("mfma_pack3", 0)
-    try:
+    with engine.options(mfma_pack3=1):
+        a = fn()
+    with engine.options(mfma_pack3=0):
         b = fn()
-    finally:
-        engine.set_option("mfma_pack3", 1)
     return a, b
 
 
@@ -86,11 +76,8 @@ def test_pack3_vs_oracle_and_pack(forced, n, k, nq, nbytes):
         assert forced.stats()["mfma_pack_launches"] > before["mfma_pack_launches"], "the batch did not run on the packed kernels"
         _assert_equal(got, oracle_topk(0, keys, words, None, q, None, k, fixed_nbytes=nbytes), "pack3 against the oracle")
         _assert_equal(got, ref, "pack3 against mfma_pack_kernel")
-        forced.set_option("self_tighten", 0)                      # the level design (MODE_BOTH / MODE_STRETCH / MODE_COLLECT)
-        try:
+        with forced.options(self_tighten=0):                      # the level design (MODE_BOTH / MODE_STRETCH / MODE_COLLECT)
             levels = t.search(q, None, k)
-        finally:
-            forced.set_option("self_tighten", 1)
         _assert_equal(levels, got, "levels against the single pass")
     finally:
         t.drop()
@@ -120,19 +107,14 @@ def test_pack3_range_limited(forced, radius, nq):
 
 @pytest.mark.parametrize("k,nq", [(64, 1100), (512, 1100), (4096, 160)])
 def test_pack3_large_k_and_stretches(forced, k, nq):
-    """Two chunks of queries walk 1 MB stretches (scans from row_begin > 0, a short last one); k up to self_max_k."""
+    """Two chunks of queries walk 1 MB stretches (scans from row_begin > 0, a short last one); k up to the largest."""
     rng = np.random.default_rng(9000 + k)
     n = 600_001
     t, keys, words, mask = _table(forced, rng, n)
     try:
         q = _queries(rng, words, nq, mask)
-        forced.set_option("stretch_mb", 1)
-        forced.set_option("mfma_stretch_factor", 1)
-        try:
+        with forced.options(stretch_mb=1, mfma_stretch_factor=1):
             got, ref = _both(forced, lambda: t.search(q, None, k))
-        finally:
-            forced.set_option("stretch_mb", 128)
-            forced.set_option("mfma_stretch_factor", 3)
         _assert_equal(got, ref, "pack3 against mfma_pack_kernel")
         sel = np.arange(0, nq, 7)
         exp = oracle_topk(0, keys, words, None, q[sel], None, k, fixed_nbytes=8)

@@ -41,10 +41,9 @@ def test_wide_blocks_select_what_the_oracle_selects(hip_engine, key_words, nbyte
             q[:, 0] ^= np.uint64(1) << rng.integers(0, 64, size=nq).astype(np.uint64)
             exp = oracle_topk(0, keys, words, None, q, None, k, fixed_nbytes=nbytes)
             for wide_from in (1024, 2048, 1 << 30):
-                hip_engine.set_option("select_wide_from", wide_from)
-                got = t.search(q, None, k)
+                with hip_engine.options(select_wide_from=wide_from):
+                    got = t.search(q, None, k)
                 for g, e, name in zip(got, exp, ("keys", "hamming", "prefix_bits", "count")):
                     np.testing.assert_array_equal(g, e, err_msg=f"nq={nq} k={k} select_wide_from={wide_from}: {name}")
     finally:
-        hip_engine.set_option("select_wide_from", 2048)
         t.drop()

@@ -5,15 +5,12 @@ float64 scores compared with ``==``, the order (-score, asset), every matched ch
 ``search_assets_many`` what ``search_assets`` returns per query, with one library search per (simprint type, round).
 """
 
-import os
-
 import numpy as np
 import pytest
 
-from helpers import flip_bits, make_iscc_id, sp
+from helpers import flip_bits, hip_manager, make_iscc_id, sp
 from iscc_search_amd import codec
 from iscc_search_amd._lib import MAX_K, MAX_SCORED_SIMPRINTS
-from iscc_search_amd.index import HipIndexManager
 from iscc_search_amd.schema import IsccEntry, IsccIndex, IsccQuery
 from iscc_search_amd.simprint import DOC_FREQ_DUP_LIMIT, HipSimprintIndex, pack_chunk_pointer
 from oracle_engine import OracleEngine
@@ -191,11 +188,7 @@ def _sp_assets(n, seed=21):
 
 @pytest.fixture(scope="module")
 def manager():
-    m = HipIndexManager("hip:///")
-    eng = m._get_engine()
-    for item in filter(None, os.environ.get("ISCC_HIP_OPTS", "").split(",")):    # the engine options of a rerun (conftest.hip_engine)
-        name, value = item.split("=")
-        eng.set_option(name.strip(), int(value))
+    m = hip_manager()
     m.create_index(IsccIndex(name="s"))
     assets, base = _sp_assets(200)
     m.add_assets("s", assets)

@@ -18,7 +18,6 @@ The bodies that need nothing but the table interface take any engine: ``tests/te
 the oracle-backed engine, so model and helper are themselves checked without a GPU.
 """
 
-import contextlib
 import os
 
 import numpy as np
@@ -30,27 +29,10 @@ from store_model import StoreModel, assert_table_equals, dirty_words, key_tuples
 pytestmark = pytest.mark.gpu
 
 HAMMING, NPHD = 0, 1
-OPTION_DEFAULTS = {"tiny_rows": 16384, "mfma": 1, "mfma_min_queries": 17, "mfma_min_rows": 65536, "mfma_pack": 1, "mfma_pack3": 1}
 
 
 def is_hip(engine):
     return hasattr(engine, "stats")
-
-
-@contextlib.contextmanager
-def options(engine, **values):
-    """Engine options for one block; afterwards the session's values again (the defaults, or what ISCC_HIP_OPTS set)."""
-    session = dict(OPTION_DEFAULTS)
-    for item in filter(None, os.environ.get("ISCC_HIP_OPTS", "").split(",")):
-        name, value = item.split("=")
-        session[name.strip()] = int(value)
-    try:
-        for name, value in values.items():
-            engine.set_option(name, value)
-        yield
-    finally:
-        for name in values:
-            engine.set_option(name, session[name])
 
 
 def make_keys(rng, n, key_words, start):
@@ -630,15 +612,15 @@ def test_stale_rows_64_bit(hip_engine, r, middle):
         # swapped: the rows moved into the gap came from the tail, where their copies still lie
         codes = words[-r:] if middle else words[gone]
         for k in (10, min(n, 4096)):
-            with options(eng, tiny_rows=16384, mfma_min_rows=65536, mfma_min_queries=17):
+            with eng.options(tiny_rows=16384, mfma_min_rows=65536, mfma_min_queries=17):
                 got, ran = _launches(eng, lambda: pair.search_equals_oracle(_ask(pair, codes, 12), None, k))      # tiny_search_kernel
                 assert ran["scan_launches"] >= 1 and ran["mfma_launches"] == 0, ran
                 _no_key_twice(got)
-            with options(eng, tiny_rows=0, mfma_min_rows=65536, mfma_min_queries=17):
+            with eng.options(tiny_rows=0, mfma_min_rows=65536, mfma_min_queries=17):
                 got, ran = _launches(eng, lambda: pair.search_equals_oracle(_ask(pair, codes, 12), None, k))      # scan_kernel
                 assert ran["scan_launches"] >= 1 and ran["mfma_launches"] == 0, ran
                 _no_key_twice(got)
-            with options(eng, mfma=1, mfma_pack=1, mfma_pack3=1, mfma_min_queries=1, mfma_min_rows=1):
+            with eng.options(mfma=1, mfma_pack=1, mfma_pack3=1, mfma_min_queries=1, mfma_min_rows=1):
                 for nq in (12, 40, 160):                             # mfma_pack_kernel; 160 queries = 5 groups in a chunk: mfma_pack3_kernel
                     got, ran = _launches(eng, lambda: pair.search_equals_oracle(_ask(pair, codes, nq), None, k))
                     assert ran["mfma_pack_launches"] >= 1, (nq, ran)
@@ -647,7 +629,7 @@ def test_stale_rows_64_bit(hip_engine, r, middle):
         q = _ask(pair, codes, 24)
         expected = [np_within(mw, 8, mk, q[i], 8, 64, 0) for i in range(len(q))]
         for opts in (dict(tiny_rows=16384), dict(tiny_rows=0), dict(tiny_rows=0, mfma=1, mfma_min_queries=1, mfma_min_rows=1)):
-            with options(eng, **opts):
+            with eng.options(**opts):
                 got = pair.table.search_within(q, None, 64, 0)
                 for i, (ek, eh, _) in enumerate(expected):
                     assert int(got[3][i]) == len(ek), f"{opts} query {i}: {got[3][i]} rows at distance 0, the model holds {len(ek)}"
@@ -684,14 +666,14 @@ def test_stale_rows_128_bit(hip_engine, r, middle):
     try:
         codes = words[-r:] if middle else words[gone]
         for k in (10, min(n, 4096)):
-            with options(eng, mfma=1, mfma_min_queries=1, mfma_min_rows=1):
+            with eng.options(mfma=1, mfma_min_queries=1, mfma_min_rows=1):
                 for nq in (12, 40):
                     got, ran = _launches(eng, lambda: pair.search_equals_oracle(_ask(pair, codes, nq), None, k))
                     assert ran["mfma_launches"] >= 1 and ran["mfma_pack_launches"] == 0, (nq, ran)
                     _no_key_twice(got)
-            with options(eng, tiny_rows=0, mfma_min_rows=65536, mfma_min_queries=17):
+            with eng.options(tiny_rows=0, mfma_min_rows=65536, mfma_min_queries=17):
                 _no_key_twice(pair.search_equals_oracle(_ask(pair, codes, 12), None, k))
-            with options(eng, tiny_rows=16384, mfma_min_rows=65536, mfma_min_queries=17):
+            with eng.options(tiny_rows=16384, mfma_min_rows=65536, mfma_min_queries=17):
                 _no_key_twice(pair.search_equals_oracle(_ask(pair, codes, 12), None, k))
     finally:
         pair.drop()

@@ -17,8 +17,8 @@ def _searches(engine, t, keys, words, lens, q, qlens, metric, fixed):
     for k in (1, 10, 400, min(len(keys) + 5, 4096)):
         exp = oracle_topk(metric, keys, words, lens, q, qlens, k, fixed_nbytes=fixed)
         for tiny_rows in (16384, 0):
-            engine.set_option("tiny_rows", tiny_rows)
-            got = t.search(q, qlens, k)
+            with engine.options(tiny_rows=tiny_rows):
+                got = t.search(q, qlens, k)
             np.testing.assert_array_equal(got[3], exp[3], err_msg=f"k={k} tiny_rows={tiny_rows}: counts")
             for i in range(q.shape[0]):
                 c = int(exp[3][i])
@@ -49,13 +49,12 @@ def test_hamming_tables_of_a_few_thousand_rows(hip_engine, n, key_words):
             for radius in (0, 3):
                 ek, eh, _ = np_within(words, nbytes, keys, q1, nbytes, 50, radius)
                 for tiny_rows in (16384, 0):
-                    hip_engine.set_option("tiny_rows", tiny_rows)
-                    gk, gh, _, gc = t.search_within(q1.reshape(1, -1), None, 50, radius)
+                    with hip_engine.options(tiny_rows=tiny_rows):
+                        gk, gh, _, gc = t.search_within(q1.reshape(1, -1), None, 50, radius)
                     assert int(gc[0]) == len(eh), (radius, tiny_rows)
                     np.testing.assert_array_equal(gh[0, : len(eh)], eh)
                     np.testing.assert_array_equal(gk[0, : len(eh)], ek)
         finally:
-            hip_engine.set_option("tiny_rows", 16384)
             t.drop()
 
 
@@ -76,5 +75,4 @@ def test_nphd_segments_of_mixed_lengths(hip_engine):
         q = _mask_to_len(base[rng.integers(0, len(base), size=len(qlens))].copy(), qlens)
         _searches(hip_engine, t, keys, words, lens, q, qlens, METRIC_NPHD, 0)
     finally:
-        hip_engine.set_option("tiny_rows", 16384)
         t.drop()

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One configurable search loop for profiling: python tools/bench_one.py ROWS NBYTES NQ K [REPS] [KEYWORDS] [name=value ...]
-(trailing name=value pairs are engine options, e.g. blocks_per_cu=7 queries_per_pass=16)"""
+(trailing name=value pairs are engine options, e.g. stretch_mb=64 queries_per_pass=16)"""
 import os
 import sys
 import time

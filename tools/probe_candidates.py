@@ -4,8 +4,7 @@ What does a candidate cost the matrix-core scan, and does the time of day inside
 
 Range-limited searches run ONE scan launch over the whole table under a threshold given by the caller, so the number of
 candidates per launch is a free parameter: radius r meets ~ rows * P(binomial(64, 1/2) <= r) candidates per random query.
-Prints the scan time per launch (HIP events inside the engine) for a sweep of radii, then the per-launch times of a top-k
-search with different level growths.
+Prints the scan time per launch (HIP events inside the engine) for a sweep of radii.
 
 usage (GPU box): python tools/probe_candidates.py [rows] [queries]
 """
@@ -45,12 +44,6 @@ def main():
         found = int(out[3].sum())
         print("radius %2d: %8.1f us per scan launch (%d launches, mfma %d); results/query %.2f" % (
             radius, 1e3 * st["scan_ms"] / st["scan_launches"], st["scan_launches"], st["scan_mfma_launches"], found / nq))
-    for growth in (2, 4, 16, 64, 256):
-        engine.set_option("mfma_level_growth", growth)
-        st, out = timed(lambda: table.search(q, None, 10), 10)
-        print("growth %3d: levels %6.1f us in %4.1f launches, collect %6.1f us in %3.1f launches, per step; level rows/us %.1f collect rows/us %.1f" % (
-            growth, 1e3 * st["level_ms"] / 10, st["level_launches"] / 10, 1e3 * st["scan_ms"] / 10, st["scan_launches"] / 10,
-            st["level_pair_words"] / nq / max(1e-9, 1e3 * st["level_ms"]), st["scan_pair_words"] / nq / max(1e-9, 1e3 * st["scan_ms"])))
     engine.close()
 
 
