@@ -802,7 +802,8 @@ struct Batch {
             // (the single pass appends everything within the bootstrap threshold until the first update arrives -- 3 072 waves x
             //  128 rows at once -- so its sample grows with k (1 024 k rows): 512 k measured 4.39 -> 3.80 ms at k = 256 and 11.9 (list
             //  overflow, retry) -> 5.07 ms at k = 512 against the fixed 65 536, profiles/r03_ab_large_k.txt)
-            const uint64_t s0 = std::min<uint64_t>(s.n, self ? std::max<uint64_t>((uint64_t)h->opt.self_boot_rows, std::min<uint64_t>((uint64_t)h->opt.self_boot_per_k * k, s.n / 8))
+            //  (... and never fewer than k rows: the worst of a shorter sample bounds nothing, and rows beyond it would never be listed)
+            const uint64_t s0 = std::min<uint64_t>(s.n, self ? std::max<uint64_t>(std::max<uint64_t>((uint64_t)h->opt.self_boot_rows, k), std::min<uint64_t>((uint64_t)h->opt.self_boot_per_k * k, s.n / 8))
                                                              : std::max<uint64_t>(BOOT_ROWS, std::min<uint64_t>(65536, 64ull * k)));
             isk::BootParams bp{};
             set_cols(bp.col, s, j.W);
