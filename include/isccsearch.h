@@ -105,6 +105,8 @@ typedef struct isccsearch_stats {
     /* with option "count_candidates" = 1: candidate-list entries the scan launches appended (summed over queries; the lists of the LAST pipeline run of
        every batch, read back after its synchronisation), and the batches they were counted over */
     uint64_t candidates, candidate_batches;
+    /* kernel launches of isccsearch_join_within / isccsearch_join_between, and how many of them ran on the matrix cores */
+    uint64_t join_launches, join_mfma_launches;
 } isccsearch_stats;
 
 /* Engine lifetime.  One handle drives one GPU (one process per GPU). */
@@ -120,9 +122,12 @@ const char* isccsearch_last_error(void);
  *   select_wide_from    0..2^32-1 2048   selects whose sort buffer has at least this many slots run 1 024-thread blocks
  *   stretch_mb          0..65536  128    MB of rows per collect launch when several query groups share them; 0: one streaming pass
  *   mfma_stretch_factor 1..64     3      matrix-core launches whose query chunks share the rows take this many times stretch_mb
- *   mfma                0|1       1      large batches scan on the matrix cores (FP4 MFMA, exact sums) instead of XOR + popcount
+ *   mfma                0|1       1      large batches scan on the matrix cores (FP4 MFMA, exact sums) instead of XOR + popcount;
+ *                                        0: no matrix cores anywhere, the joins included
  *   mfma_min_queries    1..1024   17     ... from this many queries (64-bit codes and segments of up to 12 Mi rows: from 9)
  *   mfma_min_rows       >= 1      65536  ... over at least this many rows
+ *   join_mfma           0|1       1      isccsearch_join_within / _between run on the matrix cores too (same pairs, same order)
+ *   join_mfma_min_rows  >= 0      65536  ... launches whose two segments both hold at least this many rows; 0: every launch
  *   mfma_pack           0|1       1      64-bit codes: the packed kernel (two row tiles per accumulator) unless a query is all zero
  *   mfma_pack3          0|1       1      ... three row tiles per accumulator for chunks of more than four query groups
  *   self_tighten        0|1       1      the matrix-core scan is ONE pass with self-tightening thresholds instead of threshold levels

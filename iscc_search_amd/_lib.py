@@ -78,6 +78,8 @@ class Stats(ctypes.Structure):
         ("spec_misses", ctypes.c_uint64),
         ("candidates", ctypes.c_uint64),
         ("candidate_batches", ctypes.c_uint64),
+        ("join_launches", ctypes.c_uint64),
+        ("join_mfma_launches", ctypes.c_uint64),
     ]
 
     def as_dict(self):

@@ -232,6 +232,13 @@ struct Options {
     int64_t mfma_min_rows = 65536;    // launches over fewer rows do not amortise the per-block query expansion
     int64_t mfma_pack = 1;            // 64-bit codes on the matrix cores: two row tiles per accumulator, packed f16 fold (mfma_pack_kernel)
     int64_t mfma_pack3 = 1;           // ... chunks of more than four query groups: three row tiles per accumulator, OR fold (mfma_pack3_kernel); 0: mfma_pack_kernel
+    // the joins (join_api.hip.h) on the matrix cores too: mfma_join_kernel instead of join_scan_kernel.  Self-join of 1 Mi rows, A B A in
+    // one run: 4.47x the XOR + popcount kernel's pair distances/s for 64-bit rows, 5.01x for 256-bit rows (profiles/join_mfma_rate.txt)
+    int64_t join_mfma = 1;
+    // ... launches whose two segments both hold at least this many rows (0: every launch).  65 536: the smallest of 16 Ki / 64 Ki / 256 Ki
+    // rows at which the matrix cores are not slower for both widths -- matrix cores / VALU at those sizes 0.61 / 1.83 / 3.22 for 64-bit
+    // rows and 1.53 / 2.79 / 3.87 for 256-bit rows (same file)
+    int64_t join_mfma_min_rows = 65536;
     // on the matrix cores: ONE pass whose thresholds tighten themselves (MODE_SELF) instead of levels + picks --
     // every launch of that chain costs ~35 us of ramp, prologue and tail, and a step of 100 M rows had seven of them
     int64_t self_tighten = 1;
@@ -259,6 +266,8 @@ const OptionDesc OPTIONS[] = {
     {"mfma", &Options::mfma, 0, 1},
     {"mfma_min_queries", &Options::mfma_min_queries, 1, 1024},
     {"mfma_min_rows", &Options::mfma_min_rows, 1, NO_MAX},
+    {"join_mfma", &Options::join_mfma, 0, 1},
+    {"join_mfma_min_rows", &Options::join_mfma_min_rows, 0, NO_MAX},
     {"mfma_pack", &Options::mfma_pack, 0, 1},
     {"mfma_pack3", &Options::mfma_pack3, 0, 1},
     {"self_tighten", &Options::self_tighten, 0, 1},

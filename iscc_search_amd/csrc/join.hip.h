@@ -42,7 +42,8 @@ struct JoinEmit {
     uint32_t* out_hamming;
     uint16_t* out_prefix_bits;
     uint32_t prefix_bits, kw;
-    uint32_t sgpr_side_is_b;      // cross join: the side in SGPRs is table B, its keys go to out_keys_b (else to out_keys_a)
+    uint32_t sgpr_side_is_b;      // cross join: the side in SGPRs (mfma_join_kernel: the side held in LDS) is table B, its keys go to
+                                  // out_keys_b (else to out_keys_a)
 };
 struct JoinParams {
     const uint64_t* col_a[4];     // side A: rows held in SGPRs, TQ per block

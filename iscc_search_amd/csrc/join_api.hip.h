@@ -1,5 +1,5 @@
 // join_api.hip.h -- isccsearch_join_within and isccsearch_join_between: the self-join of a table and the cross join of two
-// tables by the kernel of join.hip.h.
+// tables by the XOR + popcount kernel of join.hip.h or, for launches over enough rows, its matrix-core form (mfma_join_kernel.hip.h).
 // Needs the store of isccsearch.hip (Segment, Table; get_table of store.hip.h) and its scratch buffers.
 namespace {
 // one launch of the join kernel (join.hip.h)
@@ -24,7 +24,8 @@ constexpr uint32_t join_rows_per_block(uint32_t W) {
 // One call's launches: one per pair of segments, all appending to one output.  What only the emit path reads goes to the
 // device as one array of descriptors.
 struct JoinPlan {
-    struct Launch { isk::JoinParams jp; uint32_t W; bool mask; uint64_t blocks; };
+    // mfma: the launch takes mfma_join_kernel (mp, chunks of `groups` * 32 held rows), else join_scan_kernel (jp, blocks)
+    struct Launch { isk::JoinParams jp; uint32_t W; bool mask; uint64_t blocks; bool mfma; isk::MfmaJoinParams mp; uint32_t groups; uint64_t chunks; };
     std::vector<Launch> launches;
     std::vector<isk::JoinEmit> emits;
     bool cross = false;
@@ -60,6 +61,8 @@ int join_begin(isccsearch_handle* h, JoinPlan& plan, bool cross, uint32_t KW, ui
 // One launch: segment A (one block per TQ rows, the rows in SGPRs) against segment B (streamed by every block) over a common
 // prefix of pbytes bytes under tau.  `same`: A and B are one segment (the self-join keeps row_a < row_b).  `sgpr_side_is_b`:
 // a cross join whose segment A belongs to the call's table_b.
+// On the matrix cores (options mfma, join_mfma; both segments of at least join_mfma_min_rows rows) segment A is the HELD side --
+// chunks of its rows in LDS, what the SGPRs are to join_scan_kernel -- and B is streamed: the same roles, the same JoinEmit.
 int join_add(isccsearch_handle* h, JoinPlan& plan, Segment& A, Segment& B, uint32_t pbytes, int tau, bool same, bool sgpr_side_is_b) {
     const uint32_t W = (pbytes + 7) / 8;
     JoinPlan::Launch L{};
@@ -88,6 +91,19 @@ int join_add(isccsearch_handle* h, JoinPlan& plan, Segment& A, Segment& B, uint3
     L.blocks = (a_rows + join_rows_per_block(W) - 1) / join_rows_per_block(W);
     if (L.blocks >= (1ull << 31) || B.n >= (1ull << 40))
         return fail(-E2BIG, "segments of %llu x %llu rows exceed the join kernel's grid", (unsigned long long)A.n, (unsigned long long)B.n);
+    const uint64_t min_rows = (uint64_t)h->opt.join_mfma_min_rows;
+    L.mfma = h->opt.mfma && h->opt.join_mfma && A.n >= min_rows && B.n >= min_rows;
+    if (L.mfma) {
+        set_cols(L.mp.col_q, A, W);
+        set_cols(L.mp.col_s, B, W);
+        L.mp.n_q = A.n; L.mp.n_s = B.n;
+        L.mp.mask_lo = (uint32_t)L.jp.mask; L.mp.mask_hi = (uint32_t)(L.jp.mask >> 32);
+        L.mp.tau = L.jp.tau;
+        L.mp.same = L.jp.same;
+        // (any count from 2^20 rows on sizes the chunk alike: as many groups as 40 KB of LDS hold)
+        L.groups = isk::mfma_groups_per_chunk((int)W, (uint32_t)std::min<uint64_t>(A.n, 1u << 20), false);
+        L.chunks = (A.n + L.groups * 32 - 1) / (L.groups * 32);
+    }
     plan.launches.push_back(L);
     plan.emits.push_back(e);
     return 0;
@@ -104,10 +120,25 @@ int join_finish(isccsearch_handle* h, JoinPlan& plan, uint64_t* out_keys_a, uint
         HIPOK(hipMemcpyAsync(h->d_join_emit.p, plan.emits.data(), plan.emits.size() * sizeof(isk::JoinEmit), hipMemcpyHostToDevice, h->stream));
         for (size_t i = 0; i < plan.launches.size(); ++i) {
             JoinPlan::Launch& L = plan.launches[i];
-            L.jp.e = h->d_join_emit.p + i;
+            L.jp.e = L.mp.e = h->d_join_emit.p + i;
+            if (L.mfma) {
+                // grid.y is 16 bits: a segment of more chunks than one launch takes goes in several, each from its chunk_base
+                const uint32_t blocks_x = isk::mfma_join_blocks_x(L.mp.n_s);
+                for (uint64_t c = 0; c < L.chunks; c += isk::MFMA_JOIN_MAX_CHUNKS) {
+                    L.mp.chunk_base = c;
+                    const uint32_t chunks = (uint32_t)std::min<uint64_t>(L.chunks - c, isk::MFMA_JOIN_MAX_CHUNKS);
+                    const int lrc = isk::launch_mfma_join((int)L.W, plan.cross, blocks_x, chunks, L.groups, h->stream, L.mp);
+                    if (lrc) return fail(-EINVAL, "the matrix-core join does not take chunks of %u groups of %u words", L.groups, L.W);
+                    HIPOK(hipGetLastError());
+                    h->stats.join_launches += 1;
+                    h->stats.join_mfma_launches += 1;
+                }
+                continue;
+            }
             if (plan.cross) launch_join<true>(L.W, L.jp, L.mask, L.blocks, h->stream);
             else launch_join<false>(L.W, L.jp, L.mask, L.blocks, h->stream);
             HIPOK(hipGetLastError());
+            h->stats.join_launches += 1;
         }
     }
     uint64_t total = 0;
@@ -148,7 +179,8 @@ int join_finish(isccsearch_handle* h, JoinPlan& plan, uint64_t* out_keys_a, uint
 }
 }  // namespace
 
-// One join_scan_kernel launch per pair of segments (join.hip.h), all appending to one output; the pairs are sorted on the host.
+// One join launch per pair of segments (join_scan_kernel of join.hip.h or mfma_join_kernel, see join_add), all appending to one
+// output; the pairs are sorted on the host.
 extern "C" int isccsearch_join_within(isccsearch_handle* h, uint32_t table, const int16_t* max_hamming, uint64_t capacity,
                            uint64_t* out_keys_a, uint64_t* out_keys_b, uint32_t* out_hamming, uint16_t* out_prefix_bits,
                            uint64_t* out_total) {
@@ -167,7 +199,7 @@ extern "C" int isccsearch_join_within(isccsearch_handle* h, uint32_t table, cons
         for (uint32_t lb = la; lb <= ISCCSEARCH_MAX_BYTES; ++lb) {
             const bool same = la == lb;
             if (!t.seg[lb].n || (same && t.seg[la].n < 2)) continue;
-            // side A (one block per TQ rows) is the segment with more rows; side B is streamed by every block
+            // side A (one block per TQ rows, or held in LDS chunk by chunk) is the segment with more rows; side B is streamed by every block
             Segment& A = t.seg[lb].n > t.seg[la].n ? t.seg[lb] : t.seg[la];
             Segment& B = &A == &t.seg[la] ? t.seg[lb] : t.seg[la];
             if ((rc = join_add(h, plan, A, B, la, max_hamming[la], same, false))) return rc;
@@ -176,7 +208,7 @@ extern "C" int isccsearch_join_within(isccsearch_handle* h, uint32_t table, cons
     return join_finish(h, plan, out_keys_a, out_keys_b, out_hamming, out_prefix_bits, out_total);
 }
 
-// One join_scan_kernel<W, MASK, true> launch per pair of non-empty segments (la of table_a, lb of table_b), in either order of
+// One cross-join launch (join_scan_kernel<W, MASK, true> or mfma_join_kernel<W, true>) per pair of non-empty segments (la of table_a, lb of table_b), in either order of
 // lengths: the pair compares min(la, lb) bytes.  Both tables live on this handle, so one lock covers the call.
 extern "C" int isccsearch_join_between(isccsearch_handle* h, uint32_t table_a, uint32_t table_b, const int16_t* max_hamming,
                             uint64_t capacity, uint64_t* out_keys_a, uint64_t* out_keys_b, uint32_t* out_hamming,
@@ -201,7 +233,7 @@ extern "C" int isccsearch_join_between(isccsearch_handle* h, uint32_t table_a, u
         for (uint32_t lb = 1; lb <= ISCCSEARCH_MAX_BYTES; ++lb) {
             const uint32_t p = std::min(la, lb);
             if (!tb->seg[lb].n || max_hamming[p] < 0) continue;
-            // as in the self-join the segment with more rows goes into SGPRs: that may be table B's
+            // as in the self-join the segment with more rows goes into SGPRs (on the matrix cores: is held in LDS): that may be table B's
             const bool b_in_sgprs = tb->seg[lb].n > ta->seg[la].n;
             Segment& A = b_in_sgprs ? tb->seg[lb] : ta->seg[la];
             Segment& B = b_in_sgprs ? ta->seg[la] : tb->seg[lb];

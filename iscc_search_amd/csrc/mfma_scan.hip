@@ -32,6 +32,9 @@
 // candidate is counted per distance, and the lane that proves "k rows within t" lowers the threshold (see Pending, emit_self,
 // lower_threshold).  The default for k <= 512.
 //
+// The joins (isccsearch_join_within / _between) run the same arithmetic under ONE fixed threshold, with a chunk of a table's own rows
+// where the queries are: mfma_join_kernel.hip.h, launch_mfma_join.
+//
 // Built with -mllvm -amdgpu-mfma-vgpr-form=1 -ffinite-math-only: hipcc otherwise puts the accumulators in AGPRs and pays one
 // v_accvgpr_read per result before the fold (16 extra VALU instructions per tile and group), and canonicalises the inputs of
 // every 2-input fminf (two v_max per group: the values are small integers, never NaN).
@@ -41,6 +44,7 @@
 #include "mfma_scan_kernel.hip.h"
 #include "mfma_pack_kernel.hip.h"
 #include "mfma_pack3_kernel.hip.h"
+#include "mfma_join_kernel.hip.h"
 
 namespace isk {
 
@@ -132,6 +136,28 @@ int launch_mfma_scan(int W, int mode, bool pack, uint32_t blocks_x, uint32_t gro
         case 3: return launch_w<3>(mode, grid, lds, st, p, groups);
         default: return launch_w<4>(mode, grid, lds, st, p, groups);
     }
+}
+
+template <int W>
+static void launch_join_w(bool cross, dim3 grid, size_t lds, hipStream_t st, const MfmaJoinParams& p, uint32_t groups) {
+    if (cross) hipLaunchKernelGGL((mfma_join_kernel<W, true>), grid, dim3(MBLOCK), lds, st, p, groups);
+    else hipLaunchKernelGGL((mfma_join_kernel<W, false>), grid, dim3(MBLOCK), lds, st, p, groups);
+}
+
+int launch_mfma_join(int W, bool cross, uint32_t blocks_x, uint32_t chunks, uint32_t groups, hipStream_t st, const MfmaJoinParams& p) {
+    static_assert(MFMA_JOIN_WAVES == MBLOCK / 64, "the grid rule counts the kernel's waves");
+    const size_t lds = mfma_lds_bytes(W, groups);
+    // the group pipeline walks pairs of groups; grid.y is 16 bits
+    if (lds > (size_t)MFMA_MAX_LDS || groups < 2 || (groups & 1) || !blocks_x || !chunks || chunks > MFMA_JOIN_MAX_CHUNKS) return (int)hipErrorInvalidValue;
+    const dim3 grid(blocks_x, chunks);
+    switch (W) {
+        case 1: launch_join_w<1>(cross, grid, lds, st, p, groups); break;
+        case 2: launch_join_w<2>(cross, grid, lds, st, p, groups); break;
+        case 3: launch_join_w<3>(cross, grid, lds, st, p, groups); break;
+        case 4: launch_join_w<4>(cross, grid, lds, st, p, groups); break;
+        default: return (int)hipErrorInvalidValue;
+    }
+    return 0;
 }
 
 }  // namespace isk

@@ -32,7 +32,7 @@ import sys
 KERNEL_RE = re.compile(r"^(_ZN3isk\w+):\s*(;.*)?$")
 LABEL_RE = re.compile(r"^(\.LBB\d+_\d+):")
 VREG_RE = re.compile(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]")
-AUDITED = ("scan_kernel", "scan_adapt_kernel", "mfma_scan_kernel", "mfma_pack_kernel", "mfma_pack3_kernel")
+AUDITED = ("scan_kernel", "scan_adapt_kernel", "mfma_scan_kernel", "mfma_pack_kernel", "mfma_pack3_kernel", "mfma_join_kernel")
 # an 8-pass MFMA (v_mfma_f32_32x32x64_f8f6f4 with FP4 operands) may be read by the VALU 11 wait states after it was issued
 # (LLVM: passes + 3); one more for margin
 MFMA_WAIT_STATES = 12
@@ -295,7 +295,7 @@ def main():
                 n_groups += n
     n_pack = n_mfma = 0
     for name, ins in kernels.items():
-        if "mfma_pack_kernel" in name or "mfma_pack3_kernel" in name or "mfma_scan_kernel" in name:     # every matrix-core kernel: their stages are inline asm
+        if "mfma_pack_kernel" in name or "mfma_pack3_kernel" in name or "mfma_scan_kernel" in name or "mfma_join_kernel" in name:     # every matrix-core kernel: their stages are inline asm
             b, n = audit_mfma_distances(name, ins)
             bad += b
             n_pack += 1

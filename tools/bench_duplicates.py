@@ -1,24 +1,29 @@
 #!/usr/bin/env python3
 """
-Rate of the device joins (isccsearch_join_within and isccsearch_join_between, csrc/join.hip.h) on synthetic tables.
+Rate of the device joins (isccsearch_join_within and isccsearch_join_between) on synthetic tables, on the XOR + popcount kernel
+(csrc/join.hip.h), on the matrix cores (csrc/mfma_join_kernel.hip.h) or on both in one run.
 
-Tables: 64-bit HAMMING rows at 1 M and 10 M rows, and a 256-bit NPHD table (all rows 32 bytes).  Synthetic rows are random
-words (isccsearch_add_synthetic), so almost no pair is within the threshold and the time is that of the scan: n(n-1)/2 pair
-distances.  Prints one line per table: seconds (best of --reps after one warm-up), pair distances per second, and the
-fraction of the VALU issue rate -- 64 lanes / ((4 W + 0.5) instructions x 4 cycles) per SIMD and clock, the figure bench.py
-uses for the XOR + popcount scan (W = 64-bit words per row).
+Tables: 64-bit HAMMING rows at 64 Ki, 256 Ki, 1 Mi and 4 Mi rows, and 256-bit NPHD tables (all rows 32 bytes) at 256 Ki and 1 Mi
+rows.  Synthetic rows are random words (isccsearch_add_synthetic), so almost no pair is within the threshold and the time is that
+of the scan: n(n-1)/2 pair distances for the self-join, n x n for --between (two tables of n different random rows each, or of
+--rows-a x --rows-b rows).  One JSON line per table.
 
---between: the cross join of two synthetic tables of --rows-a and --rows-b rows (rows_a x rows_b pair distances), for 64-bit
-HAMMING and 256-bit NPHD rows, each next to the self-join of the --rows-a table: one line per width with both rates and
-their ratio.
+--mfma 0 | 1: the XOR + popcount kernel (option join_mfma=0) or the matrix cores for every launch (join_mfma=1,
+join_mfma_min_rows=0).  A leg is one warm-up call and the MEDIAN of --reps timed calls.  The line carries seconds and pair
+distances per second; for the XOR + popcount kernel also the fraction of the VALU issue rate -- 64 lanes / ((4 W + 0.5)
+instructions x 4 cycles) per SIMD and clock, the figure bench.py uses for that scan (W = 64-bit words per row).
+--mfma both (the default): three legs per table in the order VALU, matrix cores, VALU (A B A), so that a drift of the box shows
+between the two VALU legs.  The line carries the three rates and `ratio` = matrix cores / mean of the two VALU legs, and the tool
+asserts that the legs found the same number of pairs.
 
-usage: python tools/bench_duplicates.py [--reps 3] [--sizes 1000000,10000000] [--nphd-rows 1000000] [--tau 6]
-       python tools/bench_duplicates.py --between [--rows-a 1000000] [--rows-b 1000000] [--reps 3] [--tau 6]
+usage: python tools/bench_duplicates.py [--mfma both] [--reps 5] [--sizes 65536,262144,1048576,4194304] [--nphd-sizes 262144,1048576] [--tau 6]
+       python tools/bench_duplicates.py --between [--rows-a N --rows-b M] [the same options]
 """
 
 import argparse
 import json
 import os
+import statistics
 import sys
 import time
 
@@ -41,53 +46,76 @@ def table_name(metric, nbytes):
     return f"{'HAMMING' if metric == _lib.METRIC_HAMMING else 'NPHD'} {8 * nbytes}-bit"
 
 
-def best_of(join, reps):
-    """(seconds, pairs found): best of `reps` calls after one warm-up (code objects, buffers)."""
+def median_of(join, reps):
+    """(seconds, pairs found): median of `reps` calls after one warm-up (code objects, buffers)."""
     join()
-    best, pairs_found = None, 0
+    times, pairs_found = [], 0
     for _ in range(reps):
         t0 = time.perf_counter()
         out = join()                                    # ends in a device synchronise (the pair count is read back)
-        dt = time.perf_counter() - t0
-        best = dt if best is None else min(best, dt)
+        times.append(time.perf_counter() - t0)
         pairs_found = len(out[2])
-    return best, pairs_found
+    return statistics.median(times), pairs_found
 
 
-def run(engine, metric, nbytes, n, tau, reps):
+def leg(engine, mfma, join, reps):
+    """One leg on one kernel; the statistics must say that kernel ran, and no other."""
+    opts = dict(mfma=1, join_mfma=1, join_mfma_min_rows=0) if mfma else dict(join_mfma=0)
+    before = engine.stats()
+    with engine.options(**opts):
+        seconds, pairs_found = median_of(join, reps)
+    after = engine.stats()
+    launches = after["join_launches"] - before["join_launches"]
+    on_mfma = after["join_mfma_launches"] - before["join_mfma_launches"]
+    assert launches > 0 and on_mfma == (launches if mfma else 0), (mfma, launches, on_mfma)
+    return seconds, pairs_found
+
+
+def measure(engine, which, join, pairs, words, reps):
+    """The legs `which` asks for over one join: {seconds, rates, ratio, pairs_found}."""
+    out = {}
+    if which != "both":
+        seconds, found = leg(engine, which == "1", join, reps)
+        out.update(kernel="mfma" if which == "1" else "valu", seconds=round(seconds, 5), pair_distances_per_s=float(f"{pairs / seconds:.4g}"), pairs_found=found)
+        if which == "0":
+            out["valu_issue_fraction"] = round(pairs / seconds / valu_peak_pairs(words), 3)
+        return out
+    a1, f1 = leg(engine, False, join, reps)
+    b, fb = leg(engine, True, join, reps)
+    a2, f2 = leg(engine, False, join, reps)
+    assert f1 == fb == f2, f"the kernels disagree on the number of pairs: VALU {f1}, matrix cores {fb}, VALU {f2}"
+    rates = [pairs / s for s in (a1, b, a2)]
+    out.update(valu_seconds=[round(a1, 5), round(a2, 5)], mfma_seconds=round(b, 5),
+               valu_pair_distances_per_s=[float(f"{rates[0]:.4g}"), float(f"{rates[2]:.4g}")], mfma_pair_distances_per_s=float(f"{rates[1]:.4g}"),
+               ratio=round(rates[1] / ((rates[0] + rates[2]) / 2), 3), pairs_found=fb,
+               valu_issue_fraction=round((rates[0] + rates[2]) / 2 / valu_peak_pairs(words), 3))
+    return out
+
+
+def run(engine, which, metric, nbytes, n, tau, reps):
     t = engine.open_table(metric, 1, nbytes)
     try:
         t.add_synthetic(nbytes, n, seed=1234 + n, first_row=0, key_base=1)
         mh = np.full(_lib.MAX_BYTES + 1, -1, dtype=np.int16)
         mh[nbytes] = tau
-        best, pairs_found = best_of(lambda: t.join_within(mh, 1 << 20), reps)
-        words = (nbytes + 7) // 8
-        pairs = n * (n - 1) / 2
-        rate = pairs / best
-        return {"table": table_name(metric, nbytes), "rows": n, "tau": tau,
-                "seconds": round(best, 5), "pair_distances_per_s": float(f"{rate:.4g}"), "pairs_found": pairs_found,
-                "valu_issue_fraction": round(rate / valu_peak_pairs(words), 3)}
+        out = {"join": "within", "table": table_name(metric, nbytes), "rows": n, "tau": tau}
+        out.update(measure(engine, which, lambda: t.join_within(mh, 1 << 20), n * (n - 1) / 2, (nbytes + 7) // 8, reps))
+        return out
     finally:
         t.drop()
 
 
-def run_between(engine, metric, nbytes, n_a, n_b, tau, reps):
-    """The cross join of two tables of different random rows, and the self-join of the first for comparison."""
+def run_between(engine, which, metric, nbytes, n_a, n_b, tau, reps):
+    """The cross join of two tables of different random rows."""
     ta, tb = engine.open_table(metric, 1, nbytes), engine.open_table(metric, 1, nbytes)
     try:
         ta.add_synthetic(nbytes, n_a, seed=1234 + n_a, first_row=0, key_base=1)
         tb.add_synthetic(nbytes, n_b, seed=4321 + n_b, first_row=0, key_base=1)
         mh = np.full(_lib.MAX_BYTES + 1, -1, dtype=np.int16)
         mh[nbytes] = tau
-        within_s, _ = best_of(lambda: ta.join_within(mh, 1 << 20), reps)
-        between_s, pairs_found = best_of(lambda: ta.join_between(tb, mh, 1 << 20), reps)
-        within_rate = n_a * (n_a - 1) / 2 / within_s
-        between_rate = n_a * n_b / between_s
-        return {"table": table_name(metric, nbytes), "rows_a": n_a, "rows_b": n_b, "tau": tau,
-                "between_seconds": round(between_s, 5), "between_pair_distances_per_s": float(f"{between_rate:.4g}"),
-                "within_seconds": round(within_s, 5), "within_pair_distances_per_s": float(f"{within_rate:.4g}"),
-                "between_over_within": round(between_rate / within_rate, 3), "pairs_found": pairs_found,
-                "valu_issue_fraction": round(between_rate / valu_peak_pairs((nbytes + 7) // 8), 3)}
+        out = {"join": "between", "table": table_name(metric, nbytes), "rows_a": n_a, "rows_b": n_b, "tau": tau}
+        out.update(measure(engine, which, lambda: ta.join_between(tb, mh, 1 << 20), float(n_a) * n_b, (nbytes + 7) // 8, reps))
+        return out
     finally:
         ta.drop()
         tb.drop()
@@ -95,25 +123,31 @@ def run_between(engine, metric, nbytes, n_a, n_b, tau, reps):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--sizes", default="1000000,10000000", help="row counts of the 64-bit tables")
-    ap.add_argument("--nphd-rows", type=int, default=1_000_000, help="rows of the 256-bit NPHD table (0: skip)")
+    ap.add_argument("--mfma", choices=("0", "1", "both"), default="both", help="the kernel: XOR + popcount, matrix cores, or A B A over both")
+    ap.add_argument("--reps", type=int, default=5, help="timed calls per leg (their median counts)")
+    ap.add_argument("--sizes", default="65536,262144,1048576,4194304", help="row counts of the 64-bit HAMMING tables")
+    ap.add_argument("--nphd-sizes", default="262144,1048576", help="row counts of the 256-bit NPHD tables (empty: none)")
     ap.add_argument("--tau", type=int, default=6, help="max Hamming distance of the 64-bit tables (4x that for 256 bits)")
-    ap.add_argument("--between", action="store_true", help="the cross join of two tables next to the self-join's rate")
-    ap.add_argument("--rows-a", type=int, default=1_000_000, help="--between: rows of table A")
-    ap.add_argument("--rows-b", type=int, default=1_000_000, help="--between: rows of table B")
+    ap.add_argument("--between", action="store_true", help="the cross join of two tables of each size instead of the self-join")
+    ap.add_argument("--rows-a", type=int, default=0, help="--between: rows of table A (with --rows-b: this one pair of sizes only)")
+    ap.add_argument("--rows-b", type=int, default=0, help="--between: rows of table B")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args()
+    sizes = [int(s) for s in a.sizes.split(",") if s]
+    nphd_sizes = [int(s) for s in a.nphd_sizes.split(",") if s]
     engine = HipEngine(a.device)
     try:
         if a.between:
-            print(json.dumps(run_between(engine, _lib.METRIC_HAMMING, 8, a.rows_a, a.rows_b, a.tau, a.reps)), flush=True)
-            print(json.dumps(run_between(engine, _lib.METRIC_NPHD, 32, a.rows_a, a.rows_b, 4 * a.tau, a.reps)), flush=True)
+            given = a.rows_a > 0 and a.rows_b > 0
+            for n_a, n_b in [(a.rows_a, a.rows_b)] if given else [(n, n) for n in sizes]:
+                print(json.dumps(run_between(engine, a.mfma, _lib.METRIC_HAMMING, 8, n_a, n_b, a.tau, a.reps)), flush=True)
+            for n_a, n_b in [(a.rows_a, a.rows_b)] if given else [(n, n) for n in nphd_sizes]:
+                print(json.dumps(run_between(engine, a.mfma, _lib.METRIC_NPHD, 32, n_a, n_b, 4 * a.tau, a.reps)), flush=True)
             return
-        for n in [int(s) for s in a.sizes.split(",") if s]:
-            print(json.dumps(run(engine, _lib.METRIC_HAMMING, 8, n, a.tau, a.reps)), flush=True)
-        if a.nphd_rows:
-            print(json.dumps(run(engine, _lib.METRIC_NPHD, 32, a.nphd_rows, 4 * a.tau, a.reps)), flush=True)
+        for n in sizes:
+            print(json.dumps(run(engine, a.mfma, _lib.METRIC_HAMMING, 8, n, a.tau, a.reps)), flush=True)
+        for n in nphd_sizes:
+            print(json.dumps(run(engine, a.mfma, _lib.METRIC_NPHD, 32, n, 4 * a.tau, a.reps)), flush=True)
     finally:
         engine.close()
 
