@@ -107,6 +107,9 @@ typedef struct isccsearch_stats {
     uint64_t candidates, candidate_batches;
     /* kernel launches of isccsearch_join_within / isccsearch_join_between, and how many of them ran on the matrix cores */
     uint64_t join_launches, join_mfma_launches;
+    /* queries that a fixed-radius pass of a large batch (option "radius_batches") left short of k rows and that were asked again,
+       alone, under the whole hint -- counted when that second pass completed them (the step is then one of spec_hits) */
+    uint64_t spec_repairs;
 } isccsearch_stats;
 
 /* Engine lifetime.  One handle drives one GPU (one process per GPU). */
@@ -136,6 +139,8 @@ const char* isccsearch_last_error(void);
  *   speculate           0|1       1      small batches first try ONE range-limited pass under the previous k-th distance, verified
  *   spec_max_queries    0..1024   128    ... batches of up to this many queries
  *   self_hint           0|1       1      larger batches START their single pass under that hint instead of a sample, verified
+ *   radius_batches      0|1       1      ... those that would run the three-tile kernel: ONE fixed-radius pass under the hint's worst k-th
+ *                                        distance instead, the few queries it leaves short asked again under the hint; 0: the hinted single pass
  *   device_search_hint  -1..256   -1     one-shot: the next isccsearch_search_device_async starts under this distance (the caller verifies)
  *   candidate_cap       64..2^22  16384  floor of the per-query candidate buffer, in entries
  * An unknown name, a NULL argument or a value outside the range fails with -EINVAL and changes nothing. */

@@ -80,6 +80,7 @@ class Stats(ctypes.Structure):
         ("candidate_batches", ctypes.c_uint64),
         ("join_launches", ctypes.c_uint64),
         ("join_mfma_launches", ctypes.c_uint64),
+        ("spec_repairs", ctypes.c_uint64),
     ]
 
     def as_dict(self):

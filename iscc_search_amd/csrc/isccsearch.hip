@@ -210,6 +210,14 @@ constexpr uint32_t FOLD_TAU = 11;          // 64-bit codes: groups whose thresho
 constexpr uint32_t MFMA_PACK_MIN_QUERIES = 9;    // 64-bit codes (packed matrix-core kernel): from this many queries (see use_mfma)
 constexpr uint64_t MFMA_FEW_ROWS = 12ull << 20;  // longer codes: segments up to this many rows take the matrix cores from MFMA_PACK_MIN_QUERIES queries too
 constexpr uint32_t SELF_REFRESH_STEPS = 1;       // the single pass: steps of a full chunk between two looks at the live thresholds (power of two)
+// The fixed-radius pass of large pack3 batches (search_locked, Spec::tight; option "radius_batches"): its radius is the hint minus the hint's
+// margin -- the worst k-th distance the class last ended at -- plus this many bits, and up to RADIUS_BATCH_MAX_REPAIRS queries (one query
+// group) that come up short are asked again under the whole hint (a pass for 9-32 queries: 0.19 ms, profiles/r04_operating_points.txt)
+// (0 against 1 on the flagship step, 100 M x 64-bit rows, 1 024 queries, k = 10, three runs each alternating: 533.6 against 514.8 k
+//  queries/s, scan 1.837 against 1.912 ms per step -- 59 against 224 appended rows per query, and 0.6 queries per step to repair against
+//  none: the second small pass costs less than the wider radius does on every step.  profiles/radius_batches_ab.txt)
+constexpr int RADIUS_BATCH_SLACK = 0;
+constexpr uint32_t RADIUS_BATCH_MAX_REPAIRS = 32;
 // Every k takes the single self-tightening pass (it stopped at 512 until the pass was measured beyond it: k = 1 000 / 2 000 over 100 M rows
 // 6.0 / 9.0 ms against 8.5 / 14.0 of the level design, 4.2 / 6.6 under a hint; the unpruned lists hold ~k ln(n / sample) entries + the
 // first steps' flood: see the cap in Batch::begin.  100 M rows, k = 100 / 256 / 512: 3.80 / 4.52 / 6.04 ms against 4.60 / 5.35 / 7.37 with levels).
@@ -246,6 +254,8 @@ struct Options {
                                       // short sample floods the first steps with candidates (4 096 rows: ~860 per query)
     int64_t self_boot_per_k = 1024;   // ... and at least this many rows per wanted neighbour
     int64_t self_hint = 1;            // batches above spec_max_queries: start the single self-tightening pass under the hint (no bootstrap sample)
+    int64_t radius_batches = 1;       // ... those that would run mfma_pack3_kernel: ONE fixed-radius pass under the hint's worst k-th distance, the
+                                      // few queries it leaves short asked again under the hint (search_locked, Spec::tight); 0: the hinted single pass
     int64_t speculate = 1;            // small batches: try one range-limited pass under the previous search's k-th distance first
     int64_t spec_max_queries = 128;   // ... batches of up to this many queries
     int64_t device_search_hint = -1;  // one-shot: the next isccsearch_search_device_async starts its single pass under this threshold (the caller verifies)
@@ -274,6 +284,7 @@ const OptionDesc OPTIONS[] = {
     {"self_boot_rows", &Options::self_boot_rows, 256, 1 << 20},
     {"self_boot_per_k", &Options::self_boot_per_k, 0, 1 << 20},
     {"self_hint", &Options::self_hint, 0, 1},
+    {"radius_batches", &Options::radius_batches, 0, 1},
     {"speculate", &Options::speculate, 0, 1},
     {"spec_max_queries", &Options::spec_max_queries, 0, 1024},
     {"device_search_hint", &Options::device_search_hint, -1, 8 * ISCCSEARCH_MAX_BYTES},
@@ -524,6 +535,9 @@ struct Batch {
     bool allow_self = true, used_self = false;   // the single self-tightening pass, and whether a job of this batch took it
     int self_hint = -1;       // >= 0: the single pass starts under THIS threshold instead of a bootstrap sample's (search_locked verifies)
     bool used_hint = false;
+    // the batch scans on the matrix cores however few its queries are: the repair pass of search_locked is part of a matrix-core step, and
+    // a step's collect launches are of ONE kind (scan_mfma_launches == scan_launches is how a reader of the statistics tells which)
+    bool on_matrix_cores = false;
     std::vector<Job> jobs;
 
     Batch(H* h_, Table& t_, uint32_t nq_, uint32_t qbytes_, uint32_t k_, isk::Record* out, uint32_t* out_cnt)
@@ -602,8 +616,14 @@ struct Batch {
     bool use_mfma(const Job& j, uint64_t rows) const {
         const bool from_nine = j.pack || j.seg->n <= MFMA_FEW_ROWS;
         const uint32_t min_queries = (uint32_t)h->opt.mfma_min_queries;
-        return h->opt.mfma && nq_pad >= (from_nine ? std::min(min_queries, MFMA_PACK_MIN_QUERIES) : min_queries) && rows >= (uint64_t)h->opt.mfma_min_rows;
+        return h->opt.mfma && (on_matrix_cores || nq_pad >= (from_nine ? std::min(min_queries, MFMA_PACK_MIN_QUERIES) : min_queries)) && rows >= (uint64_t)h->opt.mfma_min_rows;
     }
+    // a top-k search of this job is the single self-tightening pass
+    bool single_pass(const Job& j) const { return allow_self && h->opt.self_tighten && use_mfma(j, j.seg->n); }
+    // a matrix-core launch of this job runs mfma_pack3_kernel (one-word codes, a chunk of more than PK_DEEP_GROUPS groups)
+    bool pack3(const Job& j) const { return j.pack && h->opt.mfma_pack3 && isk::mfma_pack3_fits(isk::mfma_groups_per_chunk((int)j.W, nq_pad, j.pack)); }
+    // ... and one launch over the job's whole segment is such a launch
+    bool pack3_pass(const Job& j) const { return use_mfma(j, j.seg->n) && pack3(j); }
     int scan(const Job& j, const isk::ScanParams& sp, int mode, bool sample) {
         const uint64_t rows = sp.n_rows - sp.row_begin;
         // A self-tightening pass is decided once per job (use_mfma over the whole segment) and lives on the matrix cores: EVERY
@@ -611,7 +631,7 @@ struct Batch {
         if (use_mfma(j, rows) || mode == isk::MODE_SELF) {
             const uint32_t g = isk::mfma_groups_per_chunk((int)j.W, nq_pad, j.pack);
             const uint32_t chunks = (nq_pad + g * 32 - 1) / (g * 32);
-            const bool pack3 = j.pack && h->opt.mfma_pack3 && isk::mfma_pack3_fits(g);
+            const bool pack3 = this->pack3(j);
             const uint64_t rps = isk::mfma_rows_per_wave_step((int)j.W, j.pack, pack3);
             const uint64_t steps = (rows + rps - 1) / rps;
             const uint64_t wpb = isk::mfma_waves_per_block();
@@ -630,9 +650,10 @@ struct Batch {
     }
 
     // hq: host query words [nq][max_words]
-    int begin(const uint64_t* hq) {
+    // The batch's padding and its jobs, one per non-empty segment.  begin() starts with it; a caller that chooses the batch's path by what
+    // its jobs would run (search_locked) may ask first.
+    void plan(const uint64_t* hq) {
         jobs.clear();
-        used_self = false;
         tq = (int)h->opt.queries_per_pass;
         // 9..16 queries: ONE pass of 16 instead of two passes of 8 -- the pass is VALU-bound then, but the rows cross the memory
         // system once and half the launches go (100 M x 64-bit: 0.31 against 0.41 ms; 256-bit: 0.87 against 1.48; no loss at 10 M)
@@ -655,6 +676,10 @@ struct Batch {
                 for (uint32_t q = 0; q < nq && j.pack; ++q) j.pack = hq[(size_t)q * t.max_words] != 0;
             jobs.push_back(j);
         }
+    }
+    int begin(const uint64_t* hq) {
+        plan(hq);
+        used_self = false;
         if (jobs.empty()) {
             HIPOK(hipMemsetAsync(d_out_cnt, 0, nq * sizeof(uint32_t), h->stream));
             return 0;
@@ -806,7 +831,7 @@ struct Batch {
             //    tile could see a new threshold -- before any update reaches them, and fresh thresholds must be read past the
             //    per-XCD L2s (sc1 / glc), where 8 192 waves hammering one line serialise: measured 0.24-0.53 ms for 1-8
             //    queries over 100 M rows against 0.10 ms for the collect pass of the level design.)
-            const bool self = allow_self && h->opt.self_tighten && use_mfma(j, s.n);
+            const bool self = single_pass(j);
             used_self = used_self || self;
             // (the single pass appends everything within the bootstrap threshold until the first update arrives -- 3 072 waves x
             //  128 rows at once -- so its sample grows with k (1 024 k rows): 512 k measured 4.39 -> 3.80 ms at k = 256 and 11.9 (list
@@ -1076,12 +1101,15 @@ struct Batch {
 // where a batch's lists ended -- the worst k-th distance, read off the records or off `kth` (the lists' last distances) -- is
 // where the next small batch of the class starts (+ a margin: P(h <= t) grows ~3x per step at these distances, so it costs a
 // handful of candidates and absorbs the spread between queries): hit() after a speculative pass that held, seed() after any other
+void record_hint(Segment::SpecHint& hint, bool spec_ok, uint32_t k, uint32_t worst) {
+    if (spec_ok) hint.hit(worst);
+    else hint.seed(k, worst);
+}
 void record_hint(Segment::SpecHint& hint, bool spec_ok, uint32_t nq, uint32_t k, const uint32_t* cnt, const isk::Record* rec, const uint32_t* kth) {
     uint32_t worst = 0;
     for (uint32_t i = 0; i < nq; ++i)
         if (cnt[i]) worst = std::max<uint32_t>(worst, kth ? kth[i] : rec[(size_t)i * k + cnt[i] - 1].hamming);
-    if (spec_ok) hint.hit(worst);
-    else hint.seed(k, worst);
+    record_hint(hint, spec_ok, k, worst);
 }
 
 // Records -> the caller's arrays.  A large block (k in the hundreds x a full batch: 10^5..10^6 records, 0.1-0.5 ms on one core,

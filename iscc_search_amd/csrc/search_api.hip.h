@@ -104,16 +104,31 @@ static int search_locked(isccsearch_handle* h, uint32_t table, uint32_t nq, cons
         //              stands if no list overflowed, every query has k rows and its k-th NPHD is <= hint + 1/32: a row outside a
         //              segment's radius lies strictly beyond that ratio, a row inside it but not listed has k nearer rows of its own
         //              segment before it.
-        enum class Spec { none, radius, self_hint, ratio } spec = Spec::none;
+        //   tight      LARGER batches whose pass would run mfma_pack3_kernel (one-word codes, more than four query groups; host lists).
+        //              That kernel's fold flags lanes against ONE threshold per wave, the largest of its chunk + 1, and per-query
+        //              thresholds only choose among the flagged rows: they save no fold work, while keeping them live costs 9-10 % of
+        //              the pass (profiles/r05_pack3_ab.txt).  So the pass runs as a RANGE-LIMITED search under one radius for every
+        //              query: the worst k-th distance the class last ended at (the hint without its margin, + RADIUS_BATCH_SLACK).
+        //              Up to RADIUS_BATCH_MAX_REPAIRS queries that find fewer than k rows there are asked again, alone, under the
+        //              whole hint and their lists spliced in; more of them send the batch through the self_hint pass.  Either way
+        //              the step stands exactly when every query has k rows within the hint and no list overflowed, as with self_hint.
+        enum class Spec { none, radius, self_hint, tight, ratio } spec = Spec::none;
         // radius / self_hint: an ordinary top-k search over ONE segment that has been searched with this k before
         Segment* const spec_seg = t.sole_segment();
         // (a segment small enough for the one-launch search -- Batch::tiny -- has nothing to gain from a radius: it is exact in that launch either way)
         const bool one_launch = spec_seg && spec_seg->n <= (uint64_t)h->opt.tiny_rows && spec_seg->n < (uint64_t)h->opt.mfma_min_rows && spec_seg->n <= (uint64_t)h->opt.candidate_cap;
         const bool hintable = spec_seg && radius < 0 && !out_freq && one_copy && k <= spec_seg->n && !one_launch;
         const bool small_batch = hintable && m <= (uint32_t)h->opt.spec_max_queries;
+        // (tight: the batch's one job would take the single pass, and that pass is ONE launch of mfma_pack3_kernel)
+        auto runs_pack3 = [&]() { batch.plan(hq.data()); return batch.jobs.size() == 1 && batch.single_pass(batch.jobs[0]) && batch.pack3_pass(batch.jobs[0]); };
+        int tau = -1;                   // radius / self_hint / tight: the hint this batch speculates under
         if (hintable && h->opt.speculate && !h->spec_suppress && (small_batch || h->opt.self_hint) && spec_seg->hint(m, len).ready(k)) {
-            if (small_batch) { spec = Spec::radius; batch.radius = (int)spec_seg->hint(m, len).tau; }
-            else { spec = Spec::self_hint; batch.self_hint = (int)spec_seg->hint(m, len).tau; }
+            tau = (int)spec_seg->hint(m, len).tau;
+            if (small_batch) { spec = Spec::radius; batch.radius = tau; }
+            else if (h->opt.radius_batches && !sink && runs_pack3()) {
+                spec = Spec::tight;
+                batch.radius = std::max(0, tau - (int)Segment::SpecHint::margin(k) + RADIUS_BATCH_SLACK);
+            } else { spec = Spec::self_hint; batch.self_hint = tau; }
         }
         const bool mhintable = segments > 1 && radius < 0 && !out_freq && (m <= (uint32_t)h->opt.spec_max_queries || h->opt.self_hint) && k <= t.total;
         if (mhintable && h->opt.speculate && !h->spec_suppress && t.mhint(m, len).ready(k)) {
@@ -170,13 +185,80 @@ static int search_locked(isccsearch_handle* h, uint32_t table, uint32_t nq, cons
         }
         if (spec == Spec::self_hint && !batch.used_hint) spec = Spec::none;     // (no job took the single pass: nothing to verify)
         bool spec_ok = false;
-        if (spec != Spec::none) {
-            if ((rc = batch.merge())) return rc;
-            if ((rc = batch.copy_flags())) return rc;
-            if ((rc = copy_results())) return rc;
+        bool handed_out = false;        // (tight, repaired) the lists are in the caller's arrays already
+        // accounting (tools/probe_candidate_path.py, option "count_candidates"): how many candidates the scan appended for a batch
+        auto appended = [&](const Batch& b, uint64_t& sum) -> int {
+            std::vector<uint32_t> hc((size_t)b.nq_pad * isk::CNT_STRIDE);
+            HIPOK(hipMemcpyAsync(hc.data(), h->d_cnt.p, hc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
             HIPOK(hipStreamSynchronize(h->stream));
+            for (uint32_t i = 0; i < b.nq; ++i) sum += hc[(size_t)i * isk::CNT_STRIDE];
+            return 0;
+        };
+        // tight: the queries in `short_q` (positions in this batch) alone, as a range-limited search under the whole hint -- which
+        // neither reads nor updates a hint.  `ok`: each of them holds k rows now and no list overflowed; their lists are spliced in.
+        auto repair = [&](const std::vector<uint32_t>& short_q, bool& ok) -> int {
+            int rr;
+            // The main pass's lists leave first: the repair reuses p_block, d_block and d_cnt (as pass 3a of isccsearch_search_many
+            // hands every deferred result out before pass 3b runs)
+            unpack_records(p_rec, p_cnt, m, k, t.key_words, &order[pos], out.keys, out.hamming, out.prefix_bits, out.count);
+            uint64_t cand = 0;
+            if (h->opt.count_candidates && (rr = appended(batch, cand))) return rr;
+            const uint32_t ns = (uint32_t)short_q.size();
+            std::vector<uint64_t> rq((size_t)ns * t.max_words);
+            std::vector<uint32_t> dest(ns);
+            for (uint32_t j = 0; j < ns; ++j) {
+                memcpy(&rq[(size_t)j * t.max_words], &hq[(size_t)short_q[j] * t.max_words], (size_t)t.max_words * 8);
+                dest[j] = order[pos + short_q[j]];
+            }
+            // its block {records [ns][k] | counts [ns] | flags} is smaller than the batch's: it fits both mirrors as they are
+            const size_t r_rec_bytes = (size_t)ns * k * sizeof(isk::Record);
+            const bool r_direct = r_rec_bytes + ((size_t)ns + flag_slots_for(ns)) * sizeof(uint32_t) <= DIRECT_RESULT_BYTES;
+            unsigned char* const r_base = r_direct ? h->p_block.p : h->d_block.p;
+            uint32_t* const rd_cnt = reinterpret_cast<uint32_t*>(r_base + r_rec_bytes);
+            const uint32_t* const rp_cnt = reinterpret_cast<const uint32_t*>(h->p_block.p + r_rec_bytes);
+            Batch rb(h, t, ns, len, k, reinterpret_cast<isk::Record*>(r_base), rd_cnt);
+            rb.radius = tau;
+            rb.on_matrix_cores = true;
+            rb.d_flags = rd_cnt + ns;
+            rb.h_flags = rp_cnt + ns;
+            if ((rr = rb.begin(rq.data()))) return rr;
+            if (!r_direct) HIPOK(hipMemcpyAsync(h->p_block.p, h->d_block.p, r_rec_bytes + ((size_t)ns + rb.flag_words()) * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+            HIPOK(hipStreamSynchronize(h->stream));
+            if (h->opt.count_candidates && (rr = appended(rb, cand))) return rr;
+            ok = rb.complete(rp_cnt, spec_seg->n);
+            if (!ok) return 0;          // (the ordinary pass answers the whole batch again, and is what gets counted)
+            unpack_records(p_rec, rp_cnt, ns, k, t.key_words, dest.data(), out.keys, out.hamming, out.prefix_bits, out.count);
+            handed_out = true;
+            h->stats.candidates += cand;
+            h->stats.spec_repairs += ns;
+            return 0;
+        };
+        if (spec != Spec::none) {
+            auto settle = [&]() -> int {
+                int rs;
+                if ((rs = batch.merge())) return rs;
+                if ((rs = batch.copy_flags())) return rs;
+                if ((rs = copy_results())) return rs;
+                HIPOK(hipStreamSynchronize(h->stream));
+                return 0;
+            };
+            if ((rc = settle())) return rc;
+            if (spec == Spec::tight) {
+                std::vector<uint32_t> short_q;          // (hintable: k <= rows, so a query is short of k)
+                for (uint32_t i = 0; i < m; ++i) if (p_cnt[i] < k) short_q.push_back(i);
+                if (batch.any_flag()) spec_ok = false;
+                else if (short_q.empty()) spec_ok = true;
+                else if (short_q.size() <= RADIUS_BATCH_MAX_REPAIRS) { if ((rc = repair(short_q, spec_ok))) return rc; }
+                else {
+                    // too many for one small pass: the hinted single pass for the whole batch, whose own check gives the verdict
+                    batch.radius = radius; batch.self_hint = tau;
+                    if ((rc = batch.begin(hq.data()))) return rc;
+                    if ((rc = settle())) return rc;
+                    spec_ok = batch.used_hint && batch.complete(p_cnt, spec_seg->n);
+                }
+            }
             // (ratio: a row outside a radius lies beyond floor(ratio x bits) + 1 bits, strictly farther than the worst k-th NPHD)
-            spec_ok = spec == Spec::ratio ? batch.complete(p_cnt, k) && worst_ratio() <= batch.radius_ratio : batch.complete(p_cnt, spec_seg->n);
+            else spec_ok = spec == Spec::ratio ? batch.complete(p_cnt, k) && worst_ratio() <= batch.radius_ratio : batch.complete(p_cnt, spec_seg->n);
             if (spec_ok) h->stats.spec_hits += 1;
             else {
                 h->stats.spec_misses += 1;
@@ -188,15 +270,20 @@ static int search_locked(isccsearch_handle* h, uint32_t table, uint32_t nq, cons
         }
         if (!spec_ok && (rc = batch.finish(hq.data(), copy_results))) return rc;
         if (h->opt.count_candidates && batch.jobs.size() == 1) {
-            // accounting (tools/probe_candidate_path.py, option "count_candidates"): how many candidates the scan appended for this batch
-            std::vector<uint32_t> hc((size_t)batch.nq_pad * isk::CNT_STRIDE);
-            HIPOK(hipMemcpyAsync(hc.data(), h->d_cnt.p, hc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-            HIPOK(hipStreamSynchronize(h->stream));
-            for (uint32_t i = 0; i < m; ++i) h->stats.candidates += hc[(size_t)i * isk::CNT_STRIDE];
+            // (a repaired step has counted both of its passes before the second reused the counters)
+            if (!handed_out && (rc = appended(batch, h->stats.candidates))) return rc;
             h->stats.candidate_batches += 1;
         }
         // where this batch's lists ended: the next batch of its class starts there (+ the hint's margin)
-        if (hintable && !batch.jobs.empty()) record_hint(spec_seg->hint(m, len), spec_ok, m, k, p_cnt, p_rec, sink ? p_kth : nullptr);
+        if (handed_out) {
+            // (the pinned block holds the repair's lists by now: the batch's worst k-th distance, repaired queries included, is in the caller's arrays)
+            uint32_t worst = 0;
+            for (uint32_t i = 0; i < m; ++i) {
+                const size_t dq = order[pos + i];
+                if (out.count[dq]) worst = std::max(worst, out.hamming[dq * k + out.count[dq] - 1]);
+            }
+            record_hint(spec_seg->hint(m, len), spec_ok, k, worst);
+        } else if (hintable && !batch.jobs.empty()) record_hint(spec_seg->hint(m, len), spec_ok, m, k, p_cnt, p_rec, sink ? p_kth : nullptr);
         if (mhintable) {
             const double worst = worst_ratio();
             if (spec_ok) t.mhint(m, len).hit(worst);
@@ -223,7 +310,7 @@ static int search_locked(isccsearch_handle* h, uint32_t table, uint32_t nq, cons
             else for (uint32_t i = 0; i < m; ++i) out_freq[order[pos + i]] = p_cnt[i];
             if (out_collisions)
                 for (uint32_t i = 0; i < m; ++i) out_collisions[order[pos + i]] = batch.jobs.empty() ? 0 : p_cnt[m + flag_slots + i];
-        } else {
+        } else if (!handed_out) {
             unpack_records(p_rec, p_cnt, m, k, t.key_words, &order[pos], out.keys, out.hamming, out.prefix_bits, out.count);
         }
         pos = end;
