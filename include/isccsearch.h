@@ -373,6 +373,29 @@ int isccsearch_join_between(isccsearch_handle* h, uint32_t table_a, uint32_t tab
                             uint64_t* out_keys_a, uint64_t* out_keys_b,
                             uint32_t* out_hamming, uint16_t* out_prefix_bits, uint64_t* out_total);
 
+/* Connected components under the pairs of isccsearch_join_within, without the pairs: max_hamming, the prefix rule, the masking
+ * and the launches (one per pair of segments, la <= lb, the larger segment held) are those of isccsearch_join_within, but a row
+ * pair within its threshold is not written -- the labels of its two rows are united in a union-find array on the device.
+ * Memory: 4 bytes per label and 4 bytes per row, whatever the number of pairs; the call has no capacity and no -ENOSPC.
+ *   live_keys[n_live]    strictly ascending: the rows that take part.  A row of key live_keys[i] has label live_labels[i]
+ *                        (< n_labels; several keys may share a label).  A row whose key is not listed has no label: it is
+ *                        compared, but never linked and never counted.  A listed key the table does not hold does nothing.
+ *                        Both arrays may be NULL only when n_live is 0.
+ *   parent[n_labels]     in/out.  On entry a forest with parent[i] <= i for every i (the identity: no links yet).  On exit
+ *                        FLAT: parent[i] is the smallest label of i's component under the links of the input forest plus one
+ *                        link per qualifying row pair.  The output of one call is a valid input of the next (another table,
+ *                        other thresholds): the components then are those of all the calls' pairs together.
+ *   *out_links           the row pairs within their threshold whose two rows both have labels (for live_keys = all keys of the
+ *                        table: the *out_total of isccsearch_join_within).
+ * -EINVAL, each naming the offending index, all checked on the host before anything is launched, `parent` left unchanged:
+ * a NULL argument; a table with key_words != 1; n_labels = 0 or 2^32 - 1 (the value that means "no label"); live_keys not
+ * strictly ascending; a label >= n_labels; parent[i] > i (the bound of every loop of the device code: nothing runs on an
+ * array that fails it).
+ * No reference counterpart (the reference has no index-wide join and no grouping of its assets). */
+int isccsearch_join_components(isccsearch_handle* h, uint32_t table, const int16_t* max_hamming /* [33] */,
+                               uint64_t n_live, const uint64_t* live_keys, const uint32_t* live_labels,
+                               uint32_t n_labels, uint32_t* parent /* in/out [n_labels] */, uint64_t* out_links);
+
 /* Multi-GPU building blocks (row-range shards, one process per GPU).
  * search_device: same search, results left in caller-provided DEVICE memory
  *   d_records[nq*k] (isccsearch_record), d_counts[nq]; queries must share one byte length.

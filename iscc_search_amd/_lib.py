@@ -30,7 +30,7 @@ EXPORTS = (
     "isccsearch_segments", "isccsearch_export", "isccsearch_add_columns",
     "isccsearch_add_synthetic", "isccsearch_search", "isccsearch_search_within", "isccsearch_search_many", "isccsearch_doc_freq", "isccsearch_doc_freq_counted", "isccsearch_get_freq",
     "isccsearch_simprint_score", "isccsearch_simprint_score_many", "isccsearch_simprint_exact", "isccsearch_match_assets",
-    "isccsearch_join_within", "isccsearch_join_between",
+    "isccsearch_join_within", "isccsearch_join_between", "isccsearch_join_components",
     "isccsearch_search_device", "isccsearch_search_within_device", "isccsearch_merge_device",
     "isccsearch_search_device_async", "isccsearch_merge_device_after", "isccsearch_merge_many_after", "isccsearch_stream",
 )
@@ -192,6 +192,7 @@ def load_library():
                                         u64p, vp, u32p, u8p, vp, u32p]),
         "isccsearch_join_within": (i, [vp, u32, vp, u64, u64p, u64p, u32p, u16p, u64p]),
         "isccsearch_join_between": (i, [vp, u32, u32, vp, u64, u64p, u64p, u32p, u16p, u64p]),
+        "isccsearch_join_components": (i, [vp, u32, vp, u64, u64p, u32p, u32, u32p, u64p]),
         "isccsearch_search_device": (i, [vp, u32, u32, u64p, u8p, u32, vp, vp]),
         "isccsearch_search_within_device": (i, [vp, u32, u32, u64p, u8p, u32, u32, vp, vp]),
         "isccsearch_merge_device": (i, [vp, u32, u32, u32, i, vp, vp, u64, u64, u64p, u32p, u16p, u32p]),

@@ -357,6 +357,9 @@ struct isccsearch_handle {
     DevBuf<uint32_t> d_join_ham;
     DevBuf<uint16_t> d_join_pb;
     DevBuf<isk::JoinEmit> d_join_emit;             // one descriptor per launch
+    // isccsearch_join_components: the caller's live keys and their labels, a label per row (segment by segment), the union-find array
+    DevBuf<uint64_t> d_join_live_keys;
+    DevBuf<uint32_t> d_join_live_labels, d_join_row_labels, d_join_parent;
     size_t am_lds_allowed = 0;                   // dynamic LDS the scoring kernel was allowed on this handle's device
     // asynchronous device searches: "results ready" for the consumer stream, "query upload done" for the pinned staging
     hipEvent_t ev_done = nullptr, ev_staged = nullptr, ev_producer = nullptr;

@@ -18,6 +18,10 @@
 // join_scan_kernel<W, MASK, true>: the same scan over segments of two tables.  Only the emit path differs: every (row_a, row_b)
 //   is a pair, and the keys are not ordered -- the key of the side in SGPRs goes to the output column of the table it came
 //   from (JoinEmit::sgpr_side_is_b).  A template parameter, so that the self-join's code does not change.
+// join_scan_kernel<W, MASK, false, true> (LINK, isccsearch_join_components): the self-join's scan again, and again only the emit
+//   path differs: it keeps the pair test and drops the prefix scan, the slots, the key gathers and the stores -- per pair it loads
+//   the two rows' labels (JoinEmit::labels_a / labels_b; UF_NONE: the row takes no part), unites them in JoinEmit::parent
+//   (uf_union of unionfind.hip.h) and counts the pair; one atomic per wave adds the count to JoinEmit::total.
 // Slabs are read up to the next multiple of the slab size: column capacities are multiples of ROW_ALIGN (2 048 rows), which
 // every slab size divides, so those reads stay inside the allocation (rows past n are dropped in the emit path).
 #pragma once
@@ -25,6 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "unionfind.hip.h"
 #include "valu_scan_kernel.hip.h"
 
 namespace isk {
@@ -44,6 +49,11 @@ struct JoinEmit {
     uint32_t prefix_bits, kw;
     uint32_t sgpr_side_is_b;      // cross join: the side in SGPRs (mfma_join_kernel: the side held in LDS) is table B, its keys go to
                                   // out_keys_b (else to out_keys_a)
+    // the LINK form (isccsearch_join_components): a label per row of either side (UF_NONE: none) and the union-find array over
+    // the labels; `total` counts the pairs whose two rows have labels, and the outputs above are not used
+    const uint32_t* labels_a;
+    const uint32_t* labels_b;
+    uint32_t* parent;
 };
 struct JoinParams {
     const uint64_t* col_a[4];     // side A: rows held in SGPRs, TQ per block
@@ -64,8 +74,24 @@ template <int W> struct JoinCfg {
 template <int W> constexpr uint32_t join_rows_per_block() { return JoinCfg<W>::TQ; }
 template <int W> constexpr uint32_t join_slab_rows() { return JoinCfg<W>::SLAB; }
 
-template <int W, bool MASK, bool CROSS = false>
+// the sum of c over the wave's lanes, in every lane
+__device__ __forceinline__ uint32_t wave_sum(uint32_t c) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) c += (uint32_t)__shfl_xor((int)c, d, 64);
+    return c;
+}
+
+// LINK form of both emit paths, per pair (held / SGPR-side row i, streamed row j): unite the two rows' labels; 1 if both have one
+__device__ __forceinline__ uint32_t link_pair(const JoinEmit& e, uint64_t i, uint64_t j) {
+    const uint32_t la = e.labels_a[i], lb = e.labels_b[j];
+    if (la == UF_NONE || lb == UF_NONE) return 0u;
+    uf_union(e.parent, la, lb);
+    return 1u;
+}
+
+template <int W, bool MASK, bool CROSS = false, bool LINK = false>
 __global__ __launch_bounds__(BLOCK) void join_scan_kernel(const JoinParams p) {
+    static_assert(!(LINK && CROSS), "components are those of one table");
     constexpr int TQ = JoinCfg<W>::TQ, U = JoinCfg<W>::U;
     constexpr uint32_t SLAB = JoinCfg<W>::SLAB;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -135,7 +161,16 @@ __global__ __launch_bounds__(BLOCK) void join_scan_kernel(const JoinParams p) {
 #pragma unroll
             for (int u = 0; u < U; ++u)
 #pragma unroll
-                for (int rr = 0; rr < 2; ++rr) c += is_pair(i, base + u * 128 + rr, dist(r, u, rr, al, ah)) ? 1u : 0u;
+                for (int rr = 0; rr < 2; ++rr) {
+                    const bool pair = is_pair(i, base + u * 128 + rr, dist(r, u, rr, al, ah));
+                    if (LINK) c += pair ? link_pair(e, i, base + u * 128 + rr) : 0u;
+                    else c += pair ? 1u : 0u;
+                }
+        }
+        if (LINK) {                                // one pass: the labelled pairs are united as they are counted, nothing is written
+            const uint32_t linked = wave_sum(c);
+            if (linked != 0 && lane == 0) atomicAdd(e.total, (unsigned long long)linked);
+            return;
         }
         // wave-inclusive prefix of the counts; lane 63 holds the wave's total
         uint32_t incl = c;

@@ -1,20 +1,22 @@
 // join_api.hip.h -- isccsearch_join_within and isccsearch_join_between: the self-join of a table and the cross join of two
-// tables by the XOR + popcount kernel of join.hip.h or, for launches over enough rows, its matrix-core form (mfma_join_kernel.hip.h).
+// tables by the XOR + popcount kernel of join.hip.h or, for launches over enough rows, its matrix-core form (mfma_join_kernel.hip.h);
+// and isccsearch_join_components: the self-join's launches in their LINK form, whose pairs are united in a union-find array
+// (unionfind.hip.h) instead of written.
 // Needs the store of isccsearch.hip (Segment, Table; get_table of store.hip.h) and its scratch buffers.
 namespace {
 // one launch of the join kernel (join.hip.h)
-template <int W, bool CROSS>
+template <int W, bool CROSS, bool LINK>
 void launch_join(const isk::JoinParams& jp, bool mask, uint64_t blocks, hipStream_t stream) {
-    if (mask) hipLaunchKernelGGL((isk::join_scan_kernel<W, true, CROSS>), dim3((uint32_t)blocks), dim3(isk::BLOCK), 0, stream, jp);
-    else hipLaunchKernelGGL((isk::join_scan_kernel<W, false, CROSS>), dim3((uint32_t)blocks), dim3(isk::BLOCK), 0, stream, jp);
+    if (mask) hipLaunchKernelGGL((isk::join_scan_kernel<W, true, CROSS, LINK>), dim3((uint32_t)blocks), dim3(isk::BLOCK), 0, stream, jp);
+    else hipLaunchKernelGGL((isk::join_scan_kernel<W, false, CROSS, LINK>), dim3((uint32_t)blocks), dim3(isk::BLOCK), 0, stream, jp);
 }
-template <bool CROSS>
+template <bool CROSS, bool LINK = false>
 void launch_join(uint32_t W, const isk::JoinParams& jp, bool mask, uint64_t blocks, hipStream_t stream) {
     switch (W) {
-        case 1: launch_join<1, CROSS>(jp, mask, blocks, stream); break;
-        case 2: launch_join<2, CROSS>(jp, mask, blocks, stream); break;
-        case 3: launch_join<3, CROSS>(jp, mask, blocks, stream); break;
-        default: launch_join<4, CROSS>(jp, mask, blocks, stream); break;
+        case 1: launch_join<1, CROSS, LINK>(jp, mask, blocks, stream); break;
+        case 2: launch_join<2, CROSS, LINK>(jp, mask, blocks, stream); break;
+        case 3: launch_join<3, CROSS, LINK>(jp, mask, blocks, stream); break;
+        default: launch_join<4, CROSS, LINK>(jp, mask, blocks, stream); break;
     }
 }
 constexpr uint32_t join_rows_per_block(uint32_t W) {
@@ -29,6 +31,7 @@ struct JoinPlan {
     std::vector<Launch> launches;
     std::vector<isk::JoinEmit> emits;
     bool cross = false;
+    bool link = false;     // isccsearch_join_components: the LINK form of either kernel (JoinEmit::labels_a, labels_b, parent are set)
     uint32_t KW = 1;
     uint64_t capacity = 0, cap_alloc = 1;
 };
@@ -109,11 +112,8 @@ int join_add(isccsearch_handle* h, JoinPlan& plan, Segment& A, Segment& B, uint3
     return 0;
 }
 
-// The shared tail of both joins: the launches, the total read back, the pairs copied to the host and sorted by (key_a, key_b).
-int join_finish(isccsearch_handle* h, JoinPlan& plan, uint64_t* out_keys_a, uint64_t* out_keys_b, uint32_t* out_hamming,
-                uint16_t* out_prefix_bits, uint64_t* out_total) {
-    const uint32_t KW = plan.KW;
-    const uint64_t capacity = plan.capacity, cap_alloc = plan.cap_alloc;
+// The launches of one call, in order on the handle's stream.
+int join_run(isccsearch_handle* h, JoinPlan& plan) {
     if (!plan.launches.empty()) {
         int rc;
         if ((rc = h->d_join_emit.ensure(plan.emits.size()))) return rc;
@@ -127,7 +127,7 @@ int join_finish(isccsearch_handle* h, JoinPlan& plan, uint64_t* out_keys_a, uint
                 for (uint64_t c = 0; c < L.chunks; c += isk::MFMA_JOIN_MAX_CHUNKS) {
                     L.mp.chunk_base = c;
                     const uint32_t chunks = (uint32_t)std::min<uint64_t>(L.chunks - c, isk::MFMA_JOIN_MAX_CHUNKS);
-                    const int lrc = isk::launch_mfma_join((int)L.W, plan.cross, blocks_x, chunks, L.groups, h->stream, L.mp);
+                    const int lrc = isk::launch_mfma_join((int)L.W, plan.cross, blocks_x, chunks, L.groups, h->stream, L.mp, plan.link);
                     if (lrc) return fail(-EINVAL, "the matrix-core join does not take chunks of %u groups of %u words", L.groups, L.W);
                     HIPOK(hipGetLastError());
                     h->stats.join_launches += 1;
@@ -135,16 +135,34 @@ int join_finish(isccsearch_handle* h, JoinPlan& plan, uint64_t* out_keys_a, uint
                 }
                 continue;
             }
-            if (plan.cross) launch_join<true>(L.W, L.jp, L.mask, L.blocks, h->stream);
+            if (plan.link) launch_join<false, true>(L.W, L.jp, L.mask, L.blocks, h->stream);
+            else if (plan.cross) launch_join<true>(L.W, L.jp, L.mask, L.blocks, h->stream);
             else launch_join<false>(L.W, L.jp, L.mask, L.blocks, h->stream);
             HIPOK(hipGetLastError());
             h->stats.join_launches += 1;
         }
     }
+    return 0;
+}
+
+// The call's one synchronisation: the total read back behind everything the call put on the stream.
+int join_total(isccsearch_handle* h, uint64_t* out_total) {
     uint64_t total = 0;
     HIPOK(hipMemcpyAsync(&total, h->d_join_total.p, 8, hipMemcpyDeviceToHost, h->stream));
     HIPOK(hipStreamSynchronize(h->stream));
     *out_total = total;
+    return 0;
+}
+
+// The shared tail of the two pair joins: the launches, the total read back, the pairs copied to the host and sorted by (key_a, key_b).
+int join_finish(isccsearch_handle* h, JoinPlan& plan, uint64_t* out_keys_a, uint64_t* out_keys_b, uint32_t* out_hamming,
+                uint16_t* out_prefix_bits, uint64_t* out_total) {
+    const uint32_t KW = plan.KW;
+    const uint64_t capacity = plan.capacity, cap_alloc = plan.cap_alloc;
+    int rc;
+    if ((rc = join_run(h, plan))) return rc;
+    if ((rc = join_total(h, out_total))) return rc;
+    const uint64_t total = *out_total;
     if (total > capacity)
         return fail(-ENOSPC, "%llu pairs do not fit the capacity of %llu", (unsigned long long)total, (unsigned long long)capacity);
     if (!total) return 0;
@@ -241,4 +259,83 @@ extern "C" int isccsearch_join_between(isccsearch_handle* h, uint32_t table_a, u
         }
     }
     return join_finish(h, plan, out_keys_a, out_keys_b, out_hamming, out_prefix_bits, out_total);
+}
+
+// The launches of isccsearch_join_within in their LINK form (join_scan_kernel<W, MASK, false, true> / mfma_join_kernel<W, false, true>)
+// between label_rows_kernel (one per segment: the host never sees the table's keys) and flatten_kernel, all on one stream; then
+// `parent` and the links come back behind one synchronisation.  Everything the device code relies on -- labels < n_labels,
+// parent[i] <= i -- is checked on the host before anything is launched.
+extern "C" int isccsearch_join_components(isccsearch_handle* h, uint32_t table, const int16_t* max_hamming, uint64_t n_live,
+                               const uint64_t* live_keys, const uint32_t* live_labels, uint32_t n_labels, uint32_t* parent,
+                               uint64_t* out_links) {
+    if (!h) return fail(-EINVAL, "handle is NULL");
+    if (!max_hamming || !parent || !out_links || (n_live && (!live_keys || !live_labels))) return fail(-EINVAL, "NULL argument");
+    *out_links = 0;
+    if (n_labels == 0 || n_labels == isk::UF_NONE) return fail(-EINVAL, "n_labels must be in 1 .. 2^32 - 2, got %u", n_labels);
+    for (uint64_t i = 0; i < n_live; ++i) {
+        if (i && live_keys[i] <= live_keys[i - 1])
+            return fail(-EINVAL, "live_keys must be strictly ascending: live_keys[%llu] <= live_keys[%llu]", (unsigned long long)i, (unsigned long long)(i - 1));
+        if (live_labels[i] >= n_labels)
+            return fail(-EINVAL, "live_labels[%llu] = %u is not below n_labels = %u", (unsigned long long)i, live_labels[i], n_labels);
+    }
+    for (uint32_t i = 0; i < n_labels; ++i)
+        if (parent[i] > i) return fail(-EINVAL, "parent[%u] = %u is above its index: the input forest needs parent[i] <= i", i, parent[i]);
+    std::lock_guard<std::mutex> lk(h->mu);
+    Table* tp;
+    int rc;
+    if ((rc = get_table(h, table, tp))) return rc;
+    Table& t = *tp;
+    if (t.key_words != 1) return fail(-EINVAL, "join_components needs a table of 64-bit keys (key_words 1), table %u has key_words %d", table, t.key_words);
+    HIPOK(hipSetDevice(h->device));
+    JoinPlan plan;
+    plan.link = true;
+    if ((rc = join_begin(h, plan, false, 1, 0))) return rc;
+    if ((rc = h->d_join_live_keys.ensure(std::max<uint64_t>(n_live, 1)))) return rc;
+    if ((rc = h->d_join_live_labels.ensure(std::max<uint64_t>(n_live, 1)))) return rc;
+    uint64_t all_rows = 0;
+    for (uint32_t l = 1; l <= ISCCSEARCH_MAX_BYTES; ++l) all_rows += t.seg[l].n;
+    if ((rc = h->d_join_row_labels.ensure(std::max<uint64_t>(all_rows, 1)))) return rc;
+    if ((rc = h->d_join_parent.ensure(n_labels))) return rc;
+    if (n_live) {
+        HIPOK(hipMemcpyAsync(h->d_join_live_keys.p, live_keys, n_live * 8, hipMemcpyHostToDevice, h->stream));
+        HIPOK(hipMemcpyAsync(h->d_join_live_labels.p, live_labels, n_live * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    HIPOK(hipMemcpyAsync(h->d_join_parent.p, parent, (size_t)n_labels * 4, hipMemcpyHostToDevice, h->stream));
+    // a label per row, segment by segment
+    uint32_t* row_labels[ISCCSEARCH_MAX_BYTES + 1] = {};
+    uint64_t rows = 0;
+    for (uint32_t l = 1; l <= ISCCSEARCH_MAX_BYTES; ++l) {
+        const Segment& s = t.seg[l];
+        if (!s.n) continue;
+        row_labels[l] = h->d_join_row_labels.p + rows;
+        rows += s.n;
+        isk::LabelParams lp{s.keys, h->d_join_live_keys.p, h->d_join_live_labels.p, row_labels[l], s.n, n_live};
+        const uint32_t blocks = (uint32_t)std::min<uint64_t>((s.n + isk::BLOCK - 1) / isk::BLOCK, 1u << 16);
+        hipLaunchKernelGGL(isk::label_rows_kernel, dim3(blocks), dim3(isk::BLOCK), 0, h->stream, lp);
+        HIPOK(hipGetLastError());
+    }
+    // the launches of isccsearch_join_within
+    for (uint32_t la = 1; la <= ISCCSEARCH_MAX_BYTES; ++la) {
+        if (!t.seg[la].n || max_hamming[la] < 0) continue;
+        for (uint32_t lb = la; lb <= ISCCSEARCH_MAX_BYTES; ++lb) {
+            const bool same = la == lb;
+            if (!t.seg[lb].n || (same && t.seg[la].n < 2)) continue;
+            const uint32_t a_len = t.seg[lb].n > t.seg[la].n ? lb : la, b_len = a_len == la ? lb : la;
+            if ((rc = join_add(h, plan, t.seg[a_len], t.seg[b_len], la, max_hamming[la], same, false))) return rc;
+            isk::JoinEmit& e = plan.emits.back();
+            e.labels_a = row_labels[a_len];
+            e.labels_b = row_labels[b_len];
+            e.parent = h->d_join_parent.p;
+        }
+    }
+    if ((rc = join_run(h, plan))) return rc;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n_labels + isk::BLOCK - 1) / isk::BLOCK, 1u << 16);
+    hipLaunchKernelGGL(isk::flatten_kernel, dim3(blocks), dim3(isk::BLOCK), 0, h->stream, h->d_join_parent.p, n_labels);
+    HIPOK(hipGetLastError());
+    // the array goes to a copy first: `parent` changes only once the whole call has succeeded
+    std::vector<uint32_t> flat(n_labels);
+    HIPOK(hipMemcpyAsync(flat.data(), h->d_join_parent.p, (size_t)n_labels * 4, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = join_total(h, out_links))) return rc;
+    memcpy(parent, flat.data(), (size_t)n_labels * 4);
+    return 0;
 }

@@ -17,6 +17,8 @@
 //   ONE returned atomic on JoinEmit::total for the walk and writes (key_a, key_b, hamming, prefix bits) with vector stores --
 //   the self-join orders the keys, the cross join routes the held side's key by JoinEmit::sgpr_side_is_b (the held side takes
 //   the part the SGPR side has in join_scan_kernel).  Pairs past `capacity` are counted and not written.
+//   LINK (mfma_join_kernel<W, false, true>, isccsearch_join_components): the ring is walked ONCE -- per pair the two rows' labels are
+//   loaded and united (link_pair of join.hip.h), the labelled pairs counted, one atomic per walk; nothing is written.
 #pragma once
 
 #include "join.hip.h"
@@ -26,8 +28,9 @@
 namespace isk {
 
 // LDS image of a chunk: B fragments [groups][W][64] v4i | thr[groups * 32] (float) | popc[groups * 32] | the waves' rings
-template <int W, bool CROSS>
+template <int W, bool CROSS, bool LINK = false>
 __global__ __launch_bounds__(MBLOCK, mfma_min_waves<W>()) void mfma_join_kernel(const MfmaJoinParams p, const uint32_t groups) {
+    static_assert(!(LINK && CROSS), "components are those of one table");
     constexpr int MT = 2;       // row tiles (32 rows) per wave and step
     constexpr uint32_t WAVES = MBLOCK / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -112,6 +115,18 @@ __global__ __launch_bounds__(MBLOCK, mfma_min_waves<W>()) void mfma_join_kernel(
             return v <= thr && j <= last_row && (CROSS || !p.same || j > i);
         };
         uint32_t c = 0;
+        if (LINK) {                                // one walk: the labelled pairs are united as they are counted, nothing is written
+            const JoinEmit& e = *p.e;
+            for (uint32_t en = 0; en < rcount; en += 2) {
+                uint64_t i, j;
+                uint32_t hd;
+                if (pair_at(en + sub, i, j, hd)) c += link_pair(e, i, j);
+            }
+            const uint32_t linked = wave_sum(c);
+            if (linked != 0 && lane == 0) atomicAdd(e.total, (unsigned long long)linked);
+            rcount = 0;
+            return;
+        }
         for (uint32_t en = 0; en < rcount; en += 2) {
             uint64_t i, j;
             uint32_t hd;

@@ -139,22 +139,23 @@ int launch_mfma_scan(int W, int mode, bool pack, uint32_t blocks_x, uint32_t gro
 }
 
 template <int W>
-static void launch_join_w(bool cross, dim3 grid, size_t lds, hipStream_t st, const MfmaJoinParams& p, uint32_t groups) {
-    if (cross) hipLaunchKernelGGL((mfma_join_kernel<W, true>), grid, dim3(MBLOCK), lds, st, p, groups);
+static void launch_join_w(bool cross, bool link, dim3 grid, size_t lds, hipStream_t st, const MfmaJoinParams& p, uint32_t groups) {
+    if (link) hipLaunchKernelGGL((mfma_join_kernel<W, false, true>), grid, dim3(MBLOCK), lds, st, p, groups);
+    else if (cross) hipLaunchKernelGGL((mfma_join_kernel<W, true>), grid, dim3(MBLOCK), lds, st, p, groups);
     else hipLaunchKernelGGL((mfma_join_kernel<W, false>), grid, dim3(MBLOCK), lds, st, p, groups);
 }
 
-int launch_mfma_join(int W, bool cross, uint32_t blocks_x, uint32_t chunks, uint32_t groups, hipStream_t st, const MfmaJoinParams& p) {
+int launch_mfma_join(int W, bool cross, uint32_t blocks_x, uint32_t chunks, uint32_t groups, hipStream_t st, const MfmaJoinParams& p, bool link) {
     static_assert(MFMA_JOIN_WAVES == MBLOCK / 64, "the grid rule counts the kernel's waves");
     const size_t lds = mfma_lds_bytes(W, groups);
-    // the group pipeline walks pairs of groups; grid.y is 16 bits
-    if (lds > (size_t)MFMA_MAX_LDS || groups < 2 || (groups & 1) || !blocks_x || !chunks || chunks > MFMA_JOIN_MAX_CHUNKS) return (int)hipErrorInvalidValue;
+    // the group pipeline walks pairs of groups; grid.y is 16 bits; the LINK form is the self-join's only
+    if (lds > (size_t)MFMA_MAX_LDS || groups < 2 || (groups & 1) || !blocks_x || !chunks || chunks > MFMA_JOIN_MAX_CHUNKS || (link && cross)) return (int)hipErrorInvalidValue;
     const dim3 grid(blocks_x, chunks);
     switch (W) {
-        case 1: launch_join_w<1>(cross, grid, lds, st, p, groups); break;
-        case 2: launch_join_w<2>(cross, grid, lds, st, p, groups); break;
-        case 3: launch_join_w<3>(cross, grid, lds, st, p, groups); break;
-        case 4: launch_join_w<4>(cross, grid, lds, st, p, groups); break;
+        case 1: launch_join_w<1>(cross, link, grid, lds, st, p, groups); break;
+        case 2: launch_join_w<2>(cross, link, grid, lds, st, p, groups); break;
+        case 3: launch_join_w<3>(cross, link, grid, lds, st, p, groups); break;
+        case 4: launch_join_w<4>(cross, link, grid, lds, st, p, groups); break;
         default: return (int)hipErrorInvalidValue;
     }
     return 0;

@@ -1,10 +1,12 @@
-// table_kernels.hip.h -- upkeep of the column store: synthetic fill, row moves, row gathers, the ingest split and mask, u32 gathers.
+// table_kernels.hip.h -- upkeep of the column store: synthetic fill, row moves, row gathers, the ingest split and mask, u32 gathers;
+// the two kernels around the joins of isccsearch_join_components (row labels before them, the flatten step after them).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "scan_params.hip.h"
+#include "unionfind.hip.h"
 
 namespace isk {
 
@@ -93,6 +95,34 @@ __global__ __launch_bounds__(BLOCK) void mask_column_kernel(uint64_t* col, uint6
 // out[i] = src[rows[i]]  (document-frequency column lookups)
 __global__ __launch_bounds__(BLOCK) void gather_u32_kernel(const uint32_t* src, const uint64_t* rows, uint32_t* out, uint64_t n) {
     for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += (uint64_t)gridDim.x * BLOCK) out[i] = src[rows[i]];
+}
+
+// isccsearch_join_components: out[i] = the label of row i of a segment -- live_labels[r] where live_keys[r] (strictly ascending) is
+// the row's key, 0xFFFFFFFF (no label) where the key is not listed.  64-bit keys.
+struct LabelParams {
+    const uint64_t* keys;          // the segment's key column [n]
+    const uint64_t* live_keys;     // [n_live]
+    const uint32_t* live_labels;   // [n_live]
+    uint32_t* out;                 // [n]
+    uint64_t n, n_live;
+};
+__global__ __launch_bounds__(BLOCK) void label_rows_kernel(const LabelParams p) {
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < p.n; i += (uint64_t)gridDim.x * BLOCK) {
+        const uint64_t key = p.keys[i];
+        uint64_t lo = 0, hi = p.n_live;            // the first listed key >= key lies in [lo, hi]
+        while (lo < hi) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if (p.live_keys[mid] < key) lo = mid + 1;
+            else hi = mid;
+        }
+        p.out[i] = lo < p.n_live && p.live_keys[lo] == key ? p.live_labels[lo] : UF_NONE;
+    }
+}
+
+// after the last join launch of isccsearch_join_components: every label's entry becomes its component's smallest label
+// (uf_flatten of unionfind.hip.h; the caller has checked parent[i] <= i, which bounds every walk)
+__global__ __launch_bounds__(BLOCK) void flatten_kernel(uint32_t* parent, uint32_t n_labels) {
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n_labels; i += (uint64_t)gridDim.x * BLOCK) uf_flatten(parent, (uint32_t)i);
 }
 
 }  // namespace isk

@@ -391,6 +391,35 @@ class HipTable(TableChecks):
             raise ValueError("join_between needs two tables of one engine: the other table belongs to another engine")
         return self._join("isccsearch_join_between", (self.id, other.id), max_hamming_by_prefix, max_pairs)
 
+    def join_components(self, max_hamming_by_prefix, live_keys, live_labels, parent):
+        # type: (object, np.ndarray, np.ndarray, np.ndarray) -> int
+        """
+        Connected components under the row pairs of ``join_within(max_hamming_by_prefix, ...)``, without the pairs: the labels of
+        the two rows of every pair are united in ``parent`` on the device (4 bytes per label and per row, whatever the number of
+        pairs).  ``live_keys`` (uint64, strictly ascending) names the rows that take part and ``live_labels`` (uint32, below
+        ``len(parent)``) their labels; a row whose key is not listed is compared but links nothing.  ``parent`` (uint32,
+        C-contiguous, ``parent[i] <= i``; ``np.arange`` for no links yet) is updated IN PLACE to the smallest label of every
+        label's component, so one array can be carried through several tables.  Returns the number of row pairs within their
+        threshold whose two rows have labels.  64-bit keys only.
+        """
+        mh = np.ascontiguousarray(max_hamming_by_prefix, dtype=np.int16)
+        if mh.shape != (_lib.MAX_BYTES + 1,):
+            raise ValueError(f"max_hamming_by_prefix must have {_lib.MAX_BYTES + 1} entries (prefix bytes 0..{_lib.MAX_BYTES})")
+        if self.key_words != 1:
+            raise ValueError("join_components needs a table of 64-bit keys")
+        if not (isinstance(parent, np.ndarray) and parent.dtype == np.uint32 and parent.ndim == 1 and parent.flags.c_contiguous and parent.flags.writeable):
+            raise ValueError("parent must be a writeable C-contiguous uint32 array shaped [n_labels]: it is updated in place")
+        live_keys = np.ascontiguousarray(live_keys, dtype=np.uint64)
+        live_labels = np.ascontiguousarray(live_labels, dtype=np.uint32)
+        if live_keys.ndim != 1 or live_labels.shape != live_keys.shape:
+            raise ValueError("live_keys and live_labels must be shaped [n_live]")
+        links = ctypes.c_uint64()
+        n_live = live_keys.shape[0]
+        _lib.check(self.engine._lib.isccsearch_join_components(
+            self.engine.handle, self.id, _lib.ptr(mh), n_live, _lib.ptr(live_keys) if n_live else None,
+            _lib.ptr(live_labels) if n_live else None, parent.shape[0], _lib.ptr(parent), ctypes.byref(links)))
+        return int(links.value)
+
     def _join(self, symbol, tables, max_hamming_by_prefix, max_pairs):
         # type: (str, tuple, object, int) -> tuple
         """One join call of the library, retried once with exactly the reported total when that did not fit."""

@@ -22,7 +22,7 @@ import numpy as np
 from iscc_search_amd import chunk_match, codec, snapshot, unit_match
 from iscc_search_amd._lib import MAX_K
 from iscc_search_amd.nphd import HipNphdIndex
-from iscc_search_amd.pairs import DuplicatePair, IndexMatch, join_sides
+from iscc_search_amd.pairs import DuplicateGroup, DuplicatePair, IndexMatch, group_side, join_sides
 from iscc_search_amd.schema import IsccAddResult, IsccEntry, IsccGlobalMatch, IsccQuery, IsccSearchResult, Status
 from iscc_search_amd.simprint import HipSimprintIndex, pack_chunk_pointer, unpack_chunk_pointer
 from iscc_search_amd.unit_match import INSTANCE_FIRST_K, UnitMatches, _checked_limit, _is_instance, _unit_map, _unit_max_hamming  # noqa: F401
@@ -308,6 +308,25 @@ class HipIndex:
         side, realm = self._join_side(unit_types)
         return [DuplicatePair(codec.iscc_id_from_int(a, realm), codec.iscc_id_from_int(b, realm), score, types)
                 for a, b, score, types in join_sides("find_duplicates", side, side, self._opts, min_score, max_pairs)]
+
+    def find_duplicate_groups(self, unit_types=None, threshold=None, min_size=2):
+        # type: (Optional[List[str]], Optional[float], int) -> List[DuplicateGroup]
+        """
+        The groups of near-duplicate assets: the connected components of the graph whose vertices are this index's assets and
+        whose edges are exactly the pairs ``find_duplicates(unit_types=unit_types)`` lists on an index whose
+        ``match_threshold_units`` is ``threshold`` (default: this index's own; outside (0, 1]: ValueError) -- one confident unit
+        of a type BOTH assets carry as indexed.  Found without the pairs: every unit table's self-join unites the two assets of
+        a pair in a union-find array on the device (``HipTable.join_components``), 4 bytes per asset and per row however many
+        pairs there are, so 10 000 copies of one file are one group and not 5 * 10^7 pairs over ``max_pairs``.  Groups of at least
+        ``min_size`` assets, by size descending, then by smallest key; ``iscc_ids`` ascending by key.  There is no
+        ``min_score``: an aggregated score needs every table's unit scores per pair, which is what ``find_duplicates`` computes.
+        """
+        threshold = self._opts.match_threshold_units if threshold is None else float(threshold)
+        if not 0.0 < threshold <= 1.0:
+            raise ValueError(f"threshold must be in (0, 1], got {threshold}")
+        side, realm = self._join_side(unit_types)
+        return [DuplicateGroup([codec.iscc_id_from_int(k, realm) for k in group.tolist()], len(group))
+                for group in group_side("find_duplicate_groups", side, threshold, min_size)]
 
     def find_matches(self, other, min_score=None, unit_types=None, max_pairs=1_000_000):
         # type: (HipIndex, Optional[float], Optional[List[str]], int) -> List[IndexMatch]

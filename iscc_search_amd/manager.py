@@ -14,7 +14,7 @@ from typing import Dict, List, Optional
 from urllib.parse import parse_qs, urlparse
 
 from iscc_search_amd.index import HipIndex, HipOptions
-from iscc_search_amd.pairs import DuplicatePair, IndexMatch
+from iscc_search_amd.pairs import DuplicateGroup, DuplicatePair, IndexMatch
 from iscc_search_amd.schema import IsccAddResult, IsccEntry, IsccIndex, IsccQuery, IsccSearchResult
 
 INDEX_NAME_RE = re.compile(r"^[a-z][a-z0-9]*$")
@@ -276,6 +276,12 @@ class HipIndexManager:
         """Near-duplicate asset pairs of one index (``HipIndex.find_duplicates``).  Not available on a sharded index."""
         self._refuse_sharded("find_duplicates")
         return self._locked_index(index_name).find_duplicates(min_score=min_score, unit_types=unit_types, max_pairs=max_pairs)
+
+    def find_duplicate_groups(self, index_name, unit_types=None, threshold=None, min_size=2):
+        # type: (str, Optional[List[str]], Optional[float], int) -> List[DuplicateGroup]
+        """Groups of near-duplicate assets of one index (``HipIndex.find_duplicate_groups``).  Not available on a sharded index."""
+        self._refuse_sharded("find_duplicate_groups")
+        return self._locked_index(index_name).find_duplicate_groups(unit_types=unit_types, threshold=threshold, min_size=min_size)
 
     def find_matches(self, index_a, index_b, min_score=None, unit_types=None, max_pairs=1_000_000):
         # type: (str, str, Optional[float], Optional[List[str]], int) -> List[IndexMatch]

@@ -1,11 +1,14 @@
 """
 Asset pairs by device joins: the host side of ``HipIndex.find_duplicates`` (``HipTable.join_within``) and ``find_matches``
 (``HipTable.join_between``), scored as ``search_assets`` scores (``unit_match``).  A *side* of a join is ``(tables, asset_units)``:
-unit type -> ``HipNphdIndex``, and asset key -> {unit_type: body} as indexed.
+unit type -> ``HipNphdIndex``, and asset key -> {unit_type: body} as indexed.  And asset GROUPS by the same joins with a union-find
+on the device where the pairs were (``find_duplicate_groups``, ``HipTable.join_components``).
 """
 
 from dataclasses import dataclass
-from typing import Dict, Optional
+from typing import Dict, List, Optional
+
+import numpy as np
 
 from iscc_search_amd.unit_match import _confidence_total, _is_instance, _unit_max_hamming, _unit_scores
 
@@ -28,6 +31,14 @@ class IndexMatch:
     iscc_id_b: str      # the asset of the other index
     score: float
     types: Dict[str, float]   # the confident unit scores, in the unit order of asset a
+
+
+@dataclass
+class DuplicateGroup:
+    """One group of ``find_duplicate_groups``: a connected component of the near-duplicate pairs."""
+
+    iscc_ids: List[str]     # ascending by key
+    size: int
 
 
 def _merge_join(pair_scores, unit_type, join, instance, units_a, units_b):
@@ -80,3 +91,37 @@ def join_sides(caller, side_a, side_b, opts, min_score, max_pairs):
         join = table_a.join_within(max_hamming, max_pairs) if side_b is side_a else table_a.join_between(table_b, max_hamming, max_pairs)
         _merge_join(pair_scores, unit_type, join, instance, units_a, units_b)
     return _rank_pairs(pair_scores, units_a, thr, exp, min_score)
+
+
+def group_side(caller, side, threshold, min_size):
+    # type: (str, tuple, float, int) -> list
+    """
+    The connected components of ``side``'s assets under the pairs ``join_sides(caller, side, side, ...)`` lists at
+    ``match_threshold_units = threshold``: one uint64 array of asset keys (ascending) per component of at least ``min_size``
+    assets, by size descending, then by smallest key.  Labels are the ranks of the sorted asset keys, so a component's smallest
+    label is its smallest key; ONE ``join_components`` per unit table, in sorted type order, carries one ``parent`` array through
+    them all.  Per table the live rows are those of the assets that carry its type: a row an update left behind in a table of a
+    type its asset no longer carries links nothing (``_merge_join`` says the same for pairs).  Tables without ``join_components``
+    (a sharded engine's) raise NotImplementedError naming ``caller``.
+    """
+    tables, units = side
+    keys = np.array(sorted(units), dtype=np.uint64)
+    if len(keys) >= 0xFFFFFFFF:
+        raise ValueError(f"{caller} labels assets with 32 bits: {len(keys)} assets are too many")
+    parent = np.arange(len(keys), dtype=np.uint32)
+    for unit_type in sorted(tables):
+        table = tables[unit_type]._table
+        if not hasattr(table, "join_components"):
+            raise NotImplementedError(f"{caller} needs a single-GPU engine: pairs across shards need their rows exchanged")
+        if not len(keys):
+            continue
+        live_keys = np.array(sorted(k for k, by_type in units.items() if unit_type in by_type), dtype=np.uint64)
+        live_labels = np.searchsorted(keys, live_keys).astype(np.uint32)
+        table.join_components(_unit_max_hamming(threshold, _is_instance(unit_type)), live_keys, live_labels, parent)
+    # parent is flat: parent[i] is the component's smallest label.  Members by (root, label); groups by (-size, root)
+    roots, counts = np.unique(parent, return_counts=True)
+    members = np.argsort(parent, kind="stable")
+    starts = np.concatenate(([0], np.cumsum(counts)[:-1])).astype(np.int64)
+    order = np.lexsort((roots, -counts.astype(np.int64)))
+    order = order[counts[order] >= min_size]
+    return [keys[members[starts[g]:starts[g] + counts[g]]] for g in order.tolist()]

@@ -16,8 +16,17 @@ instructions x 4 cycles) per SIMD and clock, the figure bench.py uses for that s
 between the two VALU legs.  The line carries the three rates and `ratio` = matrix cores / mean of the two VALU legs, and the tool
 asserts that the legs found the same number of pairs.
 
+--components: isccsearch_join_components (the joins' LINK form: pairs united in a union-find array on the device) against
+isccsearch_join_within of the SAME build and run, on the same tables.  Per table and kernel three legs A B A (join_within,
+join_components, join_within), each one warm-up call and the median of --reps; `ratio` = join_components / mean of the two
+join_within legs, and `around_the_joins_seconds` is a join_components call with every prefix excluded: the labels of the rows, the
+flatten step and the copies of the arrays, without a join launch.  Then the DENSE table join_within cannot answer under the default
+max_pairs: --dense-rows 64-bit rows (default 1 Mi) in clusters of --cluster identical rows, tau 0, on both kernels: seconds, links,
+nanoseconds per link.
+
 usage: python tools/bench_duplicates.py [--mfma both] [--reps 5] [--sizes 65536,262144,1048576,4194304] [--nphd-sizes 262144,1048576] [--tau 6]
        python tools/bench_duplicates.py --between [--rows-a N --rows-b M] [the same options]
+       python tools/bench_duplicates.py --components [--sizes 1048576 --nphd-sizes 1048576] [--dense-rows 1048576 --cluster 1000]
 """
 
 import argparse
@@ -46,7 +55,7 @@ def table_name(metric, nbytes):
     return f"{'HAMMING' if metric == _lib.METRIC_HAMMING else 'NPHD'} {8 * nbytes}-bit"
 
 
-def median_of(join, reps):
+def median_of(join, reps, found=lambda out: len(out[2])):
     """(seconds, pairs found): median of `reps` calls after one warm-up (code objects, buffers)."""
     join()
     times, pairs_found = [], 0
@@ -54,20 +63,20 @@ def median_of(join, reps):
         t0 = time.perf_counter()
         out = join()                                    # ends in a device synchronise (the pair count is read back)
         times.append(time.perf_counter() - t0)
-        pairs_found = len(out[2])
+        pairs_found = found(out)
     return statistics.median(times), pairs_found
 
 
-def leg(engine, mfma, join, reps):
+def leg(engine, mfma, join, reps, found=lambda out: len(out[2]), launches_expected=True):
     """One leg on one kernel; the statistics must say that kernel ran, and no other."""
     opts = dict(mfma=1, join_mfma=1, join_mfma_min_rows=0) if mfma else dict(join_mfma=0)
     before = engine.stats()
     with engine.options(**opts):
-        seconds, pairs_found = median_of(join, reps)
+        seconds, pairs_found = median_of(join, reps, found)
     after = engine.stats()
     launches = after["join_launches"] - before["join_launches"]
     on_mfma = after["join_mfma_launches"] - before["join_mfma_launches"]
-    assert launches > 0 and on_mfma == (launches if mfma else 0), (mfma, launches, on_mfma)
+    assert (launches > 0) == launches_expected and on_mfma == (launches if mfma else 0), (mfma, launches, on_mfma)
     return seconds, pairs_found
 
 
@@ -121,6 +130,66 @@ def run_between(engine, which, metric, nbytes, n_a, n_b, tau, reps):
         tb.drop()
 
 
+def components_call(t, mh, n):
+    """join_components over all rows of a table whose keys are 1..n (label = row of add_synthetic), from the identity each time."""
+    live_keys = np.arange(1, n + 1, dtype=np.uint64)
+    live_labels = np.arange(n, dtype=np.uint32)
+    start, parent = live_labels.copy(), live_labels.copy()
+
+    def call():
+        np.copyto(parent, start)
+        return t.join_components(mh, live_keys, live_labels, parent), parent
+    return call
+
+
+def run_components(engine, metric, nbytes, n, tau, reps):
+    """join_components against join_within on one synthetic table: A B A per kernel."""
+    t = engine.open_table(metric, 1, nbytes)
+    try:
+        t.add_synthetic(nbytes, n, seed=1234 + n, first_row=0, key_base=1)
+        mh = np.full(_lib.MAX_BYTES + 1, -1, dtype=np.int16)
+        mh[nbytes] = tau
+        within = lambda: t.join_within(mh, 1 << 20)                   # noqa: E731
+        components = components_call(t, mh, n)
+        around = components_call(t, np.full(_lib.MAX_BYTES + 1, -1, dtype=np.int16), n)
+        out = {"join": "components", "table": table_name(metric, nbytes), "rows": n, "tau": tau}
+        for mfma in (False, True):
+            a1, f1 = leg(engine, mfma, within, reps)
+            b, links = leg(engine, mfma, components, reps, found=lambda o: o[0])
+            a2, f2 = leg(engine, mfma, within, reps)
+            assert f1 == links == f2, f"join_within found {f1} and {f2} pairs, join_components {links} links"
+            extra, _ = leg(engine, mfma, around, reps, found=lambda o: o[0], launches_expected=False)
+            out["mfma" if mfma else "valu"] = dict(within_seconds=[round(a1, 5), round(a2, 5)], components_seconds=round(b, 5),
+                                                   ratio=round(b / ((a1 + a2) / 2), 4), around_the_joins_seconds=round(extra, 5), links=links)
+        return out
+    finally:
+        t.drop()
+
+
+def run_dense(engine, n, cluster, reps):
+    """64-bit rows in clusters of `cluster` identical rows, stored in random order: every pair of a cluster is a link at tau 0."""
+    rng = np.random.default_rng(99)
+    t = engine.open_table(_lib.METRIC_HAMMING, 1, 8)
+    try:
+        codes = rng.integers(0, 2**64, size=(n + cluster - 1) // cluster, dtype=np.uint64)
+        words = np.repeat(codes, cluster)[:n][rng.permutation(n)]
+        t.add(np.arange(1, n + 1, dtype=np.uint64), words[:, None])
+        mh = np.full(_lib.MAX_BYTES + 1, -1, dtype=np.int16)
+        mh[8] = 0
+        call = components_call(t, mh, n)
+        sizes = np.unique(words, return_counts=True)[1].astype(np.int64)
+        expected = int((sizes * (sizes - 1) // 2).sum())
+        out = {"join": "components, dense", "table": table_name(_lib.METRIC_HAMMING, 8), "rows": n, "cluster": cluster, "tau": 0}
+        for mfma in (False, True):
+            seconds, links = leg(engine, mfma, call, reps, found=lambda o: o[0])
+            groups = len(np.unique(call()[1]))
+            assert links == expected and groups == len(sizes), (links, expected, groups, len(sizes))
+            out["mfma" if mfma else "valu"] = dict(seconds=round(seconds, 5), links=links, ns_per_link=round(seconds / links * 1e9, 4), groups=groups)
+        return out
+    finally:
+        t.drop()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--mfma", choices=("0", "1", "both"), default="both", help="the kernel: XOR + popcount, matrix cores, or A B A over both")
@@ -131,12 +200,23 @@ def main():
     ap.add_argument("--between", action="store_true", help="the cross join of two tables of each size instead of the self-join")
     ap.add_argument("--rows-a", type=int, default=0, help="--between: rows of table A (with --rows-b: this one pair of sizes only)")
     ap.add_argument("--rows-b", type=int, default=0, help="--between: rows of table B")
+    ap.add_argument("--components", action="store_true", help="join_components against join_within (A B A per kernel), then the dense table")
+    ap.add_argument("--dense-rows", type=int, default=1 << 20, help="--components: rows of the dense table (0: skip it)")
+    ap.add_argument("--cluster", type=int, default=1000, help="--components: identical rows per cluster of the dense table")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args()
     sizes = [int(s) for s in a.sizes.split(",") if s]
     nphd_sizes = [int(s) for s in a.nphd_sizes.split(",") if s]
     engine = HipEngine(a.device)
     try:
+        if a.components:
+            for n in sizes:
+                print(json.dumps(run_components(engine, _lib.METRIC_HAMMING, 8, n, a.tau, a.reps)), flush=True)
+            for n in nphd_sizes:
+                print(json.dumps(run_components(engine, _lib.METRIC_NPHD, 32, n, 4 * a.tau, a.reps)), flush=True)
+            if a.dense_rows:
+                print(json.dumps(run_dense(engine, a.dense_rows, a.cluster, a.reps)), flush=True)
+            return
         if a.between:
             given = a.rows_a > 0 and a.rows_b > 0
             for n_a, n_b in [(a.rows_a, a.rows_b)] if given else [(n, n) for n in sizes]:
