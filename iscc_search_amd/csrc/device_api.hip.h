@@ -67,26 +67,24 @@ int merge_device_impl(isccsearch_handle* h, uint32_t n_lists, uint32_t nq, uint3
     // device's address space): 240 bytes per query cross PCIe as the kernel's own stores, and the host needs a single
     // synchronisation -- no device->host copies to launch (each cost ~25 us of queue hand-over after the kernel).
     // (Blocks above DIRECT_RESULT_BYTES -- large k x many queries -- go through device memory and two DMA copies as before.)
-    const size_t rec_bytes = (size_t)nq * k * sizeof(isk::Record);
-    const bool direct = rec_bytes + (size_t)nq * sizeof(uint32_t) <= DIRECT_RESULT_BYTES;
-    if ((rc = h->p_block.ensure(rec_bytes + (size_t)nq * sizeof(uint32_t)))) return rc;
+    const ResultBlock blk = ResultBlock::merged(nq, k);
+    const bool direct = blk.bytes() <= DIRECT_RESULT_BYTES;
+    if ((rc = h->p_block.ensure(blk.bytes()))) return rc;
     if (!direct) {
         if ((rc = h->d_final.ensure((size_t)nq * k))) return rc;
         if ((rc = h->d_outcnt.ensure(nq))) return rc;
     }
     isk::MergeParams mp{static_cast<const unsigned char*>(d_records), static_cast<const unsigned char*>(d_counts),
                         list_stride, count_stride,
-                        direct ? reinterpret_cast<isk::Record*>(h->p_block.p) : h->d_final.p,
-                        direct ? reinterpret_cast<uint32_t*>(h->p_block.p + rec_bytes) : h->d_outcnt.p, n_lists, nq, k};
+                        direct ? blk.records(h->p_block.p) : h->d_final.p, direct ? blk.counts(h->p_block.p) : h->d_outcnt.p, n_lists, nq, k};
     hipLaunchKernelGGL(isk::merge_kernel, dim3(nq), dim3(isk::BLOCK), 0, h->stream, mp);
     HIPOK(hipGetLastError());
     if (!direct) {
-        HIPOK(hipMemcpyAsync(h->p_block.p, h->d_final.p, rec_bytes, hipMemcpyDeviceToHost, h->stream));
-        HIPOK(hipMemcpyAsync(h->p_block.p + rec_bytes, h->d_outcnt.p, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPOK(hipMemcpyAsync(blk.records(h->p_block.p), h->d_final.p, blk.records_bytes(), hipMemcpyDeviceToHost, h->stream));
+        HIPOK(hipMemcpyAsync(blk.counts(h->p_block.p), h->d_outcnt.p, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     }
     HIPOK(hipStreamSynchronize(h->stream));
-    unpack_records(reinterpret_cast<const isk::Record*>(h->p_block.p), reinterpret_cast<const uint32_t*>(h->p_block.p + rec_bytes), nq, k, key_words,
-                   nullptr, out_keys, out_hamming, out_prefix_bits, out_count);
+    unpack_records(blk.records(h->p_block.p), blk.counts(h->p_block.p), nq, k, key_words, nullptr, out_keys, out_hamming, out_prefix_bits, out_count);
     return 0;
 }
 }  // namespace
@@ -134,7 +132,7 @@ int isccsearch_merge_many_after(isccsearch_handle* h, uint32_t n, isccsearch_mer
         if (!r.d_records || !r.d_counts || !r.out_keys || !r.out_hamming || !r.out_prefix_bits || !r.out_count) return fail(-EINVAL, "NULL argument (merge %u)", i);
         if (r.list_stride % 8 || r.count_stride % 4 || (uintptr_t)r.d_records % 8 || (uintptr_t)r.d_counts % 4) return fail(-EINVAL, "misaligned record/count blocks (merge %u)", i);
         off[i] = total;
-        total += ((size_t)r.nq * r.k * sizeof(isk::Record) + (size_t)r.nq * sizeof(uint32_t) + 15) & ~(size_t)15;
+        total += ResultBlock::merged(r.nq, r.k).slice_bytes();
     }
     std::lock_guard<std::mutex> lk(h->mu);
     HIPOK(hipSetDevice(h->device));
@@ -146,17 +144,17 @@ int isccsearch_merge_many_after(isccsearch_handle* h, uint32_t n, isccsearch_mer
     if ((rc = wait_for_producer(h, producer_stream))) return rc;
     for (uint32_t i = 0; i < n; ++i) {
         isccsearch_merge_request& r = reqs[i];
-        const size_t rec_bytes = (size_t)r.nq * r.k * sizeof(isk::Record);
+        const ResultBlock blk = ResultBlock::merged(r.nq, r.k);
         isk::MergeParams mp{static_cast<const unsigned char*>(r.d_records), static_cast<const unsigned char*>(r.d_counts), r.list_stride, r.count_stride,
-                            reinterpret_cast<isk::Record*>(h->p_block.p + off[i]), reinterpret_cast<uint32_t*>(h->p_block.p + off[i] + rec_bytes), r.n_lists, r.nq, r.k};
+                            blk.records(h->p_block.p + off[i]), blk.counts(h->p_block.p + off[i]), r.n_lists, r.nq, r.k};
         hipLaunchKernelGGL(isk::merge_kernel, dim3(r.nq), dim3(isk::BLOCK), 0, h->stream, mp);
     }
     HIPOK(hipGetLastError());
     HIPOK(hipStreamSynchronize(h->stream));
     for (uint32_t i = 0; i < n; ++i) {
         isccsearch_merge_request& r = reqs[i];
-        const size_t rec_bytes = (size_t)r.nq * r.k * sizeof(isk::Record);
-        unpack_records(reinterpret_cast<const isk::Record*>(h->p_block.p + off[i]), reinterpret_cast<const uint32_t*>(h->p_block.p + off[i] + rec_bytes), r.nq, r.k, r.key_words,
+        const ResultBlock blk = ResultBlock::merged(r.nq, r.k);
+        unpack_records(blk.records(h->p_block.p + off[i]), blk.counts(h->p_block.p + off[i]), r.nq, r.k, r.key_words,
                        nullptr, r.out_keys, r.out_hamming, r.out_prefix_bits, r.out_count);
     }
     return 0;

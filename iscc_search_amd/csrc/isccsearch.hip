@@ -11,7 +11,7 @@
 //   range-limited (search_within / doc_freq): radius_init -> scan(COLLECT) -> select   (fixed threshold)
 //
 // Everything runs on one HIP stream owned by the handle; the only host synchronisation of a
-// search is the final result copy (one block {records | counts | flags}); search_many shares it between
+// search is the final result copy (one block, laid out by ResultBlock below); search_many shares it between
 // the requests of one call.  Built for gfx950 only (hipcc --offload-arch=gfx950).
 #include <hip/hip_runtime.h>
 
@@ -147,6 +147,39 @@ constexpr uint32_t QB_MAX = 1024;        // queries per pipeline run
 // its slice of the pinned query staging before the batch exists takes m + 16 flag slots, and four staged words for each of them
 constexpr size_t flag_slots_for(size_t m) { return m + 16; }
 constexpr size_t staged_words_for(size_t m) { return (m + 16) * 4; }
+// One batch's results as ONE block {records [m][k] | counts [m] | flags [m + 16] | extra [m] | info}, the same on the device and in its pinned
+// mirror.  records: not when the lists stay on the device (a scoring sink); extra: the lists' lengths of a counted document-frequency call, or
+// the k-th distances of a sink; info: the scoring kernels' info words.  A merge of device-resident lists writes {records | counts} only.
+struct ResultBlock {
+    size_t m, k;
+    bool with_records = true, with_extra = false, with_info = false, with_flags = true;
+    static constexpr ResultBlock merged(size_t m, size_t k) { return ResultBlock{m, k, true, false, false, false}; }
+    constexpr size_t records_bytes() const { return with_records ? m * k * sizeof(isk::Record) : 0; }
+    constexpr size_t counts_off() const { return records_bytes(); }
+    constexpr size_t flags_off() const { return counts_off() + m * sizeof(uint32_t); }
+    constexpr size_t extra_off() const { return flags_off() + (with_flags ? flag_slots_for(m) : 0) * sizeof(uint32_t); }
+    constexpr size_t info_off() const { return extra_off() + (with_extra ? m : 0) * sizeof(uint32_t); }
+    constexpr size_t bytes() const { return info_off() + (with_info ? isksp::INFO_WORDS : 0) * sizeof(uint32_t); }
+    constexpr size_t slice_bytes() const { return (bytes() + 15) & ~(size_t)15; }      // (blocks queued back to back in one buffer)
+    // {records | counts | the flag words a begun batch really has}: what the copy of a batch's lists moves
+    constexpr size_t bytes_with(size_t flag_words) const { return flags_off() + flag_words * sizeof(uint32_t); }
+    static uint32_t* words(unsigned char* base, size_t off) { return reinterpret_cast<uint32_t*>(base + off); }
+    isk::Record* records(unsigned char* base) const { return reinterpret_cast<isk::Record*>(base); }
+    uint32_t* counts(unsigned char* base) const { return words(base, counts_off()); }
+    uint32_t* flags(unsigned char* base) const { return words(base, flags_off()); }
+    uint32_t* extra(unsigned char* base) const { return words(base, extra_off()); }
+    uint32_t* info(unsigned char* base) const { return words(base, info_off()); }
+};
+constexpr size_t RB_REC = sizeof(isk::Record), RB_W = sizeof(uint32_t);
+static_assert(ResultBlock{1, 1}.counts_off() == 1 * 1 * RB_REC && ResultBlock{1, 1}.flags_off() == 1 * 1 * RB_REC + 1 * RB_W &&
+              ResultBlock{1, 1}.bytes() == 1 * 1 * RB_REC + (1 + (1 + 16)) * RB_W, "one query, one record");
+constexpr ResultBlock RB_SINK{5, 3, false, true, true};
+static_assert(RB_SINK.counts_off() == 0 && RB_SINK.flags_off() == 5 * RB_W && RB_SINK.extra_off() == (5 + (5 + 16)) * RB_W &&
+              RB_SINK.info_off() == (5 + (5 + 16) + 5) * RB_W && RB_SINK.bytes() == (5 + (5 + 16) + 5 + isksp::INFO_WORDS) * RB_W, "a sink's block");
+static_assert(ResultBlock{1024, 10}.counts_off() == 1024 * 10 * RB_REC && ResultBlock{1024, 10}.bytes() == 1024 * 10 * RB_REC + (1024 + (1024 + 16)) * RB_W &&
+              ResultBlock{1024, 10}.bytes_with(1024) == 1024 * 10 * RB_REC + (1024 + 1024) * RB_W, "a full batch of lists");
+static_assert(ResultBlock{1, 2}.bytes() == 120 && ResultBlock{1, 2}.slice_bytes() == ((1 * 2 * RB_REC + (1 + (1 + 16)) * RB_W + 15) & ~(size_t)15) &&
+              ResultBlock::merged(3, 1).slice_bytes() == ((3 * 1 * RB_REC + 3 * RB_W + 15) & ~(size_t)15) && ResultBlock::merged(3, 1).slice_bytes() == 96, "slices of 16 bytes");
 constexpr uint64_t CACHE_STRETCH_BYTES = 128ull << 20;   // half of the 256 MiB Infinity Cache
 constexpr uint64_t ROW_ALIGN = 2048;     // column capacities are multiples of the largest tile
 
@@ -311,7 +344,6 @@ struct isccsearch_handle {
     hipStream_t stream = nullptr;
     std::vector<std::unique_ptr<Table>> tables;
     Options opt;                      // what isccsearch_set_option / isccsearch_get_option reach (OPTIONS)
-    bool spec_suppress = false;       // (isccsearch_search_many: the ordinary rerun of a request whose speculative pass just missed)
     // NPHD distance ranks: rank[p_bytes][h] (u16), row 0 = identity (Hamming tables)
     uint16_t* d_rank = nullptr;
     // scratch
@@ -322,7 +354,7 @@ struct isccsearch_handle {
     DevBuf<isk::Record> d_lists, d_final;
     PinBuf<uint64_t> p_queries;     // pinned staging: queries in, flags / results out
     PinBuf<uint32_t> p_flags;
-    // one batch's results as ONE block {records [m][k] | counts [m] | overflow flags}: a single device->host copy
+    // one batch's results as ONE block (ResultBlock): a single device->host copy
     DevBuf<unsigned char> d_block;
     PinBuf<unsigned char> p_block;
     DevBuf<uint64_t> d_misc;        // moves / gather rows / single query

@@ -1,5 +1,6 @@
-// search_api.hip.h -- search_locked (every host-result search ends there), the combining queue of isccsearch_search, search_many,
-// search_within and the document-frequency calls.  Needs Batch and the query checks of isccsearch.hip, get_table of store.hip.h.
+// search_api.hip.h -- search_locked (every host-result search ends there: the steps of a LockedBatch), the speculation steps it shares
+// with search_many, the combining queue of isccsearch_search, search_many, search_within and the document-frequency calls.
+// Needs Batch, ResultBlock, record_hint and the query checks of isccsearch.hip, get_table of store.hip.h.
 extern "C" {
 static_assert(isksp::MAX_QUERY_SIMPRINTS == ISCCSEARCH_MAX_SCORED_SIMPRINTS, "header and kernels disagree");
 // isccsearch_simprint_score: where a search leaves its lists for the scoring kernels instead of handing them to the host
@@ -32,60 +33,79 @@ struct SearchOut {
     static SearchOut doc_freq(uint32_t* freq, uint32_t* collisions = nullptr) { SearchOut o; o.freq = freq; o.collisions = collisions; return o; }
     static SearchOut to_sink(ScoreSink* sink) { SearchOut o; o.sink = sink; return o; }
 };
+// The speculation steps that search_locked and isccsearch_search_many share (LockedBatch::choose explains the kinds); record_hint is the third.
+// choose: a segment's hints serve ordinary top-k searches of a table whose ONE segment it is, and that it can give k rows
+// (skip_one_launch: a segment small enough for the one-launch search -- Batch::tiny -- has nothing to gain from a radius: it is exact in that launch either way)
+static bool hints_serve(const isccsearch_handle* h, const Segment* seg, uint32_t k, int radius, bool skip_one_launch) {
+    if (!seg || radius >= 0 || k > seg->n) return false;
+    const bool one_launch = seg->n <= (uint64_t)h->opt.tiny_rows && seg->n < (uint64_t)h->opt.mfma_min_rows && seg->n <= (uint64_t)h->opt.candidate_cap;
+    return !(skip_one_launch && one_launch);
+}
+// choose: the hint a batch speculates under now, or -1.  (Asking counts a backed-off hint's skipped batches down: once per batch, and last.)
+static int ready_hint(const isccsearch_handle* h, Segment* seg, uint32_t m, uint32_t len, uint32_t k, bool allowed) {
+    return allowed && h->opt.speculate && seg->hint(m, len).ready(k) ? (int)seg->hint(m, len).tau : -1;
+}
+// verify: the verdict is counted, and a miss backs the hint off
+static bool count_verdict(isccsearch_handle* h, HintBackoff& hint, bool ok) {
+    if (ok) h->stats.spec_hits += 1;
+    else { h->stats.spec_misses += 1; hint.miss(); }
+    return ok;
+}
+// accounting (tools/probe_candidate_path.py, option "count_candidates"): how many candidates the scan appended for a batch
+static int appended(isccsearch_handle* h, const Batch& b, uint64_t& sum) {
+    std::vector<uint32_t> hc((size_t)b.nq_pad * isk::CNT_STRIDE);
+    HIPOK(hipMemcpyAsync(hc.data(), h->d_cnt.p, hc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPOK(hipStreamSynchronize(h->stream));
+    for (uint32_t i = 0; i < b.nq; ++i) sum += hc[(size_t)i * isk::CNT_STRIDE];
+    return 0;
+}
 
-// The search itself; h->mu is held by the caller.  radius >= 0: range-limited search (fixed threshold).
-static int search_locked(isccsearch_handle* h, uint32_t table, uint32_t nq, const uint64_t* q_words, const uint8_t* q_nbytes, uint32_t k,
-                         int radius, const SearchOut& out) {
-    uint32_t* const out_freq = out.freq; uint32_t* const out_collisions = out.collisions; ScoreSink* const sink = out.sink;
-    Table* tp;
-    int rc = get_table(h, table, tp);
-    if (rc) return rc;
-    Table& t = *tp;
-    if ((rc = check_query_lengths(t, nq, q_nbytes))) return rc;
-    HIPOK(hipSetDevice(h->device));
-    h->stats.queries += nq;
+enum class Spec { none, radius, self_hint, tight, ratio };
+// What a search_locked call gives each of its batches
+struct LockedCall {
+    isccsearch_handle* h; Table& t; uint32_t k; int radius; const SearchOut& out;
+    bool may_speculate;                     // false: the rerun of a request whose speculative pass just missed (isccsearch_search_many)
+    const std::vector<uint32_t>& order;     // the call's queries, grouped by byte length
+    const std::vector<uint64_t>& hq;        // this batch's query words [m][max_words]
+};
+// One batch of a search_locked call -- the queries order[pos .. pos + m), all of `len` bytes -- and its steps; run() is their order.
+// Both mirrors of the result block are sized before it is made.
+struct LockedBatch : LockedCall {
+    const uint32_t pos, m, len;
+    const ResultBlock blk;
+    ScoreSink* const sink;
+    const uint32_t segments;
+    const bool one_copy;                // flags ride in the block: results leave in ONE copy
+    // ... or in none: select_kernel writes a small block straight into the pinned mirror (page-locked memory is mapped
+    // into the device's address space), so the host only synchronises.  A device->host copy costs ~25 us of queue
+    // hand-over after the kernel, more than the 240 bytes per query take to cross PCIe as plain stores.  Large blocks
+    // (big k x many queries) keep the DMA copy.
+    const bool direct;
+    unsigned char* const d_base;        // the block the kernels write: the pinned mirror itself when direct
+    const isk::Record* const p_rec; const uint32_t* const p_cnt;    // records and counts of the pinned mirror
+    Batch batch;
+    Segment* const seg;                 // radius / self_hint / tight: the table's only segment (else nullptr)
+    bool hintable = false, mhintable = false;   // this batch's class keeps a hint with its segment / (several segments) with its table
+    Spec spec = Spec::none;
+    int tau = -1;                       // radius / self_hint / tight: the hint this batch speculates under
+    bool spec_ok = false;               // the speculative step stands: its lists are the answer
+    bool handed_out = false;            // (tight, repaired) the lists are in the caller's arrays already
 
-    // group queries by byte length (NPHD prefix length differs per class)
-    std::vector<uint32_t> order(nq);
-    for (uint32_t q = 0; q < nq; ++q) order[q] = q;
-    auto qlen = [&](uint32_t q) -> uint32_t { return (t.metric == ISCCSEARCH_METRIC_NPHD) ? q_nbytes[q] : (uint32_t)t.max_bytes; };
-    if (t.metric == ISCCSEARCH_METRIC_NPHD)
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return q_nbytes[a] < q_nbytes[b]; });
-
-    std::vector<uint64_t> hq;
-    uint32_t pos = 0;
-    while (pos < nq) {
-        const uint32_t len = qlen(order[pos]);
-        uint32_t end = pos;
-        while (end < nq && end - pos < QB_MAX && qlen(order[end]) == len) ++end;
-        const uint32_t m = end - pos;
-        hq.resize((size_t)m * t.max_words);
-        for (uint32_t i = 0; i < m; ++i)
-            memcpy(&hq[(size_t)i * t.max_words], q_words + (size_t)order[pos + i] * t.max_words, (size_t)t.max_words * 8);
-        // result block {records [m][k] | counts [m] | flags [<= m + 15]} on the device and, mirrored, in pinned memory
-        const size_t rec_bytes = sink ? 0 : (size_t)m * k * sizeof(isk::Record);     // (a sink keeps the records on the device)
-        const size_t flag_slots = flag_slots_for(m);
-        // (+ m counts behind the flags when a document-frequency call also wants the lists' lengths;
-        //  + m k-th distances and the scoring kernels' info words when the lists stay on the device)
-        const size_t block_bytes = rec_bytes + ((size_t)m + flag_slots + (out_collisions || sink ? m : 0) + (sink ? isksp::INFO_WORDS : 0)) * sizeof(uint32_t);
-        if ((rc = h->d_block.ensure(block_bytes))) return rc;
-        if ((rc = h->p_block.ensure(block_bytes))) return rc;
-        const isk::Record* const p_rec = reinterpret_cast<const isk::Record*>(h->p_block.p);
-        uint32_t* const p_cnt = reinterpret_cast<uint32_t*>(h->p_block.p + rec_bytes);
-        const uint32_t segments = t.segments();
-        const bool one_copy = segments == 1 && !out_freq;   // flags ride in the block: results leave in ONE copy
-        // ... or in none: select_kernel writes a small block straight into the pinned mirror (page-locked memory is mapped
-        // into the device's address space), so the host only synchronises.  A device->host copy costs ~25 us of queue
-        // hand-over after the kernel, more than the 240 bytes per query take to cross PCIe as plain stores.  Large blocks
-        // (big k x many queries) keep the DMA copy.
-        const bool direct = one_copy && block_bytes <= DIRECT_RESULT_BYTES && !sink;
-        isk::Record* const d_rec = sink ? h->d_sp_rec.p + (size_t)pos * k : reinterpret_cast<isk::Record*>(direct ? h->p_block.p : h->d_block.p);
-        uint32_t* const d_cnt = reinterpret_cast<uint32_t*>((direct ? h->p_block.p : h->d_block.p) + rec_bytes);
-        uint32_t* const p_kth = p_cnt + m + flag_slots;                  // (sink) hamming of every query's last result
-        Batch batch(h, t, m, len, k, d_rec, d_cnt);
+    LockedBatch(const LockedCall& c, uint32_t pos_, uint32_t m_, uint32_t len_, const ResultBlock& b)
+        : LockedCall(c), pos(pos_), m(m_), len(len_), blk(b), sink(c.out.sink), segments(c.t.segments()), one_copy(segments == 1 && !c.out.freq),
+          direct(one_copy && b.bytes() <= DIRECT_RESULT_BYTES && !sink), d_base(direct ? c.h->p_block.p : c.h->d_block.p),
+          p_rec(b.records(c.h->p_block.p)), p_cnt(b.counts(c.h->p_block.p)),
+          // (a sink keeps the records on the device)
+          batch(c.h, c.t, m_, len_, c.k, sink ? c.h->d_sp_rec.p + (size_t)pos_ * c.k : b.records(d_base), b.counts(d_base)), seg(c.t.sole_segment()) {
         batch.radius = radius;
-        if (sink) { if (!sink->exact) batch.d_out_rows = h->d_sp_rows.p + (size_t)pos * k; batch.d_out_kth = d_cnt + m + flag_slots; }
-        if (one_copy) { batch.d_flags = d_cnt + m; batch.h_flags = p_cnt + m; }
+        if (sink) { if (!sink->exact) batch.d_out_rows = h->d_sp_rows.p + (size_t)pos * k; batch.d_out_kth = blk.extra(d_base); }
+        if (one_copy) { batch.d_flags = blk.flags(d_base); batch.h_flags = blk.flags(h->p_block.p); }
+    }
+
+    // (tight: the batch's one job would take the single pass, and that pass is ONE launch of mfma_pack3_kernel)
+    bool runs_pack3() { batch.plan(hq.data()); return batch.jobs.size() == 1 && batch.single_pass(batch.jobs[0]) && batch.pack3_pass(batch.jobs[0]); }
+    // choose: the kind of speculation and the value it runs under
+    void choose() {
         // Speculation: ONE pass under where an earlier batch of this size and query length ended, verified by one look at its
         // lists; a miss (a list overflowed, a query came up short) sends the batch through the ordinary path -- nothing is ever
         // returned unverified.
@@ -112,169 +132,141 @@ static int search_locked(isccsearch_handle* h, uint32_t table, uint32_t nq, cons
         //              Up to RADIUS_BATCH_MAX_REPAIRS queries that find fewer than k rows there are asked again, alone, under the
         //              whole hint and their lists spliced in; more of them send the batch through the self_hint pass.  Either way
         //              the step stands exactly when every query has k rows within the hint and no list overflowed, as with self_hint.
-        enum class Spec { none, radius, self_hint, tight, ratio } spec = Spec::none;
-        // radius / self_hint: an ordinary top-k search over ONE segment that has been searched with this k before
-        Segment* const spec_seg = t.sole_segment();
-        // (a segment small enough for the one-launch search -- Batch::tiny -- has nothing to gain from a radius: it is exact in that launch either way)
-        const bool one_launch = spec_seg && spec_seg->n <= (uint64_t)h->opt.tiny_rows && spec_seg->n < (uint64_t)h->opt.mfma_min_rows && spec_seg->n <= (uint64_t)h->opt.candidate_cap;
-        const bool hintable = spec_seg && radius < 0 && !out_freq && one_copy && k <= spec_seg->n && !one_launch;
+        // radius / self_hint / tight: an ordinary top-k search over ONE segment that has been searched with this k before
+        hintable = hints_serve(h, seg, k, radius, /*skip_one_launch=*/true) && !out.freq && one_copy;
         const bool small_batch = hintable && m <= (uint32_t)h->opt.spec_max_queries;
-        // (tight: the batch's one job would take the single pass, and that pass is ONE launch of mfma_pack3_kernel)
-        auto runs_pack3 = [&]() { batch.plan(hq.data()); return batch.jobs.size() == 1 && batch.single_pass(batch.jobs[0]) && batch.pack3_pass(batch.jobs[0]); };
-        int tau = -1;                   // radius / self_hint / tight: the hint this batch speculates under
-        if (hintable && h->opt.speculate && !h->spec_suppress && (small_batch || h->opt.self_hint) && spec_seg->hint(m, len).ready(k)) {
-            tau = (int)spec_seg->hint(m, len).tau;
+        tau = ready_hint(h, seg, m, len, k, hintable && may_speculate && (small_batch || h->opt.self_hint));
+        if (tau >= 0) {
             if (small_batch) { spec = Spec::radius; batch.radius = tau; }
             else if (h->opt.radius_batches && !sink && runs_pack3()) {
                 spec = Spec::tight;
                 batch.radius = std::max(0, tau - (int)Segment::SpecHint::margin(k) + RADIUS_BATCH_SLACK);
             } else { spec = Spec::self_hint; batch.self_hint = tau; }
         }
-        const bool mhintable = segments > 1 && radius < 0 && !out_freq && (m <= (uint32_t)h->opt.spec_max_queries || h->opt.self_hint) && k <= t.total;
-        if (mhintable && h->opt.speculate && !h->spec_suppress && t.mhint(m, len).ready(k)) {
+        mhintable = segments > 1 && radius < 0 && !out.freq && (m <= (uint32_t)h->opt.spec_max_queries || h->opt.self_hint) && k <= t.total;
+        if (mhintable && h->opt.speculate && may_speculate && t.mhint(m, len).ready(k)) {
             spec = Spec::ratio;
             batch.radius_ratio = t.mhint(m, len).ratio + 1.0 / 32.0;      // the margin: 2 bits of 64, 8 of 256
             batch.ratio_starts_self = m > (uint32_t)h->opt.spec_max_queries;             // larger batches: each segment's single pass STARTS under it
         }
-        auto copy_results = [&]() -> int {
-            if (out_freq) {
-                // only the distinct-asset count of every list leaves the device
-                int rf;
-                if ((rf = h->d_freq.ensure(m))) return rf;
-                isk::DistinctParams dp{d_rec, d_cnt, h->d_freq.p, k, (uint32_t)t.key_words};
-                hipLaunchKernelGGL(isk::distinct_kernel, dim3(m), dim3(isk::BLOCK), 0, h->stream, dp);
-                HIPOK(hipGetLastError());
-                if (out_collisions) HIPOK(hipMemcpyAsync(p_cnt + m + flag_slots, d_cnt, m * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-                HIPOK(hipMemcpyAsync(p_cnt, h->d_freq.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-                return 0;
-            }
-            if (direct) return 0;                                  // already written where the host reads it
-            if (sink) {
-                // the lists are final on the device (or will be redone and this queued again): mark the best chunk of every
-                // (asset, query), append them to the request's entry list; the host gets counts, flags, k-th distances and info
-                uint32_t* const d_info = d_cnt + m + flag_slots + m;
-                if (sink->exact) {
-                    HIPOK(hipMemcpyAsync(h->d_sp_cnt.p + pos, d_cnt, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
-                    if (pos == 0 && m == sink->nd && sink->d_of_g)
-                        HIPOK(isksp::exact_prepare(sink->buf, d_cnt, sink->d_of_g, sink->nd, sink->ng, k, d_info, h->stream));
-                } else {
-                    isksp::BatchArgs ba{pos, m, k, d_cnt, sink->h_max, sink->dup_limit, sink->entries, d_info};
-                    HIPOK(isksp::queue_batch(sink->buf, ba, h->stream));
-                }
-                HIPOK(hipMemcpyAsync(h->p_block.p, h->d_block.p, block_bytes, hipMemcpyDeviceToHost, h->stream));
-                return 0;
-            }
-            const size_t bytes = rec_bytes + (size_t)m * sizeof(uint32_t) + (one_copy ? batch.flag_words() * sizeof(uint32_t) : 0);
-            HIPOK(hipMemcpyAsync(h->p_block.p, h->d_block.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    }
+    // queue results: whatever of the block is not yet where the host reads it, behind the kernels that turn lists into what the caller asked for
+    int queue_results() {
+        if (out.freq) {
+            // only the distinct-asset count of every list leaves the device
+            int rf;
+            if ((rf = h->d_freq.ensure(m))) return rf;
+            isk::DistinctParams dp{batch.d_out, batch.d_out_cnt, h->d_freq.p, k, (uint32_t)t.key_words};
+            hipLaunchKernelGGL(isk::distinct_kernel, dim3(m), dim3(isk::BLOCK), 0, h->stream, dp);
+            HIPOK(hipGetLastError());
+            if (out.collisions) HIPOK(hipMemcpyAsync(blk.extra(h->p_block.p), batch.d_out_cnt, m * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+            HIPOK(hipMemcpyAsync(blk.counts(h->p_block.p), h->d_freq.p, m * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
             return 0;
-        };
-        auto worst_ratio = [&]() -> double {                 // worst k-th NPHD of the merged lists; < 0: some query holds fewer than k rows
-            double worst = 0.0;
-            for (uint32_t i = 0; i < m; ++i) {
-                if (p_cnt[i] < k) return -1.0;
-                const isk::Record& r = p_rec[(size_t)i * k + k - 1];
-                worst = std::max(worst, r.prefix_bits ? (double)r.hamming / (double)r.prefix_bits : 0.0);
-            }
-            return worst;
-        };
-        if ((rc = batch.begin(hq.data()))) return rc;
-        if (spec == Spec::ratio && !batch.multi) {          // (every non-empty segment is a job: cannot happen; never answer unverified)
-            spec = Spec::none;
-            batch.radius_ratio = -1.0;
-            if ((rc = batch.begin(hq.data()))) return rc;
         }
-        if (spec == Spec::self_hint && !batch.used_hint) spec = Spec::none;     // (no job took the single pass: nothing to verify)
-        bool spec_ok = false;
-        bool handed_out = false;        // (tight, repaired) the lists are in the caller's arrays already
-        // accounting (tools/probe_candidate_path.py, option "count_candidates"): how many candidates the scan appended for a batch
-        auto appended = [&](const Batch& b, uint64_t& sum) -> int {
-            std::vector<uint32_t> hc((size_t)b.nq_pad * isk::CNT_STRIDE);
-            HIPOK(hipMemcpyAsync(hc.data(), h->d_cnt.p, hc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-            HIPOK(hipStreamSynchronize(h->stream));
-            for (uint32_t i = 0; i < b.nq; ++i) sum += hc[(size_t)i * isk::CNT_STRIDE];
-            return 0;
-        };
-        // tight: the queries in `short_q` (positions in this batch) alone, as a range-limited search under the whole hint -- which
-        // neither reads nor updates a hint.  `ok`: each of them holds k rows now and no list overflowed; their lists are spliced in.
-        auto repair = [&](const std::vector<uint32_t>& short_q, bool& ok) -> int {
-            int rr;
-            // The main pass's lists leave first: the repair reuses p_block, d_block and d_cnt (as pass 3a of isccsearch_search_many
-            // hands every deferred result out before pass 3b runs)
-            unpack_records(p_rec, p_cnt, m, k, t.key_words, &order[pos], out.keys, out.hamming, out.prefix_bits, out.count);
-            uint64_t cand = 0;
-            if (h->opt.count_candidates && (rr = appended(batch, cand))) return rr;
-            const uint32_t ns = (uint32_t)short_q.size();
-            std::vector<uint64_t> rq((size_t)ns * t.max_words);
-            std::vector<uint32_t> dest(ns);
-            for (uint32_t j = 0; j < ns; ++j) {
-                memcpy(&rq[(size_t)j * t.max_words], &hq[(size_t)short_q[j] * t.max_words], (size_t)t.max_words * 8);
-                dest[j] = order[pos + short_q[j]];
+        if (direct) return 0;                                  // already written where the host reads it
+        if (sink) {
+            // the lists are final on the device (or will be redone and this queued again): mark the best chunk of every
+            // (asset, query), append them to the request's entry list; the host gets counts, flags, k-th distances and info
+            if (sink->exact) {
+                HIPOK(hipMemcpyAsync(h->d_sp_cnt.p + pos, batch.d_out_cnt, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
+                if (pos == 0 && m == sink->nd && sink->d_of_g)
+                    HIPOK(isksp::exact_prepare(sink->buf, batch.d_out_cnt, sink->d_of_g, sink->nd, sink->ng, k, blk.info(d_base), h->stream));
+            } else {
+                isksp::BatchArgs ba{pos, m, k, batch.d_out_cnt, sink->h_max, sink->dup_limit, sink->entries, blk.info(d_base)};
+                HIPOK(isksp::queue_batch(sink->buf, ba, h->stream));
             }
-            // its block {records [ns][k] | counts [ns] | flags} is smaller than the batch's: it fits both mirrors as they are
-            const size_t r_rec_bytes = (size_t)ns * k * sizeof(isk::Record);
-            const bool r_direct = r_rec_bytes + ((size_t)ns + flag_slots_for(ns)) * sizeof(uint32_t) <= DIRECT_RESULT_BYTES;
-            unsigned char* const r_base = r_direct ? h->p_block.p : h->d_block.p;
-            uint32_t* const rd_cnt = reinterpret_cast<uint32_t*>(r_base + r_rec_bytes);
-            const uint32_t* const rp_cnt = reinterpret_cast<const uint32_t*>(h->p_block.p + r_rec_bytes);
-            Batch rb(h, t, ns, len, k, reinterpret_cast<isk::Record*>(r_base), rd_cnt);
-            rb.radius = tau;
-            rb.on_matrix_cores = true;
-            rb.d_flags = rd_cnt + ns;
-            rb.h_flags = rp_cnt + ns;
-            if ((rr = rb.begin(rq.data()))) return rr;
-            if (!r_direct) HIPOK(hipMemcpyAsync(h->p_block.p, h->d_block.p, r_rec_bytes + ((size_t)ns + rb.flag_words()) * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-            HIPOK(hipStreamSynchronize(h->stream));
-            if (h->opt.count_candidates && (rr = appended(rb, cand))) return rr;
-            ok = rb.complete(rp_cnt, spec_seg->n);
-            if (!ok) return 0;          // (the ordinary pass answers the whole batch again, and is what gets counted)
-            unpack_records(p_rec, rp_cnt, ns, k, t.key_words, dest.data(), out.keys, out.hamming, out.prefix_bits, out.count);
-            handed_out = true;
-            h->stats.candidates += cand;
-            h->stats.spec_repairs += ns;
+            HIPOK(hipMemcpyAsync(h->p_block.p, h->d_block.p, blk.bytes(), hipMemcpyDeviceToHost, h->stream));
             return 0;
-        };
-        if (spec != Spec::none) {
-            auto settle = [&]() -> int {
-                int rs;
-                if ((rs = batch.merge())) return rs;
-                if ((rs = batch.copy_flags())) return rs;
-                if ((rs = copy_results())) return rs;
-                HIPOK(hipStreamSynchronize(h->stream));
-                return 0;
-            };
-            if ((rc = settle())) return rc;
-            if (spec == Spec::tight) {
-                std::vector<uint32_t> short_q;          // (hintable: k <= rows, so a query is short of k)
-                for (uint32_t i = 0; i < m; ++i) if (p_cnt[i] < k) short_q.push_back(i);
-                if (batch.any_flag()) spec_ok = false;
-                else if (short_q.empty()) spec_ok = true;
-                else if (short_q.size() <= RADIUS_BATCH_MAX_REPAIRS) { if ((rc = repair(short_q, spec_ok))) return rc; }
-                else {
-                    // too many for one small pass: the hinted single pass for the whole batch, whose own check gives the verdict
-                    batch.radius = radius; batch.self_hint = tau;
-                    if ((rc = batch.begin(hq.data()))) return rc;
-                    if ((rc = settle())) return rc;
-                    spec_ok = batch.used_hint && batch.complete(p_cnt, spec_seg->n);
-                }
-            }
-            // (ratio: a row outside a radius lies beyond floor(ratio x bits) + 1 bits, strictly farther than the worst k-th NPHD)
-            else spec_ok = spec == Spec::ratio ? batch.complete(p_cnt, k) && worst_ratio() <= batch.radius_ratio : batch.complete(p_cnt, spec_seg->n);
-            if (spec_ok) h->stats.spec_hits += 1;
+        }
+        HIPOK(hipMemcpyAsync(h->p_block.p, h->d_block.p, blk.bytes_with(one_copy ? batch.flag_words() : 0), hipMemcpyDeviceToHost, h->stream));
+        return 0;
+    }
+    // settle: merge, flags, results, one synchronisation
+    int settle() {
+        int rs;
+        if ((rs = batch.merge())) return rs;
+        if ((rs = batch.copy_flags())) return rs;
+        if ((rs = queue_results())) return rs;
+        HIPOK(hipStreamSynchronize(h->stream));
+        return 0;
+    }
+    double worst_ratio() const {                 // worst k-th NPHD of the merged lists; < 0: some query holds fewer than k rows
+        double worst = 0.0;
+        for (uint32_t i = 0; i < m; ++i) {
+            if (p_cnt[i] < k) return -1.0;
+            const isk::Record& r = p_rec[(size_t)i * k + k - 1];
+            worst = std::max(worst, r.prefix_bits ? (double)r.hamming / (double)r.prefix_bits : 0.0);
+        }
+        return worst;
+    }
+    // repair (tight): the queries in `short_q` (positions in this batch) alone, as a range-limited search under the whole hint -- which
+    // neither reads nor updates a hint.  spec_ok: each of them holds k rows now and no list overflowed; their lists are spliced in.
+    int repair(const std::vector<uint32_t>& short_q) {
+        int rr;
+        // The main pass's lists leave first: the repair reuses p_block, d_block and d_cnt (as pass 3a of isccsearch_search_many
+        // hands every deferred result out before pass 3b runs)
+        unpack_records(p_rec, p_cnt, m, k, t.key_words, &order[pos], out.keys, out.hamming, out.prefix_bits, out.count);
+        uint64_t cand = 0;
+        if (h->opt.count_candidates && (rr = appended(h, batch, cand))) return rr;
+        const uint32_t ns = (uint32_t)short_q.size();
+        std::vector<uint64_t> rq((size_t)ns * t.max_words);
+        std::vector<uint32_t> dest(ns);
+        for (uint32_t j = 0; j < ns; ++j) {
+            memcpy(&rq[(size_t)j * t.max_words], &hq[(size_t)short_q[j] * t.max_words], (size_t)t.max_words * 8);
+            dest[j] = order[pos + short_q[j]];
+        }
+        // its block {records [ns][k] | counts [ns] | flags} is smaller than the batch's: it fits both mirrors as they are
+        const ResultBlock rblk{ns, k};
+        const bool r_direct = rblk.bytes() <= DIRECT_RESULT_BYTES;
+        unsigned char* const r_base = r_direct ? h->p_block.p : h->d_block.p;
+        const uint32_t* const rp_cnt = rblk.counts(h->p_block.p);
+        Batch rb(h, t, ns, len, k, rblk.records(r_base), rblk.counts(r_base));
+        rb.radius = tau;
+        rb.on_matrix_cores = true;
+        rb.d_flags = rblk.flags(r_base);
+        rb.h_flags = rblk.flags(h->p_block.p);
+        if ((rr = rb.begin(rq.data()))) return rr;
+        if (!r_direct) HIPOK(hipMemcpyAsync(h->p_block.p, h->d_block.p, rblk.bytes_with(rb.flag_words()), hipMemcpyDeviceToHost, h->stream));
+        HIPOK(hipStreamSynchronize(h->stream));
+        if (h->opt.count_candidates && (rr = appended(h, rb, cand))) return rr;
+        spec_ok = rb.complete(rp_cnt, seg->n);
+        if (!spec_ok) return 0;         // (the ordinary pass answers the whole batch again, and is what gets counted)
+        unpack_records(p_rec, rp_cnt, ns, k, t.key_words, dest.data(), out.keys, out.hamming, out.prefix_bits, out.count);
+        handed_out = true;
+        h->stats.candidates += cand;
+        h->stats.spec_repairs += ns;
+        return 0;
+    }
+    // verify: does the settled speculative step stand (spec_ok)?
+    int verify() {
+        int rc;
+        // (ratio: a row outside a radius lies beyond floor(ratio x bits) + 1 bits, strictly farther than the worst k-th NPHD)
+        if (spec == Spec::ratio) spec_ok = batch.complete(p_cnt, k) && worst_ratio() <= batch.radius_ratio;
+        else if (spec != Spec::tight) spec_ok = batch.complete(p_cnt, seg->n);
+        else {
+            std::vector<uint32_t> short_q;          // (hintable: k <= rows, so a query is short of k)
+            for (uint32_t i = 0; i < m; ++i) if (p_cnt[i] < k) short_q.push_back(i);
+            if (batch.any_flag()) spec_ok = false;
+            else if (short_q.empty()) spec_ok = true;
+            else if (short_q.size() <= RADIUS_BATCH_MAX_REPAIRS) { if ((rc = repair(short_q))) return rc; }
             else {
-                h->stats.spec_misses += 1;
-                if (spec == Spec::ratio) t.mhint(m, len).miss();
-                else spec_seg->hint(m, len).miss();
-                batch.radius = radius; batch.self_hint = -1; batch.used_hint = false; batch.radius_ratio = -1.0;     // the ordinary pass
+                // too many for one small pass: the hinted single pass for the whole batch, whose own check gives the verdict
+                batch.radius = radius; batch.self_hint = tau;
                 if ((rc = batch.begin(hq.data()))) return rc;
+                if ((rc = settle())) return rc;
+                spec_ok = batch.used_hint && batch.complete(p_cnt, seg->n);
             }
         }
-        if (!spec_ok && (rc = batch.finish(hq.data(), copy_results))) return rc;
+        return 0;
+    }
+    // record: candidate accounting, and where this batch's lists ended -- the next batch of its class starts there (+ the hint's margin)
+    int record() {
+        int rc;
         if (h->opt.count_candidates && batch.jobs.size() == 1) {
             // (a repaired step has counted both of its passes before the second reused the counters)
-            if (!handed_out && (rc = appended(batch, h->stats.candidates))) return rc;
+            if (!handed_out && (rc = appended(h, batch, h->stats.candidates))) return rc;
             h->stats.candidate_batches += 1;
         }
-        // where this batch's lists ended: the next batch of its class starts there (+ the hint's margin)
         if (handed_out) {
             // (the pinned block holds the repair's lists by now: the batch's worst k-th distance, repaired queries included, is in the caller's arrays)
             uint32_t worst = 0;
@@ -282,37 +274,99 @@ static int search_locked(isccsearch_handle* h, uint32_t table, uint32_t nq, cons
                 const size_t dq = order[pos + i];
                 if (out.count[dq]) worst = std::max(worst, out.hamming[dq * k + out.count[dq] - 1]);
             }
-            record_hint(spec_seg->hint(m, len), spec_ok, k, worst);
-        } else if (hintable && !batch.jobs.empty()) record_hint(spec_seg->hint(m, len), spec_ok, m, k, p_cnt, p_rec, sink ? p_kth : nullptr);
+            record_hint(seg->hint(m, len), spec_ok, k, worst);
+        } else if (hintable && !batch.jobs.empty()) record_hint(seg->hint(m, len), spec_ok, m, k, p_cnt, p_rec, sink ? blk.extra(h->p_block.p) : nullptr);
         if (mhintable) {
             const double worst = worst_ratio();
             if (spec_ok) t.mhint(m, len).hit(worst);
             else if (worst >= 0.0) t.mhint(m, len).seed(k, worst);
         }
+        return 0;
+    }
+    // hand out: the sink's bookkeeping, document frequencies (and collisions), or the lists
+    void hand_out() {
+        const bool none = batch.jobs.empty();
         if (sink) {
-            if (!batch.jobs.empty()) {
-                const uint32_t* p_info = p_kth + m;
-                if (!sink->exact) {
-                    sink->entries = p_info[0];
-                    sink->unknown_any = sink->unknown_any || p_info[1] != 0;
-                } else if (pos == 0 && m == sink->nd && sink->d_of_g) {
-                    sink->entries = p_info[0];
-                    sink->prepared = true;
-                }
-                for (uint32_t i = 0; i < m; ++i) sink->max_count = std::max(sink->max_count, std::min(p_cnt[i], k));
-                if (sink->q_count) for (uint32_t i = 0; i < m; ++i) sink->q_count[pos + i] = std::min(p_cnt[i], k);
+            if (none) return;
+            const uint32_t* p_info = blk.info(h->p_block.p);
+            if (!sink->exact) {
+                sink->entries = p_info[0];
+                sink->unknown_any = sink->unknown_any || p_info[1] != 0;
+            } else if (pos == 0 && m == sink->nd && sink->d_of_g) {
+                sink->entries = p_info[0];
+                sink->prepared = true;
             }
-            pos = end;
-            continue;
-        }
-        if (out_freq) {
-            if (batch.jobs.empty()) for (uint32_t i = 0; i < m; ++i) out_freq[order[pos + i]] = 0;
-            else for (uint32_t i = 0; i < m; ++i) out_freq[order[pos + i]] = p_cnt[i];
-            if (out_collisions)
-                for (uint32_t i = 0; i < m; ++i) out_collisions[order[pos + i]] = batch.jobs.empty() ? 0 : p_cnt[m + flag_slots + i];
+            for (uint32_t i = 0; i < m; ++i) sink->max_count = std::max(sink->max_count, std::min(p_cnt[i], k));
+            if (sink->q_count) for (uint32_t i = 0; i < m; ++i) sink->q_count[pos + i] = std::min(p_cnt[i], k);
+        } else if (out.freq) {
+            for (uint32_t i = 0; i < m; ++i) out.freq[order[pos + i]] = none ? 0 : p_cnt[i];
+            if (out.collisions) for (uint32_t i = 0; i < m; ++i) out.collisions[order[pos + i]] = none ? 0 : blk.extra(h->p_block.p)[i];
         } else if (!handed_out) {
             unpack_records(p_rec, p_cnt, m, k, t.key_words, &order[pos], out.keys, out.hamming, out.prefix_bits, out.count);
         }
+    }
+    int run() {
+        int rc;
+        choose();
+        if ((rc = batch.begin(hq.data()))) return rc;
+        if (spec == Spec::ratio && !batch.multi) {          // (every non-empty segment is a job: cannot happen; never answer unverified)
+            spec = Spec::none;
+            batch.radius_ratio = -1.0;
+            if ((rc = batch.begin(hq.data()))) return rc;
+        }
+        if (spec == Spec::self_hint && !batch.used_hint) spec = Spec::none;     // (no job took the single pass: nothing to verify)
+        if (spec != Spec::none) {
+            if ((rc = settle()) || (rc = verify())) return rc;
+            HintBackoff& hint = spec == Spec::ratio ? static_cast<HintBackoff&>(t.mhint(m, len)) : seg->hint(m, len);
+            if (!count_verdict(h, hint, spec_ok)) {
+                // on a miss: the ordinary pass
+                batch.radius = radius; batch.self_hint = -1; batch.used_hint = false; batch.radius_ratio = -1.0;
+                if ((rc = batch.begin(hq.data()))) return rc;
+            }
+        }
+        if (!spec_ok && (rc = batch.finish(hq.data(), [this] { return queue_results(); }))) return rc;
+        if ((rc = record())) return rc;
+        hand_out();
+        return 0;
+    }
+};
+
+// The search itself; h->mu is held by the caller.  radius >= 0: range-limited search (fixed threshold).
+static int search_locked(isccsearch_handle* h, uint32_t table, uint32_t nq, const uint64_t* q_words, const uint8_t* q_nbytes, uint32_t k,
+                         int radius, const SearchOut& out, bool may_speculate = true) {
+    Table* tp;
+    int rc = get_table(h, table, tp);
+    if (rc) return rc;
+    Table& t = *tp;
+    if ((rc = check_query_lengths(t, nq, q_nbytes))) return rc;
+    HIPOK(hipSetDevice(h->device));
+    h->stats.queries += nq;
+
+    // group queries by byte length (NPHD prefix length differs per class)
+    std::vector<uint32_t> order(nq);
+    for (uint32_t q = 0; q < nq; ++q) order[q] = q;
+    auto qlen = [&](uint32_t q) -> uint32_t { return (t.metric == ISCCSEARCH_METRIC_NPHD) ? q_nbytes[q] : (uint32_t)t.max_bytes; };
+    if (t.metric == ISCCSEARCH_METRIC_NPHD)
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return q_nbytes[a] < q_nbytes[b]; });
+
+    std::vector<uint64_t> hq;
+    const LockedCall call{h, t, k, radius, out, may_speculate, order, hq};
+    uint32_t pos = 0;
+    while (pos < nq) {
+        const uint32_t len = qlen(order[pos]);
+        uint32_t end = pos;
+        while (end < nq && end - pos < QB_MAX && qlen(order[end]) == len) ++end;
+        const uint32_t m = end - pos;
+        hq.resize((size_t)m * t.max_words);
+        for (uint32_t i = 0; i < m; ++i)
+            memcpy(&hq[(size_t)i * t.max_words], q_words + (size_t)order[pos + i] * t.max_words, (size_t)t.max_words * 8);
+        // (+ the lists' lengths when a document-frequency call also wants them; a sink keeps the records on the device and gets the
+        //  k-th distances and the scoring kernels' info words)
+        const ResultBlock blk{m, k, !out.sink, out.collisions || out.sink, out.sink != nullptr};
+        if ((rc = h->d_block.ensure(blk.bytes()))) return rc;
+        if ((rc = h->p_block.ensure(blk.bytes()))) return rc;
+        LockedBatch lb(call, pos, m, len, blk);
+        if ((rc = lb.run())) return rc;
         pos = end;
     }
     return 0;
@@ -436,6 +490,25 @@ int isccsearch_search(isccsearch_handle* h, uint32_t table, uint32_t nq, const u
     return me.rc;
 }
 
+struct ManySlot {            // a deferred request of isccsearch_search_many
+    std::unique_ptr<Batch> batch;
+    std::vector<uint64_t> hq;
+    size_t off = 0;         // its result block in p_block ...
+    ResultBlock blk{};      // ... and that block's layout (in d_block every request's block starts at 0)
+    Segment* seg = nullptr;
+    bool small = false;     // its class keeps a hint with the segment
+    int tau = -1;           // >= 0: the hint it speculates under
+    uint32_t len = 0;       // compared prefix length of the request (the hint is kept per length)
+};
+// a request of isccsearch_search_many with queries, checked; on success `tp` is its table
+static int check_request(isccsearch_handle* h, const isccsearch_request& r, Table*& tp) {
+    if (int rk = check_count(r.k)) return rk;
+    if (r.max_hamming > 256) return fail(-EINVAL, "max_hamming %d exceeds 256", r.max_hamming);
+    if (!r.q_words || !r.out_keys || !r.out_hamming || !r.out_prefix_bits || !r.out_count) return fail(-EINVAL, "NULL argument");
+    const int rc = get_table(h, r.table, tp);
+    return rc ? rc : check_query_lengths(*tp, r.nq, r.q_nbytes);
+}
+
 // Several searches, ONE synchronisation.  Requests over single-segment tables whose queries share one length are
 // enqueued back to back (the device buffers are reused in stream order; only the pinned staging is sliced per
 // request) and their result blocks are read after a single hipStreamSynchronize; everything else -- and any
@@ -446,15 +519,7 @@ int isccsearch_search_many(isccsearch_handle* h, uint32_t n, isccsearch_request*
     if (!reqs) return fail(-EINVAL, "NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
     HIPOK(hipSetDevice(h->device));
-    struct Slot {
-        std::unique_ptr<Batch> batch;
-        std::vector<uint64_t> hq;
-        size_t block_off = 0, rec_bytes = 0;
-        Segment* seg = nullptr;
-        bool small = false, spec = false;
-        uint32_t len = 0;      // compared prefix length of the request (the hint is kept per length)
-    };
-    std::vector<Slot> slots(n);
+    std::vector<ManySlot> slots(n);
     std::vector<bool> deferred(n, false);
     int first_error = 0;
     auto reject = [&](isccsearch_request& r, int rc) { r.status = rc; if (!first_error) first_error = rc; };
@@ -466,22 +531,14 @@ int isccsearch_search_many(isccsearch_handle* h, uint32_t n, isccsearch_request*
         isccsearch_request& r = reqs[i];
         r.status = 0;
         if (r.nq == 0) continue;
-        if (int rk = check_count(r.k)) { reject(r, rk); continue; }
-        if (r.max_hamming > 256) { reject(r, fail(-EINVAL, "max_hamming %d exceeds 256", r.max_hamming)); continue; }
-        if (!r.q_words || !r.out_keys || !r.out_hamming || !r.out_prefix_bits || !r.out_count) { reject(r, fail(-EINVAL, "NULL argument")); continue; }
         Table* tp;
-        int rc = get_table(h, r.table, tp);
-        if (!rc) rc = check_query_lengths(*tp, r.nq, r.q_nbytes);
-        if (rc) { reject(r, rc); continue; }
-        const Table& t = *tp;
-        if (t.segments() != 1 || first_other_length(t, r.nq, r.q_nbytes) != r.nq || r.nq > QB_MAX) continue;     // ordinary path below
+        if (int rc = check_request(h, r, tp)) { reject(r, rc); continue; }
+        if (tp->segments() != 1 || first_other_length(*tp, r.nq, r.q_nbytes) != r.nq || r.nq > QB_MAX) continue;     // ordinary path below
         deferred[i] = true;
-        Slot& sl = slots[i];
-        sl.rec_bytes = (size_t)r.nq * r.k * sizeof(isk::Record);
-        const size_t bytes = (sl.rec_bytes + ((size_t)r.nq + flag_slots_for(r.nq)) * sizeof(uint32_t) + 15) & ~(size_t)15;
-        sl.block_off = block_total;
-        block_total += bytes;
-        block_max = std::max(block_max, bytes);
+        slots[i].blk = ResultBlock{r.nq, r.k};
+        slots[i].off = block_total;
+        block_total += slots[i].blk.slice_bytes();
+        block_max = std::max(block_max, slots[i].blk.slice_bytes());
         pq_words += staged_words_for(r.nq);
     }
     int rc;
@@ -496,30 +553,27 @@ int isccsearch_search_many(isccsearch_handle* h, uint32_t n, isccsearch_request*
         if (!deferred[i]) continue;
         isccsearch_request& r = reqs[i];
         Table& t = *h->tables[r.table];
-        Slot& sl = slots[i];
-        const uint32_t len = t.metric == ISCCSEARCH_METRIC_NPHD ? r.q_nbytes[0] : (uint32_t)t.max_bytes;
-        isk::Record* const d_rec = reinterpret_cast<isk::Record*>(h->d_block.p);
-        uint32_t* const d_cnt = reinterpret_cast<uint32_t*>(h->d_block.p + sl.rec_bytes);
-        uint32_t* const p_cnt = reinterpret_cast<uint32_t*>(h->p_block.p + sl.block_off + sl.rec_bytes);
-        sl.batch.reset(new Batch(h, t, r.nq, len, r.k, d_rec, d_cnt));
+        ManySlot& sl = slots[i];
+        sl.len = t.metric == ISCCSEARCH_METRIC_NPHD ? r.q_nbytes[0] : (uint32_t)t.max_bytes;
+        sl.batch.reset(new Batch(h, t, r.nq, sl.len, r.k, sl.blk.records(h->d_block.p), sl.blk.counts(h->d_block.p)));
         Batch& b = *sl.batch;
         b.radius = r.max_hamming < 0 ? -1 : r.max_hamming;
-        // small top-k batches: the speculative single pass of search_locked (see there), verified in pass 3a
+        // small top-k batches: the speculative single pass of search_locked (LockedBatch::choose), verified in pass 3a.  Not as there:
+        // the hints of a segment small enough for the one-launch search are kept and used too, ...
         sl.seg = t.sole_segment();
-        sl.small = r.max_hamming < 0 && r.nq <= (uint32_t)h->opt.spec_max_queries && sl.seg && r.k <= sl.seg->n;
-        sl.len = len;
-        sl.spec = sl.small && h->opt.speculate && sl.seg->hint(r.nq, len).ready(r.k);
-        if (sl.spec) b.radius = (int)sl.seg->hint(r.nq, len).tau;
+        sl.small = hints_serve(h, sl.seg, r.k, b.radius, /*skip_one_launch=*/false) && r.nq <= (uint32_t)h->opt.spec_max_queries;
+        // ... and a request speculates by radius or not at all: one above spec_max_queries neither starts its pass under a hint nor seeds one
+        sl.tau = ready_hint(h, sl.seg, r.nq, sl.len, r.k, /*allowed=*/sl.small);
+        if (sl.tau >= 0) b.radius = sl.tau;
         b.pq_off = pq_off;
-        b.d_flags = d_cnt + r.nq;
-        b.h_flags = p_cnt + r.nq;
+        b.d_flags = sl.blk.flags(h->d_block.p);
+        b.h_flags = sl.blk.flags(h->p_block.p + sl.off);
         pq_off += staged_words_for(r.nq);
         sl.hq.assign(r.q_words, r.q_words + (size_t)r.nq * t.max_words);
         h->stats.searches += 1;
         h->stats.queries += r.nq;
         if ((rc = b.begin(sl.hq.data()))) return rc;
-        const size_t bytes = sl.rec_bytes + ((size_t)r.nq + b.flag_words()) * sizeof(uint32_t);
-        HIPOK(hipMemcpyAsync(h->p_block.p + sl.block_off, h->d_block.p, bytes, hipMemcpyDeviceToHost, h->stream));
+        HIPOK(hipMemcpyAsync(h->p_block.p + sl.off, h->d_block.p, sl.blk.bytes_with(b.flag_words()), hipMemcpyDeviceToHost, h->stream));
     }
     HIPOK(hipStreamSynchronize(h->stream));
 
@@ -530,16 +584,14 @@ int isccsearch_search_many(isccsearch_handle* h, uint32_t n, isccsearch_request*
         isccsearch_request& r = reqs[i];
         if (r.status || r.nq == 0) continue;
         if (!deferred[i]) { ordinary[i] = true; continue; }
-        Batch& b = *slots[i].batch;
-        const isk::Record* p_rec = reinterpret_cast<const isk::Record*>(h->p_block.p + slots[i].block_off);
-        const uint32_t* p_cnt = reinterpret_cast<const uint32_t*>(h->p_block.p + slots[i].block_off + slots[i].rec_bytes);
-        Slot& sl = slots[i];
-        if (sl.spec) {
-            if (b.complete(p_cnt, sl.seg->n)) h->stats.spec_hits += 1;
-            else { h->stats.spec_misses += 1; sl.seg->hint(r.nq, sl.len).miss(); ordinary[i] = true; respec[i] = false; continue; }      // (the ordinary path re-seeds the radius)
-        }
+        ManySlot& sl = slots[i];
+        Batch& b = *sl.batch;
+        const isk::Record* p_rec = sl.blk.records(h->p_block.p + sl.off);
+        const uint32_t* p_cnt = sl.blk.counts(h->p_block.p + sl.off);
+        // (after a miss the ordinary path re-seeds the radius)
+        if (sl.tau >= 0 && !count_verdict(h, sl.seg->hint(r.nq, sl.len), b.complete(p_cnt, sl.seg->n))) { ordinary[i] = true; respec[i] = false; continue; }
         if (b.any_flag()) { ordinary[i] = true; continue; }   // rare: exact fallback through the normal path
-        if (sl.small && !b.jobs.empty()) record_hint(sl.seg->hint(r.nq, sl.len), sl.spec, r.nq, r.k, p_cnt, p_rec, nullptr);
+        if (sl.small && !b.jobs.empty()) record_hint(sl.seg->hint(r.nq, sl.len), sl.tau >= 0, r.nq, r.k, p_cnt, p_rec, nullptr);
         unpack_records(p_rec, p_cnt, r.nq, r.k, h->tables[r.table]->key_words, nullptr, r.out_keys, r.out_hamming, r.out_prefix_bits, r.out_count);
     }
     // pass 3b: overflowed and non-deferred requests run the ordinary pipeline
@@ -547,10 +599,8 @@ int isccsearch_search_many(isccsearch_handle* h, uint32_t n, isccsearch_request*
         if (!ordinary[i]) continue;
         isccsearch_request& r = reqs[i];
         if (!deferred[i]) h->stats.searches += 1;
-        h->spec_suppress = !respec[i];
         rc = search_locked(h, r.table, r.nq, r.q_words, r.q_nbytes, r.k, r.max_hamming < 0 ? -1 : r.max_hamming,
-                           SearchOut::lists(r.out_keys, r.out_hamming, r.out_prefix_bits, r.out_count));
-        h->spec_suppress = false;
+                           SearchOut::lists(r.out_keys, r.out_hamming, r.out_prefix_bits, r.out_count), /*may_speculate=*/respec[i]);
         if (rc) reject(r, rc);
     }
     return first_error;
