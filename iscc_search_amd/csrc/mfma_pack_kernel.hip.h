@@ -24,7 +24,7 @@
 // and the compare); the first and the last group of a step, whose MFMAs / fold stand alone, are padded with s_nop.
 //
 // d2 = +64 (query == 0 against a row of all ones) would carry into the exponent and halve the resolution of the low half:
-// the host routes a batch holding an all-zero 64-bit query to mfma_scan_kernel (Batch::begin, isccsearch.hip).
+// the host routes a batch holding an all-zero 64-bit query to mfma_scan_kernel (Batch::plan, batch.hip.h).
 #pragma once
 
 #include "mfma_common.hip.h"

@@ -48,28 +48,19 @@
 
 namespace isk {
 
-template <int MODE>
-static void launch_pack3_mode(dim3 grid, size_t lds, hipStream_t st, const ScanParams& p, uint32_t groups) {
-    if (groups & 1) hipLaunchKernelGGL((mfma_pack3_kernel<MODE, true>), grid, dim3(MBLOCK), lds, st, p, groups);
-    else hipLaunchKernelGGL((mfma_pack3_kernel<MODE, false>), grid, dim3(MBLOCK), lds, st, p, groups);
-}
-
 template <int DEPTH, int G>
 static void launch_pack_depth(int mode, dim3 grid, size_t lds, hipStream_t st, const ScanParams& p, uint32_t groups) {
-    if (mode == MODE_COLLECT) hipLaunchKernelGGL((mfma_pack_kernel<MODE_COLLECT, DEPTH, G>), grid, dim3(MBLOCK), lds, st, p, groups);
-    else if (mode == MODE_STRETCH) hipLaunchKernelGGL((mfma_pack_kernel<MODE_STRETCH, DEPTH, G>), grid, dim3(MBLOCK), lds, st, p, groups);
-    else if (mode == MODE_SELF) hipLaunchKernelGGL((mfma_pack_kernel<MODE_SELF, DEPTH, G>), grid, dim3(MBLOCK), lds, st, p, groups);
-    else hipLaunchKernelGGL((mfma_pack_kernel<MODE_BOTH, DEPTH, G>), grid, dim3(MBLOCK), lds, st, p, groups);
+    with_mode(mode, [&](auto m) { hipLaunchKernelGGL((mfma_pack_kernel<decltype(m)::value, DEPTH, G>), grid, dim3(MBLOCK), lds, st, p, groups); });
 }
 
 static int launch_pack(int mode, dim3 grid, size_t lds, hipStream_t st, const ScanParams& p, uint32_t groups, bool pack3) {
     if (pack3 && mfma_pack3_fits(groups)) {
         lds += P3_LDS_EXTRA;
         if (lds > (size_t)MFMA_MAX_LDS) return (int)hipErrorInvalidValue;
-        if (mode == MODE_COLLECT) launch_pack3_mode<MODE_COLLECT>(grid, lds, st, p, groups);
-        else if (mode == MODE_STRETCH) launch_pack3_mode<MODE_STRETCH>(grid, lds, st, p, groups);
-        else if (mode == MODE_SELF) launch_pack3_mode<MODE_SELF>(grid, lds, st, p, groups);
-        else launch_pack3_mode<MODE_BOTH>(grid, lds, st, p, groups);
+        with_mode(mode, [&](auto m) {
+            if (groups & 1) hipLaunchKernelGGL((mfma_pack3_kernel<decltype(m)::value, true>), grid, dim3(MBLOCK), lds, st, p, groups);
+            else hipLaunchKernelGGL((mfma_pack3_kernel<decltype(m)::value, false>), grid, dim3(MBLOCK), lds, st, p, groups);
+        });
         return 0;
     }
     if (lds > (size_t)MFMA_MAX_LDS) return (int)hipErrorInvalidValue;
@@ -81,17 +72,6 @@ static int launch_pack(int mode, dim3 grid, size_t lds, hipStream_t st, const Sc
         case 4: launch_pack_depth<4, 4>(mode, grid, lds, st, p, groups); break;
         default: launch_pack_depth<1, 0>(mode, grid, lds, st, p, groups);
     }
-    return 0;
-}
-
-template <int W>
-static int launch_w(int mode, dim3 grid, size_t lds, hipStream_t st, const ScanParams& p, uint32_t groups) {
-    // a chunk's LDS image is <= 40 KB: inside the default dynamic-LDS limit, no per-device function attribute to set
-    if (lds > (size_t)MFMA_MAX_LDS) return (int)hipErrorInvalidValue;
-    if (mode == MODE_COLLECT) hipLaunchKernelGGL((mfma_scan_kernel<W, MODE_COLLECT>), grid, dim3(MBLOCK), lds, st, p, groups);
-    else if (mode == MODE_STRETCH) hipLaunchKernelGGL((mfma_scan_kernel<W, MODE_STRETCH>), grid, dim3(MBLOCK), lds, st, p, groups);
-    else if (mode == MODE_SELF) hipLaunchKernelGGL((mfma_scan_kernel<W, MODE_SELF>), grid, dim3(MBLOCK), lds, st, p, groups);
-    else hipLaunchKernelGGL((mfma_scan_kernel<W, MODE_BOTH>), grid, dim3(MBLOCK), lds, st, p, groups);
     return 0;
 }
 
@@ -130,12 +110,12 @@ int launch_mfma_scan(int W, int mode, bool pack, uint32_t blocks_x, uint32_t gro
     const dim3 grid(blocks_x, chunks);
     const size_t lds = mfma_lds_bytes(W, groups);
     if (pack) return W == 1 ? launch_pack(mode, grid, lds, st, p, groups, pack3) : (int)hipErrorInvalidValue;
-    switch (W) {
-        case 1: return launch_w<1>(mode, grid, lds, st, p, groups);
-        case 2: return launch_w<2>(mode, grid, lds, st, p, groups);
-        case 3: return launch_w<3>(mode, grid, lds, st, p, groups);
-        default: return launch_w<4>(mode, grid, lds, st, p, groups);
-    }
+    // a chunk's LDS image is <= 40 KB: inside the default dynamic-LDS limit, no per-device function attribute to set
+    if (lds > (size_t)MFMA_MAX_LDS) return (int)hipErrorInvalidValue;
+    with_words(W, [&](auto w) { with_mode(mode, [&](auto m) {
+        hipLaunchKernelGGL((mfma_scan_kernel<decltype(w)::value, decltype(m)::value>), grid, dim3(MBLOCK), lds, st, p, groups);
+    }); });
+    return 0;
 }
 
 template <int W>
@@ -149,15 +129,8 @@ int launch_mfma_join(int W, bool cross, uint32_t blocks_x, uint32_t chunks, uint
     static_assert(MFMA_JOIN_WAVES == MBLOCK / 64, "the grid rule counts the kernel's waves");
     const size_t lds = mfma_lds_bytes(W, groups);
     // the group pipeline walks pairs of groups; grid.y is 16 bits; the LINK form is the self-join's only
-    if (lds > (size_t)MFMA_MAX_LDS || groups < 2 || (groups & 1) || !blocks_x || !chunks || chunks > MFMA_JOIN_MAX_CHUNKS || (link && cross)) return (int)hipErrorInvalidValue;
-    const dim3 grid(blocks_x, chunks);
-    switch (W) {
-        case 1: launch_join_w<1>(cross, link, grid, lds, st, p, groups); break;
-        case 2: launch_join_w<2>(cross, link, grid, lds, st, p, groups); break;
-        case 3: launch_join_w<3>(cross, link, grid, lds, st, p, groups); break;
-        case 4: launch_join_w<4>(cross, link, grid, lds, st, p, groups); break;
-        default: return (int)hipErrorInvalidValue;
-    }
+    if (W < 1 || W > 4 || lds > (size_t)MFMA_MAX_LDS || groups < 2 || (groups & 1) || !blocks_x || !chunks || chunks > MFMA_JOIN_MAX_CHUNKS || (link && cross)) return (int)hipErrorInvalidValue;
+    with_words(W, [&](auto w) { launch_join_w<decltype(w)::value>(cross, link, dim3(blocks_x, chunks), lds, st, p, groups); });
     return 0;
 }
 

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace isk {
 
@@ -23,6 +24,31 @@ constexpr int MODE_STRETCH = 3;   // as MODE_BOTH, for the stretches of the coll
 constexpr int MODE_SELF = 4;      // single pass with SELF-TIGHTENING thresholds (mfma_scan.hip): candidates are appended and counted
                                   // in a cumulative histogram; the lane that makes "k rows within t" true lowers the live
                                   // threshold of its query, and every wave re-reads the live thresholds once per step
+
+// A run-time value as a template argument (host side): each helper calls the generic lambda `f` with the value as a std::integral_constant
+// -- decltype(c)::value of f's parameter `auto c` is the constant -- and returns what f returns.  A call site keeps a combination that has
+// no kernel out of the build with `if constexpr`.
+template <int V> using int_c = std::integral_constant<int, V>;
+template <typename F> auto with_mode(int mode, F&& f) {          // a launch mode (MODE_HIST has no launch of its own: every other value is MODE_BOTH)
+    switch (mode) {
+        case MODE_COLLECT: return f(int_c<MODE_COLLECT>{});
+        case MODE_STRETCH: return f(int_c<MODE_STRETCH>{});
+        case MODE_SELF: return f(int_c<MODE_SELF>{});
+        default: return f(int_c<MODE_BOTH>{});
+    }
+}
+template <typename F> auto with_words(int W, F&& f) {            // compared code words: 1 .. 4
+    switch (W) {
+        case 1: return f(int_c<1>{});
+        case 2: return f(int_c<2>{});
+        case 3: return f(int_c<3>{});
+        default: return f(int_c<4>{});
+    }
+}
+template <typename F> auto with_key_words(int key_words, F&& f) {   // words of a table's keys: 1 or 2
+    if (key_words == 2) return f(int_c<2>{});
+    return f(int_c<1>{});
+}
 
 struct ScanParams {
     const uint64_t* col[4];   // segment columns (word-major)

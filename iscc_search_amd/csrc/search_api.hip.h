@@ -103,7 +103,7 @@ struct LockedBatch : LockedCall {
     }
 
     // (tight: the batch's one job would take the single pass, and that pass is ONE launch of mfma_pack3_kernel)
-    bool runs_pack3() { batch.plan(hq.data()); return batch.jobs.size() == 1 && batch.single_pass(batch.jobs[0]) && batch.pack3_pass(batch.jobs[0]); }
+    bool runs_pack3() { batch.plan(hq.data()); return batch.jobs.size() == 1 && batch.path(batch.jobs[0]) == Batch::Path::single && batch.pack3_pass(batch.jobs[0]); }
     // choose: the kind of speculation and the value it runs under
     void choose() {
         // Speculation: ONE pass under where an earlier batch of this size and query length ended, verified by one look at its
