@@ -396,6 +396,52 @@ int isccsearch_join_components(isccsearch_handle* h, uint32_t table, const int16
                                uint64_t n_live, const uint64_t* live_keys, const uint32_t* live_labels,
                                uint32_t n_labels, uint32_t* parent /* in/out [n_labels] */, uint64_t* out_links);
 
+/* The pairs of ASSETS that share chunks: a self-join of ONE simprint table (HAMMING, key_words 2, one code length of ndim bits),
+ * aggregated on the device.  A row is a chunk; its asset is the first key word (the ISCC-ID body), the second is
+ * offset << 32 | size.
+ *   asset_keys[n_assets]  strictly ascending: the assets that take part.  The LABEL of an asset is its rank in this array.  A
+ *                         row is live if its asset is listed; a listed asset the table does not hold has no rows.
+ *   max_hamming           the radius, in bits over the ndim bits (>= 0; values above ndim mean ndim).
+ *   max_doc_freq          a live row is a STOP CHUNK if its entry in the segment's frequency column, built with dup_limit (the
+ *   dup_limit             value isccsearch_get_freq returns for it: distinct assets among the first dup_limit rows of equal code
+ *                         by ascending key), is greater than max_doc_freq.  max_doc_freq 0: no cut, and the column is neither
+ *                         read nor built (dup_limit is then not looked at).
+ * A chunk pair is an unordered pair of rows (i, j), both live, neither a stop chunk, asset(i) != asset(j), hamming(i, j) <=
+ * max_hamming.  Pairs of rows of one asset, rows of unlisted assets and stop chunks are compared, but take no room and are not
+ * counted.
+ *   out_pairs[2 * capacity]  one record per ORDERED pair of assets (src, dst) with at least one chunk pair -- so every unordered
+ *                         pair of assets has two, (a, b) and (b, a) -- sorted ascending by (src, dst).  Every field is an integer
+ *                         and defined by the set of chunk pairs alone: the records do not depend on which kernel ran (see the
+ *                         options join_mfma, join_mfma_min_rows) or on the order in which pairs were found.
+ *   out_chunks[n_assets]  live rows per asset, stop chunks included: the denominator of a coverage.
+ *   out_info[4]           {chunk pairs found, records written, live rows, stop chunks}.
+ * Capacity protocol as for isccsearch_join_within, counted in chunk pairs: more than `capacity` return -ENOSPC with out_info[0]
+ * exact and every other output unspecified, and a retry with exactly that capacity succeeds; pairs past the capacity are
+ * counted and not written.  Device memory: 192 bytes per chunk pair of the capacity, 4 bytes per row and 12 per asset, kept by
+ * the handle as its other scratch buffers are.
+ * -EINVAL, each naming the offending index, all checked on the host before anything is launched, the outputs left untouched:
+ * a NULL argument (out_pairs may be NULL only when capacity is 0); a table that is not HAMMING with key_words 2; n_assets = 0 or
+ * 2^32 - 1 (the value that means "no label"); asset_keys not strictly ascending; max_hamming < 0; max_doc_freq > dup_limit when
+ * max_doc_freq > 0 (the column counts no further than dup_limit rows).  -E2BIG, checked likewise: a segment of 2^32 rows or more
+ * (row numbers travel as 32 bits), a capacity of 2^31 chunk pairs or more (their hits are numbered with 32 bits).
+ * One lock covers the call; everything runs on the handle's one stream -- labelling, the join launch (the one
+ * isccsearch_join_within would make for the table), sort, reduction -- and ONE synchronisation comes before the results are copied.
+ * No reference counterpart (the reference has no index-wide join: it finds shared chunks one query asset at a time). */
+typedef struct isccsearch_overlap {
+    uint32_t src, dst;       /* labels (ranks in asset_keys) */
+    uint32_t matched;        /* distinct rows of src with >= 1 row of dst within max_hamming */
+    uint32_t reserved;       /* 0 */
+    uint64_t sum_hamming;    /* over those rows, the SMALLEST distance to a row of dst, summed */
+    uint64_t chunk_pairs;    /* chunk pairs between the two assets (equal in both directions) */
+} isccsearch_overlap;        /* 32 bytes */
+int isccsearch_join_overlaps(isccsearch_handle* h, uint32_t table, int32_t max_hamming,
+                             uint32_t max_doc_freq, uint32_t dup_limit,
+                             uint32_t n_assets, const uint64_t* asset_keys,
+                             uint64_t capacity,                    /* chunk pairs */
+                             isccsearch_overlap* out_pairs,        /* [2 * capacity] */
+                             uint32_t* out_chunks,                 /* [n_assets] */
+                             uint64_t* out_info                    /* [4] */);
+
 /* Multi-GPU building blocks (row-range shards, one process per GPU).
  * search_device: same search, results left in caller-provided DEVICE memory
  *   d_records[nq*k] (isccsearch_record), d_counts[nq]; queries must share one byte length.

@@ -38,6 +38,7 @@
 #include "docfreq.h"
 #include "simprint_score.h"
 #include "asset_score.h"
+#include "overlap.h"
 #include "keymap.h"
 
 namespace {
@@ -392,7 +393,13 @@ struct isccsearch_handle {
     // isccsearch_join_components: the caller's live keys and their labels, a label per row (segment by segment), the union-find array
     DevBuf<uint64_t> d_join_live_keys;
     DevBuf<uint32_t> d_join_live_labels, d_join_row_labels, d_join_parent;
-    size_t am_lds_allowed = 0;                   // dynamic LDS the scoring kernel was allowed on this handle's device
+    // isccsearch_join_overlaps: the hits of one call {appended | sorted}, the one-hit records and the reduced ones, rocPRIM's temporary
+    // storage (overlap.hip), chunks per asset; its asset keys go to d_join_live_keys, its row labels to d_join_row_labels
+    DevBuf<iskov::Hit> d_ov_hits;
+    DevBuf<isccsearch_overlap> d_ov_marks, d_ov_records;
+    DevBuf<unsigned char> d_ov_temp;
+    DevBuf<uint32_t> d_ov_chunks;
+    size_t am_lds_allowed = 0;                  // dynamic LDS the scoring kernel was allowed on this handle's device
     // asynchronous device searches: "results ready" for the consumer stream, "query upload done" for the pinned staging
     hipEvent_t ev_done = nullptr, ev_staged = nullptr, ev_producer = nullptr;
     bool ev_staged_pending = false;

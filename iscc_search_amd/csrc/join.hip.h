@@ -22,6 +22,11 @@
 //   path differs: it keeps the pair test and drops the prefix scan, the slots, the key gathers and the stores -- per pair it loads
 //   the two rows' labels (JoinEmit::labels_a / labels_b; UF_NONE: the row takes no part), unites them in JoinEmit::parent
 //   (uf_union of unionfind.hip.h) and counts the pair; one atomic per wave adds the count to JoinEmit::total.
+// join_scan_kernel<W, MASK, false, false, true> (OVERLAP, isccsearch_join_overlaps): the self-join's scan a third time, and only the
+//   emit path differs: per pair it loads the two rows' labels (the ranks of their assets; UF_NONE: the row is not listed or is a
+//   stop chunk) and only a pair of two DIFFERENT labels takes a slot (overlap_pair) -- from the same wave-aggregated counter,
+//   one returned atomic per wave (overlap_slots).  A pair with a slot writes two directed hits (label_i, label_j, row_i, hamming)
+//   and (label_j, label_i, row_j, hamming) with vector stores (overlap_write); overlap.hip sorts and reduces them.
 // Slabs are read up to the next multiple of the slab size: column capacities are multiples of ROW_ALIGN (2 048 rows), which
 // every slab size divides, so those reads stay inside the allocation (rows past n are dropped in the emit path).
 #pragma once
@@ -54,6 +59,9 @@ struct JoinEmit {
     const uint32_t* labels_a;
     const uint32_t* labels_b;
     uint32_t* parent;
+    // the OVERLAP form (isccsearch_join_overlaps): labels_a / labels_b as above (the ranks of the rows' assets); `total` counts the pairs
+    // of two different labels, `capacity` of them have room in out_hits, two directed hits (src, dst, row, hamming) each
+    uint4* out_hits;              // [2 * capacity]
 };
 struct JoinParams {
     const uint64_t* col_a[4];     // side A: rows held in SGPRs, TQ per block
@@ -89,9 +97,44 @@ __device__ __forceinline__ uint32_t link_pair(const JoinEmit& e, uint64_t i, uin
     return 1u;
 }
 
-template <int W, bool MASK, bool CROSS = false, bool LINK = false>
+// OVERLAP form of both emit paths, per pair (held / SGPR-side row i, streamed row j): the two rows' labels; true if the pair takes a
+// slot -- both rows have a label (their assets are listed, neither is a stop chunk) and the labels differ
+__device__ __forceinline__ bool overlap_pair(const JoinEmit& e, uint64_t i, uint64_t j, uint32_t& la, uint32_t& lb) {
+    la = e.labels_a[i];
+    lb = e.labels_b[j];
+    return la != UF_NONE && lb != UF_NONE && la != lb;
+}
+// ... the slots of one wave (one ring walk): lane `lane` has counted c pairs; ONE returned atomic on JoinEmit::total for all of them.
+// `slot`: the first of this lane's c slots.  False when no lane of the wave has a pair.
+__device__ __forceinline__ bool overlap_slots(const JoinEmit& e, uint32_t c, uint32_t lane, uint64_t& slot) {
+    uint32_t incl = c;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = (uint32_t)__shfl_up((int)incl, d, 64);
+        if (lane >= (uint32_t)d) incl += t;
+    }
+    const uint32_t wave_total = (uint32_t)__shfl((int)incl, 63, 64);
+    if (wave_total == 0) return false;
+    uint32_t lo = 0, hi = 0;
+    if (lane == 0) {
+        const unsigned long long b = atomicAdd(e.total, (unsigned long long)wave_total);
+        lo = (uint32_t)b; hi = (uint32_t)(b >> 32);
+    }
+    slot = ((uint64_t)(uint32_t)__shfl((int)hi, 0, 64) << 32 | (uint32_t)__shfl((int)lo, 0, 64)) + (incl - c);
+    return true;
+}
+// ... the two directed hits of the pair that holds `slot` (rows travel as 32 bits: the host refuses longer segments); a pair past
+// the capacity was counted and is not written
+__device__ __forceinline__ void overlap_write(const JoinEmit& e, uint64_t slot, uint32_t la, uint32_t lb, uint64_t i, uint64_t j, uint32_t h) {
+    if (slot >= e.capacity) return;
+    e.out_hits[2 * slot] = make_uint4(la, lb, (uint32_t)i, h);
+    e.out_hits[2 * slot + 1] = make_uint4(lb, la, (uint32_t)j, h);
+}
+
+template <int W, bool MASK, bool CROSS = false, bool LINK = false, bool OVERLAP = false>
 __global__ __launch_bounds__(BLOCK) void join_scan_kernel(const JoinParams p) {
     static_assert(!(LINK && CROSS), "components are those of one table");
+    static_assert(!(OVERLAP && (CROSS || LINK)), "overlaps are those of one table, and a form of their own");
     constexpr int TQ = JoinCfg<W>::TQ, U = JoinCfg<W>::U;
     constexpr uint32_t SLAB = JoinCfg<W>::SLAB;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -164,12 +207,34 @@ __global__ __launch_bounds__(BLOCK) void join_scan_kernel(const JoinParams p) {
                 for (int rr = 0; rr < 2; ++rr) {
                     const bool pair = is_pair(i, base + u * 128 + rr, dist(r, u, rr, al, ah));
                     if (LINK) c += pair ? link_pair(e, i, base + u * 128 + rr) : 0u;
+                    else if (OVERLAP) { uint32_t la, lb; c += pair && overlap_pair(e, i, base + u * 128 + rr, la, lb) ? 1u : 0u; }
                     else c += pair ? 1u : 0u;
                 }
         }
         if (LINK) {                                // one pass: the labelled pairs are united as they are counted, nothing is written
             const uint32_t linked = wave_sum(c);
             if (linked != 0 && lane == 0) atomicAdd(e.total, (unsigned long long)linked);
+            return;
+        }
+        if (OVERLAP) {                             // the second pass writes the hits of the pairs the first one counted (at most TQ trips, as the first)
+            uint64_t slot;
+            if (!overlap_slots(e, c, lane, slot) || c == 0) return;
+#pragma unroll 1
+            for (uint64_t i = a0; i < a_end; ++i) {
+                uint32_t al[W], ah[W];
+                a_row(i, al, ah);
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+#pragma unroll
+                    for (int rr = 0; rr < 2; ++rr) {
+                        const uint64_t j = base + u * 128 + rr;
+                        const uint32_t h = dist(r, u, rr, al, ah);
+                        uint32_t la, lb;
+                        if (!is_pair(i, j, h) || !overlap_pair(e, i, j, la, lb)) continue;
+                        overlap_write(e, slot, la, lb, i, j, h);
+                        ++slot;
+                    }
+            }
             return;
         }
         // wave-inclusive prefix of the counts; lane 63 holds the wave's total

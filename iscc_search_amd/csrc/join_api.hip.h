@@ -1,22 +1,23 @@
 // join_api.hip.h -- isccsearch_join_within and isccsearch_join_between: the self-join of a table and the cross join of two
 // tables by the XOR + popcount kernel of join.hip.h or, for launches over enough rows, its matrix-core form (mfma_join_kernel.hip.h);
 // and isccsearch_join_components: the self-join's launches in their LINK form, whose pairs are united in a union-find array
-// (unionfind.hip.h) instead of written.
+// (unionfind.hip.h) instead of written; and isccsearch_join_overlaps: the self-join of a simprint table in the launches' OVERLAP form,
+// whose directed hits overlap.hip sorts and reduces to one record per ordered pair of assets.
 // Needs the store of isccsearch.hip (Segment, Table; get_table of store.hip.h) and its scratch buffers.
 namespace {
 // one launch of the join kernel (join.hip.h)
-template <int W, bool CROSS, bool LINK>
+template <int W, bool CROSS, bool LINK, bool OVERLAP>
 void launch_join(const isk::JoinParams& jp, bool mask, uint64_t blocks, hipStream_t stream) {
-    if (mask) hipLaunchKernelGGL((isk::join_scan_kernel<W, true, CROSS, LINK>), dim3((uint32_t)blocks), dim3(isk::BLOCK), 0, stream, jp);
-    else hipLaunchKernelGGL((isk::join_scan_kernel<W, false, CROSS, LINK>), dim3((uint32_t)blocks), dim3(isk::BLOCK), 0, stream, jp);
+    if (mask) hipLaunchKernelGGL((isk::join_scan_kernel<W, true, CROSS, LINK, OVERLAP>), dim3((uint32_t)blocks), dim3(isk::BLOCK), 0, stream, jp);
+    else hipLaunchKernelGGL((isk::join_scan_kernel<W, false, CROSS, LINK, OVERLAP>), dim3((uint32_t)blocks), dim3(isk::BLOCK), 0, stream, jp);
 }
-template <bool CROSS, bool LINK = false>
+template <bool CROSS, bool LINK = false, bool OVERLAP = false>
 void launch_join(uint32_t W, const isk::JoinParams& jp, bool mask, uint64_t blocks, hipStream_t stream) {
     switch (W) {
-        case 1: launch_join<1, CROSS, LINK>(jp, mask, blocks, stream); break;
-        case 2: launch_join<2, CROSS, LINK>(jp, mask, blocks, stream); break;
-        case 3: launch_join<3, CROSS, LINK>(jp, mask, blocks, stream); break;
-        default: launch_join<4, CROSS, LINK>(jp, mask, blocks, stream); break;
+        case 1: launch_join<1, CROSS, LINK, OVERLAP>(jp, mask, blocks, stream); break;
+        case 2: launch_join<2, CROSS, LINK, OVERLAP>(jp, mask, blocks, stream); break;
+        case 3: launch_join<3, CROSS, LINK, OVERLAP>(jp, mask, blocks, stream); break;
+        default: launch_join<4, CROSS, LINK, OVERLAP>(jp, mask, blocks, stream); break;
     }
 }
 constexpr uint32_t join_rows_per_block(uint32_t W) {
@@ -32,6 +33,7 @@ struct JoinPlan {
     std::vector<isk::JoinEmit> emits;
     bool cross = false;
     bool link = false;     // isccsearch_join_components: the LINK form of either kernel (JoinEmit::labels_a, labels_b, parent are set)
+    bool overlap = false;  // isccsearch_join_overlaps: the OVERLAP form of either kernel (JoinEmit::labels_a, labels_b, out_hits are set)
     uint32_t KW = 1;
     uint64_t capacity = 0, cap_alloc = 1;
 };
@@ -127,7 +129,7 @@ int join_run(isccsearch_handle* h, JoinPlan& plan) {
                 for (uint64_t c = 0; c < L.chunks; c += isk::MFMA_JOIN_MAX_CHUNKS) {
                     L.mp.chunk_base = c;
                     const uint32_t chunks = (uint32_t)std::min<uint64_t>(L.chunks - c, isk::MFMA_JOIN_MAX_CHUNKS);
-                    const int lrc = isk::launch_mfma_join((int)L.W, plan.cross, blocks_x, chunks, L.groups, h->stream, L.mp, plan.link);
+                    const int lrc = isk::launch_mfma_join((int)L.W, plan.cross, blocks_x, chunks, L.groups, h->stream, L.mp, plan.link, plan.overlap);
                     if (lrc) return fail(-EINVAL, "the matrix-core join does not take chunks of %u groups of %u words", L.groups, L.W);
                     HIPOK(hipGetLastError());
                     h->stats.join_launches += 1;
@@ -135,7 +137,8 @@ int join_run(isccsearch_handle* h, JoinPlan& plan) {
                 }
                 continue;
             }
-            if (plan.link) launch_join<false, true>(L.W, L.jp, L.mask, L.blocks, h->stream);
+            if (plan.overlap) launch_join<false, false, true>(L.W, L.jp, L.mask, L.blocks, h->stream);
+            else if (plan.link) launch_join<false, true>(L.W, L.jp, L.mask, L.blocks, h->stream);
             else if (plan.cross) launch_join<true>(L.W, L.jp, L.mask, L.blocks, h->stream);
             else launch_join<false>(L.W, L.jp, L.mask, L.blocks, h->stream);
             HIPOK(hipGetLastError());
@@ -337,5 +340,108 @@ extern "C" int isccsearch_join_components(isccsearch_handle* h, uint32_t table, 
     HIPOK(hipMemcpyAsync(flat.data(), h->d_join_parent.p, (size_t)n_labels * 4, hipMemcpyDeviceToHost, h->stream));
     if ((rc = join_total(h, out_links))) return rc;
     memcpy(parent, flat.data(), (size_t)n_labels * 4);
+    return 0;
+}
+
+// The self-join launch of a simprint table's one segment in its OVERLAP form (join_scan_kernel<W, MASK, false, false, true> /
+// mfma_join_kernel<W, false, false, true>, chosen by join_add's rule) between label_chunks_kernel (the host never sees the table's keys)
+// and the aggregation of overlap.hip, all on one stream; the counters and the chunks per asset come back behind ONE synchronisation,
+// then the records are copied.  The hit buffer is filled with ones first, so that the aggregation runs over 2 * capacity slots
+// without the host asking how many were written.  Everything the device code relies on -- asset_keys ascending and fewer than
+// 2^32 - 1 (labels and the bound of the label search), rows and hit positions below 2^32 -- is checked before anything is launched.
+extern "C" int isccsearch_join_overlaps(isccsearch_handle* h, uint32_t table, int32_t max_hamming, uint32_t max_doc_freq, uint32_t dup_limit,
+                             uint32_t n_assets, const uint64_t* asset_keys, uint64_t capacity, isccsearch_overlap* out_pairs,
+                             uint32_t* out_chunks, uint64_t* out_info) {
+    if (!h) return fail(-EINVAL, "handle is NULL");
+    if (!asset_keys || !out_chunks || !out_info) return fail(-EINVAL, "NULL argument");
+    if (capacity && !out_pairs) return fail(-EINVAL, "out_pairs is NULL with capacity %llu", (unsigned long long)capacity);
+    if (n_assets == 0 || n_assets == isk::UF_NONE) return fail(-EINVAL, "n_assets must be in 1 .. 2^32 - 2, got %u", n_assets);
+    for (uint32_t i = 1; i < n_assets; ++i)
+        if (asset_keys[i] <= asset_keys[i - 1])
+            return fail(-EINVAL, "asset_keys must be strictly ascending: asset_keys[%u] <= asset_keys[%u]", i, i - 1);
+    if (max_hamming < 0) return fail(-EINVAL, "max_hamming must be >= 0, got %d", max_hamming);
+    if (max_doc_freq > 0 && max_doc_freq > dup_limit)
+        return fail(-EINVAL, "max_doc_freq %u exceeds dup_limit %u: the frequency column counts no further", max_doc_freq, dup_limit);
+    if (capacity >= (1ull << 31))
+        return fail(-E2BIG, "capacity %llu: the two hits of a chunk pair are numbered with 32 bits", (unsigned long long)capacity);
+    std::lock_guard<std::mutex> lk(h->mu);
+    Table* tp;
+    int rc;
+    if ((rc = get_table(h, table, tp))) return rc;
+    Table& t = *tp;
+    if (t.metric != ISCCSEARCH_METRIC_HAMMING || t.key_words != 2)
+        return fail(-EINVAL, "join_overlaps needs a simprint table (HAMMING, key_words 2), table %u has metric %d and key_words %d", table, t.metric, t.key_words);
+    Segment& s = t.seg[t.max_bytes];
+    if (s.n >= (1ull << 32)) return fail(-E2BIG, "a segment of %llu rows: row numbers travel as 32 bits", (unsigned long long)s.n);
+    HIPOK(hipSetDevice(h->device));
+    // the call's counters {chunk pairs, live rows, stop chunks, records}, asset keys, chunks per asset, row labels; for m = 2 * capacity
+    // hits {appended | sorted}, one-hit records, records and rocPRIM's temporary storage: 192 bytes per chunk pair of the capacity
+    const uint64_t m = 2 * capacity;
+    size_t temp_bytes = 0;
+    if ((rc = h->d_join_total.ensure(4))) return rc;
+    if ((rc = h->d_join_live_keys.ensure(n_assets))) return rc;
+    if ((rc = h->d_ov_chunks.ensure(n_assets))) return rc;
+    if ((rc = h->d_join_row_labels.ensure(std::max<uint64_t>(s.n, 1)))) return rc;
+    if (m) {
+        std::string err;
+        if ((rc = iskov::aggregate_temp_bytes(m, &temp_bytes, &err))) return fail(rc, "%s", err.c_str());
+        if ((rc = h->d_ov_hits.ensure(2 * m))) return rc;
+        if ((rc = h->d_ov_marks.ensure(m))) return rc;
+        if ((rc = h->d_ov_records.ensure(m))) return rc;
+        if ((rc = h->d_ov_temp.ensure(std::max<size_t>(temp_bytes, 1)))) return rc;
+    }
+    // (the frequency column is built by a call of its own that drains the stream: nothing of this call is queued yet)
+    if (max_doc_freq > 0 && s.n && (rc = ensure_freq_column(h, t, s, dup_limit))) return rc;
+    unsigned long long* const counters = reinterpret_cast<unsigned long long*>(h->d_join_total.p);
+    HIPOK(hipMemsetAsync(counters, 0, 4 * 8, h->stream));
+    HIPOK(hipMemsetAsync(h->d_ov_chunks.p, 0, (size_t)n_assets * 4, h->stream));
+    if (m) HIPOK(hipMemsetAsync(h->d_ov_hits.p, 0xFF, m * sizeof(iskov::Hit), h->stream));
+    HIPOK(hipMemcpyAsync(h->d_join_live_keys.p, asset_keys, (size_t)n_assets * 8, hipMemcpyHostToDevice, h->stream));
+    if (s.n) {
+        isk::OverlapLabelParams lp{s.keys, h->d_join_live_keys.p, max_doc_freq > 0 ? s.freq : nullptr, h->d_join_row_labels.p, h->d_ov_chunks.p,
+                                   counters, s.n, n_assets, max_doc_freq};
+        const uint32_t blocks = (uint32_t)std::min<uint64_t>((s.n + isk::BLOCK - 1) / isk::BLOCK, 1u << 16);
+        hipLaunchKernelGGL(isk::label_chunks_kernel, dim3(blocks), dim3(isk::BLOCK), 0, h->stream, lp);
+        HIPOK(hipGetLastError());
+    }
+    if (s.n >= 2) {
+        JoinPlan plan;
+        plan.overlap = true;
+        plan.KW = 2;
+        plan.capacity = capacity;
+        if ((rc = join_add(h, plan, s, s, (uint32_t)t.max_bytes, max_hamming, true, false))) return rc;
+        isk::JoinEmit& e = plan.emits.back();
+        e.out_keys_a = e.out_keys_b = nullptr;        // the pair form's outputs: not this form's
+        e.out_hamming = nullptr;
+        e.out_prefix_bits = nullptr;
+        e.labels_a = e.labels_b = h->d_join_row_labels.p;
+        e.out_hits = reinterpret_cast<uint4*>(h->d_ov_hits.p);
+        if ((rc = join_run(h, plan))) return rc;
+    }
+    if (m) {
+        std::string err;
+        if ((rc = iskov::aggregate(h->d_ov_hits.p, h->d_ov_hits.p + m, h->d_ov_marks.p, h->d_ov_records.p, counters + 3, m, h->d_ov_temp.p,
+                                   temp_bytes, h->stream, &err)))
+            return fail(rc, "%s", err.c_str());
+    }
+    // the call's one synchronisation; the outputs change only from here on
+    uint64_t got[4] = {0, 0, 0, 0};
+    std::vector<uint32_t> chunks(n_assets);
+    HIPOK(hipMemcpyAsync(got, counters, sizeof got, hipMemcpyDeviceToHost, h->stream));
+    HIPOK(hipMemcpyAsync(chunks.data(), h->d_ov_chunks.p, (size_t)n_assets * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPOK(hipStreamSynchronize(h->stream));
+    const uint64_t total = got[0];
+    if (total > capacity) {
+        out_info[0] = total;
+        return fail(-ENOSPC, "%llu chunk pairs do not fit the capacity of %llu", (unsigned long long)total, (unsigned long long)capacity);
+    }
+    // (slots were left unused: the run of ones behind the hits reduced to one more record, the last)
+    const uint64_t n_records = m ? got[3] - (total < capacity ? 1 : 0) : 0;
+    if (n_records) {
+        HIPOK(hipMemcpyAsync(out_pairs, h->d_ov_records.p, n_records * sizeof(isccsearch_overlap), hipMemcpyDeviceToHost, h->stream));
+        HIPOK(hipStreamSynchronize(h->stream));
+    }
+    memcpy(out_chunks, chunks.data(), (size_t)n_assets * 4);
+    out_info[0] = total; out_info[1] = n_records; out_info[2] = got[1]; out_info[3] = got[2];
     return 0;
 }

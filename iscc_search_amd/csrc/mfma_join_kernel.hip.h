@@ -19,6 +19,9 @@
 //   the part the SGPR side has in join_scan_kernel).  Pairs past `capacity` are counted and not written.
 //   LINK (mfma_join_kernel<W, false, true>, isccsearch_join_components): the ring is walked ONCE -- per pair the two rows' labels are
 //   loaded and united (link_pair of join.hip.h), the labelled pairs counted, one atomic per walk; nothing is written.
+//   OVERLAP (mfma_join_kernel<W, false, false, true>, isccsearch_join_overlaps): the ring is walked twice as for the pairs -- only a pair
+//   whose rows carry two different labels is counted (overlap_pair of join.hip.h), one returned atomic per walk (overlap_slots), and
+//   the second walk writes the pair's two directed hits (overlap_write).
 #pragma once
 
 #include "join.hip.h"
@@ -28,9 +31,10 @@
 namespace isk {
 
 // LDS image of a chunk: B fragments [groups][W][64] v4i | thr[groups * 32] (float) | popc[groups * 32] | the waves' rings
-template <int W, bool CROSS, bool LINK = false>
+template <int W, bool CROSS, bool LINK = false, bool OVERLAP = false>
 __global__ __launch_bounds__(MBLOCK, mfma_min_waves<W>()) void mfma_join_kernel(const MfmaJoinParams p, const uint32_t groups) {
     static_assert(!(LINK && CROSS), "components are those of one table");
+    static_assert(!(OVERLAP && (CROSS || LINK)), "overlaps are those of one table, and a form of their own");
     constexpr int MT = 2;       // row tiles (32 rows) per wave and step
     constexpr uint32_t WAVES = MBLOCK / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -124,6 +128,26 @@ __global__ __launch_bounds__(MBLOCK, mfma_min_waves<W>()) void mfma_join_kernel(
             }
             const uint32_t linked = wave_sum(c);
             if (linked != 0 && lane == 0) atomicAdd(e.total, (unsigned long long)linked);
+            rcount = 0;
+            return;
+        }
+        if (OVERLAP) {                             // two walks (each rcount / 2 <= RING_E / 2 trips): count the pairs of two different labels, one atomic, write their hits
+            const JoinEmit& e = *p.e;
+            for (uint32_t en = 0; en < rcount; en += 2) {
+                uint64_t i, j;
+                uint32_t hd, la, lb;
+                c += pair_at(en + sub, i, j, hd) && overlap_pair(e, i, j, la, lb) ? 1u : 0u;
+            }
+            uint64_t slot;
+            if (overlap_slots(e, c, lane, slot)) {
+                for (uint32_t en = 0; c != 0 && en < rcount; en += 2) {
+                    uint64_t i, j;
+                    uint32_t hd, la, lb;
+                    if (!pair_at(en + sub, i, j, hd) || !overlap_pair(e, i, j, la, lb)) continue;
+                    overlap_write(e, slot, la, lb, i, j, hd);
+                    ++slot;
+                }
+            }
             rcount = 0;
             return;
         }

@@ -55,6 +55,8 @@ inline uint32_t mfma_join_blocks_x(uint64_t n_streamed) {
 // rows of the held segment per chunk: mfma_groups_per_chunk(W, n_held, false) * 32
 // grid = (blocks_x, chunks); p.chunk_base names the first of them.  Returns 0 or a hipError_t as launch_mfma_scan does
 // link: mfma_join_kernel<W, false, true>, whose ring walk unites the pairs' labels (JoinEmit::labels_a, labels_b, parent) and writes no pair
-int launch_mfma_join(int W, bool cross, uint32_t blocks_x, uint32_t chunks, uint32_t groups, hipStream_t st, const MfmaJoinParams& p, bool link = false);
+// overlap: mfma_join_kernel<W, false, false, true>, whose ring walk writes two directed hits per pair of two different labels (JoinEmit::out_hits)
+int launch_mfma_join(int W, bool cross, uint32_t blocks_x, uint32_t chunks, uint32_t groups, hipStream_t st, const MfmaJoinParams& p, bool link = false,
+                     bool overlap = false);
 
 }  // namespace isk

@@ -119,6 +119,57 @@ __global__ __launch_bounds__(BLOCK) void label_rows_kernel(const LabelParams p) 
     }
 }
 
+// isccsearch_join_overlaps: the label of row i of a simprint segment (128-bit keys: the asset is the FIRST key word) -- the rank of
+// its asset in asset_keys (strictly ascending), the search of label_rows_kernel at stride 2.  0xFFFFFFFF (no label) where the asset
+// is not listed, and where the row is a stop chunk: its entry in the segment's frequency column exceeds max_doc_freq (freq NULL:
+// no cut).  Every LISTED row, stop chunks included, adds 1 to chunks[rank]; counters[1] counts the listed rows, counters[2] the
+// stop chunks among them (one atomic per wave each).  Integer atomics: the result does not depend on their order.
+// Bounds: the row loop runs ceil(n / grid size) trips, the search at most 64 (hi - lo halves; n_assets < 2^32 is checked by the host).
+struct OverlapLabelParams {
+    const uint64_t* keys;          // the segment's key column [n][2]
+    const uint64_t* asset_keys;    // [n_assets]
+    const uint32_t* freq;          // the segment's frequency column [n], or NULL
+    uint32_t* out;                 // [n]
+    uint32_t* chunks;              // [n_assets], zeroed
+    unsigned long long* counters;  // [4]: the call's {pairs, live rows, stop chunks, records}
+    uint64_t n, n_assets;
+    uint32_t max_doc_freq;
+};
+__global__ __launch_bounds__(BLOCK) void label_chunks_kernel(const OverlapLabelParams p) {
+    uint32_t live = 0, stop = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < p.n; i += (uint64_t)gridDim.x * BLOCK) {
+        const uint64_t key = p.keys[2 * i];
+        uint64_t lo = 0, hi = p.n_assets;          // the first listed asset >= key lies in [lo, hi]
+        while (lo < hi) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if (p.asset_keys[mid] < key) lo = mid + 1;
+            else hi = mid;
+        }
+        // (the label is SELECTED at the end, not assigned inside the branches: hipcc's code for the branchy form kept the rank in the
+        //  register the frequency load overwrites, and every row lost its label whenever a frequency column was given)
+        const bool listed = lo < p.n_assets && p.asset_keys[lo] == key;
+        const uint32_t rank = (uint32_t)lo;
+        bool is_stop = false;
+        if (listed) {
+            atomicAdd(p.chunks + rank, 1u);
+            if (p.freq) is_stop = p.freq[i] > p.max_doc_freq;
+        }
+        live += listed ? 1u : 0u;
+        stop += is_stop ? 1u : 0u;
+        p.out[i] = listed && !is_stop ? rank : UF_NONE;
+    }
+    // every lane of the block gets here (no lane returns early): the shuffles see whole waves
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        live += (uint32_t)__shfl_xor((int)live, d, 64);
+        stop += (uint32_t)__shfl_xor((int)stop, d, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (live) atomicAdd(p.counters + 1, (unsigned long long)live);
+        if (stop) atomicAdd(p.counters + 2, (unsigned long long)stop);
+    }
+}
+
 // after the last join launch of isccsearch_join_components: every label's entry becomes its component's smallest label
 // (uf_flatten of unionfind.hip.h; the caller has checked parent[i] <= i, which bounds every walk)
 __global__ __launch_bounds__(BLOCK) void flatten_kernel(uint32_t* parent, uint32_t n_labels) {

@@ -420,6 +420,44 @@ class HipTable(TableChecks):
             _lib.ptr(live_labels) if n_live else None, parent.shape[0], _lib.ptr(parent), ctypes.byref(links)))
         return int(links.value)
 
+    def join_overlaps(self, max_hamming, asset_keys, max_doc_freq, max_pairs, dup_limit=1000):
+        # type: (int, np.ndarray, int, int, int) -> tuple
+        """
+        The pairs of assets that share chunks, by a self-join of this simprint table (128-bit keys: the asset is the first key word)
+        aggregated on the device (``isccsearch_join_overlaps``).  ``asset_keys`` (uint64, strictly ascending) names the assets that
+        take part; an asset's label is its rank there.  A chunk pair is two rows of two different listed assets within
+        ``max_hamming`` bits, neither of them a stop chunk: a row whose document frequency (``get_freq(.., dup_limit)``) exceeds
+        ``max_doc_freq`` (0: no cut).  Returns ``(records, chunks, info)``: one ``OVERLAP_DTYPE`` record per ORDERED pair of labels
+        (src, dst) with a chunk pair, sorted by (src, dst) -- ``matched`` rows of src with a row of dst in reach, ``sum_hamming`` their
+        smallest distances summed, ``chunk_pairs`` --; the rows per listed asset, stop chunks included (uint32); and
+        ``{"chunk_pairs", "records", "live_rows", "stop_chunks"}``.  One library call with room for ``min(max_pairs, 2^20)`` chunk
+        pairs, retried once with exactly the total when more were found.  More than ``max_pairs`` chunk pairs raise ValueError:
+        the cap is never applied silently.
+        """
+        asset_keys = np.ascontiguousarray(asset_keys, dtype=np.uint64)
+        if asset_keys.ndim != 1:
+            raise ValueError("asset_keys must be shaped [n_assets]")
+        n_assets = asset_keys.shape[0]
+        call = self.engine._lib.isccsearch_join_overlaps
+        chunks = np.zeros(n_assets, dtype=np.uint32)
+        info = np.zeros(4, dtype=np.uint64)
+        capacity = min(int(max_pairs), 1 << 20)
+        for attempt in range(2):
+            records = np.empty(2 * capacity, dtype=_lib.OVERLAP_DTYPE)
+            rc = call(self.engine.handle, self.id, int(max_hamming), int(max_doc_freq), int(dup_limit), n_assets, _lib.ptr(asset_keys) if n_assets else None,
+                      capacity, _lib.ptr(records) if capacity else None, _lib.ptr(chunks), _lib.ptr(info))
+            if rc == -errno.ENOSPC or rc == 0:
+                n = int(info[0])
+                if n > max_pairs:
+                    raise ValueError(f"{n} chunk pairs exceed max_pairs={max_pairs}")
+                if rc == -errno.ENOSPC and attempt == 0:
+                    capacity = n
+                    continue
+            _lib.check(rc)
+            names = ("chunk_pairs", "records", "live_rows", "stop_chunks")
+            return records[: int(info[1])], chunks, dict(zip(names, (int(v) for v in info)))
+        raise RuntimeError("isccsearch_join_overlaps: the retry with the reported total did not fit")
+
     def _join(self, symbol, tables, max_hamming_by_prefix, max_pairs):
         # type: (str, tuple, object, int) -> tuple
         """One join call of the library, retried once with exactly the reported total when that did not fit."""

@@ -22,7 +22,7 @@ import numpy as np
 from iscc_search_amd import chunk_match, codec, snapshot, unit_match
 from iscc_search_amd._lib import MAX_K
 from iscc_search_amd.nphd import HipNphdIndex
-from iscc_search_amd.pairs import DuplicateGroup, DuplicatePair, IndexMatch, group_side, join_sides
+from iscc_search_amd.pairs import DuplicateGroup, DuplicatePair, IndexMatch, SharedContent, group_side, join_sides, shared_content
 from iscc_search_amd.schema import IsccAddResult, IsccEntry, IsccGlobalMatch, IsccQuery, IsccSearchResult, Status
 from iscc_search_amd.simprint import HipSimprintIndex, pack_chunk_pointer, unpack_chunk_pointer
 from iscc_search_amd.unit_match import INSTANCE_FIRST_K, UnitMatches, _checked_limit, _is_instance, _unit_map, _unit_max_hamming  # noqa: F401
@@ -347,6 +347,29 @@ class HipIndex:
         side_b, realm_b = other._join_side()
         return [IndexMatch(codec.iscc_id_from_int(a, realm_a), codec.iscc_id_from_int(b, realm_b), score, types)
                 for a, b, score, types in join_sides("find_matches", side_a, side_b, other._opts, min_score, max_pairs)]
+
+    def find_shared_content(self, min_chunks=1, min_coverage=None, simprint_types=None, threshold=None, max_doc_freq=100, max_pairs=1_000_000):
+        # type: (int, Optional[float], Optional[List[str]], Optional[float], int, int) -> List[SharedContent]
+        """
+        Every pair of assets {a, b} that share content: in some simprint type a chunk of a and a chunk of b whose similarity passes
+        ``threshold`` (default: ``match_threshold_simprints``) -- a clip inside a longer video, a quoted passage, a sampled loop.
+        Found by ONE self-join per simprint table, aggregated on the device (``HipSimprintIndex.overlaps``), instead of a
+        ``search_assets`` by simprints per asset and its top-``limit`` cut.  Chunks of one asset never pair with each other, and a chunk
+        whose simprint more than ``max_doc_freq`` assets hold (black frames, licence text; 0: no cut) pairs with nothing, though it
+        still counts among its asset's chunks.  Per type ``SharedChunks`` says how many chunks of each asset found a match and
+        ``coverage_x``, the mean over x's chunks of the best similarity found in the other asset (0 where none): what
+        ``search_raw`` by x's simprints scores the other asset with under constant IDF.  The type's score is the larger coverage,
+        ``score`` the mean over the types in which the pair matches.  Kept when ``max(matched_a, matched_b) >= min_chunks`` in some
+        type (and ``score >= min_coverage``, if given); ordered by score descending, then (key_a, key_b).  ``simprint_types``
+        restricts the tables joined.  More than ``max_pairs`` matching chunk pairs in one table raise ValueError.
+        """
+        threshold = self._opts.match_threshold_simprints if threshold is None else float(threshold)
+        with self._lock:
+            tables = {t: idx for t, idx in self._sp_tables.items() if simprint_types is None or t in simprint_types}
+            bodies = {t: list(self._sp_assets.get(t, {})) for t in tables}
+            realm = self._realm_id or 0
+        return [SharedContent(codec.iscc_id_from_int(a, realm), codec.iscc_id_from_int(b, realm), score, types)
+                for a, b, score, types in shared_content("find_shared_content", tables, bodies, threshold, max_doc_freq, max_pairs, min_chunks, min_coverage)]
 
     # -- bulk search -------------------------------------------------------------------------------
     def _prepare_many(self, queries):

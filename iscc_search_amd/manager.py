@@ -14,7 +14,7 @@ from typing import Dict, List, Optional
 from urllib.parse import parse_qs, urlparse
 
 from iscc_search_amd.index import HipIndex, HipOptions
-from iscc_search_amd.pairs import DuplicateGroup, DuplicatePair, IndexMatch
+from iscc_search_amd.pairs import DuplicateGroup, DuplicatePair, IndexMatch, SharedContent
 from iscc_search_amd.schema import IsccAddResult, IsccEntry, IsccIndex, IsccQuery, IsccSearchResult
 
 INDEX_NAME_RE = re.compile(r"^[a-z][a-z0-9]*$")
@@ -282,6 +282,13 @@ class HipIndexManager:
         """Groups of near-duplicate assets of one index (``HipIndex.find_duplicate_groups``).  Not available on a sharded index."""
         self._refuse_sharded("find_duplicate_groups")
         return self._locked_index(index_name).find_duplicate_groups(unit_types=unit_types, threshold=threshold, min_size=min_size)
+
+    def find_shared_content(self, index_name, min_chunks=1, min_coverage=None, simprint_types=None, threshold=None, max_doc_freq=100, max_pairs=1_000_000):
+        # type: (str, int, Optional[float], Optional[List[str]], Optional[float], int, int) -> List[SharedContent]
+        """Asset pairs of one index that share chunks (``HipIndex.find_shared_content``).  Not available on a sharded index."""
+        self._refuse_sharded("find_shared_content")
+        return self._locked_index(index_name).find_shared_content(min_chunks=min_chunks, min_coverage=min_coverage, simprint_types=simprint_types,
+                                                                  threshold=threshold, max_doc_freq=max_doc_freq, max_pairs=max_pairs)
 
     def find_matches(self, index_a, index_b, min_score=None, unit_types=None, max_pairs=1_000_000):
         # type: (str, str, Optional[float], Optional[List[str]], int) -> List[IndexMatch]

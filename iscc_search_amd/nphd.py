@@ -439,6 +439,17 @@ class HipIndex128:
         q_words, _ = pack_bytes(self._vectors(vectors), self._table.max_words)
         return self._table.simprint_exact(q_words, given, queried, dup_limit, threshold, limit, detailed)
 
+    @property
+    def joins_overlaps(self):
+        # type: () -> bool
+        """Whether the table joins itself into asset overlaps (``isccsearch_join_overlaps``; a sharded table does not)."""
+        return hasattr(self._table, "join_overlaps")
+
+    def join_overlaps(self, max_hamming, asset_keys, max_doc_freq, max_pairs, dup_limit=1000):
+        # type: (int, np.ndarray, int, int, int) -> tuple
+        """``HipTable.join_overlaps``: the assets are the first 8 bytes of the 16-byte keys, as big-endian integers."""
+        return self._table.join_overlaps(max_hamming, asset_keys, max_doc_freq, max_pairs, dup_limit)
+
     def get_freq(self, keys, dup_limit=1000):
         # type: (list[bytes], int) -> np.ndarray
         """Document frequency of the vector stored under each key (0 for absent keys), from the frequency column."""

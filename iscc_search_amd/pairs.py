@@ -2,7 +2,8 @@
 Asset pairs by device joins: the host side of ``HipIndex.find_duplicates`` (``HipTable.join_within``) and ``find_matches``
 (``HipTable.join_between``), scored as ``search_assets`` scores (``unit_match``).  A *side* of a join is ``(tables, asset_units)``:
 unit type -> ``HipNphdIndex``, and asset key -> {unit_type: body} as indexed.  And asset GROUPS by the same joins with a union-find
-on the device where the pairs were (``find_duplicate_groups``, ``HipTable.join_components``).
+on the device where the pairs were (``find_duplicate_groups``, ``HipTable.join_components``).  And asset pairs that share CHUNKS, by a
+self-join of every simprint table aggregated on the device (``find_shared_content``, ``HipSimprintIndex.overlaps``).
 """
 
 from dataclasses import dataclass
@@ -39,6 +40,29 @@ class DuplicateGroup:
 
     iscc_ids: List[str]     # ascending by key
     size: int
+
+
+@dataclass
+class SharedChunks:
+    """One simprint type of a ``SharedContent`` pair: how much of each asset's chunks has a match in the other asset."""
+
+    matched_a: int          # chunks of a with at least one chunk of b within the match threshold
+    chunks_a: int           # chunks of a of this type, stop chunks included
+    matched_b: int
+    chunks_b: int
+    chunk_pairs: int        # matching (chunk of a, chunk of b) pairs
+    coverage_a: float       # mean over a's chunks of the best similarity 1 - d / ndim found in b, 0 where none
+    coverage_b: float
+
+
+@dataclass
+class SharedContent:
+    """One pair of ``find_shared_content``: two assets that share chunks in at least one simprint type."""
+
+    iscc_id_a: str          # the smaller key
+    iscc_id_b: str
+    score: float            # mean over ``types`` of max(coverage_a, coverage_b)
+    types: Dict[str, SharedChunks]
 
 
 def _merge_join(pair_scores, unit_type, join, instance, units_a, units_b):
@@ -125,3 +149,47 @@ def group_side(caller, side, threshold, min_size):
     order = np.lexsort((roots, -counts.astype(np.int64)))
     order = order[counts[order] >= min_size]
     return [keys[members[starts[g]:starts[g] + counts[g]]] for g in order.tolist()]
+
+
+def shared_content(caller, tables, bodies, threshold, max_doc_freq, max_pairs, min_chunks, min_coverage):
+    # type: (str, dict, dict, float, int, int, int, Optional[float]) -> list
+    """
+    [(key_a, key_b, score, {sp_type: SharedChunks})] of the asset pairs that share chunks, key_a < key_b: ONE self-join per simprint
+    type in ``tables`` (sp_type -> ``HipSimprintIndex``, sorted type order) over the assets ``bodies[sp_type]`` (8-byte bodies).  Per
+    type a pair has two device records, (a, b) and (b, a); ``coverage_x = (matched_x - sum_hamming_x / ndim) / chunks_x`` and the
+    type's score is the larger coverage (the smaller work lies inside the larger).  ``score`` is the mean of the types' scores over
+    the types in which the pair has a record -- the rule ``chunk_match.rank_simprint_matches`` uses across types.  Kept: pairs with
+    ``max(matched_a, matched_b) >= min_chunks`` in some type and ``score >= min_coverage`` (if given); ordered by score descending,
+    then (key_a, key_b).  More than ``max_pairs`` chunk pairs in one table raise ValueError; tables without the join (a sharded
+    engine's) raise NotImplementedError naming ``caller``.
+    """
+    by_pair = {}  # type: Dict[tuple, Dict[str, SharedChunks]]
+    for sp_type in sorted(tables):
+        table = tables[sp_type]
+        if not table.joins_overlaps:
+            raise NotImplementedError(f"{caller} needs a single-GPU engine: pairs across shards need their rows exchanged")
+        listed = sorted(bodies.get(sp_type, ()))
+        if not listed:
+            continue
+        records, chunks, _ = table.overlaps(listed, threshold, max_doc_freq, max_pairs)
+        keys = [int.from_bytes(b, "big") for b in listed]
+        ndim = table.ndim
+        chunks = chunks.tolist()
+        rows = {(s, d): (m, h, p) for s, d, m, h, p in zip(records["src"].tolist(), records["dst"].tolist(), records["matched"].tolist(),
+                                                          records["sum_hamming"].tolist(), records["chunk_pairs"].tolist())}
+        for (a, b), (matched_a, sum_a, pairs) in rows.items():
+            if a > b:
+                continue
+            matched_b, sum_b, _ = rows[(b, a)]
+            by_pair.setdefault((keys[a], keys[b]), {})[sp_type] = SharedChunks(
+                matched_a, chunks[a], matched_b, chunks[b], pairs, (matched_a - sum_a / ndim) / chunks[a], (matched_b - sum_b / ndim) / chunks[b])
+    out = []
+    for (a, b), types in by_pair.items():
+        if not any(max(t.matched_a, t.matched_b) >= min_chunks for t in types.values()):
+            continue
+        score = sum(max(t.coverage_a, t.coverage_b) for t in types.values()) / len(types)
+        if min_coverage is not None and score < min_coverage:
+            continue
+        out.append((a, b, score, types))
+    out.sort(key=lambda r: (-r[2], r[0], r[1]))
+    return out

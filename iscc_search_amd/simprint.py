@@ -478,6 +478,30 @@ class HipSimprintIndex:
         results.sort(key=lambda r: (-r.score, r.iscc_id_body))
         return results[:limit]
 
+    @property
+    def joins_overlaps(self):
+        # type: () -> bool
+        """Whether ``overlaps`` is available (a single-GPU table; a sharded one has no self-join)."""
+        return self._index.joins_overlaps
+
+    def overlaps(self, asset_bodies, threshold, max_doc_freq, max_pairs):
+        # type: (list[bytes], float, int, int) -> tuple
+        """
+        The pairs of assets among ``asset_bodies`` (8-byte ISCC-ID bodies, ascending, no repeats) that share chunks: two chunks of
+        two assets match when their similarity ``1 - d / ndim`` passes ``threshold`` (the radius of ``search_raw``, ``_radius_for``);
+        a chunk whose simprint more than ``max_doc_freq`` assets hold (0: no cut; counted as ``doc_freq`` counts, up to
+        ``DOC_FREQ_DUP_LIMIT`` rows) matches nothing.  One self-join of the table on the device (``HipTable.join_overlaps``) --
+        ``(records, chunks, info)`` as it returns them, an asset's label being its position in ``asset_bodies``.  More than
+        ``max_pairs`` matching chunk pairs raise ValueError.
+        """
+        keys = np.frombuffer(b"".join(bytes(b) for b in asset_bodies), dtype=">u8").astype(np.uint64)
+        if len(keys) != len(asset_bodies):
+            raise ValueError("asset_bodies must be 8-byte ISCC-ID bodies")
+        if len(keys) > 1 and not bool(np.all(keys[1:] > keys[:-1])):
+            raise ValueError("asset_bodies must be ascending without repeats: an asset's label is its position")
+        dup_limit = max(DOC_FREQ_DUP_LIMIT, int(max_doc_freq))
+        return self._index.join_overlaps(self._radius_for(threshold), keys, int(max_doc_freq), max_pairs, dup_limit)
+
     def doc_freq(self, simprints, dup_limit=1000):
         # type: (list[bytes], int) -> list[int]
         """Distinct assets holding each simprint, counted on the device (``lmdb_ops.count_doc_freq``, :139-166)."""

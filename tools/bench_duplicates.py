@@ -24,9 +24,17 @@ flatten step and the copies of the arrays, without a join launch.  Then the DENS
 max_pairs: --dense-rows 64-bit rows (default 1 Mi) in clusters of --cluster identical rows, tau 0, on both kernels: seconds, links,
 nanoseconds per link.
 
+--overlaps: isccsearch_join_overlaps (the joins' OVERLAP form and the aggregation of csrc/overlap.hip) on simprint tables: 64-bit and
+128-bit simprints, 128-bit keys, about 16 chunks per asset in random row order, --shared per cent of the assets containing a run of
+4-8 chunks of another asset (0-2 bits flipped).  Three legs A B A over both kernels (VALU, matrix cores, VALU); per leg join_overlaps
+and isccsearch_join_within on the same table and tau -- the same scan, so their difference is the price of the emit form plus the
+aggregation -- each one warm-up call and the median of --reps.  For tables of up to --search-rows rows also the only way there was
+before: one HipSimprintIndex.search_raw per asset (limit 100, the threshold that gives the same radius), timed once.
+
 usage: python tools/bench_duplicates.py [--mfma both] [--reps 5] [--sizes 65536,262144,1048576,4194304] [--nphd-sizes 262144,1048576] [--tau 6]
        python tools/bench_duplicates.py --between [--rows-a N --rows-b M] [the same options]
        python tools/bench_duplicates.py --components [--sizes 1048576 --nphd-sizes 1048576] [--dense-rows 1048576 --cluster 1000]
+       python tools/bench_duplicates.py --overlaps [--sizes 65536,262144,1048576] [--shared 3] [--search-rows 65536]
 """
 
 import argparse
@@ -190,6 +198,66 @@ def run_dense(engine, n, cluster, reps):
         t.drop()
 
 
+def simprint_rows(rng, n, nbytes, per_asset, shared_pct):
+    """(keys [n, 2], words [n, W], asset keys): n chunks dealt to assets of `per_asset`, some assets containing runs of another's."""
+    W = nbytes // 8
+    words = rng.integers(0, 2**64, size=(n, W), dtype=np.uint64)
+    n_assets = max(2, n // per_asset)
+    asset_of = (np.arange(n) // per_asset).clip(max=n_assets - 1)
+    for a in rng.choice(n_assets, size=max(1, n_assets * shared_pct // 100), replace=False).tolist():
+        b = int(rng.integers(0, n_assets - 1))
+        b += b >= a
+        run = int(rng.integers(4, 9))
+        dst, src = a * per_asset, b * per_asset + int(rng.integers(0, per_asset - run + 1))
+        words[dst:dst + run] = words[src:src + run]
+        for _ in range(2):
+            words[dst:dst + run, 0] ^= np.left_shift(np.uint64(1), rng.integers(0, 64, size=run).astype(np.uint64)) * (rng.random(run) < 0.5)
+    asset_keys = np.arange(1, n_assets + 1, dtype=np.uint64) * np.uint64(1000003)
+    keys = np.stack([asset_keys[asset_of], (np.arange(n, dtype=np.uint64) << np.uint64(32)) | np.uint64(1)], axis=1)       # offset: the chunk's number
+    order = rng.permutation(n)
+    return keys[order], words[order], asset_keys
+
+
+def run_overlaps(engine, nbytes, n, tau, reps, shared_pct, search_rows):
+    """join_overlaps and join_within on one simprint table, A B A over both kernels; the search_raw loop for small tables."""
+    from iscc_search_amd.simprint import HipSimprintIndex
+
+    rng = np.random.default_rng(4242 + n + nbytes)
+    keys, words, asset_keys = simprint_rows(rng, n, nbytes, 16, shared_pct)
+    index = HipSimprintIndex(engine, ndim=8 * nbytes)
+    t = index._index._table
+    try:
+        for lo in range(0, n, 1 << 18):
+            t.add(keys[lo:lo + (1 << 18)], words[lo:lo + (1 << 18)], None, trusted_unique=True)
+        mh = np.full(_lib.MAX_BYTES + 1, -1, dtype=np.int16)
+        mh[nbytes] = tau
+        overlaps = lambda: t.join_overlaps(tau, asset_keys, 0, 1 << 22)      # noqa: E731
+        within = lambda: t.join_within(mh, 1 << 22)                          # noqa: E731
+        out = {"join": "overlaps", "table": f"simprints {8 * nbytes}-bit", "rows": n, "assets": len(asset_keys), "tau": tau, "legs": []}
+        for mfma in (False, True, False):
+            o_s, info = leg(engine, mfma, overlaps, reps, found=lambda o: o[2])
+            w_s, pairs = leg(engine, mfma, within, reps)
+            out["legs"].append(dict(kernel="mfma" if mfma else "valu", overlaps_seconds=round(o_s, 5), within_seconds=round(w_s, 5),
+                                    overlaps_minus_within_seconds=round(o_s - w_s, 5), chunk_pairs=info["chunk_pairs"], records=info["records"],
+                                    within_row_pairs=pairs))
+        assert len({(l["chunk_pairs"], l["records"]) for l in out["legs"]}) == 1, "the legs disagree"
+        if n <= search_rows:
+            # the only way before: one search per asset by its own simprints, the other assets read off every result list
+            by_asset = {}
+            raw = np.ascontiguousarray(words).astype(">u8").tobytes()
+            for i, key in enumerate(keys[:, 0].tolist()):
+                by_asset.setdefault(key, []).append(raw[i * nbytes:(i + 1) * nbytes])
+            threshold = 1.0 - tau / (8.0 * nbytes)
+            t0 = time.perf_counter()
+            listed = 0
+            for key, simprints in by_asset.items():
+                listed += len(index.search_raw(simprints, limit=100, threshold=threshold, total_assets=len(by_asset))) - 1
+            out["search_raw_loop"] = dict(seconds=round(time.perf_counter() - t0, 3), searches=len(by_asset), assets_listed=listed)
+        return out
+    finally:
+        index.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--mfma", choices=("0", "1", "both"), default="both", help="the kernel: XOR + popcount, matrix cores, or A B A over both")
@@ -203,12 +271,20 @@ def main():
     ap.add_argument("--components", action="store_true", help="join_components against join_within (A B A per kernel), then the dense table")
     ap.add_argument("--dense-rows", type=int, default=1 << 20, help="--components: rows of the dense table (0: skip it)")
     ap.add_argument("--cluster", type=int, default=1000, help="--components: identical rows per cluster of the dense table")
+    ap.add_argument("--overlaps", action="store_true", help="join_overlaps against join_within on simprint tables (A B A over both kernels)")
+    ap.add_argument("--shared", type=int, default=3, help="--overlaps: per cent of the assets that contain a run of another asset's chunks")
+    ap.add_argument("--search-rows", type=int, default=65536, help="--overlaps: tables of up to this many rows also time one search_raw per asset")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args()
     sizes = [int(s) for s in a.sizes.split(",") if s]
     nphd_sizes = [int(s) for s in a.nphd_sizes.split(",") if s]
     engine = HipEngine(a.device)
     try:
+        if a.overlaps:
+            for nbytes in (8, 16):
+                for n in sizes:
+                    print(json.dumps(run_overlaps(engine, nbytes, n, a.tau * nbytes // 8, a.reps, a.shared, a.search_rows)), flush=True)
+            return
         if a.components:
             for n in sizes:
                 print(json.dumps(run_components(engine, _lib.METRIC_HAMMING, 8, n, a.tau, a.reps)), flush=True)
