@@ -374,9 +374,10 @@ static int search_locked(isccsearch_handle* h, uint32_t table, uint32_t nq, cons
 
 // Searches arriving from many threads are COMBINED: the reference calls `search` once per query unit from
 // FastAPI's thread pool (usearch/index.py:786-806, docs/explanation/architecture.md:120-126), and a
-// streaming pass costs the same for one query as for T_q.  The first caller becomes the leader, takes every
-// request waiting on the same (table, k) and runs them as ONE batch; the others sleep until their slice of
-// the results has been written.  A single-threaded caller pays nothing for this.
+// streaming pass costs the same for one query as for T_q.  The first caller becomes the leader of a round and
+// takes EVERY request waiting on the handle; run_combined groups them by (table, k) and runs each group as ONE
+// batch; the others sleep until their slice of the results has been written.  A request that arrives while a
+// round runs waits for the next one.  A single-threaded caller pays nothing for this.
 struct PendingSearch {
     uint32_t table, nq, k;
     const uint64_t* q_words;
