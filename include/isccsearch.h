@@ -442,6 +442,56 @@ int isccsearch_join_overlaps(isccsearch_handle* h, uint32_t table, int32_t max_h
                              uint32_t* out_chunks,                 /* [n_assets] */
                              uint64_t* out_info                    /* [4] */);
 
+/* The pairs of assets of TWO simprint tables of one handle that share chunks: the cross join of table_a and table_b (both HAMMING,
+ * key_words 2, equal max_bytes), aggregated on the device as isccsearch_join_overlaps aggregates the self-join.  A row is a chunk; its
+ * asset is the first key word.
+ *   asset_keys_a[n_assets_a]  strictly ascending each: the assets that take part on either side.  There are TWO label spaces: an asset
+ *   asset_keys_b[n_assets_b]  of table_a is labelled by its rank in asset_keys_a, an asset of table_b by its rank in asset_keys_b.  A row
+ *                         is live if its asset is listed on its own side; a listed asset its table does not hold has no rows.
+ *   max_hamming           the radius, as for isccsearch_join_overlaps.
+ *   max_doc_freq          stop chunks are decided PER TABLE, from that table's own frequency column built with dup_limit, exactly as
+ *   dup_limit             isccsearch_join_overlaps decides them: a live row is a stop chunk if its frequency in its own table exceeds
+ *                         max_doc_freq.  max_doc_freq 0: no cut, and no column is read or built.
+ *   flags                 ISCCSEARCH_OVERLAPS_SKIP_SAME_ASSET: a pair whose two rows have the same asset key (one asset held by both
+ *                         tables) is not a chunk pair, as the self-join treats the chunks of one asset -- it takes no slot, is not
+ *                         counted and cannot push a call over its capacity.  Without the flag it is a pair like any other
+ *                         (isccsearch_join_between's rule for equal keys).  No other bit is defined.
+ * A chunk pair is (row i of table_a, row j of table_b), both live, neither a stop chunk in its own table, hamming(i, j) <= max_hamming.
+ *   out_pairs[2 * capacity]  one record per ORDERED pair of assets with at least one chunk pair, in both directions: `reserved` 0 means
+ *                         src is a label of side A and dst a label of side B, `reserved` 1 means src is a label of side B and dst a
+ *                         label of side A.  Sorted ascending by (reserved, src, dst).  matched, sum_hamming and chunk_pairs as for
+ *                         isccsearch_join_overlaps; every pair of assets has exactly one record in each direction, with equal
+ *                         chunk_pairs.  Every field is an integer and defined by the set of chunk pairs alone: which kernel ran, which
+ *                         table was held and the order in which pairs were found never show.
+ *   out_chunks_a[n_assets_a]  live rows per asset of either side, stop chunks included.
+ *   out_chunks_b[n_assets_b]
+ *   out_info[6]           {chunk pairs found, records written, live rows a, stop chunks a, live rows b, stop chunks b}.
+ * Capacity protocol as for isccsearch_join_overlaps: more than `capacity` chunk pairs return -ENOSPC with out_info[0] exact and every
+ * other output unspecified, and a retry with exactly that capacity succeeds; pairs past the capacity are counted and not written.
+ * Device memory: 192 bytes per chunk pair of the capacity, 4 bytes per row of both tables and 12 per listed asset of both sides, kept
+ * in the handle's scratch buffers.
+ * -EINVAL, each naming the offending index or argument, all checked on the host before anything is launched, the outputs left
+ * untouched: a NULL argument (out_pairs may be NULL only when capacity is 0); table_a == table_b (isccsearch_join_overlaps joins a
+ * table with itself); a table that is not HAMMING with key_words 2, or tables that differ in max_bytes; n_assets_a or n_assets_b
+ * outside 1 .. 2^31 - 1 (a label of side B carries one more bit inside the device's hit format); either key array not strictly
+ * ascending; max_hamming < 0; max_doc_freq > dup_limit when max_doc_freq > 0; unknown flag bits.  -E2BIG, checked likewise: a segment
+ * of 2^32 rows or more, a capacity of 2^31 chunk pairs or more.
+ * One lock covers the call; everything runs on the handle's one stream.  The two frequency columns are built first (each build drains
+ * the stream), then labelling (once per table), ONE join launch (the one isccsearch_join_between would make for the two tables: the
+ * table with more rows is held), sort and reduction are queued, and ONE synchronisation comes before the records are copied.  If
+ * either table has no row nothing is launched; chunks and info are filled all the same.
+ * No reference counterpart (the reference has no index-wide join: it finds shared chunks one query asset at a time). */
+#define ISCCSEARCH_OVERLAPS_SKIP_SAME_ASSET 1u
+int isccsearch_join_overlaps_between(isccsearch_handle* h, uint32_t table_a, uint32_t table_b, int32_t max_hamming,
+                                     uint32_t max_doc_freq, uint32_t dup_limit,
+                                     uint32_t n_assets_a, const uint64_t* asset_keys_a,
+                                     uint32_t n_assets_b, const uint64_t* asset_keys_b,
+                                     uint32_t flags, uint64_t capacity,    /* chunk pairs */
+                                     isccsearch_overlap* out_pairs,        /* [2 * capacity] */
+                                     uint32_t* out_chunks_a,               /* [n_assets_a] */
+                                     uint32_t* out_chunks_b,               /* [n_assets_b] */
+                                     uint64_t* out_info                    /* [6] */);
+
 /* Multi-GPU building blocks (row-range shards, one process per GPU).
  * search_device: same search, results left in caller-provided DEVICE memory
  *   d_records[nq*k] (isccsearch_record), d_counts[nq]; queries must share one byte length.

@@ -395,6 +395,7 @@ struct isccsearch_handle {
     DevBuf<uint32_t> d_join_live_labels, d_join_row_labels, d_join_parent;
     // isccsearch_join_overlaps: the hits of one call {appended | sorted}, the one-hit records and the reduced ones, rocPRIM's temporary
     // storage (overlap.hip), chunks per asset; its asset keys go to d_join_live_keys, its row labels to d_join_row_labels
+    // (isccsearch_join_overlaps_between: the same buffers, keys, chunks and labels of table A first and of table B behind them)
     DevBuf<iskov::Hit> d_ov_hits;
     DevBuf<isccsearch_overlap> d_ov_marks, d_ov_records;
     DevBuf<unsigned char> d_ov_temp;

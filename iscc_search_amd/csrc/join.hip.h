@@ -27,6 +27,10 @@
 //   stop chunk) and only a pair of two DIFFERENT labels takes a slot (overlap_pair) -- from the same wave-aggregated counter,
 //   one returned atomic per wave (overlap_slots).  A pair with a slot writes two directed hits (label_i, label_j, row_i, hamming)
 //   and (label_j, label_i, row_j, hamming) with vector stores (overlap_write); overlap.hip sorts and reduces them.
+// join_scan_kernel<W, MASK, true, false, true> (CROSS + OVERLAP, isccsearch_join_overlaps_between): the cross join's scan with the
+//   OVERLAP emit path.  The two tables' labels live in two spaces told apart by LABEL_SIDE_B, so two labelled rows never carry equal
+//   labels; what a pair can share is its asset KEY (one asset held by both tables), and with JoinEmit::skip_same_key such a pair
+//   takes no slot -- the two rows' first key words are compared, in the emit path only.
 // Slabs are read up to the next multiple of the slab size: column capacities are multiples of ROW_ALIGN (2 048 rows), which
 // every slab size divides, so those reads stay inside the allocation (rows past n are dropped in the emit path).
 #pragma once
@@ -62,7 +66,13 @@ struct JoinEmit {
     // the OVERLAP form (isccsearch_join_overlaps): labels_a / labels_b as above (the ranks of the rows' assets); `total` counts the pairs
     // of two different labels, `capacity` of them have room in out_hits, two directed hits (src, dst, row, hamming) each
     uint4* out_hits;              // [2 * capacity]
+    // the CROSS + OVERLAP form (isccsearch_join_overlaps_between): keys_a / keys_b are read too (128-bit keys, the asset is the first
+    // word) -- when this is set, a pair of rows of equal asset key takes no slot
+    uint32_t skip_same_key;
 };
+// isccsearch_join_overlaps_between: a label of a row of table B carries this bit, a label of table A does not (ranks stay below 2^31 - 1,
+// so that no label is UF_NONE)
+constexpr uint32_t LABEL_SIDE_B = 0x80000000u;
 struct JoinParams {
     const uint64_t* col_a[4];     // side A: rows held in SGPRs, TQ per block
     const uint64_t* col_b[4];     // side B: streamed
@@ -98,10 +108,17 @@ __device__ __forceinline__ uint32_t link_pair(const JoinEmit& e, uint64_t i, uin
 }
 
 // OVERLAP form of both emit paths, per pair (held / SGPR-side row i, streamed row j): the two rows' labels; true if the pair takes a
-// slot -- both rows have a label (their assets are listed, neither is a stop chunk) and the labels differ
+// slot -- both rows have a label (their assets are listed, neither is a stop chunk) and the labels differ.  CROSS: the labels of two
+// tables always differ (LABEL_SIDE_B); with JoinEmit::skip_same_key the pair takes no slot when the two rows' asset keys are equal.
+// Both passes of an emit path call this, so the slots and the count agree.
+template <bool CROSS = false>
 __device__ __forceinline__ bool overlap_pair(const JoinEmit& e, uint64_t i, uint64_t j, uint32_t& la, uint32_t& lb) {
     la = e.labels_a[i];
     lb = e.labels_b[j];
+    if (CROSS) {
+        if (la == UF_NONE || lb == UF_NONE) return false;
+        return !(e.skip_same_key != 0 && e.keys_a[2 * i] == e.keys_b[2 * j]);
+    }
     return la != UF_NONE && lb != UF_NONE && la != lb;
 }
 // ... the slots of one wave (one ring walk): lane `lane` has counted c pairs; ONE returned atomic on JoinEmit::total for all of them.
@@ -134,7 +151,7 @@ __device__ __forceinline__ void overlap_write(const JoinEmit& e, uint64_t slot, 
 template <int W, bool MASK, bool CROSS = false, bool LINK = false, bool OVERLAP = false>
 __global__ __launch_bounds__(BLOCK) void join_scan_kernel(const JoinParams p) {
     static_assert(!(LINK && CROSS), "components are those of one table");
-    static_assert(!(OVERLAP && (CROSS || LINK)), "overlaps are those of one table, and a form of their own");
+    static_assert(!(OVERLAP && LINK), "overlaps are a form of their own");
     constexpr int TQ = JoinCfg<W>::TQ, U = JoinCfg<W>::U;
     constexpr uint32_t SLAB = JoinCfg<W>::SLAB;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -207,7 +224,7 @@ __global__ __launch_bounds__(BLOCK) void join_scan_kernel(const JoinParams p) {
                 for (int rr = 0; rr < 2; ++rr) {
                     const bool pair = is_pair(i, base + u * 128 + rr, dist(r, u, rr, al, ah));
                     if (LINK) c += pair ? link_pair(e, i, base + u * 128 + rr) : 0u;
-                    else if (OVERLAP) { uint32_t la, lb; c += pair && overlap_pair(e, i, base + u * 128 + rr, la, lb) ? 1u : 0u; }
+                    else if (OVERLAP) { uint32_t la, lb; c += pair && overlap_pair<CROSS>(e, i, base + u * 128 + rr, la, lb) ? 1u : 0u; }
                     else c += pair ? 1u : 0u;
                 }
         }
@@ -230,7 +247,7 @@ __global__ __launch_bounds__(BLOCK) void join_scan_kernel(const JoinParams p) {
                         const uint64_t j = base + u * 128 + rr;
                         const uint32_t h = dist(r, u, rr, al, ah);
                         uint32_t la, lb;
-                        if (!is_pair(i, j, h) || !overlap_pair(e, i, j, la, lb)) continue;
+                        if (!is_pair(i, j, h) || !overlap_pair<CROSS>(e, i, j, la, lb)) continue;
                         overlap_write(e, slot, la, lb, i, j, h);
                         ++slot;
                     }

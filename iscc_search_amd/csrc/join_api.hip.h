@@ -2,7 +2,8 @@
 // tables by the XOR + popcount kernel of join.hip.h or, for launches over enough rows, its matrix-core form (mfma_join_kernel.hip.h);
 // and isccsearch_join_components: the self-join's launches in their LINK form, whose pairs are united in a union-find array
 // (unionfind.hip.h) instead of written; and isccsearch_join_overlaps: the self-join of a simprint table in the launches' OVERLAP form,
-// whose directed hits overlap.hip sorts and reduces to one record per ordered pair of assets.
+// whose directed hits overlap.hip sorts and reduces to one record per ordered pair of assets; and isccsearch_join_overlaps_between: the
+// cross join of two simprint tables in the same OVERLAP form, with a label space per table.
 // Needs the store of isccsearch.hip (Segment, Table; get_table of store.hip.h) and its scratch buffers.
 namespace {
 // one launch of the join kernel (join.hip.h)
@@ -33,7 +34,8 @@ struct JoinPlan {
     std::vector<isk::JoinEmit> emits;
     bool cross = false;
     bool link = false;     // isccsearch_join_components: the LINK form of either kernel (JoinEmit::labels_a, labels_b, parent are set)
-    bool overlap = false;  // isccsearch_join_overlaps: the OVERLAP form of either kernel (JoinEmit::labels_a, labels_b, out_hits are set)
+    bool overlap = false;  // isccsearch_join_overlaps: the OVERLAP form of either kernel (JoinEmit::labels_a, labels_b, out_hits are set);
+                           // with `cross`: isccsearch_join_overlaps_between
     uint32_t KW = 1;
     uint64_t capacity = 0, cap_alloc = 1;
 };
@@ -137,7 +139,8 @@ int join_run(isccsearch_handle* h, JoinPlan& plan) {
                 }
                 continue;
             }
-            if (plan.overlap) launch_join<false, false, true>(L.W, L.jp, L.mask, L.blocks, h->stream);
+            if (plan.overlap && plan.cross) launch_join<true, false, true>(L.W, L.jp, L.mask, L.blocks, h->stream);
+            else if (plan.overlap) launch_join<false, false, true>(L.W, L.jp, L.mask, L.blocks, h->stream);
             else if (plan.link) launch_join<false, true>(L.W, L.jp, L.mask, L.blocks, h->stream);
             else if (plan.cross) launch_join<true>(L.W, L.jp, L.mask, L.blocks, h->stream);
             else launch_join<false>(L.W, L.jp, L.mask, L.blocks, h->stream);
@@ -399,7 +402,7 @@ extern "C" int isccsearch_join_overlaps(isccsearch_handle* h, uint32_t table, in
     HIPOK(hipMemcpyAsync(h->d_join_live_keys.p, asset_keys, (size_t)n_assets * 8, hipMemcpyHostToDevice, h->stream));
     if (s.n) {
         isk::OverlapLabelParams lp{s.keys, h->d_join_live_keys.p, max_doc_freq > 0 ? s.freq : nullptr, h->d_join_row_labels.p, h->d_ov_chunks.p,
-                                   counters, s.n, n_assets, max_doc_freq};
+                                   counters, s.n, n_assets, max_doc_freq, 0u};
         const uint32_t blocks = (uint32_t)std::min<uint64_t>((s.n + isk::BLOCK - 1) / isk::BLOCK, 1u << 16);
         hipLaunchKernelGGL(isk::label_chunks_kernel, dim3(blocks), dim3(isk::BLOCK), 0, h->stream, lp);
         HIPOK(hipGetLastError());
@@ -443,5 +446,149 @@ extern "C" int isccsearch_join_overlaps(isccsearch_handle* h, uint32_t table, in
     }
     memcpy(out_chunks, chunks.data(), (size_t)n_assets * 4);
     out_info[0] = total; out_info[1] = n_records; out_info[2] = got[1]; out_info[3] = got[2];
+    return 0;
+}
+
+// isccsearch_join_overlaps between TWO simprint tables: label_chunks_kernel once per table (its own asset keys, frequency column,
+// chunks and counters; table B's labels carry isk::LABEL_SIDE_B), then the ONE cross-join launch isccsearch_join_between would make for
+// the two segments in its OVERLAP form (join_scan_kernel<W, MASK, true, false, true> / mfma_join_kernel<W, true, false, true>, the
+// table with more rows held, by join_add's rule), then the aggregation of overlap.hip, all on one stream.  The sort by (src, dst)
+// puts the records of direction A -> B (src without the bit) before those of B -> A; the bit moves into `reserved` on the host, after
+// the copy.  Both frequency columns are built before anything of the call is queued (each build drains the stream).  Everything the
+// device code relies on -- both key arrays ascending and shorter than 2^31 - 1 (labels with the side bit stay below UF_NONE), rows and
+// hit positions below 2^32 -- is checked before anything is launched.
+extern "C" int isccsearch_join_overlaps_between(isccsearch_handle* h, uint32_t table_a, uint32_t table_b, int32_t max_hamming,
+                                     uint32_t max_doc_freq, uint32_t dup_limit, uint32_t n_assets_a, const uint64_t* asset_keys_a,
+                                     uint32_t n_assets_b, const uint64_t* asset_keys_b, uint32_t flags, uint64_t capacity,
+                                     isccsearch_overlap* out_pairs, uint32_t* out_chunks_a, uint32_t* out_chunks_b, uint64_t* out_info) {
+    if (!h) return fail(-EINVAL, "handle is NULL");
+    if (!asset_keys_a || !asset_keys_b || !out_chunks_a || !out_chunks_b || !out_info) return fail(-EINVAL, "NULL argument");
+    if (capacity && !out_pairs) return fail(-EINVAL, "out_pairs is NULL with capacity %llu", (unsigned long long)capacity);
+    if (table_a == table_b)
+        return fail(-EINVAL, "join_overlaps_between needs two tables (table %u given twice): isccsearch_join_overlaps joins a table with itself", table_a);
+    if (flags & ~ISCCSEARCH_OVERLAPS_SKIP_SAME_ASSET) return fail(-EINVAL, "unknown flags 0x%x", flags & ~ISCCSEARCH_OVERLAPS_SKIP_SAME_ASSET);
+    if (n_assets_a == 0 || n_assets_a > 0x7FFFFFFFu) return fail(-EINVAL, "n_assets_a must be in 1 .. 2^31 - 1, got %u", n_assets_a);
+    if (n_assets_b == 0 || n_assets_b > 0x7FFFFFFFu) return fail(-EINVAL, "n_assets_b must be in 1 .. 2^31 - 1, got %u", n_assets_b);
+    for (uint32_t i = 1; i < n_assets_a; ++i)
+        if (asset_keys_a[i] <= asset_keys_a[i - 1])
+            return fail(-EINVAL, "asset_keys_a must be strictly ascending: asset_keys_a[%u] <= asset_keys_a[%u]", i, i - 1);
+    for (uint32_t i = 1; i < n_assets_b; ++i)
+        if (asset_keys_b[i] <= asset_keys_b[i - 1])
+            return fail(-EINVAL, "asset_keys_b must be strictly ascending: asset_keys_b[%u] <= asset_keys_b[%u]", i, i - 1);
+    if (max_hamming < 0) return fail(-EINVAL, "max_hamming must be >= 0, got %d", max_hamming);
+    if (max_doc_freq > 0 && max_doc_freq > dup_limit)
+        return fail(-EINVAL, "max_doc_freq %u exceeds dup_limit %u: the frequency column counts no further", max_doc_freq, dup_limit);
+    if (capacity >= (1ull << 31))
+        return fail(-E2BIG, "capacity %llu: the two hits of a chunk pair are numbered with 32 bits", (unsigned long long)capacity);
+    std::lock_guard<std::mutex> lk(h->mu);
+    Table* tabs[2];
+    int rc;
+    if ((rc = get_table(h, table_a, tabs[0]))) return rc;
+    if ((rc = get_table(h, table_b, tabs[1]))) return rc;
+    const uint32_t ids[2] = {table_a, table_b};
+    for (int x = 0; x < 2; ++x)
+        if (tabs[x]->metric != ISCCSEARCH_METRIC_HAMMING || tabs[x]->key_words != 2)
+            return fail(-EINVAL, "join_overlaps_between needs simprint tables (HAMMING, key_words 2), table %u has metric %d and key_words %d", ids[x],
+                        tabs[x]->metric, tabs[x]->key_words);
+    if (tabs[0]->max_bytes != tabs[1]->max_bytes)
+        return fail(-EINVAL, "simprint tables %u and %u hold codes of different lengths (max_bytes %d, %d)", table_a, table_b, tabs[0]->max_bytes, tabs[1]->max_bytes);
+    const uint32_t nbytes = (uint32_t)tabs[0]->max_bytes;
+    Segment* const segs[2] = {&tabs[0]->seg[nbytes], &tabs[1]->seg[nbytes]};
+    for (int x = 0; x < 2; ++x)
+        if (segs[x]->n >= (1ull << 32))
+            return fail(-E2BIG, "a segment of %llu rows in table %u: row numbers travel as 32 bits", (unsigned long long)segs[x]->n, ids[x]);
+    HIPOK(hipSetDevice(h->device));
+    // the call's counters {chunk pairs, live rows a, stop chunks a, live rows b, stop chunks b, records}; per side (A first, B behind it)
+    // asset keys, chunks per asset, row labels; the hits and records of isccsearch_join_overlaps for m = 2 * capacity
+    const uint32_t n_assets[2] = {n_assets_a, n_assets_b};
+    const uint64_t* const asset_keys[2] = {asset_keys_a, asset_keys_b};
+    const uint64_t all_assets = (uint64_t)n_assets_a + n_assets_b, all_rows = segs[0]->n + segs[1]->n;
+    const uint64_t m = 2 * capacity;
+    size_t temp_bytes = 0;
+    if ((rc = h->d_join_total.ensure(6))) return rc;
+    if ((rc = h->d_join_live_keys.ensure(all_assets))) return rc;
+    if ((rc = h->d_ov_chunks.ensure(all_assets))) return rc;
+    if ((rc = h->d_join_row_labels.ensure(std::max<uint64_t>(all_rows, 1)))) return rc;
+    if (m) {
+        std::string err;
+        if ((rc = iskov::aggregate_temp_bytes(m, &temp_bytes, &err))) return fail(rc, "%s", err.c_str());
+        if ((rc = h->d_ov_hits.ensure(2 * m))) return rc;
+        if ((rc = h->d_ov_marks.ensure(m))) return rc;
+        if ((rc = h->d_ov_records.ensure(m))) return rc;
+        if ((rc = h->d_ov_temp.ensure(std::max<size_t>(temp_bytes, 1)))) return rc;
+    }
+    // (each frequency column is built by a call of its own that drains the stream: nothing of this call is queued yet)
+    for (int x = 0; x < 2; ++x)
+        if (max_doc_freq > 0 && segs[x]->n && (rc = ensure_freq_column(h, *tabs[x], *segs[x], dup_limit))) return rc;
+    unsigned long long* const counters = reinterpret_cast<unsigned long long*>(h->d_join_total.p);
+    HIPOK(hipMemsetAsync(counters, 0, 6 * 8, h->stream));
+    HIPOK(hipMemsetAsync(h->d_ov_chunks.p, 0, (size_t)all_assets * 4, h->stream));
+    const bool launch = segs[0]->n && segs[1]->n;
+    if (m && launch) HIPOK(hipMemsetAsync(h->d_ov_hits.p, 0xFF, m * sizeof(iskov::Hit), h->stream));
+    uint32_t* row_labels[2] = {h->d_join_row_labels.p, h->d_join_row_labels.p + segs[0]->n};
+    for (int x = 0; x < 2; ++x) {
+        uint64_t* const d_keys = h->d_join_live_keys.p + (x ? n_assets_a : 0);
+        HIPOK(hipMemcpyAsync(d_keys, asset_keys[x], (size_t)n_assets[x] * 8, hipMemcpyHostToDevice, h->stream));
+        const Segment& s = *segs[x];
+        if (!s.n) continue;
+        // (label_chunks_kernel adds to counters[1] and [2] of the pointer it is given: table B's pair lies two further)
+        isk::OverlapLabelParams lp{s.keys, d_keys, max_doc_freq > 0 ? s.freq : nullptr, row_labels[x], h->d_ov_chunks.p + (x ? n_assets_a : 0),
+                                   counters + 2 * x, s.n, n_assets[x], max_doc_freq, x ? isk::LABEL_SIDE_B : 0u};
+        const uint32_t blocks = (uint32_t)std::min<uint64_t>((s.n + isk::BLOCK - 1) / isk::BLOCK, 1u << 16);
+        hipLaunchKernelGGL(isk::label_chunks_kernel, dim3(blocks), dim3(isk::BLOCK), 0, h->stream, lp);
+        HIPOK(hipGetLastError());
+    }
+    if (launch) {
+        JoinPlan plan;
+        plan.cross = true;
+        plan.overlap = true;
+        plan.KW = 2;
+        plan.capacity = capacity;
+        // as in isccsearch_join_between the segment with more rows is held: JoinEmit::labels_a are the HELD segment's labels
+        const int held = segs[1]->n > segs[0]->n ? 1 : 0;
+        if ((rc = join_add(h, plan, *segs[held], *segs[1 - held], nbytes, max_hamming, false, held == 1))) return rc;
+        isk::JoinEmit& e = plan.emits.back();
+        e.out_keys_a = e.out_keys_b = nullptr;        // the pair form's outputs: not this form's
+        e.out_hamming = nullptr;
+        e.out_prefix_bits = nullptr;
+        e.labels_a = row_labels[held];
+        e.labels_b = row_labels[1 - held];
+        e.out_hits = reinterpret_cast<uint4*>(h->d_ov_hits.p);
+        e.skip_same_key = flags & ISCCSEARCH_OVERLAPS_SKIP_SAME_ASSET ? 1u : 0u;
+        if ((rc = join_run(h, plan))) return rc;
+        if (m) {
+            std::string err;
+            if ((rc = iskov::aggregate(h->d_ov_hits.p, h->d_ov_hits.p + m, h->d_ov_marks.p, h->d_ov_records.p, counters + 5, m, h->d_ov_temp.p,
+                                       temp_bytes, h->stream, &err)))
+                return fail(rc, "%s", err.c_str());
+        }
+    }
+    // the call's one synchronisation; the outputs change only from here on
+    uint64_t got[6] = {0, 0, 0, 0, 0, 0};
+    std::vector<uint32_t> chunks(all_assets);
+    HIPOK(hipMemcpyAsync(got, counters, sizeof got, hipMemcpyDeviceToHost, h->stream));
+    HIPOK(hipMemcpyAsync(chunks.data(), h->d_ov_chunks.p, (size_t)all_assets * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPOK(hipStreamSynchronize(h->stream));
+    const uint64_t total = got[0];
+    if (total > capacity) {
+        out_info[0] = total;
+        return fail(-ENOSPC, "%llu chunk pairs do not fit the capacity of %llu", (unsigned long long)total, (unsigned long long)capacity);
+    }
+    // (slots were left unused: the run of ones behind the hits reduced to one more record, the last)
+    const uint64_t n_records = m && launch ? got[5] - (total < capacity ? 1 : 0) : 0;
+    if (n_records) {
+        HIPOK(hipMemcpyAsync(out_pairs, h->d_ov_records.p, n_records * sizeof(isccsearch_overlap), hipMemcpyDeviceToHost, h->stream));
+        HIPOK(hipStreamSynchronize(h->stream));
+        // the side bit of src becomes the direction; the order by (src, dst) with the bit is the order by (reserved, src, dst) without
+        for (uint64_t r = 0; r < n_records; ++r) {
+            isccsearch_overlap& o = out_pairs[r];
+            o.reserved = o.src >> 31;
+            o.src &= ~isk::LABEL_SIDE_B;
+            o.dst &= ~isk::LABEL_SIDE_B;
+        }
+    }
+    memcpy(out_chunks_a, chunks.data(), (size_t)n_assets_a * 4);
+    memcpy(out_chunks_b, chunks.data() + n_assets_a, (size_t)n_assets_b * 4);
+    out_info[0] = total; out_info[1] = n_records; out_info[2] = got[1]; out_info[3] = got[2]; out_info[4] = got[3]; out_info[5] = got[4];
     return 0;
 }

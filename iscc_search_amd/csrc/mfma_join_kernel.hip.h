@@ -22,6 +22,8 @@
 //   OVERLAP (mfma_join_kernel<W, false, false, true>, isccsearch_join_overlaps): the ring is walked twice as for the pairs -- only a pair
 //   whose rows carry two different labels is counted (overlap_pair of join.hip.h), one returned atomic per walk (overlap_slots), and
 //   the second walk writes the pair's two directed hits (overlap_write).
+//   CROSS + OVERLAP (mfma_join_kernel<W, true, false, true>, isccsearch_join_overlaps_between): the same two walks over the pairs of
+//   two tables; overlap_pair<true> drops the pairs of one asset key when JoinEmit::skip_same_key says so.
 #pragma once
 
 #include "join.hip.h"
@@ -34,7 +36,7 @@ namespace isk {
 template <int W, bool CROSS, bool LINK = false, bool OVERLAP = false>
 __global__ __launch_bounds__(MBLOCK, mfma_min_waves<W>()) void mfma_join_kernel(const MfmaJoinParams p, const uint32_t groups) {
     static_assert(!(LINK && CROSS), "components are those of one table");
-    static_assert(!(OVERLAP && (CROSS || LINK)), "overlaps are those of one table, and a form of their own");
+    static_assert(!(OVERLAP && LINK), "overlaps are a form of their own");
     constexpr int MT = 2;       // row tiles (32 rows) per wave and step
     constexpr uint32_t WAVES = MBLOCK / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -136,14 +138,14 @@ __global__ __launch_bounds__(MBLOCK, mfma_min_waves<W>()) void mfma_join_kernel(
             for (uint32_t en = 0; en < rcount; en += 2) {
                 uint64_t i, j;
                 uint32_t hd, la, lb;
-                c += pair_at(en + sub, i, j, hd) && overlap_pair(e, i, j, la, lb) ? 1u : 0u;
+                c += pair_at(en + sub, i, j, hd) && overlap_pair<CROSS>(e, i, j, la, lb) ? 1u : 0u;
             }
             uint64_t slot;
             if (overlap_slots(e, c, lane, slot)) {
                 for (uint32_t en = 0; c != 0 && en < rcount; en += 2) {
                     uint64_t i, j;
                     uint32_t hd, la, lb;
-                    if (!pair_at(en + sub, i, j, hd) || !overlap_pair(e, i, j, la, lb)) continue;
+                    if (!pair_at(en + sub, i, j, hd) || !overlap_pair<CROSS>(e, i, j, la, lb)) continue;
                     overlap_write(e, slot, la, lb, i, j, hd);
                     ++slot;
                 }

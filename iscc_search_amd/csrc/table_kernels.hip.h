@@ -124,6 +124,8 @@ __global__ __launch_bounds__(BLOCK) void label_rows_kernel(const LabelParams p) 
 // is not listed, and where the row is a stop chunk: its entry in the segment's frequency column exceeds max_doc_freq (freq NULL:
 // no cut).  Every LISTED row, stop chunks included, adds 1 to chunks[rank]; counters[1] counts the listed rows, counters[2] the
 // stop chunks among them (one atomic per wave each).  Integer atomics: the result does not depend on their order.
+// isccsearch_join_overlaps_between runs it once per table; side_bit (0, or LABEL_SIDE_B of join.hip.h for table B) is set in every label
+// given, and `counters` points one pair of counters further for table B.
 // Bounds: the row loop runs ceil(n / grid size) trips, the search at most 64 (hi - lo halves; n_assets < 2^32 is checked by the host).
 struct OverlapLabelParams {
     const uint64_t* keys;          // the segment's key column [n][2]
@@ -131,9 +133,10 @@ struct OverlapLabelParams {
     const uint32_t* freq;          // the segment's frequency column [n], or NULL
     uint32_t* out;                 // [n]
     uint32_t* chunks;              // [n_assets], zeroed
-    unsigned long long* counters;  // [4]: the call's {pairs, live rows, stop chunks, records}
+    unsigned long long* counters;  // [4]: the call's {pairs, live rows, stop chunks, records}; [1] and [2] are written
     uint64_t n, n_assets;
     uint32_t max_doc_freq;
+    uint32_t side_bit;             // set in every label given (ranks do not reach it: the host bounds n_assets)
 };
 __global__ __launch_bounds__(BLOCK) void label_chunks_kernel(const OverlapLabelParams p) {
     uint32_t live = 0, stop = 0;
@@ -156,7 +159,7 @@ __global__ __launch_bounds__(BLOCK) void label_chunks_kernel(const OverlapLabelP
         }
         live += listed ? 1u : 0u;
         stop += is_stop ? 1u : 0u;
-        p.out[i] = listed && !is_stop ? rank : UF_NONE;
+        p.out[i] = listed && !is_stop ? rank | p.side_bit : UF_NONE;
     }
     // every lane of the block gets here (no lane returns early): the shuffles see whole waves
 #pragma unroll

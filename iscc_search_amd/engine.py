@@ -441,11 +441,22 @@ class HipTable(TableChecks):
         call = self.engine._lib.isccsearch_join_overlaps
         chunks = np.zeros(n_assets, dtype=np.uint32)
         info = np.zeros(4, dtype=np.uint64)
+        records = self._overlap_records("isccsearch_join_overlaps", max_pairs, info, lambda capacity, out: call(
+            self.engine.handle, self.id, int(max_hamming), int(max_doc_freq), int(dup_limit), n_assets, _lib.ptr(asset_keys) if n_assets else None,
+            capacity, out, _lib.ptr(chunks), _lib.ptr(info)))
+        names = ("chunk_pairs", "records", "live_rows", "stop_chunks")
+        return records, chunks, dict(zip(names, (int(v) for v in info)))
+
+    def _overlap_records(self, symbol, max_pairs, info, call):
+        # type: (str, int, np.ndarray, object) -> np.ndarray
+        """
+        The records of one overlap join of the library: ``call(capacity, out_pairs)`` with room for ``min(max_pairs, 2^20)`` chunk
+        pairs, retried once with exactly the total (``info[0]``) when that did not fit; more than ``max_pairs`` raise ValueError.
+        """
         capacity = min(int(max_pairs), 1 << 20)
         for attempt in range(2):
             records = np.empty(2 * capacity, dtype=_lib.OVERLAP_DTYPE)
-            rc = call(self.engine.handle, self.id, int(max_hamming), int(max_doc_freq), int(dup_limit), n_assets, _lib.ptr(asset_keys) if n_assets else None,
-                      capacity, _lib.ptr(records) if capacity else None, _lib.ptr(chunks), _lib.ptr(info))
+            rc = call(capacity, _lib.ptr(records) if capacity else None)
             if rc == -errno.ENOSPC or rc == 0:
                 n = int(info[0])
                 if n > max_pairs:
@@ -454,9 +465,42 @@ class HipTable(TableChecks):
                     capacity = n
                     continue
             _lib.check(rc)
-            names = ("chunk_pairs", "records", "live_rows", "stop_chunks")
-            return records[: int(info[1])], chunks, dict(zip(names, (int(v) for v in info)))
-        raise RuntimeError("isccsearch_join_overlaps: the retry with the reported total did not fit")
+            return records[: int(info[1])]
+        raise RuntimeError(f"{symbol}: the retry with the reported total did not fit")
+
+    def join_overlaps_between(self, other, max_hamming, asset_keys_a, asset_keys_b, max_doc_freq, max_pairs, dup_limit=1000, skip_same_asset=True):
+        # type: (HipTable, int, np.ndarray, np.ndarray, int, int, int, bool) -> tuple
+        """
+        The pairs (asset of this simprint table, asset of ``other``) that share chunks, by a cross join of the two tables aggregated
+        on the device (``isccsearch_join_overlaps_between``).  ``asset_keys_a`` / ``asset_keys_b`` (uint64, strictly ascending) name
+        the assets that take part on either side; an asset's label is its rank in its own side's array.  A chunk pair is a row of
+        this table and a row of ``other``, both of listed assets, within ``max_hamming`` bits, neither a stop chunk IN ITS OWN
+        TABLE (document frequency above ``max_doc_freq``; 0: no cut).  ``skip_same_asset``: two rows of one asset key (an asset held
+        by both tables) are no chunk pair.  Returns ``(records, chunks_a, chunks_b, info)``: ``OVERLAP_DTYPE`` records sorted by
+        (reserved, src, dst) -- ``reserved`` 0: src is a label of this side and dst of the other, 1: the other way round; one record
+        per direction and pair of assets --, the rows per listed asset of either side (uint32), and ``{"chunk_pairs", "records",
+        "live_rows_a", "stop_chunks_a", "live_rows_b", "stop_chunks_b"}``.  One library call with room for ``min(max_pairs, 2^20)``
+        chunk pairs, retried once with exactly the total when more were found.  More than ``max_pairs`` chunk pairs raise
+        ValueError: the cap is never applied silently.  Both tables must belong to one engine.
+        """
+        if getattr(other, "engine", None) is not self.engine:
+            raise ValueError("join_overlaps_between needs two tables of one engine: the other table belongs to another engine")
+        asset_keys_a = np.ascontiguousarray(asset_keys_a, dtype=np.uint64)
+        asset_keys_b = np.ascontiguousarray(asset_keys_b, dtype=np.uint64)
+        if asset_keys_a.ndim != 1 or asset_keys_b.ndim != 1:
+            raise ValueError("asset_keys_a and asset_keys_b must be shaped [n_assets]")
+        n_a, n_b = asset_keys_a.shape[0], asset_keys_b.shape[0]
+        call = self.engine._lib.isccsearch_join_overlaps_between
+        chunks_a = np.zeros(n_a, dtype=np.uint32)
+        chunks_b = np.zeros(n_b, dtype=np.uint32)
+        info = np.zeros(6, dtype=np.uint64)
+        flags = _lib.OVERLAPS_SKIP_SAME_ASSET if skip_same_asset else 0
+        records = self._overlap_records("isccsearch_join_overlaps_between", max_pairs, info, lambda capacity, out: call(
+            self.engine.handle, self.id, other.id, int(max_hamming), int(max_doc_freq), int(dup_limit),
+            n_a, _lib.ptr(asset_keys_a) if n_a else None, n_b, _lib.ptr(asset_keys_b) if n_b else None, flags,
+            capacity, out, _lib.ptr(chunks_a), _lib.ptr(chunks_b), _lib.ptr(info)))
+        names = ("chunk_pairs", "records", "live_rows_a", "stop_chunks_a", "live_rows_b", "stop_chunks_b")
+        return records, chunks_a, chunks_b, dict(zip(names, (int(v) for v in info)))
 
     def _join(self, symbol, tables, max_hamming_by_prefix, max_pairs):
         # type: (str, tuple, object, int) -> tuple

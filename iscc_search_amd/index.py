@@ -22,7 +22,8 @@ import numpy as np
 from iscc_search_amd import chunk_match, codec, snapshot, unit_match
 from iscc_search_amd._lib import MAX_K
 from iscc_search_amd.nphd import HipNphdIndex
-from iscc_search_amd.pairs import DuplicateGroup, DuplicatePair, IndexMatch, SharedContent, group_side, join_sides, shared_content
+from iscc_search_amd.pairs import (DuplicateGroup, DuplicatePair, IndexMatch, SharedContent, SharedMatch, group_side, join_sides, shared_content,
+                                   shared_matches)
 from iscc_search_amd.schema import IsccAddResult, IsccEntry, IsccGlobalMatch, IsccQuery, IsccSearchResult, Status
 from iscc_search_amd.simprint import HipSimprintIndex, pack_chunk_pointer, unpack_chunk_pointer
 from iscc_search_amd.unit_match import INSTANCE_FIRST_K, UnitMatches, _checked_limit, _is_instance, _unit_map, _unit_max_hamming  # noqa: F401
@@ -370,6 +371,36 @@ class HipIndex:
             realm = self._realm_id or 0
         return [SharedContent(codec.iscc_id_from_int(a, realm), codec.iscc_id_from_int(b, realm), score, types)
                 for a, b, score, types in shared_content("find_shared_content", tables, bodies, threshold, max_doc_freq, max_pairs, min_chunks, min_coverage)]
+
+    def find_shared_matches(self, other, min_chunks=1, min_coverage=None, simprint_types=None, threshold=None, max_doc_freq=100,
+                            max_pairs=1_000_000, include_same_id=False):
+        # type: (HipIndex, int, Optional[float], Optional[List[str]], Optional[float], int, int, bool) -> List[SharedMatch]
+        """
+        Every pair (asset a of this index, asset b of ``other``) that share content, as ``find_shared_content`` defines it within one
+        index: which assets of this catalogue contain a clip, a quoted passage or a sampled loop of an asset of that registry.  Found
+        by ONE cross join per simprint type both indexes have a table for, aggregated on the device
+        (``HipSimprintIndex.overlaps_between``), instead of a simprint search per asset or a self-join of a copy of both.
+        ``threshold`` defaults to the OTHER index's ``match_threshold_simprints`` (as ``find_matches`` scores with the other index's
+        options): ``coverage_a`` is what ``other``'s ``search_raw`` by a's simprints scores b with under constant IDF.  A chunk whose
+        simprint more than ``max_doc_freq`` assets of ITS OWN index hold pairs with nothing (0: no cut) but still counts among its
+        asset's chunks.  An asset both indexes hold (one ISCC-ID body) pairs with itself only with ``include_same_id``.  Score,
+        ``min_chunks``, ``min_coverage``, ``simprint_types``, ``max_pairs`` and the order (score descending, then (key_a, key_b)) as
+        for ``find_shared_content``; each side's ISCC-IDs carry its own realm.  Both indexes must live on one engine.
+        """
+        if other is self:
+            raise ValueError("find_shared_matches compares two indexes: find_shared_content lists the pairs within one")
+        if other._engine is not self._engine:
+            raise ValueError("find_shared_matches needs both indexes on one engine: their tables must share the device's memory")
+        threshold = other._opts.match_threshold_simprints if threshold is None else float(threshold)
+        sides = []
+        for idx in (self, other):
+            with idx._lock:
+                tables = {t: table for t, table in idx._sp_tables.items() if simprint_types is None or t in simprint_types}
+                sides.append((tables, {t: list(idx._sp_assets.get(t, {})) for t in tables}, idx._realm_id or 0))
+        (tables_a, bodies_a, realm_a), (tables_b, bodies_b, realm_b) = sides
+        return [SharedMatch(codec.iscc_id_from_int(a, realm_a), codec.iscc_id_from_int(b, realm_b), score, types)
+                for a, b, score, types in shared_matches("find_shared_matches", tables_a, tables_b, bodies_a, bodies_b, threshold, max_doc_freq,
+                                                         max_pairs, min_chunks, min_coverage, not include_same_id)]
 
     # -- bulk search -------------------------------------------------------------------------------
     def _prepare_many(self, queries):

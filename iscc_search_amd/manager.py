@@ -14,7 +14,7 @@ from typing import Dict, List, Optional
 from urllib.parse import parse_qs, urlparse
 
 from iscc_search_amd.index import HipIndex, HipOptions
-from iscc_search_amd.pairs import DuplicateGroup, DuplicatePair, IndexMatch, SharedContent
+from iscc_search_amd.pairs import DuplicateGroup, DuplicatePair, IndexMatch, SharedContent, SharedMatch
 from iscc_search_amd.schema import IsccAddResult, IsccEntry, IsccIndex, IsccQuery, IsccSearchResult
 
 INDEX_NAME_RE = re.compile(r"^[a-z][a-z0-9]*$")
@@ -300,6 +300,19 @@ class HipIndexManager:
             idx_a = self._index(index_a)
             idx_b = self._index(index_b)
         return idx_a.find_matches(idx_b, min_score=min_score, unit_types=unit_types, max_pairs=max_pairs)
+
+    def find_shared_matches(self, index_a, index_b, min_chunks=1, min_coverage=None, simprint_types=None, threshold=None, max_doc_freq=100,
+                            max_pairs=1_000_000, include_same_id=False):
+        # type: (str, str, int, Optional[float], Optional[List[str]], Optional[float], int, int, bool) -> List[SharedMatch]
+        """Asset pairs (a of ``index_a``, b of ``index_b``) that share chunks (``HipIndex.find_shared_matches``).  Not available on a sharded index."""
+        self._refuse_sharded("find_shared_matches")
+        if index_a == index_b:
+            raise ValueError(f"find_shared_matches compares two indexes, got '{index_a}' twice: find_shared_content lists the pairs within one index")
+        with self._lock:
+            idx_a = self._index(index_a)
+            idx_b = self._index(index_b)
+        return idx_a.find_shared_matches(idx_b, min_chunks=min_chunks, min_coverage=min_coverage, simprint_types=simprint_types, threshold=threshold,
+                                         max_doc_freq=max_doc_freq, max_pairs=max_pairs, include_same_id=include_same_id)
 
     def close(self):
         # type: () -> None

@@ -450,6 +450,17 @@ class HipIndex128:
         """``HipTable.join_overlaps``: the assets are the first 8 bytes of the 16-byte keys, as big-endian integers."""
         return self._table.join_overlaps(max_hamming, asset_keys, max_doc_freq, max_pairs, dup_limit)
 
+    @property
+    def joins_overlaps_between(self):
+        # type: () -> bool
+        """Whether the table joins another into asset overlaps (``isccsearch_join_overlaps_between``; a sharded table does not)."""
+        return hasattr(self._table, "join_overlaps_between")
+
+    def join_overlaps_between(self, other, max_hamming, asset_keys_a, asset_keys_b, max_doc_freq, max_pairs, dup_limit=1000, skip_same_asset=True):
+        # type: (HipIndex128, int, np.ndarray, np.ndarray, int, int, int, bool) -> tuple
+        """``HipTable.join_overlaps_between`` with the table of ``other``: the assets are the first 8 bytes of the 16-byte keys."""
+        return self._table.join_overlaps_between(other._table, max_hamming, asset_keys_a, asset_keys_b, max_doc_freq, max_pairs, dup_limit, skip_same_asset)
+
     def get_freq(self, keys, dup_limit=1000):
         # type: (list[bytes], int) -> np.ndarray
         """Document frequency of the vector stored under each key (0 for absent keys), from the frequency column."""

@@ -3,7 +3,8 @@ Asset pairs by device joins: the host side of ``HipIndex.find_duplicates`` (``Hi
 (``HipTable.join_between``), scored as ``search_assets`` scores (``unit_match``).  A *side* of a join is ``(tables, asset_units)``:
 unit type -> ``HipNphdIndex``, and asset key -> {unit_type: body} as indexed.  And asset GROUPS by the same joins with a union-find
 on the device where the pairs were (``find_duplicate_groups``, ``HipTable.join_components``).  And asset pairs that share CHUNKS, by a
-self-join of every simprint table aggregated on the device (``find_shared_content``, ``HipSimprintIndex.overlaps``).
+self-join of every simprint table aggregated on the device (``find_shared_content``, ``HipSimprintIndex.overlaps``) -- or, between two
+indexes, by a cross join of the two tables of every simprint type (``find_shared_matches``, ``HipSimprintIndex.overlaps_between``).
 """
 
 from dataclasses import dataclass
@@ -61,6 +62,16 @@ class SharedContent:
 
     iscc_id_a: str          # the smaller key
     iscc_id_b: str
+    score: float            # mean over ``types`` of max(coverage_a, coverage_b)
+    types: Dict[str, SharedChunks]
+
+
+@dataclass
+class SharedMatch:
+    """One pair of ``find_shared_matches``: an asset of the calling index and an asset of the other index that share chunks."""
+
+    iscc_id_a: str          # the asset of the index find_shared_matches was called on
+    iscc_id_b: str          # the asset of the other index
     score: float            # mean over ``types`` of max(coverage_a, coverage_b)
     types: Dict[str, SharedChunks]
 
@@ -183,6 +194,12 @@ def shared_content(caller, tables, bodies, threshold, max_doc_freq, max_pairs, m
             matched_b, sum_b, _ = rows[(b, a)]
             by_pair.setdefault((keys[a], keys[b]), {})[sp_type] = SharedChunks(
                 matched_a, chunks[a], matched_b, chunks[b], pairs, (matched_a - sum_a / ndim) / chunks[a], (matched_b - sum_b / ndim) / chunks[b])
+    return _rank_shared(by_pair, min_chunks, min_coverage)
+
+
+def _rank_shared(by_pair, min_chunks, min_coverage):
+    # type: (Dict[tuple, Dict[str, SharedChunks]], int, Optional[float]) -> list
+    """[(key_a, key_b, score, types)] of the pairs kept by ``min_chunks`` / ``min_coverage``: score descending, then (key_a, key_b)."""
     out = []
     for (a, b), types in by_pair.items():
         if not any(max(t.matched_a, t.matched_b) >= min_chunks for t in types.values()):
@@ -193,3 +210,38 @@ def shared_content(caller, tables, bodies, threshold, max_doc_freq, max_pairs, m
         out.append((a, b, score, types))
     out.sort(key=lambda r: (-r[2], r[0], r[1]))
     return out
+
+
+def shared_matches(caller, tables_a, tables_b, bodies_a, bodies_b, threshold, max_doc_freq, max_pairs, min_chunks, min_coverage, skip_same_asset):
+    # type: (str, dict, dict, dict, dict, float, int, int, int, Optional[float], bool) -> list
+    """
+    [(key_a, key_b, score, {sp_type: SharedChunks})] of the pairs (asset of side a, asset of side b) that share chunks: ONE cross join
+    per simprint type BOTH sides have a table for (sorted type order) over the assets ``bodies_x[sp_type]`` of either side.  Per type a
+    pair has two device records, a -> b (``reserved`` 0) and b -> a (1); coverage, the type's score, ``score``, what is kept and the
+    order are those of ``shared_content``.  Stop chunks are decided per table; ``skip_same_asset`` keeps an asset held by both sides
+    from pairing with itself.  More than ``max_pairs`` chunk pairs in one pair of tables raise ValueError; tables without the join (a
+    sharded engine's) raise NotImplementedError naming ``caller``.
+    """
+    by_pair = {}  # type: Dict[tuple, Dict[str, SharedChunks]]
+    for sp_type in sorted(set(tables_a) & set(tables_b)):
+        table_a, table_b = tables_a[sp_type], tables_b[sp_type]
+        if not (getattr(table_a, "joins_overlaps_between", False) and getattr(table_b, "joins_overlaps_between", False)):
+            raise NotImplementedError(f"{caller} needs a single-GPU engine: pairs across shards need their rows exchanged")
+        listed_a, listed_b = sorted(bodies_a.get(sp_type, ())), sorted(bodies_b.get(sp_type, ()))
+        if not listed_a or not listed_b:
+            continue
+        records, chunks_a, chunks_b, _ = table_a.overlaps_between(table_b, listed_a, listed_b, threshold, max_doc_freq, max_pairs, skip_same_asset)
+        keys_a = [int.from_bytes(b, "big") for b in listed_a]
+        keys_b = [int.from_bytes(b, "big") for b in listed_b]
+        ndim = table_a.ndim
+        chunks_a, chunks_b = chunks_a.tolist(), chunks_b.tolist()
+        rows = {(r, s, d): (m, h, p) for r, s, d, m, h, p in zip(records["reserved"].tolist(), records["src"].tolist(), records["dst"].tolist(),
+                                                                records["matched"].tolist(), records["sum_hamming"].tolist(),
+                                                                records["chunk_pairs"].tolist())}
+        for (direction, a, b), (matched_a, sum_a, pairs) in rows.items():
+            if direction:
+                continue
+            matched_b, sum_b, _ = rows[(1, b, a)]
+            by_pair.setdefault((keys_a[a], keys_b[b]), {})[sp_type] = SharedChunks(
+                matched_a, chunks_a[a], matched_b, chunks_b[b], pairs, (matched_a - sum_a / ndim) / chunks_a[a], (matched_b - sum_b / ndim) / chunks_b[b])
+    return _rank_shared(by_pair, min_chunks, min_coverage)

@@ -502,6 +502,36 @@ class HipSimprintIndex:
         dup_limit = max(DOC_FREQ_DUP_LIMIT, int(max_doc_freq))
         return self._index.join_overlaps(self._radius_for(threshold), keys, int(max_doc_freq), max_pairs, dup_limit)
 
+    @property
+    def joins_overlaps_between(self):
+        # type: () -> bool
+        """Whether ``overlaps_between`` is available (a single-GPU table; a sharded one has no cross join)."""
+        return self._index.joins_overlaps_between
+
+    def overlaps_between(self, other, bodies_a, bodies_b, threshold, max_doc_freq, max_pairs, skip_same_asset=True):
+        # type: (HipSimprintIndex, list[bytes], list[bytes], float, int, int, bool) -> tuple
+        """
+        The pairs (asset of this table among ``bodies_a``, asset of ``other`` among ``bodies_b``) that share chunks; both lists are
+        8-byte ISCC-ID bodies, ascending, no repeats.  Chunks match as in ``overlaps`` (``_radius_for(threshold)``); a chunk whose
+        simprint more than ``max_doc_freq`` assets OF ITS OWN TABLE hold matches nothing.  ``skip_same_asset``: the chunks of one
+        ISCC-ID body held by both tables do not pair.  One cross join on the device (``HipTable.join_overlaps_between``) --
+        ``(records, chunks_a, chunks_b, info)`` as it returns them, an asset's label being its position in its side's list.  More
+        than ``max_pairs`` matching chunk pairs raise ValueError, and so do tables of different ``ndim``.
+        """
+        if other.ndim != self.ndim:
+            raise ValueError(f"overlaps_between needs simprints of one length: this table holds {self.ndim} bits, the other {other.ndim}")
+        sides = []
+        for name, bodies in (("bodies_a", bodies_a), ("bodies_b", bodies_b)):
+            keys = np.frombuffer(b"".join(bytes(b) for b in bodies), dtype=">u8").astype(np.uint64)
+            if len(keys) != len(bodies):
+                raise ValueError(f"{name} must be 8-byte ISCC-ID bodies")
+            if len(keys) > 1 and not bool(np.all(keys[1:] > keys[:-1])):
+                raise ValueError(f"{name} must be ascending without repeats: an asset's label is its position")
+            sides.append(keys)
+        dup_limit = max(DOC_FREQ_DUP_LIMIT, int(max_doc_freq))
+        return self._index.join_overlaps_between(other._index, self._radius_for(threshold), sides[0], sides[1], int(max_doc_freq), max_pairs,
+                                                 dup_limit, skip_same_asset)
+
     def doc_freq(self, simprints, dup_limit=1000):
         # type: (list[bytes], int) -> list[int]
         """Distinct assets holding each simprint, counted on the device (``lmdb_ops.count_doc_freq``, :139-166)."""

@@ -31,10 +31,17 @@ and isccsearch_join_within on the same table and tau -- the same scan, so their 
 aggregation -- each one warm-up call and the median of --reps.  For tables of up to --search-rows rows also the only way there was
 before: one HipSimprintIndex.search_raw per asset (limit 100, the threshold that gives the same radius), timed once.
 
+--overlaps-between: isccsearch_join_overlaps_between (the cross join's OVERLAP form and the same aggregation) on TWO simprint tables of
+equal size: the generator of --overlaps split over two tables -- 64-bit and 128-bit simprints, about 16 chunks per asset in random row
+order, disjoint asset keys, --shared per cent of A's assets containing a run of 4-8 chunks of an asset of B (0-2 bits flipped).  Three
+legs A B A over both kernels; per leg join_overlaps_between and, on the same two tables and tau, isccsearch_join_between -- the same
+scan --, each one warm-up call and the median of --reps.
+
 usage: python tools/bench_duplicates.py [--mfma both] [--reps 5] [--sizes 65536,262144,1048576,4194304] [--nphd-sizes 262144,1048576] [--tau 6]
        python tools/bench_duplicates.py --between [--rows-a N --rows-b M] [the same options]
        python tools/bench_duplicates.py --components [--sizes 1048576 --nphd-sizes 1048576] [--dense-rows 1048576 --cluster 1000]
        python tools/bench_duplicates.py --overlaps [--sizes 65536,262144,1048576] [--shared 3] [--search-rows 65536]
+       python tools/bench_duplicates.py --overlaps-between [--sizes 65536,262144,1048576] [--shared 3]
 """
 
 import argparse
@@ -258,6 +265,56 @@ def run_overlaps(engine, nbytes, n, tau, reps, shared_pct, search_rows):
         index.close()
 
 
+def simprint_two_tables(rng, n, nbytes, per_asset, shared_pct):
+    """Two tables of n chunks each, (keys, words, asset keys) per side: ``simprint_rows`` with every run copied from B into A."""
+    W = nbytes // 8
+    n_assets = max(2, n // per_asset)
+    asset_of = (np.arange(n) // per_asset).clip(max=n_assets - 1)
+    words_a, words_b = (rng.integers(0, 2**64, size=(n, W), dtype=np.uint64) for _ in range(2))
+    for a in rng.choice(n_assets, size=max(1, n_assets * shared_pct // 100), replace=False).tolist():
+        b = int(rng.integers(0, n_assets))
+        run = int(rng.integers(4, 9))
+        dst, src = a * per_asset, b * per_asset + int(rng.integers(0, per_asset - run + 1))
+        words_a[dst:dst + run] = words_b[src:src + run]
+        for _ in range(2):
+            words_a[dst:dst + run, 0] ^= np.left_shift(np.uint64(1), rng.integers(0, 64, size=run).astype(np.uint64)) * (rng.random(run) < 0.5)
+    sides = []
+    for first, words in ((1, words_a), (n_assets + 1, words_b)):
+        asset_keys = np.arange(first, first + n_assets, dtype=np.uint64) * np.uint64(1000003)
+        keys = np.stack([asset_keys[asset_of], (np.arange(n, dtype=np.uint64) << np.uint64(32)) | np.uint64(1)], axis=1)
+        order = rng.permutation(n)
+        sides.append((keys[order], words[order], asset_keys))
+    return sides
+
+
+def run_overlaps_between(engine, nbytes, n, tau, reps, shared_pct):
+    """join_overlaps_between and join_between on two simprint tables of n rows each, A B A over both kernels."""
+    rng = np.random.default_rng(2424 + n + nbytes)
+    (keys_a, words_a, assets_a), (keys_b, words_b, assets_b) = simprint_two_tables(rng, n, nbytes, 16, shared_pct)
+    ta, tb = engine.open_table(_lib.METRIC_HAMMING, 2, nbytes), engine.open_table(_lib.METRIC_HAMMING, 2, nbytes)
+    try:
+        for t, keys, words in ((ta, keys_a, words_a), (tb, keys_b, words_b)):
+            for lo in range(0, n, 1 << 18):
+                t.add(keys[lo:lo + (1 << 18)], words[lo:lo + (1 << 18)], None, trusted_unique=True)
+        mh = np.full(_lib.MAX_BYTES + 1, -1, dtype=np.int16)
+        mh[nbytes] = tau
+        overlaps = lambda: ta.join_overlaps_between(tb, tau, assets_a, assets_b, 0, 1 << 22)      # noqa: E731
+        between = lambda: ta.join_between(tb, mh, 1 << 22)                                        # noqa: E731
+        out = {"join": "overlaps_between", "table": f"simprints {8 * nbytes}-bit", "rows_a": n, "rows_b": n, "assets_a": len(assets_a),
+               "assets_b": len(assets_b), "tau": tau, "legs": []}
+        for mfma in (False, True, False):
+            o_s, info = leg(engine, mfma, overlaps, reps, found=lambda o: o[3])
+            b_s, pairs = leg(engine, mfma, between, reps)
+            out["legs"].append(dict(kernel="mfma" if mfma else "valu", overlaps_between_seconds=round(o_s, 5), between_seconds=round(b_s, 5),
+                                    overlaps_between_minus_between_seconds=round(o_s - b_s, 5), chunk_pairs=info["chunk_pairs"],
+                                    records=info["records"], between_row_pairs=pairs))
+        assert len({(l["chunk_pairs"], l["records"], l["between_row_pairs"]) for l in out["legs"]}) == 1, "the legs disagree"
+        return out
+    finally:
+        ta.drop()
+        tb.drop()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--mfma", choices=("0", "1", "both"), default="both", help="the kernel: XOR + popcount, matrix cores, or A B A over both")
@@ -272,7 +329,8 @@ def main():
     ap.add_argument("--dense-rows", type=int, default=1 << 20, help="--components: rows of the dense table (0: skip it)")
     ap.add_argument("--cluster", type=int, default=1000, help="--components: identical rows per cluster of the dense table")
     ap.add_argument("--overlaps", action="store_true", help="join_overlaps against join_within on simprint tables (A B A over both kernels)")
-    ap.add_argument("--shared", type=int, default=3, help="--overlaps: per cent of the assets that contain a run of another asset's chunks")
+    ap.add_argument("--overlaps-between", action="store_true", help="join_overlaps_between against join_between on two simprint tables (A B A over both kernels)")
+    ap.add_argument("--shared", type=int, default=3, help="--overlaps, --overlaps-between: per cent of the assets that contain a run of another asset's chunks")
     ap.add_argument("--search-rows", type=int, default=65536, help="--overlaps: tables of up to this many rows also time one search_raw per asset")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args()
@@ -280,6 +338,11 @@ def main():
     nphd_sizes = [int(s) for s in a.nphd_sizes.split(",") if s]
     engine = HipEngine(a.device)
     try:
+        if a.overlaps_between:
+            for nbytes in (8, 16):
+                for n in sizes:
+                    print(json.dumps(run_overlaps_between(engine, nbytes, n, a.tau * nbytes // 8, a.reps, a.shared)), flush=True)
+            return
         if a.overlaps:
             for nbytes in (8, 16):
                 for n in sizes:
