@@ -442,6 +442,57 @@ int isccsearch_join_overlaps(isccsearch_handle* h, uint32_t table, int32_t max_h
                              uint32_t* out_chunks,                 /* [n_assets] */
                              uint64_t* out_info                    /* [4] */);
 
+/* WHERE two assets share chunks: isccsearch_join_overlaps, and from the same join launch the chunk pairs of every pair of assets as
+ * aligned runs -- "chunks 40..95 of asset A are chunks 3..58 of asset B".  Table, asset_keys, max_hamming, max_doc_freq, dup_limit and
+ * capacity as for isccsearch_join_overlaps; the chunk pairs are exactly its chunk pairs (listing, stop chunk, same-asset and radius
+ * rules unchanged).
+ *   ORDINAL of a row: the number of rows of the table with the same first key word (the same asset) and a smaller second key word --
+ *                         the row's rank within its asset by ascending (offset, size).  Every row of the table counts, a stop chunk
+ *                         too: a stop chunk in the middle of a clip keeps its place and splits the run.  For a listed asset the ordinals
+ *                         are 0 .. out_chunks[asset] - 1.
+ *   SEGMENT: for an unordered pair of assets with labels src < dst let P be its chunk pairs as (o_src, o_dst, hamming), o the ordinals
+ *                         of the pair's two rows.  A segment is a maximal set {(o_src + t, o_dst + t) : t = 0 .. length - 1} in P: a
+ *                         run on one diagonal o_dst - o_src.  Every chunk pair lies in exactly one segment, so the lengths of the
+ *                         segments of (src, dst) add up to the chunk_pairs of the overlap record (src, dst).
+ *   out_pairs[2 * capacity], out_chunks[n_assets], out_info[0 .. 3]: byte for byte what isccsearch_join_overlaps returns for the same
+ *                         arguments.
+ *   out_segments[capacity]  one record per segment, sorted ascending by (src, dst, first_dst - first_src as a signed value, first_src).
+ *                         Every field is an integer defined by the set of chunk pairs and the table's keys alone: which kernel ran and
+ *                         the order in which pairs were found never show.
+ *   out_info[5]           {chunk pairs found, records written, live rows, stop chunks, segments written}.
+ * Capacity protocol as for isccsearch_join_overlaps: more than `capacity` chunk pairs return -ENOSPC with out_info[0] exact and every
+ * other output unspecified, and a retry with exactly that capacity succeeds; pairs past the capacity are counted and not written.
+ * Device memory: 352 bytes per chunk pair of the capacity (the 192 of isccsearch_join_overlaps; 64 for the pairs keyed by diagonal,
+ * unsorted and sorted, 96 for the runs before and after their reduction), 28 bytes per row (4 as isccsearch_join_overlaps; the sorted
+ * keys, 16, the sorted rows and the ordinals, 4 each) and 12 per asset, besides rocPRIM's temporary storage; kept by the handle as its
+ * other scratch buffers are.
+ * -EINVAL and -E2BIG as for isccsearch_join_overlaps, all checked on the host before anything is launched, the outputs left untouched;
+ * out_segments may be NULL only when capacity is 0, like out_pairs.  -E2BIG also for a segment of 2^31 rows or more: the difference
+ * of two ordinals travels as 32 bits.
+ * One lock covers the call; everything runs on the handle's one stream -- labelling, the ONE join launch isccsearch_join_overlaps
+ * makes, then ordinals (a sort of the table's keys on the device: the host never sees them), the pairs keyed and sorted by (src, dst,
+ * diagonal, ordinal), run heads, a reduction per run, the byte ranges gathered from the key column, then sort and reduction of
+ * isccsearch_join_overlaps -- and ONE synchronisation comes before the results are copied.  With fewer than two rows or capacity 0
+ * nothing of this is launched; chunks and info are filled all the same.
+ * Reference counterpart: IsccChunkMatch (schema.py:445-530) carries offset and size of a matched chunk for ONE query asset; the
+ * reference has no index-wide form. */
+typedef struct isccsearch_segment {
+    uint32_t src, dst;              /* labels (ranks in asset_keys), src < dst */
+    uint32_t first_src, first_dst;  /* ordinals of the run's first chunk pair */
+    uint32_t length;                /* chunk pairs in the run */
+    uint32_t sum_hamming;           /* their distances, summed */
+    uint32_t begin_src, begin_dst;  /* byte offset of the first chunk on either side (key word 1 >> 32) */
+    uint64_t end_src, end_dst;      /* offset + size of the LAST chunk on either side (may pass 2^32) */
+} isccsearch_segment;               /* 48 bytes */
+int isccsearch_join_segments(isccsearch_handle* h, uint32_t table, int32_t max_hamming,
+                             uint32_t max_doc_freq, uint32_t dup_limit,
+                             uint32_t n_assets, const uint64_t* asset_keys,
+                             uint64_t capacity,                    /* chunk pairs */
+                             isccsearch_overlap* out_pairs,        /* [2 * capacity] */
+                             isccsearch_segment* out_segments,     /* [capacity] */
+                             uint32_t* out_chunks,                 /* [n_assets] */
+                             uint64_t* out_info                    /* [5] */);
+
 /* The pairs of assets of TWO simprint tables of one handle that share chunks: the cross join of table_a and table_b (both HAMMING,
  * key_words 2, equal max_bytes), aggregated on the device as isccsearch_join_overlaps aggregates the self-join.  A row is a chunk; its
  * asset is the first key word.

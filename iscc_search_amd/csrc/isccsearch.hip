@@ -39,6 +39,7 @@
 #include "simprint_score.h"
 #include "asset_score.h"
 #include "overlap.h"
+#include "segments.h"
 #include "keymap.h"
 
 namespace {
@@ -400,6 +401,12 @@ struct isccsearch_handle {
     DevBuf<isccsearch_overlap> d_ov_marks, d_ov_records;
     DevBuf<unsigned char> d_ov_temp;
     DevBuf<uint32_t> d_ov_chunks;
+    // isccsearch_join_segments (segments.hip): the segment's keys sorted, the rows {sorted | ordinals}, the pair keys of one call
+    // {keyed | sorted} and its runs {one-pair | reduced: the segments}
+    DevBuf<isksg::RowKey> d_sg_keys;
+    DevBuf<uint32_t> d_sg_rows;
+    DevBuf<isksg::PairKey> d_sg_pairs;
+    DevBuf<isksg::Run> d_sg_runs;
     size_t am_lds_allowed = 0;                  // dynamic LDS the scoring kernel was allowed on this handle's device
     // asynchronous device searches: "results ready" for the consumer stream, "query upload done" for the pinned staging
     hipEvent_t ev_done = nullptr, ev_staged = nullptr, ev_producer = nullptr;

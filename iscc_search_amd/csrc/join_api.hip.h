@@ -2,7 +2,8 @@
 // tables by the XOR + popcount kernel of join.hip.h or, for launches over enough rows, its matrix-core form (mfma_join_kernel.hip.h);
 // and isccsearch_join_components: the self-join's launches in their LINK form, whose pairs are united in a union-find array
 // (unionfind.hip.h) instead of written; and isccsearch_join_overlaps: the self-join of a simprint table in the launches' OVERLAP form,
-// whose directed hits overlap.hip sorts and reduces to one record per ordered pair of assets; and isccsearch_join_overlaps_between: the
+// whose directed hits overlap.hip sorts and reduces to one record per ordered pair of assets; and isccsearch_join_segments: the same
+// call, whose chunk pairs segments.hip turns into aligned runs before they are reduced; and isccsearch_join_overlaps_between: the
 // cross join of two simprint tables in the same OVERLAP form, with a label space per table.
 // Needs the store of isccsearch.hip (Segment, Table; get_table of store.hip.h) and its scratch buffers.
 namespace {
@@ -352,12 +353,19 @@ extern "C" int isccsearch_join_components(isccsearch_handle* h, uint32_t table, 
 // then the records are copied.  The hit buffer is filled with ones first, so that the aggregation runs over 2 * capacity slots
 // without the host asking how many were written.  Everything the device code relies on -- asset_keys ascending and fewer than
 // 2^32 - 1 (labels and the bound of the label search), rows and hit positions below 2^32 -- is checked before anything is launched.
-extern "C" int isccsearch_join_overlaps(isccsearch_handle* h, uint32_t table, int32_t max_hamming, uint32_t max_doc_freq, uint32_t dup_limit,
-                             uint32_t n_assets, const uint64_t* asset_keys, uint64_t capacity, isccsearch_overlap* out_pairs,
-                             uint32_t* out_chunks, uint64_t* out_info) {
+//
+// `segments` (isccsearch_join_segments): the same call with the stage of segments.hip queued between the join launch and the
+// aggregation, which overwrites the hit buffer that stage reads; the segment count is the call's fifth counter and comes back behind
+// the same synchronisation.  Without the flag nothing of that stage is sized, allocated or queued.
+namespace {
+int join_overlaps_or_segments(isccsearch_handle* h, uint32_t table, int32_t max_hamming, uint32_t max_doc_freq, uint32_t dup_limit,
+                              uint32_t n_assets, const uint64_t* asset_keys, uint64_t capacity, isccsearch_overlap* out_pairs,
+                              uint32_t* out_chunks, uint64_t* out_info, bool segments, isccsearch_segment* out_segments) {
+    const char* const name = segments ? "join_segments" : "join_overlaps";
     if (!h) return fail(-EINVAL, "handle is NULL");
     if (!asset_keys || !out_chunks || !out_info) return fail(-EINVAL, "NULL argument");
     if (capacity && !out_pairs) return fail(-EINVAL, "out_pairs is NULL with capacity %llu", (unsigned long long)capacity);
+    if (segments && capacity && !out_segments) return fail(-EINVAL, "out_segments is NULL with capacity %llu", (unsigned long long)capacity);
     if (n_assets == 0 || n_assets == isk::UF_NONE) return fail(-EINVAL, "n_assets must be in 1 .. 2^32 - 2, got %u", n_assets);
     for (uint32_t i = 1; i < n_assets; ++i)
         if (asset_keys[i] <= asset_keys[i - 1])
@@ -373,21 +381,37 @@ extern "C" int isccsearch_join_overlaps(isccsearch_handle* h, uint32_t table, in
     if ((rc = get_table(h, table, tp))) return rc;
     Table& t = *tp;
     if (t.metric != ISCCSEARCH_METRIC_HAMMING || t.key_words != 2)
-        return fail(-EINVAL, "join_overlaps needs a simprint table (HAMMING, key_words 2), table %u has metric %d and key_words %d", table, t.metric, t.key_words);
+        return fail(-EINVAL, "%s needs a simprint table (HAMMING, key_words 2), table %u has metric %d and key_words %d", name, table, t.metric, t.key_words);
     Segment& s = t.seg[t.max_bytes];
     if (s.n >= (1ull << 32)) return fail(-E2BIG, "a segment of %llu rows: row numbers travel as 32 bits", (unsigned long long)s.n);
+    if (segments && s.n >= (1ull << 31))
+        return fail(-E2BIG, "a segment of %llu rows: the difference of two chunk ordinals travels as 32 bits", (unsigned long long)s.n);
     HIPOK(hipSetDevice(h->device));
     // the call's counters {chunk pairs, live rows, stop chunks, records}, asset keys, chunks per asset, row labels; for m = 2 * capacity
     // hits {appended | sorted}, one-hit records, records and rocPRIM's temporary storage: 192 bytes per chunk pair of the capacity
+    // With `segments` a fifth counter {segments} and, in buffers of their own, for the capacity pair keys {keyed | sorted} and runs
+    // {one-pair | reduced}: 160 bytes more per chunk pair; for the rows sorted keys, sorted rows and ordinals: 24 bytes per row;
+    // rocPRIM's temporary storage is shared, the larger of the two stages' needs.  The stage runs when there is a pair of rows and room.
     const uint64_t m = 2 * capacity;
+    const uint32_t n_counters = segments ? 5 : 4;
+    const bool locate = segments && capacity && s.n >= 2;
     size_t temp_bytes = 0;
-    if ((rc = h->d_join_total.ensure(4))) return rc;
+    if ((rc = h->d_join_total.ensure(n_counters))) return rc;
     if ((rc = h->d_join_live_keys.ensure(n_assets))) return rc;
     if ((rc = h->d_ov_chunks.ensure(n_assets))) return rc;
     if ((rc = h->d_join_row_labels.ensure(std::max<uint64_t>(s.n, 1)))) return rc;
     if (m) {
         std::string err;
         if ((rc = iskov::aggregate_temp_bytes(m, &temp_bytes, &err))) return fail(rc, "%s", err.c_str());
+        if (locate) {
+            size_t locate_bytes = 0;
+            if ((rc = isksg::locate_temp_bytes(s.n, capacity, &locate_bytes, &err))) return fail(rc, "%s", err.c_str());
+            temp_bytes = std::max(temp_bytes, locate_bytes);
+            if ((rc = h->d_sg_keys.ensure(s.n))) return rc;
+            if ((rc = h->d_sg_rows.ensure(2 * s.n))) return rc;
+            if ((rc = h->d_sg_pairs.ensure(m))) return rc;
+            if ((rc = h->d_sg_runs.ensure(m))) return rc;
+        }
         if ((rc = h->d_ov_hits.ensure(2 * m))) return rc;
         if ((rc = h->d_ov_marks.ensure(m))) return rc;
         if ((rc = h->d_ov_records.ensure(m))) return rc;
@@ -396,7 +420,7 @@ extern "C" int isccsearch_join_overlaps(isccsearch_handle* h, uint32_t table, in
     // (the frequency column is built by a call of its own that drains the stream: nothing of this call is queued yet)
     if (max_doc_freq > 0 && s.n && (rc = ensure_freq_column(h, t, s, dup_limit))) return rc;
     unsigned long long* const counters = reinterpret_cast<unsigned long long*>(h->d_join_total.p);
-    HIPOK(hipMemsetAsync(counters, 0, 4 * 8, h->stream));
+    HIPOK(hipMemsetAsync(counters, 0, n_counters * 8, h->stream));
     HIPOK(hipMemsetAsync(h->d_ov_chunks.p, 0, (size_t)n_assets * 4, h->stream));
     if (m) HIPOK(hipMemsetAsync(h->d_ov_hits.p, 0xFF, m * sizeof(iskov::Hit), h->stream));
     HIPOK(hipMemcpyAsync(h->d_join_live_keys.p, asset_keys, (size_t)n_assets * 8, hipMemcpyHostToDevice, h->stream));
@@ -421,6 +445,12 @@ extern "C" int isccsearch_join_overlaps(isccsearch_handle* h, uint32_t table, in
         e.out_hits = reinterpret_cast<uint4*>(h->d_ov_hits.p);
         if ((rc = join_run(h, plan))) return rc;
     }
+    if (locate) {                                     // reads the hits the aggregation below overwrites
+        std::string err;
+        if ((rc = isksg::locate(reinterpret_cast<const isksg::RowKey*>(s.keys), s.n, h->d_ov_hits.p, capacity, h->d_sg_keys.p, h->d_sg_rows.p,
+                                h->d_sg_rows.p + s.n, h->d_sg_pairs.p, h->d_sg_runs.p, counters + 4, h->d_ov_temp.p, temp_bytes, h->stream, &err)))
+            return fail(rc, "%s", err.c_str());
+    }
     if (m) {
         std::string err;
         if ((rc = iskov::aggregate(h->d_ov_hits.p, h->d_ov_hits.p + m, h->d_ov_marks.p, h->d_ov_records.p, counters + 3, m, h->d_ov_temp.p,
@@ -428,9 +458,9 @@ extern "C" int isccsearch_join_overlaps(isccsearch_handle* h, uint32_t table, in
             return fail(rc, "%s", err.c_str());
     }
     // the call's one synchronisation; the outputs change only from here on
-    uint64_t got[4] = {0, 0, 0, 0};
+    uint64_t got[5] = {0, 0, 0, 0, 0};
     std::vector<uint32_t> chunks(n_assets);
-    HIPOK(hipMemcpyAsync(got, counters, sizeof got, hipMemcpyDeviceToHost, h->stream));
+    HIPOK(hipMemcpyAsync(got, counters, n_counters * 8, hipMemcpyDeviceToHost, h->stream));
     HIPOK(hipMemcpyAsync(chunks.data(), h->d_ov_chunks.p, (size_t)n_assets * 4, hipMemcpyDeviceToHost, h->stream));
     HIPOK(hipStreamSynchronize(h->stream));
     const uint64_t total = got[0];
@@ -440,13 +470,31 @@ extern "C" int isccsearch_join_overlaps(isccsearch_handle* h, uint32_t table, in
     }
     // (slots were left unused: the run of ones behind the hits reduced to one more record, the last)
     const uint64_t n_records = m ? got[3] - (total < capacity ? 1 : 0) : 0;
-    if (n_records) {
-        HIPOK(hipMemcpyAsync(out_pairs, h->d_ov_records.p, n_records * sizeof(isccsearch_overlap), hipMemcpyDeviceToHost, h->stream));
-        HIPOK(hipStreamSynchronize(h->stream));
-    }
+    const uint64_t n_segments = locate ? got[4] - (total < capacity ? 1 : 0) : 0;       // (likewise the one run of the unused slots)
+    if (n_records) HIPOK(hipMemcpyAsync(out_pairs, h->d_ov_records.p, n_records * sizeof(isccsearch_overlap), hipMemcpyDeviceToHost, h->stream));
+    if (n_segments)
+        HIPOK(hipMemcpyAsync(out_segments, h->d_sg_runs.p + capacity, n_segments * sizeof(isccsearch_segment), hipMemcpyDeviceToHost, h->stream));
+    if (n_records || n_segments) HIPOK(hipStreamSynchronize(h->stream));
     memcpy(out_chunks, chunks.data(), (size_t)n_assets * 4);
     out_info[0] = total; out_info[1] = n_records; out_info[2] = got[1]; out_info[3] = got[2];
+    if (segments) out_info[4] = n_segments;
     return 0;
+}
+}  // namespace
+
+extern "C" int isccsearch_join_overlaps(isccsearch_handle* h, uint32_t table, int32_t max_hamming, uint32_t max_doc_freq, uint32_t dup_limit,
+                             uint32_t n_assets, const uint64_t* asset_keys, uint64_t capacity, isccsearch_overlap* out_pairs,
+                             uint32_t* out_chunks, uint64_t* out_info) {
+    return join_overlaps_or_segments(h, table, max_hamming, max_doc_freq, dup_limit, n_assets, asset_keys, capacity, out_pairs, out_chunks, out_info,
+                                     false, nullptr);
+}
+
+// isccsearch_join_overlaps and, from the same join launch, the chunk pairs of every pair of assets as aligned runs (segments.hip).
+extern "C" int isccsearch_join_segments(isccsearch_handle* h, uint32_t table, int32_t max_hamming, uint32_t max_doc_freq, uint32_t dup_limit,
+                             uint32_t n_assets, const uint64_t* asset_keys, uint64_t capacity, isccsearch_overlap* out_pairs,
+                             isccsearch_segment* out_segments, uint32_t* out_chunks, uint64_t* out_info) {
+    return join_overlaps_or_segments(h, table, max_hamming, max_doc_freq, dup_limit, n_assets, asset_keys, capacity, out_pairs, out_chunks, out_info,
+                                     true, out_segments);
 }
 
 // isccsearch_join_overlaps between TWO simprint tables: label_chunks_kernel once per table (its own asset keys, frequency column,

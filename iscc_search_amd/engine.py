@@ -447,6 +447,34 @@ class HipTable(TableChecks):
         names = ("chunk_pairs", "records", "live_rows", "stop_chunks")
         return records, chunks, dict(zip(names, (int(v) for v in info)))
 
+    def join_segments(self, max_hamming, asset_keys, max_doc_freq, max_pairs, dup_limit=1000):
+        # type: (int, np.ndarray, int, int, int) -> tuple
+        """
+        ``join_overlaps`` and, from the same join launch, WHERE the assets share chunks (``isccsearch_join_segments``).  Returns
+        ``(records, chunks, info, segments)``: the first two as ``join_overlaps`` returns them, ``info`` with ``"segments"`` besides
+        its four counts, and one ``SEGMENT_DTYPE`` record per aligned run of chunk pairs -- ``length`` consecutive chunks of asset
+        ``src`` from ordinal ``first_src`` on (a chunk's ordinal is its rank within its asset by offset, then size) that match the
+        consecutive chunks of ``dst`` from ``first_dst`` on, ``src < dst``, with the byte range on either side -- sorted by (src, dst,
+        first_dst - first_src, first_src).  Capacity, retry and ValueError as for ``join_overlaps``.
+        """
+        asset_keys = np.ascontiguousarray(asset_keys, dtype=np.uint64)
+        if asset_keys.ndim != 1:
+            raise ValueError("asset_keys must be shaped [n_assets]")
+        n_assets = asset_keys.shape[0]
+        call = self.engine._lib.isccsearch_join_segments
+        chunks = np.zeros(n_assets, dtype=np.uint32)
+        info = np.zeros(5, dtype=np.uint64)
+        held = []
+
+        def once(capacity, out):
+            held[:] = [np.empty(capacity, dtype=_lib.SEGMENT_DTYPE)]
+            return call(self.engine.handle, self.id, int(max_hamming), int(max_doc_freq), int(dup_limit), n_assets,
+                        _lib.ptr(asset_keys) if n_assets else None, capacity, out, _lib.ptr(held[0]) if capacity else None, _lib.ptr(chunks), _lib.ptr(info))
+
+        records = self._overlap_records("isccsearch_join_segments", max_pairs, info, once)
+        names = ("chunk_pairs", "records", "live_rows", "stop_chunks", "segments")
+        return records, chunks, dict(zip(names, (int(v) for v in info))), held[0][: int(info[4])]
+
     def _overlap_records(self, symbol, max_pairs, info, call):
         # type: (str, int, np.ndarray, object) -> np.ndarray
         """

@@ -349,8 +349,9 @@ class HipIndex:
         return [IndexMatch(codec.iscc_id_from_int(a, realm_a), codec.iscc_id_from_int(b, realm_b), score, types)
                 for a, b, score, types in join_sides("find_matches", side_a, side_b, other._opts, min_score, max_pairs)]
 
-    def find_shared_content(self, min_chunks=1, min_coverage=None, simprint_types=None, threshold=None, max_doc_freq=100, max_pairs=1_000_000):
-        # type: (int, Optional[float], Optional[List[str]], Optional[float], int, int) -> List[SharedContent]
+    def find_shared_content(self, min_chunks=1, min_coverage=None, simprint_types=None, threshold=None, max_doc_freq=100, max_pairs=1_000_000,
+                            segments=False, min_segment=1, max_gap=0):
+        # type: (int, Optional[float], Optional[List[str]], Optional[float], int, int, bool, int, int) -> List[SharedContent]
         """
         Every pair of assets {a, b} that share content: in some simprint type a chunk of a and a chunk of b whose similarity passes
         ``threshold`` (default: ``match_threshold_simprints``) -- a clip inside a longer video, a quoted passage, a sampled loop.
@@ -363,6 +364,13 @@ class HipIndex:
         ``score`` the mean over the types in which the pair matches.  Kept when ``max(matched_a, matched_b) >= min_chunks`` in some
         type (and ``score >= min_coverage``, if given); ordered by score descending, then (key_a, key_b).  ``simprint_types``
         restricts the tables joined.  More than ``max_pairs`` matching chunk pairs in one table raise ValueError.
+
+        ``segments=True`` also says WHERE, from the same join (``HipSimprintIndex.overlaps_located``): every ``SharedChunks`` carries
+        ``segments``, a list of ``SharedSegment`` -- "chunks 40..95 of a are chunks 3..58 of b", with the byte range on either side,
+        the number of matched chunk pairs and their mean similarity.  A segment is a run of consecutive chunks of a (ranked by offset
+        within the asset, stop chunks keeping their place) that match consecutive chunks of b.  Runs of one pair in one alignment that
+        lie at most ``max_gap`` chunks apart are merged (a re-encoded frame, a stop chunk inside a clip); merged runs of fewer than
+        ``min_segment`` matched chunks are dropped.  Ordered by (offset_a, offset_b).  Neither changes which pairs are listed.
         """
         threshold = self._opts.match_threshold_simprints if threshold is None else float(threshold)
         with self._lock:
@@ -370,7 +378,8 @@ class HipIndex:
             bodies = {t: list(self._sp_assets.get(t, {})) for t in tables}
             realm = self._realm_id or 0
         return [SharedContent(codec.iscc_id_from_int(a, realm), codec.iscc_id_from_int(b, realm), score, types)
-                for a, b, score, types in shared_content("find_shared_content", tables, bodies, threshold, max_doc_freq, max_pairs, min_chunks, min_coverage)]
+                for a, b, score, types in shared_content("find_shared_content", tables, bodies, threshold, max_doc_freq, max_pairs, min_chunks, min_coverage,
+                                                         bool(segments), int(min_segment), int(max_gap))]
 
     def find_shared_matches(self, other, min_chunks=1, min_coverage=None, simprint_types=None, threshold=None, max_doc_freq=100,
                             max_pairs=1_000_000, include_same_id=False):

@@ -283,12 +283,14 @@ class HipIndexManager:
         self._refuse_sharded("find_duplicate_groups")
         return self._locked_index(index_name).find_duplicate_groups(unit_types=unit_types, threshold=threshold, min_size=min_size)
 
-    def find_shared_content(self, index_name, min_chunks=1, min_coverage=None, simprint_types=None, threshold=None, max_doc_freq=100, max_pairs=1_000_000):
-        # type: (str, int, Optional[float], Optional[List[str]], Optional[float], int, int) -> List[SharedContent]
-        """Asset pairs of one index that share chunks (``HipIndex.find_shared_content``).  Not available on a sharded index."""
+    def find_shared_content(self, index_name, min_chunks=1, min_coverage=None, simprint_types=None, threshold=None, max_doc_freq=100, max_pairs=1_000_000,
+                            segments=False, min_segment=1, max_gap=0):
+        # type: (str, int, Optional[float], Optional[List[str]], Optional[float], int, int, bool, int, int) -> List[SharedContent]
+        """Asset pairs of one index that share chunks, and where (``HipIndex.find_shared_content``).  Not available on a sharded index."""
         self._refuse_sharded("find_shared_content")
         return self._locked_index(index_name).find_shared_content(min_chunks=min_chunks, min_coverage=min_coverage, simprint_types=simprint_types,
-                                                                  threshold=threshold, max_doc_freq=max_doc_freq, max_pairs=max_pairs)
+                                                                  threshold=threshold, max_doc_freq=max_doc_freq, max_pairs=max_pairs,
+                                                                  segments=segments, min_segment=min_segment, max_gap=max_gap)
 
     def find_matches(self, index_a, index_b, min_score=None, unit_types=None, max_pairs=1_000_000):
         # type: (str, str, Optional[float], Optional[List[str]], int) -> List[IndexMatch]

@@ -451,6 +451,17 @@ class HipIndex128:
         return self._table.join_overlaps(max_hamming, asset_keys, max_doc_freq, max_pairs, dup_limit)
 
     @property
+    def joins_segments(self):
+        # type: () -> bool
+        """Whether the table's self-join also locates the shared chunks (``isccsearch_join_segments``; a sharded table does not)."""
+        return hasattr(self._table, "join_segments")
+
+    def join_segments(self, max_hamming, asset_keys, max_doc_freq, max_pairs, dup_limit=1000):
+        # type: (int, np.ndarray, int, int, int) -> tuple
+        """``HipTable.join_segments``: the assets are the first 8 bytes of the 16-byte keys, as big-endian integers."""
+        return self._table.join_segments(max_hamming, asset_keys, max_doc_freq, max_pairs, dup_limit)
+
+    @property
     def joins_overlaps_between(self):
         # type: () -> bool
         """Whether the table joins another into asset overlaps (``isccsearch_join_overlaps_between``; a sharded table does not)."""

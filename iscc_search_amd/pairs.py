@@ -3,7 +3,8 @@ Asset pairs by device joins: the host side of ``HipIndex.find_duplicates`` (``Hi
 (``HipTable.join_between``), scored as ``search_assets`` scores (``unit_match``).  A *side* of a join is ``(tables, asset_units)``:
 unit type -> ``HipNphdIndex``, and asset key -> {unit_type: body} as indexed.  And asset GROUPS by the same joins with a union-find
 on the device where the pairs were (``find_duplicate_groups``, ``HipTable.join_components``).  And asset pairs that share CHUNKS, by a
-self-join of every simprint table aggregated on the device (``find_shared_content``, ``HipSimprintIndex.overlaps``) -- or, between two
+self-join of every simprint table aggregated on the device (``find_shared_content``, ``HipSimprintIndex.overlaps``; with
+``segments=True`` the same join also locates the shared chunks, ``HipSimprintIndex.overlaps_located``) -- or, between two
 indexes, by a cross join of the two tables of every simprint type (``find_shared_matches``, ``HipSimprintIndex.overlaps_between``).
 """
 
@@ -44,6 +45,21 @@ class DuplicateGroup:
 
 
 @dataclass
+class SharedSegment:
+    """One aligned run of a ``SharedChunks``: consecutive chunks of a (by offset) that match consecutive chunks of b."""
+
+    offset_a: int           # bytes offset_a .. end_a of asset a ...
+    end_a: int
+    offset_b: int           # ... are bytes offset_b .. end_b of asset b
+    end_b: int
+    first_chunk_a: int      # the run's first chunk on either side: its rank among its asset's chunks by (offset, size)
+    first_chunk_b: int
+    chunks: int             # matched chunk pairs in the run
+    span: int               # chunk ordinals covered on one side: ``chunks`` plus the gaps that ``max_gap`` bridged
+    similarity: float       # 1 - sum of the pairs' distances / (chunks * ndim)
+
+
+@dataclass
 class SharedChunks:
     """One simprint type of a ``SharedContent`` pair: how much of each asset's chunks has a match in the other asset."""
 
@@ -54,6 +70,7 @@ class SharedChunks:
     chunk_pairs: int        # matching (chunk of a, chunk of b) pairs
     coverage_a: float       # mean over a's chunks of the best similarity 1 - d / ndim found in b, 0 where none
     coverage_b: float
+    segments: Optional[List[SharedSegment]] = None   # with ``segments=True``: where, ordered by (offset_a, offset_b)
 
 
 @dataclass
@@ -162,8 +179,37 @@ def group_side(caller, side, threshold, min_size):
     return [keys[members[starts[g]:starts[g] + counts[g]]] for g in order.tolist()]
 
 
-def shared_content(caller, tables, bodies, threshold, max_doc_freq, max_pairs, min_chunks, min_coverage):
-    # type: (str, dict, dict, float, int, int, int, Optional[float]) -> list
+def _located(records, ndim, min_segment, max_gap):
+    # type: (np.ndarray, int, int, int) -> Dict[tuple, List[SharedSegment]]
+    """
+    {(src, dst): [SharedSegment]} of the device's segment records (sorted by (src, dst, diagonal, first_src)).  Runs of one asset pair
+    on one diagonal are merged while the next run starts at most ``max_gap`` chunks behind the end of what was merged so far: chunks
+    and distances add up, the span covers the gaps, the byte range runs from the first run's begin to the last run's end.  Kept: merged
+    runs of at least ``min_segment`` chunks; ordered by (offset_a, offset_b).
+    """
+    merged = []     # [src, dst, diagonal, first_src, first_dst, chunks, span, sum_hamming, begin_src, begin_dst, end_src, end_dst]
+    names = ("src", "dst", "first_src", "first_dst", "length", "sum_hamming", "begin_src", "begin_dst", "end_src", "end_dst")
+    for src, dst, first_src, first_dst, length, sum_hamming, begin_src, begin_dst, end_src, end_dst in zip(*(records[f].tolist() for f in names)):
+        last = merged[-1] if merged else None
+        if last is not None and last[:3] == [src, dst, first_dst - first_src] and first_src - (last[3] + last[6]) <= max_gap:
+            last[5] += length
+            last[6] = first_src + length - last[3]
+            last[7] += sum_hamming
+            last[10], last[11] = end_src, end_dst
+        else:
+            merged.append([src, dst, first_dst - first_src, first_src, first_dst, length, length, sum_hamming, begin_src, begin_dst, end_src, end_dst])
+    out = {}  # type: Dict[tuple, List[SharedSegment]]
+    for src, dst, _, first_src, first_dst, chunks, span, sum_hamming, begin_src, begin_dst, end_src, end_dst in merged:
+        if chunks >= min_segment:
+            out.setdefault((src, dst), []).append(
+                SharedSegment(begin_src, end_src, begin_dst, end_dst, first_src, first_dst, chunks, span, 1.0 - sum_hamming / (chunks * ndim)))
+    for runs in out.values():
+        runs.sort(key=lambda r: (r.offset_a, r.offset_b, r.first_chunk_a, r.first_chunk_b))
+    return out
+
+
+def shared_content(caller, tables, bodies, threshold, max_doc_freq, max_pairs, min_chunks, min_coverage, segments=False, min_segment=1, max_gap=0):
+    # type: (str, dict, dict, float, int, int, int, Optional[float], bool, int, int) -> list
     """
     [(key_a, key_b, score, {sp_type: SharedChunks})] of the asset pairs that share chunks, key_a < key_b: ONE self-join per simprint
     type in ``tables`` (sp_type -> ``HipSimprintIndex``, sorted type order) over the assets ``bodies[sp_type]`` (8-byte bodies).  Per
@@ -172,17 +218,24 @@ def shared_content(caller, tables, bodies, threshold, max_doc_freq, max_pairs, m
     the types in which the pair has a record -- the rule ``chunk_match.rank_simprint_matches`` uses across types.  Kept: pairs with
     ``max(matched_a, matched_b) >= min_chunks`` in some type and ``score >= min_coverage`` (if given); ordered by score descending,
     then (key_a, key_b).  More than ``max_pairs`` chunk pairs in one table raise ValueError; tables without the join (a sharded
-    engine's) raise NotImplementedError naming ``caller``.
+    engine's) raise NotImplementedError naming ``caller``.  ``segments``: the same join also says WHERE
+    (``HipSimprintIndex.overlaps_located``), and every ``SharedChunks`` carries its ``SharedSegment`` list, merged over gaps of at most
+    ``max_gap`` chunks and cut at ``min_segment`` chunks (``_located``); a is ``src``, since labels are ranks of ascending keys.
     """
     by_pair = {}  # type: Dict[tuple, Dict[str, SharedChunks]]
     for sp_type in sorted(tables):
         table = tables[sp_type]
-        if not table.joins_overlaps:
+        if not (getattr(table, "joins_segments", False) if segments else table.joins_overlaps):
             raise NotImplementedError(f"{caller} needs a single-GPU engine: pairs across shards need their rows exchanged")
         listed = sorted(bodies.get(sp_type, ()))
         if not listed:
             continue
-        records, chunks, _ = table.overlaps(listed, threshold, max_doc_freq, max_pairs)
+        located = None
+        if segments:
+            records, chunks, _, runs = table.overlaps_located(listed, threshold, max_doc_freq, max_pairs)
+            located = _located(runs, table.ndim, min_segment, max_gap)
+        else:
+            records, chunks, _ = table.overlaps(listed, threshold, max_doc_freq, max_pairs)
         keys = [int.from_bytes(b, "big") for b in listed]
         ndim = table.ndim
         chunks = chunks.tolist()
@@ -193,7 +246,8 @@ def shared_content(caller, tables, bodies, threshold, max_doc_freq, max_pairs, m
                 continue
             matched_b, sum_b, _ = rows[(b, a)]
             by_pair.setdefault((keys[a], keys[b]), {})[sp_type] = SharedChunks(
-                matched_a, chunks[a], matched_b, chunks[b], pairs, (matched_a - sum_a / ndim) / chunks[a], (matched_b - sum_b / ndim) / chunks[b])
+                matched_a, chunks[a], matched_b, chunks[b], pairs, (matched_a - sum_a / ndim) / chunks[a], (matched_b - sum_b / ndim) / chunks[b],
+                None if located is None else located.get((a, b), []))
     return _rank_shared(by_pair, min_chunks, min_coverage)
 
 

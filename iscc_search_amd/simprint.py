@@ -494,13 +494,36 @@ class HipSimprintIndex:
         ``(records, chunks, info)`` as it returns them, an asset's label being its position in ``asset_bodies``.  More than
         ``max_pairs`` matching chunk pairs raise ValueError.
         """
+        return self._index.join_overlaps(self._radius_for(threshold), self._asset_keys(asset_bodies), int(max_doc_freq), max_pairs,
+                                         max(DOC_FREQ_DUP_LIMIT, int(max_doc_freq)))
+
+    @staticmethod
+    def _asset_keys(asset_bodies):
+        # type: (list[bytes]) -> np.ndarray
+        """The uint64 keys of ``asset_bodies``, which must be 8-byte ISCC-ID bodies, ascending, without repeats."""
         keys = np.frombuffer(b"".join(bytes(b) for b in asset_bodies), dtype=">u8").astype(np.uint64)
         if len(keys) != len(asset_bodies):
             raise ValueError("asset_bodies must be 8-byte ISCC-ID bodies")
         if len(keys) > 1 and not bool(np.all(keys[1:] > keys[:-1])):
             raise ValueError("asset_bodies must be ascending without repeats: an asset's label is its position")
-        dup_limit = max(DOC_FREQ_DUP_LIMIT, int(max_doc_freq))
-        return self._index.join_overlaps(self._radius_for(threshold), keys, int(max_doc_freq), max_pairs, dup_limit)
+        return keys
+
+    @property
+    def joins_segments(self):
+        # type: () -> bool
+        """Whether ``overlaps_located`` is available (a single-GPU table; a sharded one has no self-join)."""
+        return self._index.joins_segments
+
+    def overlaps_located(self, asset_bodies, threshold, max_doc_freq, max_pairs):
+        # type: (list[bytes], float, int, int) -> tuple
+        """
+        ``overlaps`` and WHERE the assets share chunks, from the same self-join (``HipTable.join_segments``):
+        ``(records, chunks, info, segments)`` as it returns them.  A segment says that ``length`` consecutive chunks of asset ``src``
+        (by offset, from chunk ``first_src`` on: bytes ``begin_src`` .. ``end_src``) match consecutive chunks of asset ``dst``
+        (from ``first_dst``, bytes ``begin_dst`` .. ``end_dst``); ``src < dst`` are positions in ``asset_bodies``.
+        """
+        return self._index.join_segments(self._radius_for(threshold), self._asset_keys(asset_bodies), int(max_doc_freq), max_pairs,
+                                         max(DOC_FREQ_DUP_LIMIT, int(max_doc_freq)))
 
     @property
     def joins_overlaps_between(self):

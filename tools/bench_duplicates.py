@@ -37,11 +37,17 @@ order, disjoint asset keys, --shared per cent of A's assets containing a run of 
 legs A B A over both kernels; per leg join_overlaps_between and, on the same two tables and tau, isccsearch_join_between -- the same
 scan --, each one warm-up call and the median of --reps.
 
+--segments: isccsearch_join_segments (join_overlaps plus the run detection of csrc/segments.hip, from one join launch) against
+isccsearch_join_overlaps on the tables of --overlaps, whose planted runs of 4-8 chunks are the segments to find.  On either kernel three
+legs A B A (join_overlaps, join_segments, join_overlaps), each one warm-up call and the median of --reps; the tool asserts that both
+calls agree on chunk pairs and records and that the segments' lengths add up to the chunk pairs.
+
 usage: python tools/bench_duplicates.py [--mfma both] [--reps 5] [--sizes 65536,262144,1048576,4194304] [--nphd-sizes 262144,1048576] [--tau 6]
        python tools/bench_duplicates.py --between [--rows-a N --rows-b M] [the same options]
        python tools/bench_duplicates.py --components [--sizes 1048576 --nphd-sizes 1048576] [--dense-rows 1048576 --cluster 1000]
        python tools/bench_duplicates.py --overlaps [--sizes 65536,262144,1048576] [--shared 3] [--search-rows 65536]
        python tools/bench_duplicates.py --overlaps-between [--sizes 65536,262144,1048576] [--shared 3]
+       python tools/bench_duplicates.py --segments [--sizes 65536,1048576] [--shared 3]
 """
 
 import argparse
@@ -265,6 +271,34 @@ def run_overlaps(engine, nbytes, n, tau, reps, shared_pct, search_rows):
         index.close()
 
 
+def run_segments(engine, nbytes, n, tau, reps, shared_pct):
+    """join_overlaps, join_segments, join_overlaps (A B A) on one simprint table, on either kernel."""
+    from iscc_search_amd.simprint import HipSimprintIndex
+
+    rng = np.random.default_rng(4242 + n + nbytes)
+    keys, words, asset_keys = simprint_rows(rng, n, nbytes, 16, shared_pct)
+    index = HipSimprintIndex(engine, ndim=8 * nbytes)
+    t = index._index._table
+    try:
+        for lo in range(0, n, 1 << 18):
+            t.add(keys[lo:lo + (1 << 18)], words[lo:lo + (1 << 18)], None, trusted_unique=True)
+        overlaps = lambda: t.join_overlaps(tau, asset_keys, 0, 1 << 22)      # noqa: E731
+        segments = lambda: t.join_segments(tau, asset_keys, 0, 1 << 22)      # noqa: E731
+        out = {"join": "segments", "table": f"simprints {8 * nbytes}-bit", "rows": n, "assets": len(asset_keys), "tau": tau, "kernels": []}
+        for mfma in (False, True):
+            a1, info_a = leg(engine, mfma, overlaps, reps, found=lambda o: o[2])
+            b, info_b = leg(engine, mfma, segments, reps, found=lambda o: (o[2], int(o[3]["length"].sum()), int(o[3]["length"].max()) if len(o[3]) else 0))
+            a2, _ = leg(engine, mfma, overlaps, reps, found=lambda o: o[2])
+            info_b, in_runs, longest = info_b
+            assert {k: info_b[k] for k in info_a} == info_a and in_runs == info_b["chunk_pairs"], "join_segments disagrees with join_overlaps"
+            out["kernels"].append(dict(kernel="mfma" if mfma else "valu", overlaps_seconds=[round(a1, 5), round(a2, 5)], segments_seconds=round(b, 5),
+                                       segments_minus_overlaps_seconds=round(b - (a1 + a2) / 2, 5), chunk_pairs=info_b["chunk_pairs"],
+                                       records=info_b["records"], segments=info_b["segments"], longest_run=longest))
+        return out
+    finally:
+        index.close()
+
+
 def simprint_two_tables(rng, n, nbytes, per_asset, shared_pct):
     """Two tables of n chunks each, (keys, words, asset keys) per side: ``simprint_rows`` with every run copied from B into A."""
     W = nbytes // 8
@@ -330,7 +364,8 @@ def main():
     ap.add_argument("--cluster", type=int, default=1000, help="--components: identical rows per cluster of the dense table")
     ap.add_argument("--overlaps", action="store_true", help="join_overlaps against join_within on simprint tables (A B A over both kernels)")
     ap.add_argument("--overlaps-between", action="store_true", help="join_overlaps_between against join_between on two simprint tables (A B A over both kernels)")
-    ap.add_argument("--shared", type=int, default=3, help="--overlaps, --overlaps-between: per cent of the assets that contain a run of another asset's chunks")
+    ap.add_argument("--segments", action="store_true", help="join_segments against join_overlaps on simprint tables (A B A on either kernel)")
+    ap.add_argument("--shared", type=int, default=3, help="--overlaps, --overlaps-between, --segments: per cent of the assets that contain a run of another asset's chunks")
     ap.add_argument("--search-rows", type=int, default=65536, help="--overlaps: tables of up to this many rows also time one search_raw per asset")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args()
@@ -342,6 +377,11 @@ def main():
             for nbytes in (8, 16):
                 for n in sizes:
                     print(json.dumps(run_overlaps_between(engine, nbytes, n, a.tau * nbytes // 8, a.reps, a.shared)), flush=True)
+            return
+        if a.segments:
+            for nbytes in (8, 16):
+                for n in sizes:
+                    print(json.dumps(run_segments(engine, nbytes, n, a.tau * nbytes // 8, a.reps, a.shared)), flush=True)
             return
         if a.overlaps:
             for nbytes in (8, 16):
