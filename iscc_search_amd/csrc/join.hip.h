@@ -6,31 +6,34 @@
 // segment per code length); a pair of segments (la, lb bytes) compares W = ceil(min(la, lb)/8) words, the partial last word
 // masked as the scans mask it.
 //
-// join_scan_kernel<W, MASK>: the XOR + popcount scan of valu_scan_kernel.hip.h with a tile of the table's own rows as its queries.
+// join_scan_kernel: the XOR + popcount scan of valu_scan_kernel.hip.h with a tile of the table's own rows as its queries.
 //   grid = one block per group of TQ rows of side A (wave-uniform, in SGPRs); every block streams side B once, each lane
 //   holding 2*U rows per slab in VGPRs.  Within one segment (A == B) only pairs row_a < row_b count, and a block starts
 //   streaming at the slab of its first row: no block is launched without a pair to look at.
 //   Per (row, A row): acc = bias + popc(lo ^ a_lo) + popc(hi ^ a_hi) per word, acc < 2^31 <=> hamming <= tau; one v_min3
 //   folds two rows into the lane's minimum.  A wave whose minimum passes anywhere takes the (rare) emit path: it rescores
-//   its rows against the A rows re-read by scalar loads, drops the pairs that are not pairs (row_b <= row_a, rows past the
-//   end), counts the rest, takes ONE atomic slot range for the wave and writes (key_a < key_b, hamming, prefix bits) with
-//   vector stores.  Pairs past `capacity` are counted and not written.
-// join_scan_kernel<W, MASK, true>: the same scan over segments of two tables.  Only the emit path differs: every (row_a, row_b)
-//   is a pair, and the keys are not ordered -- the key of the side in SGPRs goes to the output column of the table it came
-//   from (JoinEmit::sgpr_side_is_b).  A template parameter, so that the self-join's code does not change.
-// join_scan_kernel<W, MASK, false, true> (LINK, isccsearch_join_components): the self-join's scan again, and again only the emit
-//   path differs: it keeps the pair test and drops the prefix scan, the slots, the key gathers and the stores -- per pair it loads
-//   the two rows' labels (JoinEmit::labels_a / labels_b; UF_NONE: the row takes no part), unites them in JoinEmit::parent
-//   (uf_union of unionfind.hip.h) and counts the pair; one atomic per wave adds the count to JoinEmit::total.
-// join_scan_kernel<W, MASK, false, false, true> (OVERLAP, isccsearch_join_overlaps): the self-join's scan a third time, and only the
-//   emit path differs: per pair it loads the two rows' labels (the ranks of their assets; UF_NONE: the row is not listed or is a
-//   stop chunk) and only a pair of two DIFFERENT labels takes a slot (overlap_pair) -- from the same wave-aggregated counter,
-//   one returned atomic per wave (overlap_slots).  A pair with a slot writes two directed hits (label_i, label_j, row_i, hamming)
-//   and (label_j, label_i, row_j, hamming) with vector stores (overlap_write); overlap.hip sorts and reduces them.
-// join_scan_kernel<W, MASK, true, false, true> (CROSS + OVERLAP, isccsearch_join_overlaps_between): the cross join's scan with the
-//   OVERLAP emit path.  The two tables' labels live in two spaces told apart by LABEL_SIDE_B, so two labelled rows never carry equal
-//   labels; what a pair can share is its asset KEY (one asset held by both tables), and with JoinEmit::skip_same_key such a pair
-//   takes no slot -- the two rows' first key words are compared, in the emit path only.
+//   its rows against the A rows re-read by scalar loads (two passes for the forms that write: count, one atomic per wave, write) and
+//   drops the pairs that are not pairs (row_b <= row_a, rows past the end); the rest are its candidates.
+// join_scan_kernel<W, MASK, F, CROSS> and mfma_join_kernel<W, F, CROSS> (mfma_join_kernel.hip.h) find their pairs alike whatever the
+// form; only the emit path -- `emit` here, `process_ring` there -- knows what a pair leaves behind.  Its candidates are (i: row of the side
+// in SGPRs / held in LDS, j: streamed row, h: distance).
+//   CROSS: the two sides are segments of two tables -- every (row_a, row_b) is a candidate; else only row_b > row_a within one segment.
+//   JoinForm::PAIRS (isccsearch_join_within / _between): every candidate is counted, the wave takes ONE atomic slot range and a second
+//     pass writes (key_a, key_b, hamming, prefix bits) with vector stores; the self-join orders the two keys, the cross join routes the
+//     key of the SGPR / held side to the output column of the table it came from (JoinEmit::sgpr_side_is_b).  Pairs past `capacity`
+//     are counted and not written.
+//   JoinForm::LINK (isccsearch_join_components, the self-join only): ONE pass -- per candidate the two rows' labels are loaded
+//     (JoinEmit::labels_a / labels_b; UF_NONE: the row takes no part) and united in JoinEmit::parent (link_pair, uf_union of
+//     unionfind.hip.h); one atomic per wave adds the labelled pairs to JoinEmit::total.  No slots, nothing written.
+//   JoinForm::OVERLAP (isccsearch_join_overlaps / _segments / _overlaps_between): labels are the ranks of the rows' assets (UF_NONE: not
+//     listed, or a stop chunk); only a candidate of two DIFFERENT labels takes a slot (overlap_pair, asked in both passes so that slots
+//     and counts agree; overlap_slots) and writes two directed hits (label_i, label_j, row_i, hamming) and (label_j, label_i, row_j,
+//     hamming) (overlap_write), which overlap.hip sorts and reduces.  CROSS: the two tables' labels live in two spaces told apart by
+//     LABEL_SIDE_B, so they always differ; what a pair can share is its asset KEY, and with JoinEmit::skip_same_key such a pair takes
+//     no slot.
+// A form is a template parameter, so that no form's code changes another's; join_form_exists says which are instantiated.  The emit
+// branches of the two kernels are kept as they stand on purpose: the XOR + popcount kernel's hot loop is register-allocated together
+// with its inlined emit path, and its machine code moves with any change to that path ("The join forms").
 // Slabs are read up to the next multiple of the slab size: column capacities are multiples of ROW_ALIGN (2 048 rows), which
 // every slab size divides, so those reads stay inside the allocation (rows past n are dropped in the emit path).
 #pragma once
@@ -99,6 +102,25 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t c) {
     return c;
 }
 
+// ---- what a join leaves behind for the pairs it finds (the file comment describes the forms)
+enum class JoinForm : int { PAIRS, LINK, OVERLAP };
+// what exists: every form over one table and over two, except LINK (components are those of one table)
+constexpr bool join_form_exists(JoinForm f, bool cross) { return !(f == JoinForm::LINK && cross); }
+template <JoinForm F, bool CROSS> struct JoinFormTag {
+    static constexpr JoinForm form = F;
+    static constexpr bool cross = CROSS;
+};
+// host: f(JoinFormTag<form, cross>{}) -- the one place that maps (form, cross) to instantiations; false if that one does not exist
+template <typename Fn> bool with_join_form(JoinForm form, bool cross, Fn&& f) {
+    if (!join_form_exists(form, cross)) return false;
+    switch (form) {
+        case JoinForm::PAIRS: cross ? f(JoinFormTag<JoinForm::PAIRS, true>{}) : f(JoinFormTag<JoinForm::PAIRS, false>{}); return true;
+        case JoinForm::LINK: f(JoinFormTag<JoinForm::LINK, false>{}); return true;
+        case JoinForm::OVERLAP: cross ? f(JoinFormTag<JoinForm::OVERLAP, true>{}) : f(JoinFormTag<JoinForm::OVERLAP, false>{}); return true;
+    }
+    return false;
+}
+
 // LINK form of both emit paths, per pair (held / SGPR-side row i, streamed row j): unite the two rows' labels; 1 if both have one
 __device__ __forceinline__ uint32_t link_pair(const JoinEmit& e, uint64_t i, uint64_t j) {
     const uint32_t la = e.labels_a[i], lb = e.labels_b[j];
@@ -148,10 +170,10 @@ __device__ __forceinline__ void overlap_write(const JoinEmit& e, uint64_t slot, 
     e.out_hits[2 * slot + 1] = make_uint4(lb, la, (uint32_t)j, h);
 }
 
-template <int W, bool MASK, bool CROSS = false, bool LINK = false, bool OVERLAP = false>
+template <int W, bool MASK, JoinForm F, bool CROSS>
 __global__ __launch_bounds__(BLOCK) void join_scan_kernel(const JoinParams p) {
-    static_assert(!(LINK && CROSS), "components are those of one table");
-    static_assert(!(OVERLAP && LINK), "overlaps are a form of their own");
+    static_assert(join_form_exists(F, CROSS), "no such join form");
+    constexpr bool LINK = F == JoinForm::LINK, OVERLAP = F == JoinForm::OVERLAP;
     constexpr int TQ = JoinCfg<W>::TQ, U = JoinCfg<W>::U;
     constexpr uint32_t SLAB = JoinCfg<W>::SLAB;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;

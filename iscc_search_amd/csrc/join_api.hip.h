@@ -7,23 +7,31 @@
 // cross join of two simprint tables in the same OVERLAP form, with a label space per table.
 // Needs the store of isccsearch.hip (Segment, Table; get_table of store.hip.h) and its scratch buffers.
 namespace {
-// one launch of the join kernel (join.hip.h)
-template <int W, bool CROSS, bool LINK, bool OVERLAP>
-void launch_join(const isk::JoinParams& jp, bool mask, uint64_t blocks, hipStream_t stream) {
-    if (mask) hipLaunchKernelGGL((isk::join_scan_kernel<W, true, CROSS, LINK, OVERLAP>), dim3((uint32_t)blocks), dim3(isk::BLOCK), 0, stream, jp);
-    else hipLaunchKernelGGL((isk::join_scan_kernel<W, false, CROSS, LINK, OVERLAP>), dim3((uint32_t)blocks), dim3(isk::BLOCK), 0, stream, jp);
-}
-template <bool CROSS, bool LINK = false, bool OVERLAP = false>
-void launch_join(uint32_t W, const isk::JoinParams& jp, bool mask, uint64_t blocks, hipStream_t stream) {
-    switch (W) {
-        case 1: launch_join<1, CROSS, LINK, OVERLAP>(jp, mask, blocks, stream); break;
-        case 2: launch_join<2, CROSS, LINK, OVERLAP>(jp, mask, blocks, stream); break;
-        case 3: launch_join<3, CROSS, LINK, OVERLAP>(jp, mask, blocks, stream); break;
-        default: launch_join<4, CROSS, LINK, OVERLAP>(jp, mask, blocks, stream); break;
-    }
+// one launch of the join kernel (join.hip.h) in the form (form, cross); false: that form is not instantiated
+bool launch_join(isk::JoinForm form, bool cross, uint32_t W, const isk::JoinParams& jp, bool mask, uint64_t blocks, hipStream_t stream) {
+    return isk::with_join_form(form, cross, [&](auto f) { isk::with_words((int)W, [&](auto w) {
+        constexpr int WORDS = decltype(w)::value;
+        constexpr isk::JoinForm F = decltype(f)::form;
+        constexpr bool CROSS = decltype(f)::cross;
+        if (mask) hipLaunchKernelGGL((isk::join_scan_kernel<WORDS, true, F, CROSS>), dim3((uint32_t)blocks), dim3(isk::BLOCK), 0, stream, jp);
+        else hipLaunchKernelGGL((isk::join_scan_kernel<WORDS, false, F, CROSS>), dim3((uint32_t)blocks), dim3(isk::BLOCK), 0, stream, jp);
+    }); });
 }
 constexpr uint32_t join_rows_per_block(uint32_t W) {
     return W == 1 ? isk::join_rows_per_block<1>() : W == 2 ? isk::join_rows_per_block<2>() : W == 3 ? isk::join_rows_per_block<3>() : isk::join_rows_per_block<4>();
+}
+// the grid of the one-thread-per-row kernels beside the joins (they stride over what a grid of 2^16 blocks leaves)
+uint32_t row_blocks(uint64_t n) { return (uint32_t)std::min<uint64_t>((n + isk::BLOCK - 1) / isk::BLOCK, 1u << 16); }
+// keys[0 .. n) strictly ascending, or the refusal that names the argument (not_ascending: the test of one entry, for a caller whose
+// pass over the keys checks more than this)
+inline bool not_ascending(const uint64_t* keys, uint64_t i) { return i && keys[i] <= keys[i - 1]; }
+int fail_not_ascending(const char* name, uint64_t i) {
+    return fail(-EINVAL, "%s must be strictly ascending: %s[%llu] <= %s[%llu]", name, name, (unsigned long long)i, name, (unsigned long long)(i - 1));
+}
+int check_ascending(const char* name, const uint64_t* keys, uint64_t n) {
+    for (uint64_t i = 1; i < n; ++i)
+        if (not_ascending(keys, i)) return fail_not_ascending(name, i);
+    return 0;
 }
 
 // One call's launches: one per pair of segments, all appending to one output.  What only the emit path reads goes to the
@@ -33,12 +41,14 @@ struct JoinPlan {
     struct Launch { isk::JoinParams jp; uint32_t W; bool mask; uint64_t blocks; bool mfma; isk::MfmaJoinParams mp; uint32_t groups; uint64_t chunks; };
     std::vector<Launch> launches;
     std::vector<isk::JoinEmit> emits;
+    isk::JoinForm form = isk::JoinForm::PAIRS;     // the form of either kernel, with `cross`: join.hip.h
     bool cross = false;
-    bool link = false;     // isccsearch_join_components: the LINK form of either kernel (JoinEmit::labels_a, labels_b, parent are set)
-    bool overlap = false;  // isccsearch_join_overlaps: the OVERLAP form of either kernel (JoinEmit::labels_a, labels_b, out_hits are set);
-                           // with `cross`: isccsearch_join_overlaps_between
     uint32_t KW = 1;
     uint64_t capacity = 0, cap_alloc = 1;
+    // what the form's emit path needs besides the rows' labels (join_add): set by the caller after join_begin
+    uint32_t* parent = nullptr;                    // LINK: the union-find array
+    uint4* out_hits = nullptr;                     // OVERLAP: [2 * capacity]
+    bool skip_same_key = false;                    // OVERLAP, cross
 };
 
 int join_check_args(isccsearch_handle* h, const int16_t* max_hamming, uint64_t capacity, uint64_t* out_keys_a, uint64_t* out_keys_b,
@@ -51,27 +61,32 @@ int join_check_args(isccsearch_handle* h, const int16_t* max_hamming, uint64_t c
     return 0;
 }
 
-// the output buffers of one call and its pair counter, zeroed
-int join_begin(isccsearch_handle* h, JoinPlan& plan, bool cross, uint32_t KW, uint64_t capacity) {
+// The plan of one call in the form (form, cross) and the call's counters, zeroed ([0] is the pair counter every launch adds to).  The
+// PAIRS form's output buffers are sized here; LINK and OVERLAP write none of them.
+int join_begin(isccsearch_handle* h, JoinPlan& plan, isk::JoinForm form, bool cross, uint32_t KW, uint64_t capacity, uint32_t n_counters = 1) {
+    plan.form = form;
     plan.cross = cross;
     plan.KW = KW;
     plan.capacity = capacity;
     plan.cap_alloc = std::max<uint64_t>(capacity, 1);
     int rc;
-    if ((rc = h->d_join_keys.ensure(plan.cap_alloc * 2 * KW))) return rc;
-    if ((rc = h->d_join_ham.ensure(plan.cap_alloc))) return rc;
-    if ((rc = h->d_join_pb.ensure(plan.cap_alloc))) return rc;
-    if ((rc = h->d_join_total.ensure(1))) return rc;
-    HIPOK(hipMemsetAsync(h->d_join_total.p, 0, 8, h->stream));
+    if (form == isk::JoinForm::PAIRS) {
+        if ((rc = h->d_join_keys.ensure(plan.cap_alloc * 2 * KW))) return rc;
+        if ((rc = h->d_join_ham.ensure(plan.cap_alloc))) return rc;
+        if ((rc = h->d_join_pb.ensure(plan.cap_alloc))) return rc;
+    }
+    if ((rc = h->d_join_total.ensure(n_counters))) return rc;
+    HIPOK(hipMemsetAsync(h->d_join_total.p, 0, n_counters * 8, h->stream));
     return 0;
 }
 
 // One launch: segment A (one block per TQ rows, the rows in SGPRs) against segment B (streamed by every block) over a common
 // prefix of pbytes bytes under tau.  `same`: A and B are one segment (the self-join keeps row_a < row_b).  `sgpr_side_is_b`:
-// a cross join whose segment A belongs to the call's table_b.
+// a cross join whose segment A belongs to the call's table_b.  labels_a / labels_b: a label per row of A / B, for LINK and OVERLAP.
 // On the matrix cores (options mfma, join_mfma; both segments of at least join_mfma_min_rows rows) segment A is the HELD side --
 // chunks of its rows in LDS, what the SGPRs are to join_scan_kernel -- and B is streamed: the same roles, the same JoinEmit.
-int join_add(isccsearch_handle* h, JoinPlan& plan, Segment& A, Segment& B, uint32_t pbytes, int tau, bool same, bool sgpr_side_is_b) {
+int join_add(isccsearch_handle* h, JoinPlan& plan, Segment& A, Segment& B, uint32_t pbytes, int tau, bool same, bool sgpr_side_is_b,
+             const uint32_t* labels_a = nullptr, const uint32_t* labels_b = nullptr) {
     const uint32_t W = (pbytes + 7) / 8;
     JoinPlan::Launch L{};
     set_cols(L.jp.col_a, A, W);
@@ -80,18 +95,33 @@ int join_add(isccsearch_handle* h, JoinPlan& plan, Segment& A, Segment& B, uint3
     L.jp.mask = mask_for(pbytes);
     L.jp.tau = (uint32_t)std::min<int>(tau, 8 * ISCCSEARCH_MAX_BYTES);
     L.jp.same = same ? 1u : 0u;
+    // the fields the plan's form reads (JoinEmit, join.hip.h); the others stay null
     isk::JoinEmit e{};
-    e.keys_a = A.keys; e.keys_b = B.keys;
     e.n_a = A.n;
     e.capacity = plan.capacity;
     e.total = reinterpret_cast<unsigned long long*>(h->d_join_total.p);
-    e.out_keys_a = h->d_join_keys.p;
-    e.out_keys_b = h->d_join_keys.p + plan.cap_alloc * plan.KW;
-    e.out_hamming = h->d_join_ham.p;
-    e.out_prefix_bits = h->d_join_pb.p;
-    e.prefix_bits = 8 * pbytes;
-    e.kw = plan.KW;
-    e.sgpr_side_is_b = sgpr_side_is_b ? 1u : 0u;
+    switch (plan.form) {
+        case isk::JoinForm::PAIRS:
+            e.keys_a = A.keys; e.keys_b = B.keys;
+            e.out_keys_a = h->d_join_keys.p;
+            e.out_keys_b = h->d_join_keys.p + plan.cap_alloc * plan.KW;
+            e.out_hamming = h->d_join_ham.p;
+            e.out_prefix_bits = h->d_join_pb.p;
+            e.prefix_bits = 8 * pbytes;
+            e.kw = plan.KW;
+            e.sgpr_side_is_b = sgpr_side_is_b ? 1u : 0u;
+            break;
+        case isk::JoinForm::LINK:
+            e.labels_a = labels_a; e.labels_b = labels_b;
+            e.parent = plan.parent;
+            break;
+        case isk::JoinForm::OVERLAP:
+            e.labels_a = labels_a; e.labels_b = labels_b;
+            e.out_hits = plan.out_hits;
+            e.keys_a = A.keys; e.keys_b = B.keys;      // (skip_same_key compares the rows' asset keys)
+            e.skip_same_key = plan.skip_same_key ? 1u : 0u;
+            break;
+    }
     // within one segment the last row pairs with no later one
     const uint64_t a_rows = same ? A.n - 1 : A.n;
     L.W = W;
@@ -117,6 +147,22 @@ int join_add(isccsearch_handle* h, JoinPlan& plan, Segment& A, Segment& B, uint3
     return 0;
 }
 
+// The launches of a table's self-join: add(a_len, b_len, pbytes, same) for every pair of non-empty segments la <= lb that
+// max_hamming admits (the pair compares pbytes = la bytes under max_hamming[la]; `same`: la == lb, which takes 2 rows).  Side A
+// (a_len: one block per TQ rows, or held in LDS chunk by chunk) is the segment with more rows; side B is streamed by every block.
+template <typename Add> int join_self_pairs(Table& t, const int16_t* max_hamming, Add&& add) {
+    for (uint32_t la = 1; la <= ISCCSEARCH_MAX_BYTES; ++la) {
+        if (!t.seg[la].n || max_hamming[la] < 0) continue;
+        for (uint32_t lb = la; lb <= ISCCSEARCH_MAX_BYTES; ++lb) {
+            const bool same = la == lb;
+            if (!t.seg[lb].n || (same && t.seg[la].n < 2)) continue;
+            const uint32_t a_len = t.seg[lb].n > t.seg[la].n ? lb : la, b_len = a_len == la ? lb : la;
+            if (int rc = add(a_len, b_len, la, same)) return rc;
+        }
+    }
+    return 0;
+}
+
 // The launches of one call, in order on the handle's stream.
 int join_run(isccsearch_handle* h, JoinPlan& plan) {
     if (!plan.launches.empty()) {
@@ -132,7 +178,7 @@ int join_run(isccsearch_handle* h, JoinPlan& plan) {
                 for (uint64_t c = 0; c < L.chunks; c += isk::MFMA_JOIN_MAX_CHUNKS) {
                     L.mp.chunk_base = c;
                     const uint32_t chunks = (uint32_t)std::min<uint64_t>(L.chunks - c, isk::MFMA_JOIN_MAX_CHUNKS);
-                    const int lrc = isk::launch_mfma_join((int)L.W, plan.cross, blocks_x, chunks, L.groups, h->stream, L.mp, plan.link, plan.overlap);
+                    const int lrc = isk::launch_mfma_join((int)L.W, plan.form, plan.cross, blocks_x, chunks, L.groups, h->stream, L.mp);
                     if (lrc) return fail(-EINVAL, "the matrix-core join does not take chunks of %u groups of %u words", L.groups, L.W);
                     HIPOK(hipGetLastError());
                     h->stats.join_launches += 1;
@@ -140,11 +186,8 @@ int join_run(isccsearch_handle* h, JoinPlan& plan) {
                 }
                 continue;
             }
-            if (plan.overlap && plan.cross) launch_join<true, false, true>(L.W, L.jp, L.mask, L.blocks, h->stream);
-            else if (plan.overlap) launch_join<false, false, true>(L.W, L.jp, L.mask, L.blocks, h->stream);
-            else if (plan.link) launch_join<false, true>(L.W, L.jp, L.mask, L.blocks, h->stream);
-            else if (plan.cross) launch_join<true>(L.W, L.jp, L.mask, L.blocks, h->stream);
-            else launch_join<false>(L.W, L.jp, L.mask, L.blocks, h->stream);
+            if (!launch_join(plan.form, plan.cross, L.W, L.jp, L.mask, L.blocks, h->stream))
+                return fail(-EINVAL, "the join kernel has no form %d%s", (int)plan.form, plan.cross ? " over two tables" : "");
             HIPOK(hipGetLastError());
             h->stats.join_launches += 1;
         }
@@ -217,23 +260,15 @@ extern "C" int isccsearch_join_within(isccsearch_handle* h, uint32_t table, cons
     Table& t = *tp;
     HIPOK(hipSetDevice(h->device));
     JoinPlan plan;
-    if ((rc = join_begin(h, plan, false, (uint32_t)t.key_words, capacity))) return rc;
-    // one launch per pair of segments (la <= lb: the pair compares la bytes under max_hamming[la])
-    for (uint32_t la = 1; la <= ISCCSEARCH_MAX_BYTES; ++la) {
-        if (!t.seg[la].n || max_hamming[la] < 0) continue;
-        for (uint32_t lb = la; lb <= ISCCSEARCH_MAX_BYTES; ++lb) {
-            const bool same = la == lb;
-            if (!t.seg[lb].n || (same && t.seg[la].n < 2)) continue;
-            // side A (one block per TQ rows, or held in LDS chunk by chunk) is the segment with more rows; side B is streamed by every block
-            Segment& A = t.seg[lb].n > t.seg[la].n ? t.seg[lb] : t.seg[la];
-            Segment& B = &A == &t.seg[la] ? t.seg[lb] : t.seg[la];
-            if ((rc = join_add(h, plan, A, B, la, max_hamming[la], same, false))) return rc;
-        }
-    }
+    if ((rc = join_begin(h, plan, isk::JoinForm::PAIRS, false, (uint32_t)t.key_words, capacity))) return rc;
+    rc = join_self_pairs(t, max_hamming, [&](uint32_t a_len, uint32_t b_len, uint32_t pbytes, bool same) {
+        return join_add(h, plan, t.seg[a_len], t.seg[b_len], pbytes, max_hamming[pbytes], same, false);
+    });
+    if (rc) return rc;
     return join_finish(h, plan, out_keys_a, out_keys_b, out_hamming, out_prefix_bits, out_total);
 }
 
-// One cross-join launch (join_scan_kernel<W, MASK, true> or mfma_join_kernel<W, true>) per pair of non-empty segments (la of table_a, lb of table_b), in either order of
+// One cross-join launch per pair of non-empty segments (la of table_a, lb of table_b), in either order of
 // lengths: the pair compares min(la, lb) bytes.  Both tables live on this handle, so one lock covers the call.
 extern "C" int isccsearch_join_between(isccsearch_handle* h, uint32_t table_a, uint32_t table_b, const int16_t* max_hamming,
                             uint64_t capacity, uint64_t* out_keys_a, uint64_t* out_keys_b, uint32_t* out_hamming,
@@ -252,7 +287,7 @@ extern "C" int isccsearch_join_between(isccsearch_handle* h, uint32_t table_a, u
         return fail(-EINVAL, "Hamming tables %u and %u hold codes of different lengths (%d, %d bytes)", table_a, table_b, ta->max_bytes, tb->max_bytes);
     HIPOK(hipSetDevice(h->device));
     JoinPlan plan;
-    if ((rc = join_begin(h, plan, true, (uint32_t)ta->key_words, capacity))) return rc;
+    if ((rc = join_begin(h, plan, isk::JoinForm::PAIRS, true, (uint32_t)ta->key_words, capacity))) return rc;
     for (uint32_t la = 1; la <= ISCCSEARCH_MAX_BYTES; ++la) {
         if (!ta->seg[la].n) continue;
         for (uint32_t lb = 1; lb <= ISCCSEARCH_MAX_BYTES; ++lb) {
@@ -268,8 +303,7 @@ extern "C" int isccsearch_join_between(isccsearch_handle* h, uint32_t table_a, u
     return join_finish(h, plan, out_keys_a, out_keys_b, out_hamming, out_prefix_bits, out_total);
 }
 
-// The launches of isccsearch_join_within in their LINK form (join_scan_kernel<W, MASK, false, true> / mfma_join_kernel<W, false, true>)
-// between label_rows_kernel (one per segment: the host never sees the table's keys) and flatten_kernel, all on one stream; then
+// The launches of isccsearch_join_within in their LINK form between label_rows_kernel (one per segment: the host never sees the table's keys) and flatten_kernel, all on one stream; then
 // `parent` and the links come back behind one synchronisation.  Everything the device code relies on -- labels < n_labels,
 // parent[i] <= i -- is checked on the host before anything is launched.
 extern "C" int isccsearch_join_components(isccsearch_handle* h, uint32_t table, const int16_t* max_hamming, uint64_t n_live,
@@ -279,9 +313,8 @@ extern "C" int isccsearch_join_components(isccsearch_handle* h, uint32_t table, 
     if (!max_hamming || !parent || !out_links || (n_live && (!live_keys || !live_labels))) return fail(-EINVAL, "NULL argument");
     *out_links = 0;
     if (n_labels == 0 || n_labels == isk::UF_NONE) return fail(-EINVAL, "n_labels must be in 1 .. 2^32 - 2, got %u", n_labels);
-    for (uint64_t i = 0; i < n_live; ++i) {
-        if (i && live_keys[i] <= live_keys[i - 1])
-            return fail(-EINVAL, "live_keys must be strictly ascending: live_keys[%llu] <= live_keys[%llu]", (unsigned long long)i, (unsigned long long)(i - 1));
+    for (uint64_t i = 0; i < n_live; ++i) {            // (one pass over both arrays: they can be millions of entries)
+        if (not_ascending(live_keys, i)) return fail_not_ascending("live_keys", i);
         if (live_labels[i] >= n_labels)
             return fail(-EINVAL, "live_labels[%llu] = %u is not below n_labels = %u", (unsigned long long)i, live_labels[i], n_labels);
     }
@@ -295,8 +328,7 @@ extern "C" int isccsearch_join_components(isccsearch_handle* h, uint32_t table, 
     if (t.key_words != 1) return fail(-EINVAL, "join_components needs a table of 64-bit keys (key_words 1), table %u has key_words %d", table, t.key_words);
     HIPOK(hipSetDevice(h->device));
     JoinPlan plan;
-    plan.link = true;
-    if ((rc = join_begin(h, plan, false, 1, 0))) return rc;
+    if ((rc = join_begin(h, plan, isk::JoinForm::LINK, false, 1, 0))) return rc;
     if ((rc = h->d_join_live_keys.ensure(std::max<uint64_t>(n_live, 1)))) return rc;
     if ((rc = h->d_join_live_labels.ensure(std::max<uint64_t>(n_live, 1)))) return rc;
     uint64_t all_rows = 0;
@@ -317,27 +349,17 @@ extern "C" int isccsearch_join_components(isccsearch_handle* h, uint32_t table, 
         row_labels[l] = h->d_join_row_labels.p + rows;
         rows += s.n;
         isk::LabelParams lp{s.keys, h->d_join_live_keys.p, h->d_join_live_labels.p, row_labels[l], s.n, n_live};
-        const uint32_t blocks = (uint32_t)std::min<uint64_t>((s.n + isk::BLOCK - 1) / isk::BLOCK, 1u << 16);
-        hipLaunchKernelGGL(isk::label_rows_kernel, dim3(blocks), dim3(isk::BLOCK), 0, h->stream, lp);
+        hipLaunchKernelGGL(isk::label_rows_kernel, dim3(row_blocks(s.n)), dim3(isk::BLOCK), 0, h->stream, lp);
         HIPOK(hipGetLastError());
     }
     // the launches of isccsearch_join_within
-    for (uint32_t la = 1; la <= ISCCSEARCH_MAX_BYTES; ++la) {
-        if (!t.seg[la].n || max_hamming[la] < 0) continue;
-        for (uint32_t lb = la; lb <= ISCCSEARCH_MAX_BYTES; ++lb) {
-            const bool same = la == lb;
-            if (!t.seg[lb].n || (same && t.seg[la].n < 2)) continue;
-            const uint32_t a_len = t.seg[lb].n > t.seg[la].n ? lb : la, b_len = a_len == la ? lb : la;
-            if ((rc = join_add(h, plan, t.seg[a_len], t.seg[b_len], la, max_hamming[la], same, false))) return rc;
-            isk::JoinEmit& e = plan.emits.back();
-            e.labels_a = row_labels[a_len];
-            e.labels_b = row_labels[b_len];
-            e.parent = h->d_join_parent.p;
-        }
-    }
+    plan.parent = h->d_join_parent.p;
+    rc = join_self_pairs(t, max_hamming, [&](uint32_t a_len, uint32_t b_len, uint32_t pbytes, bool same) {
+        return join_add(h, plan, t.seg[a_len], t.seg[b_len], pbytes, max_hamming[pbytes], same, false, row_labels[a_len], row_labels[b_len]);
+    });
+    if (rc) return rc;
     if ((rc = join_run(h, plan))) return rc;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n_labels + isk::BLOCK - 1) / isk::BLOCK, 1u << 16);
-    hipLaunchKernelGGL(isk::flatten_kernel, dim3(blocks), dim3(isk::BLOCK), 0, h->stream, h->d_join_parent.p, n_labels);
+    hipLaunchKernelGGL(isk::flatten_kernel, dim3(row_blocks(n_labels)), dim3(isk::BLOCK), 0, h->stream, h->d_join_parent.p, n_labels);
     HIPOK(hipGetLastError());
     // the array goes to a copy first: `parent` changes only once the whole call has succeeded
     std::vector<uint32_t> flat(n_labels);
@@ -347,68 +369,107 @@ extern "C" int isccsearch_join_components(isccsearch_handle* h, uint32_t table, 
     return 0;
 }
 
-// The self-join launch of a simprint table's one segment in its OVERLAP form (join_scan_kernel<W, MASK, false, false, true> /
-// mfma_join_kernel<W, false, false, true>, chosen by join_add's rule) between label_chunks_kernel (the host never sees the table's keys)
-// and the aggregation of overlap.hip, all on one stream; the counters and the chunks per asset come back behind ONE synchronisation,
-// then the records are copied.  The hit buffer is filled with ones first, so that the aggregation runs over 2 * capacity slots
-// without the host asking how many were written.  Everything the device code relies on -- asset_keys ascending and fewer than
-// 2^32 - 1 (labels and the bound of the label search), rows and hit positions below 2^32 -- is checked before anything is launched.
+// The overlap joins: isccsearch_join_overlaps and isccsearch_join_segments over ONE side (the self-join of a simprint table's one segment)
+// and isccsearch_join_overlaps_between over TWO (the one cross-join launch isccsearch_join_between would make for the two segments, the
+// side with more rows held, by join_add's rule), all in the launches' OVERLAP form.  Per side label_chunks_kernel (its own asset keys,
+// frequency column, chunks and counters; the host never sees the tables' keys; the second side's labels carry isk::LABEL_SIDE_B), then
+// the join launch, then the aggregation of overlap.hip, all on one stream; the counters and the chunks per asset come back behind ONE
+// synchronisation, then the records are copied.  The hit buffer is filled with ones first, so that the aggregation runs over
+// 2 * capacity slots without the host asking how many were written.  Every frequency column is built before anything of the call is
+// queued (each build drains the stream).  Everything the device code relies on -- asset keys ascending and few enough that no label
+// is UF_NONE (two sides: 2^31 - 1, the side bit), rows and hit positions below 2^32 -- is checked before anything is launched.
 //
-// `segments` (isccsearch_join_segments): the same call with the stage of segments.hip queued between the join launch and the
-// aggregation, which overwrites the hit buffer that stage reads; the segment count is the call's fifth counter and comes back behind
-// the same synchronisation.  Without the flag nothing of that stage is sized, allocated or queued.
+// `segments` (isccsearch_join_segments, one side only): the stage of segments.hip is queued between the join launch and the
+// aggregation, which overwrites the hit buffer that stage reads.  Without the flag nothing of that stage is sized, allocated or queued.
+//
+// Two sides: the sort by (src, dst) puts the records of direction A -> B (src without the side bit) before those of B -> A; the bit moves
+// into `reserved` on the host, after the copy.
 namespace {
-int join_overlaps_or_segments(isccsearch_handle* h, uint32_t table, int32_t max_hamming, uint32_t max_doc_freq, uint32_t dup_limit,
-                              uint32_t n_assets, const uint64_t* asset_keys, uint64_t capacity, isccsearch_overlap* out_pairs,
-                              uint32_t* out_chunks, uint64_t* out_info, bool segments, isccsearch_segment* out_segments) {
-    const char* const name = segments ? "join_segments" : "join_overlaps";
+struct OverlapSide {
+    uint32_t table;               // the caller's arguments
+    uint32_t n_assets;
+    const uint64_t* asset_keys;
+    uint32_t* out_chunks;
+    Table* t;                     // the table and its one segment, once the call holds the lock
+    Segment* seg;
+};
+// the call's device counters; out_info is {chunk pairs, records, {live rows, stop chunks} per side, segments if asked for}
+enum : uint32_t { OV_PAIRS = 0, OV_RECORDS, OV_SEGMENTS, OV_SIDE /* + 2 * side: live rows, stop chunks */, OV_COUNTERS = OV_SIDE + 4 };
+
+int join_overlap_sides(isccsearch_handle* h, const char* name, OverlapSide* sides, int n_sides, int32_t max_hamming, uint32_t max_doc_freq,
+                       uint32_t dup_limit, uint32_t flags, uint64_t capacity, isccsearch_overlap* out_pairs, uint64_t* out_info, bool segments,
+                       isccsearch_segment* out_segments) {
+    const bool cross = n_sides == 2;
+    const char* const suffix[2] = {cross ? "_a" : "", "_b"};
     if (!h) return fail(-EINVAL, "handle is NULL");
-    if (!asset_keys || !out_chunks || !out_info) return fail(-EINVAL, "NULL argument");
+    for (int x = 0; x < n_sides; ++x)
+        if (!sides[x].asset_keys || !sides[x].out_chunks || !out_info) return fail(-EINVAL, "NULL argument");
     if (capacity && !out_pairs) return fail(-EINVAL, "out_pairs is NULL with capacity %llu", (unsigned long long)capacity);
     if (segments && capacity && !out_segments) return fail(-EINVAL, "out_segments is NULL with capacity %llu", (unsigned long long)capacity);
-    if (n_assets == 0 || n_assets == isk::UF_NONE) return fail(-EINVAL, "n_assets must be in 1 .. 2^32 - 2, got %u", n_assets);
-    for (uint32_t i = 1; i < n_assets; ++i)
-        if (asset_keys[i] <= asset_keys[i - 1])
-            return fail(-EINVAL, "asset_keys must be strictly ascending: asset_keys[%u] <= asset_keys[%u]", i, i - 1);
+    if (cross && sides[0].table == sides[1].table)
+        return fail(-EINVAL, "%s needs two tables (table %u given twice): isccsearch_join_overlaps joins a table with itself", name, sides[0].table);
+    if (flags & ~ISCCSEARCH_OVERLAPS_SKIP_SAME_ASSET) return fail(-EINVAL, "unknown flags 0x%x", flags & ~ISCCSEARCH_OVERLAPS_SKIP_SAME_ASSET);
+    for (int x = 0; x < n_sides; ++x) {
+        const uint32_t n = sides[x].n_assets;
+        if (cross ? n == 0 || n > 0x7FFFFFFFu : n == 0 || n == isk::UF_NONE)
+            return fail(-EINVAL, "n_assets%s must be in 1 .. %s, got %u", suffix[x], cross ? "2^31 - 1" : "2^32 - 2", n);
+    }
+    for (int x = 0; x < n_sides; ++x)
+        if (int rc = check_ascending((std::string("asset_keys") + suffix[x]).c_str(), sides[x].asset_keys, sides[x].n_assets)) return rc;
     if (max_hamming < 0) return fail(-EINVAL, "max_hamming must be >= 0, got %d", max_hamming);
     if (max_doc_freq > 0 && max_doc_freq > dup_limit)
         return fail(-EINVAL, "max_doc_freq %u exceeds dup_limit %u: the frequency column counts no further", max_doc_freq, dup_limit);
     if (capacity >= (1ull << 31))
         return fail(-E2BIG, "capacity %llu: the two hits of a chunk pair are numbered with 32 bits", (unsigned long long)capacity);
     std::lock_guard<std::mutex> lk(h->mu);
-    Table* tp;
     int rc;
-    if ((rc = get_table(h, table, tp))) return rc;
-    Table& t = *tp;
-    if (t.metric != ISCCSEARCH_METRIC_HAMMING || t.key_words != 2)
-        return fail(-EINVAL, "%s needs a simprint table (HAMMING, key_words 2), table %u has metric %d and key_words %d", name, table, t.metric, t.key_words);
-    Segment& s = t.seg[t.max_bytes];
-    if (s.n >= (1ull << 32)) return fail(-E2BIG, "a segment of %llu rows: row numbers travel as 32 bits", (unsigned long long)s.n);
-    if (segments && s.n >= (1ull << 31))
-        return fail(-E2BIG, "a segment of %llu rows: the difference of two chunk ordinals travels as 32 bits", (unsigned long long)s.n);
+    for (int x = 0; x < n_sides; ++x)
+        if ((rc = get_table(h, sides[x].table, sides[x].t))) return rc;
+    for (int x = 0; x < n_sides; ++x)
+        if (sides[x].t->metric != ISCCSEARCH_METRIC_HAMMING || sides[x].t->key_words != 2)
+            return fail(-EINVAL, "%s needs %s (HAMMING, key_words 2), table %u has metric %d and key_words %d", name, cross ? "simprint tables" : "a simprint table",
+                        sides[x].table, sides[x].t->metric, sides[x].t->key_words);
+    if (cross && sides[0].t->max_bytes != sides[1].t->max_bytes)
+        return fail(-EINVAL, "simprint tables %u and %u hold codes of different lengths (max_bytes %d, %d)", sides[0].table, sides[1].table,
+                    sides[0].t->max_bytes, sides[1].t->max_bytes);
+    const uint32_t nbytes = (uint32_t)sides[0].t->max_bytes;
+    uint64_t all_assets = 0, all_rows = 0;
+    for (int x = 0; x < n_sides; ++x) {
+        Segment& s = *(sides[x].seg = &sides[x].t->seg[nbytes]);
+        if (s.n >= (1ull << 32))
+            return cross ? fail(-E2BIG, "a segment of %llu rows in table %u: row numbers travel as 32 bits", (unsigned long long)s.n, sides[x].table)
+                         : fail(-E2BIG, "a segment of %llu rows: row numbers travel as 32 bits", (unsigned long long)s.n);
+        if (segments && s.n >= (1ull << 31))
+            return fail(-E2BIG, "a segment of %llu rows: the difference of two chunk ordinals travels as 32 bits", (unsigned long long)s.n);
+        all_assets += sides[x].n_assets;
+        all_rows += s.n;
+    }
+    // the side with more rows is held (join_add); one side: it is joined with itself, which takes two rows
+    const int held = cross && sides[1].seg->n > sides[0].seg->n ? 1 : 0, streamed = cross ? 1 - held : 0;
+    Segment& A = *sides[held].seg;
+    Segment& B = *sides[streamed].seg;
+    const bool launch = cross ? A.n && B.n : A.n >= 2;
     HIPOK(hipSetDevice(h->device));
-    // the call's counters {chunk pairs, live rows, stop chunks, records}, asset keys, chunks per asset, row labels; for m = 2 * capacity
-    // hits {appended | sorted}, one-hit records, records and rocPRIM's temporary storage: 192 bytes per chunk pair of the capacity
-    // With `segments` a fifth counter {segments} and, in buffers of their own, for the capacity pair keys {keyed | sorted} and runs
-    // {one-pair | reduced}: 160 bytes more per chunk pair; for the rows sorted keys, sorted rows and ordinals: 24 bytes per row;
-    // rocPRIM's temporary storage is shared, the larger of the two stages' needs.  The stage runs when there is a pair of rows and room.
+    // side by side (A first): asset keys, chunks per asset, row labels; for m = 2 * capacity hits {appended | sorted}, one-hit records,
+    // records and rocPRIM's temporary storage: 192 bytes per chunk pair of the capacity.
+    // With `segments`, in buffers of their own, for the capacity pair keys {keyed | sorted} and runs {one-pair | reduced}: 160 bytes more per
+    // chunk pair; for the rows sorted keys, sorted rows and ordinals: 24 bytes per row; rocPRIM's temporary storage is shared, the larger
+    // of the two stages' needs.  Nothing is queued for the hits when there is no launch or no room.
     const uint64_t m = 2 * capacity;
-    const uint32_t n_counters = segments ? 5 : 4;
-    const bool locate = segments && capacity && s.n >= 2;
+    const bool run = m && launch, locate = segments && run;
     size_t temp_bytes = 0;
-    if ((rc = h->d_join_total.ensure(n_counters))) return rc;
-    if ((rc = h->d_join_live_keys.ensure(n_assets))) return rc;
-    if ((rc = h->d_ov_chunks.ensure(n_assets))) return rc;
-    if ((rc = h->d_join_row_labels.ensure(std::max<uint64_t>(s.n, 1)))) return rc;
+    if ((rc = h->d_join_live_keys.ensure(all_assets))) return rc;
+    if ((rc = h->d_ov_chunks.ensure(all_assets))) return rc;
+    if ((rc = h->d_join_row_labels.ensure(std::max<uint64_t>(all_rows, 1)))) return rc;
     if (m) {
         std::string err;
         if ((rc = iskov::aggregate_temp_bytes(m, &temp_bytes, &err))) return fail(rc, "%s", err.c_str());
         if (locate) {
             size_t locate_bytes = 0;
-            if ((rc = isksg::locate_temp_bytes(s.n, capacity, &locate_bytes, &err))) return fail(rc, "%s", err.c_str());
+            if ((rc = isksg::locate_temp_bytes(A.n, capacity, &locate_bytes, &err))) return fail(rc, "%s", err.c_str());
             temp_bytes = std::max(temp_bytes, locate_bytes);
-            if ((rc = h->d_sg_keys.ensure(s.n))) return rc;
-            if ((rc = h->d_sg_rows.ensure(2 * s.n))) return rc;
+            if ((rc = h->d_sg_keys.ensure(A.n))) return rc;
+            if ((rc = h->d_sg_rows.ensure(2 * A.n))) return rc;
             if ((rc = h->d_sg_pairs.ensure(m))) return rc;
             if ((rc = h->d_sg_runs.ensure(m))) return rc;
         }
@@ -417,67 +478,80 @@ int join_overlaps_or_segments(isccsearch_handle* h, uint32_t table, int32_t max_
         if ((rc = h->d_ov_records.ensure(m))) return rc;
         if ((rc = h->d_ov_temp.ensure(std::max<size_t>(temp_bytes, 1)))) return rc;
     }
-    // (the frequency column is built by a call of its own that drains the stream: nothing of this call is queued yet)
-    if (max_doc_freq > 0 && s.n && (rc = ensure_freq_column(h, t, s, dup_limit))) return rc;
+    // (a frequency column is built by a call of its own that drains the stream: nothing of this call is queued yet)
+    for (int x = 0; x < n_sides; ++x)
+        if (max_doc_freq > 0 && sides[x].seg->n && (rc = ensure_freq_column(h, *sides[x].t, *sides[x].seg, dup_limit))) return rc;
+    JoinPlan plan;
+    if ((rc = join_begin(h, plan, isk::JoinForm::OVERLAP, cross, 2, capacity, OV_COUNTERS))) return rc;
     unsigned long long* const counters = reinterpret_cast<unsigned long long*>(h->d_join_total.p);
-    HIPOK(hipMemsetAsync(counters, 0, n_counters * 8, h->stream));
-    HIPOK(hipMemsetAsync(h->d_ov_chunks.p, 0, (size_t)n_assets * 4, h->stream));
-    if (m) HIPOK(hipMemsetAsync(h->d_ov_hits.p, 0xFF, m * sizeof(iskov::Hit), h->stream));
-    HIPOK(hipMemcpyAsync(h->d_join_live_keys.p, asset_keys, (size_t)n_assets * 8, hipMemcpyHostToDevice, h->stream));
-    if (s.n) {
-        isk::OverlapLabelParams lp{s.keys, h->d_join_live_keys.p, max_doc_freq > 0 ? s.freq : nullptr, h->d_join_row_labels.p, h->d_ov_chunks.p,
-                                   counters, s.n, n_assets, max_doc_freq, 0u};
-        const uint32_t blocks = (uint32_t)std::min<uint64_t>((s.n + isk::BLOCK - 1) / isk::BLOCK, 1u << 16);
-        hipLaunchKernelGGL(isk::label_chunks_kernel, dim3(blocks), dim3(isk::BLOCK), 0, h->stream, lp);
+    HIPOK(hipMemsetAsync(h->d_ov_chunks.p, 0, (size_t)all_assets * 4, h->stream));
+    if (run) HIPOK(hipMemsetAsync(h->d_ov_hits.p, 0xFF, m * sizeof(iskov::Hit), h->stream));
+    uint32_t* row_labels[2] = {h->d_join_row_labels.p, h->d_join_row_labels.p + sides[0].seg->n};
+    const uint64_t first_asset[2] = {0, sides[0].n_assets};
+    for (int x = 0; x < n_sides; ++x) {
+        uint64_t* const d_keys = h->d_join_live_keys.p + first_asset[x];
+        HIPOK(hipMemcpyAsync(d_keys, sides[x].asset_keys, (size_t)sides[x].n_assets * 8, hipMemcpyHostToDevice, h->stream));
+        const Segment& s = *sides[x].seg;
+        if (!s.n) continue;
+        isk::OverlapLabelParams lp{s.keys, d_keys, max_doc_freq > 0 ? s.freq : nullptr, row_labels[x], h->d_ov_chunks.p + first_asset[x],
+                                   counters + OV_SIDE + 2 * x, counters + OV_SIDE + 2 * x + 1, s.n, sides[x].n_assets, max_doc_freq,
+                                   x ? isk::LABEL_SIDE_B : 0u};
+        hipLaunchKernelGGL(isk::label_chunks_kernel, dim3(row_blocks(s.n)), dim3(isk::BLOCK), 0, h->stream, lp);
         HIPOK(hipGetLastError());
     }
-    if (s.n >= 2) {
-        JoinPlan plan;
-        plan.overlap = true;
-        plan.KW = 2;
-        plan.capacity = capacity;
-        if ((rc = join_add(h, plan, s, s, (uint32_t)t.max_bytes, max_hamming, true, false))) return rc;
-        isk::JoinEmit& e = plan.emits.back();
-        e.out_keys_a = e.out_keys_b = nullptr;        // the pair form's outputs: not this form's
-        e.out_hamming = nullptr;
-        e.out_prefix_bits = nullptr;
-        e.labels_a = e.labels_b = h->d_join_row_labels.p;
-        e.out_hits = reinterpret_cast<uint4*>(h->d_ov_hits.p);
+    if (launch) {
+        plan.out_hits = reinterpret_cast<uint4*>(h->d_ov_hits.p);
+        plan.skip_same_key = (flags & ISCCSEARCH_OVERLAPS_SKIP_SAME_ASSET) != 0;
+        if ((rc = join_add(h, plan, A, B, nbytes, max_hamming, !cross, held == 1, row_labels[held], row_labels[streamed]))) return rc;
         if ((rc = join_run(h, plan))) return rc;
     }
     if (locate) {                                     // reads the hits the aggregation below overwrites
         std::string err;
-        if ((rc = isksg::locate(reinterpret_cast<const isksg::RowKey*>(s.keys), s.n, h->d_ov_hits.p, capacity, h->d_sg_keys.p, h->d_sg_rows.p,
-                                h->d_sg_rows.p + s.n, h->d_sg_pairs.p, h->d_sg_runs.p, counters + 4, h->d_ov_temp.p, temp_bytes, h->stream, &err)))
+        if ((rc = isksg::locate(reinterpret_cast<const isksg::RowKey*>(A.keys), A.n, h->d_ov_hits.p, capacity, h->d_sg_keys.p, h->d_sg_rows.p,
+                                h->d_sg_rows.p + A.n, h->d_sg_pairs.p, h->d_sg_runs.p, counters + OV_SEGMENTS, h->d_ov_temp.p, temp_bytes, h->stream, &err)))
             return fail(rc, "%s", err.c_str());
     }
-    if (m) {
+    if (run) {
         std::string err;
-        if ((rc = iskov::aggregate(h->d_ov_hits.p, h->d_ov_hits.p + m, h->d_ov_marks.p, h->d_ov_records.p, counters + 3, m, h->d_ov_temp.p,
+        if ((rc = iskov::aggregate(h->d_ov_hits.p, h->d_ov_hits.p + m, h->d_ov_marks.p, h->d_ov_records.p, counters + OV_RECORDS, m, h->d_ov_temp.p,
                                    temp_bytes, h->stream, &err)))
             return fail(rc, "%s", err.c_str());
     }
     // the call's one synchronisation; the outputs change only from here on
-    uint64_t got[5] = {0, 0, 0, 0, 0};
-    std::vector<uint32_t> chunks(n_assets);
-    HIPOK(hipMemcpyAsync(got, counters, n_counters * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPOK(hipMemcpyAsync(chunks.data(), h->d_ov_chunks.p, (size_t)n_assets * 4, hipMemcpyDeviceToHost, h->stream));
+    uint64_t got[OV_COUNTERS] = {};
+    std::vector<uint32_t> chunks(all_assets);
+    HIPOK(hipMemcpyAsync(got, counters, sizeof got, hipMemcpyDeviceToHost, h->stream));
+    HIPOK(hipMemcpyAsync(chunks.data(), h->d_ov_chunks.p, (size_t)all_assets * 4, hipMemcpyDeviceToHost, h->stream));
     HIPOK(hipStreamSynchronize(h->stream));
-    const uint64_t total = got[0];
+    const uint64_t total = got[OV_PAIRS];
     if (total > capacity) {
         out_info[0] = total;
         return fail(-ENOSPC, "%llu chunk pairs do not fit the capacity of %llu", (unsigned long long)total, (unsigned long long)capacity);
     }
-    // (slots were left unused: the run of ones behind the hits reduced to one more record, the last)
-    const uint64_t n_records = m ? got[3] - (total < capacity ? 1 : 0) : 0;
-    const uint64_t n_segments = locate ? got[4] - (total < capacity ? 1 : 0) : 0;       // (likewise the one run of the unused slots)
+    // (slots were left unused: the run of ones behind the hits reduced to one more record, the last; likewise the one run of the unused slots)
+    const uint64_t unused = total < capacity ? 1 : 0;
+    const uint64_t n_records = run ? got[OV_RECORDS] - unused : 0;
+    const uint64_t n_segments = locate ? got[OV_SEGMENTS] - unused : 0;
     if (n_records) HIPOK(hipMemcpyAsync(out_pairs, h->d_ov_records.p, n_records * sizeof(isccsearch_overlap), hipMemcpyDeviceToHost, h->stream));
     if (n_segments)
         HIPOK(hipMemcpyAsync(out_segments, h->d_sg_runs.p + capacity, n_segments * sizeof(isccsearch_segment), hipMemcpyDeviceToHost, h->stream));
     if (n_records || n_segments) HIPOK(hipStreamSynchronize(h->stream));
-    memcpy(out_chunks, chunks.data(), (size_t)n_assets * 4);
-    out_info[0] = total; out_info[1] = n_records; out_info[2] = got[1]; out_info[3] = got[2];
-    if (segments) out_info[4] = n_segments;
+    // the side bit of src becomes the direction; the order by (src, dst) with the bit is the order by (reserved, src, dst) without
+    for (uint64_t r = 0; cross && r < n_records; ++r) {
+        isccsearch_overlap& o = out_pairs[r];
+        o.reserved = o.src >> 31;
+        o.src &= ~isk::LABEL_SIDE_B;
+        o.dst &= ~isk::LABEL_SIDE_B;
+    }
+    uint64_t* info = out_info;
+    *info++ = total;
+    *info++ = n_records;
+    for (int x = 0; x < n_sides; ++x) {
+        memcpy(sides[x].out_chunks, chunks.data() + first_asset[x], (size_t)sides[x].n_assets * 4);
+        *info++ = got[OV_SIDE + 2 * x];
+        *info++ = got[OV_SIDE + 2 * x + 1];
+    }
+    if (segments) *info++ = n_segments;
     return 0;
 }
 }  // namespace
@@ -485,158 +559,23 @@ int join_overlaps_or_segments(isccsearch_handle* h, uint32_t table, int32_t max_
 extern "C" int isccsearch_join_overlaps(isccsearch_handle* h, uint32_t table, int32_t max_hamming, uint32_t max_doc_freq, uint32_t dup_limit,
                              uint32_t n_assets, const uint64_t* asset_keys, uint64_t capacity, isccsearch_overlap* out_pairs,
                              uint32_t* out_chunks, uint64_t* out_info) {
-    return join_overlaps_or_segments(h, table, max_hamming, max_doc_freq, dup_limit, n_assets, asset_keys, capacity, out_pairs, out_chunks, out_info,
-                                     false, nullptr);
+    OverlapSide side{table, n_assets, asset_keys, out_chunks, nullptr, nullptr};
+    return join_overlap_sides(h, "join_overlaps", &side, 1, max_hamming, max_doc_freq, dup_limit, 0, capacity, out_pairs, out_info, false, nullptr);
 }
 
 // isccsearch_join_overlaps and, from the same join launch, the chunk pairs of every pair of assets as aligned runs (segments.hip).
 extern "C" int isccsearch_join_segments(isccsearch_handle* h, uint32_t table, int32_t max_hamming, uint32_t max_doc_freq, uint32_t dup_limit,
                              uint32_t n_assets, const uint64_t* asset_keys, uint64_t capacity, isccsearch_overlap* out_pairs,
                              isccsearch_segment* out_segments, uint32_t* out_chunks, uint64_t* out_info) {
-    return join_overlaps_or_segments(h, table, max_hamming, max_doc_freq, dup_limit, n_assets, asset_keys, capacity, out_pairs, out_chunks, out_info,
-                                     true, out_segments);
+    OverlapSide side{table, n_assets, asset_keys, out_chunks, nullptr, nullptr};
+    return join_overlap_sides(h, "join_segments", &side, 1, max_hamming, max_doc_freq, dup_limit, 0, capacity, out_pairs, out_info, true, out_segments);
 }
 
-// isccsearch_join_overlaps between TWO simprint tables: label_chunks_kernel once per table (its own asset keys, frequency column,
-// chunks and counters; table B's labels carry isk::LABEL_SIDE_B), then the ONE cross-join launch isccsearch_join_between would make for
-// the two segments in its OVERLAP form (join_scan_kernel<W, MASK, true, false, true> / mfma_join_kernel<W, true, false, true>, the
-// table with more rows held, by join_add's rule), then the aggregation of overlap.hip, all on one stream.  The sort by (src, dst)
-// puts the records of direction A -> B (src without the bit) before those of B -> A; the bit moves into `reserved` on the host, after
-// the copy.  Both frequency columns are built before anything of the call is queued (each build drains the stream).  Everything the
-// device code relies on -- both key arrays ascending and shorter than 2^31 - 1 (labels with the side bit stay below UF_NONE), rows and
-// hit positions below 2^32 -- is checked before anything is launched.
+// isccsearch_join_overlaps between TWO simprint tables.
 extern "C" int isccsearch_join_overlaps_between(isccsearch_handle* h, uint32_t table_a, uint32_t table_b, int32_t max_hamming,
                                      uint32_t max_doc_freq, uint32_t dup_limit, uint32_t n_assets_a, const uint64_t* asset_keys_a,
                                      uint32_t n_assets_b, const uint64_t* asset_keys_b, uint32_t flags, uint64_t capacity,
                                      isccsearch_overlap* out_pairs, uint32_t* out_chunks_a, uint32_t* out_chunks_b, uint64_t* out_info) {
-    if (!h) return fail(-EINVAL, "handle is NULL");
-    if (!asset_keys_a || !asset_keys_b || !out_chunks_a || !out_chunks_b || !out_info) return fail(-EINVAL, "NULL argument");
-    if (capacity && !out_pairs) return fail(-EINVAL, "out_pairs is NULL with capacity %llu", (unsigned long long)capacity);
-    if (table_a == table_b)
-        return fail(-EINVAL, "join_overlaps_between needs two tables (table %u given twice): isccsearch_join_overlaps joins a table with itself", table_a);
-    if (flags & ~ISCCSEARCH_OVERLAPS_SKIP_SAME_ASSET) return fail(-EINVAL, "unknown flags 0x%x", flags & ~ISCCSEARCH_OVERLAPS_SKIP_SAME_ASSET);
-    if (n_assets_a == 0 || n_assets_a > 0x7FFFFFFFu) return fail(-EINVAL, "n_assets_a must be in 1 .. 2^31 - 1, got %u", n_assets_a);
-    if (n_assets_b == 0 || n_assets_b > 0x7FFFFFFFu) return fail(-EINVAL, "n_assets_b must be in 1 .. 2^31 - 1, got %u", n_assets_b);
-    for (uint32_t i = 1; i < n_assets_a; ++i)
-        if (asset_keys_a[i] <= asset_keys_a[i - 1])
-            return fail(-EINVAL, "asset_keys_a must be strictly ascending: asset_keys_a[%u] <= asset_keys_a[%u]", i, i - 1);
-    for (uint32_t i = 1; i < n_assets_b; ++i)
-        if (asset_keys_b[i] <= asset_keys_b[i - 1])
-            return fail(-EINVAL, "asset_keys_b must be strictly ascending: asset_keys_b[%u] <= asset_keys_b[%u]", i, i - 1);
-    if (max_hamming < 0) return fail(-EINVAL, "max_hamming must be >= 0, got %d", max_hamming);
-    if (max_doc_freq > 0 && max_doc_freq > dup_limit)
-        return fail(-EINVAL, "max_doc_freq %u exceeds dup_limit %u: the frequency column counts no further", max_doc_freq, dup_limit);
-    if (capacity >= (1ull << 31))
-        return fail(-E2BIG, "capacity %llu: the two hits of a chunk pair are numbered with 32 bits", (unsigned long long)capacity);
-    std::lock_guard<std::mutex> lk(h->mu);
-    Table* tabs[2];
-    int rc;
-    if ((rc = get_table(h, table_a, tabs[0]))) return rc;
-    if ((rc = get_table(h, table_b, tabs[1]))) return rc;
-    const uint32_t ids[2] = {table_a, table_b};
-    for (int x = 0; x < 2; ++x)
-        if (tabs[x]->metric != ISCCSEARCH_METRIC_HAMMING || tabs[x]->key_words != 2)
-            return fail(-EINVAL, "join_overlaps_between needs simprint tables (HAMMING, key_words 2), table %u has metric %d and key_words %d", ids[x],
-                        tabs[x]->metric, tabs[x]->key_words);
-    if (tabs[0]->max_bytes != tabs[1]->max_bytes)
-        return fail(-EINVAL, "simprint tables %u and %u hold codes of different lengths (max_bytes %d, %d)", table_a, table_b, tabs[0]->max_bytes, tabs[1]->max_bytes);
-    const uint32_t nbytes = (uint32_t)tabs[0]->max_bytes;
-    Segment* const segs[2] = {&tabs[0]->seg[nbytes], &tabs[1]->seg[nbytes]};
-    for (int x = 0; x < 2; ++x)
-        if (segs[x]->n >= (1ull << 32))
-            return fail(-E2BIG, "a segment of %llu rows in table %u: row numbers travel as 32 bits", (unsigned long long)segs[x]->n, ids[x]);
-    HIPOK(hipSetDevice(h->device));
-    // the call's counters {chunk pairs, live rows a, stop chunks a, live rows b, stop chunks b, records}; per side (A first, B behind it)
-    // asset keys, chunks per asset, row labels; the hits and records of isccsearch_join_overlaps for m = 2 * capacity
-    const uint32_t n_assets[2] = {n_assets_a, n_assets_b};
-    const uint64_t* const asset_keys[2] = {asset_keys_a, asset_keys_b};
-    const uint64_t all_assets = (uint64_t)n_assets_a + n_assets_b, all_rows = segs[0]->n + segs[1]->n;
-    const uint64_t m = 2 * capacity;
-    size_t temp_bytes = 0;
-    if ((rc = h->d_join_total.ensure(6))) return rc;
-    if ((rc = h->d_join_live_keys.ensure(all_assets))) return rc;
-    if ((rc = h->d_ov_chunks.ensure(all_assets))) return rc;
-    if ((rc = h->d_join_row_labels.ensure(std::max<uint64_t>(all_rows, 1)))) return rc;
-    if (m) {
-        std::string err;
-        if ((rc = iskov::aggregate_temp_bytes(m, &temp_bytes, &err))) return fail(rc, "%s", err.c_str());
-        if ((rc = h->d_ov_hits.ensure(2 * m))) return rc;
-        if ((rc = h->d_ov_marks.ensure(m))) return rc;
-        if ((rc = h->d_ov_records.ensure(m))) return rc;
-        if ((rc = h->d_ov_temp.ensure(std::max<size_t>(temp_bytes, 1)))) return rc;
-    }
-    // (each frequency column is built by a call of its own that drains the stream: nothing of this call is queued yet)
-    for (int x = 0; x < 2; ++x)
-        if (max_doc_freq > 0 && segs[x]->n && (rc = ensure_freq_column(h, *tabs[x], *segs[x], dup_limit))) return rc;
-    unsigned long long* const counters = reinterpret_cast<unsigned long long*>(h->d_join_total.p);
-    HIPOK(hipMemsetAsync(counters, 0, 6 * 8, h->stream));
-    HIPOK(hipMemsetAsync(h->d_ov_chunks.p, 0, (size_t)all_assets * 4, h->stream));
-    const bool launch = segs[0]->n && segs[1]->n;
-    if (m && launch) HIPOK(hipMemsetAsync(h->d_ov_hits.p, 0xFF, m * sizeof(iskov::Hit), h->stream));
-    uint32_t* row_labels[2] = {h->d_join_row_labels.p, h->d_join_row_labels.p + segs[0]->n};
-    for (int x = 0; x < 2; ++x) {
-        uint64_t* const d_keys = h->d_join_live_keys.p + (x ? n_assets_a : 0);
-        HIPOK(hipMemcpyAsync(d_keys, asset_keys[x], (size_t)n_assets[x] * 8, hipMemcpyHostToDevice, h->stream));
-        const Segment& s = *segs[x];
-        if (!s.n) continue;
-        // (label_chunks_kernel adds to counters[1] and [2] of the pointer it is given: table B's pair lies two further)
-        isk::OverlapLabelParams lp{s.keys, d_keys, max_doc_freq > 0 ? s.freq : nullptr, row_labels[x], h->d_ov_chunks.p + (x ? n_assets_a : 0),
-                                   counters + 2 * x, s.n, n_assets[x], max_doc_freq, x ? isk::LABEL_SIDE_B : 0u};
-        const uint32_t blocks = (uint32_t)std::min<uint64_t>((s.n + isk::BLOCK - 1) / isk::BLOCK, 1u << 16);
-        hipLaunchKernelGGL(isk::label_chunks_kernel, dim3(blocks), dim3(isk::BLOCK), 0, h->stream, lp);
-        HIPOK(hipGetLastError());
-    }
-    if (launch) {
-        JoinPlan plan;
-        plan.cross = true;
-        plan.overlap = true;
-        plan.KW = 2;
-        plan.capacity = capacity;
-        // as in isccsearch_join_between the segment with more rows is held: JoinEmit::labels_a are the HELD segment's labels
-        const int held = segs[1]->n > segs[0]->n ? 1 : 0;
-        if ((rc = join_add(h, plan, *segs[held], *segs[1 - held], nbytes, max_hamming, false, held == 1))) return rc;
-        isk::JoinEmit& e = plan.emits.back();
-        e.out_keys_a = e.out_keys_b = nullptr;        // the pair form's outputs: not this form's
-        e.out_hamming = nullptr;
-        e.out_prefix_bits = nullptr;
-        e.labels_a = row_labels[held];
-        e.labels_b = row_labels[1 - held];
-        e.out_hits = reinterpret_cast<uint4*>(h->d_ov_hits.p);
-        e.skip_same_key = flags & ISCCSEARCH_OVERLAPS_SKIP_SAME_ASSET ? 1u : 0u;
-        if ((rc = join_run(h, plan))) return rc;
-        if (m) {
-            std::string err;
-            if ((rc = iskov::aggregate(h->d_ov_hits.p, h->d_ov_hits.p + m, h->d_ov_marks.p, h->d_ov_records.p, counters + 5, m, h->d_ov_temp.p,
-                                       temp_bytes, h->stream, &err)))
-                return fail(rc, "%s", err.c_str());
-        }
-    }
-    // the call's one synchronisation; the outputs change only from here on
-    uint64_t got[6] = {0, 0, 0, 0, 0, 0};
-    std::vector<uint32_t> chunks(all_assets);
-    HIPOK(hipMemcpyAsync(got, counters, sizeof got, hipMemcpyDeviceToHost, h->stream));
-    HIPOK(hipMemcpyAsync(chunks.data(), h->d_ov_chunks.p, (size_t)all_assets * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPOK(hipStreamSynchronize(h->stream));
-    const uint64_t total = got[0];
-    if (total > capacity) {
-        out_info[0] = total;
-        return fail(-ENOSPC, "%llu chunk pairs do not fit the capacity of %llu", (unsigned long long)total, (unsigned long long)capacity);
-    }
-    // (slots were left unused: the run of ones behind the hits reduced to one more record, the last)
-    const uint64_t n_records = m && launch ? got[5] - (total < capacity ? 1 : 0) : 0;
-    if (n_records) {
-        HIPOK(hipMemcpyAsync(out_pairs, h->d_ov_records.p, n_records * sizeof(isccsearch_overlap), hipMemcpyDeviceToHost, h->stream));
-        HIPOK(hipStreamSynchronize(h->stream));
-        // the side bit of src becomes the direction; the order by (src, dst) with the bit is the order by (reserved, src, dst) without
-        for (uint64_t r = 0; r < n_records; ++r) {
-            isccsearch_overlap& o = out_pairs[r];
-            o.reserved = o.src >> 31;
-            o.src &= ~isk::LABEL_SIDE_B;
-            o.dst &= ~isk::LABEL_SIDE_B;
-        }
-    }
-    memcpy(out_chunks_a, chunks.data(), (size_t)n_assets_a * 4);
-    memcpy(out_chunks_b, chunks.data() + n_assets_a, (size_t)n_assets_b * 4);
-    out_info[0] = total; out_info[1] = n_records; out_info[2] = got[1]; out_info[3] = got[2]; out_info[4] = got[3]; out_info[5] = got[4];
-    return 0;
+    OverlapSide sides[2] = {{table_a, n_assets_a, asset_keys_a, out_chunks_a, nullptr, nullptr}, {table_b, n_assets_b, asset_keys_b, out_chunks_b, nullptr, nullptr}};
+    return join_overlap_sides(h, "join_overlaps_between", sides, 2, max_hamming, max_doc_freq, dup_limit, flags, capacity, out_pairs, out_info, false, nullptr);
 }

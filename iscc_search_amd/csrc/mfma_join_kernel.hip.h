@@ -13,17 +13,10 @@
 //   Within one segment (p.same) chunk c streams from the 64-row step that contains its first row and the emit path keeps only
 //   row_streamed > row_held: every unordered pair exactly once.  A chunk late in the segment has few steps left; the blocks
 //   that would run none return before the prologue (mfma_join_live_blocks: JOIN_STEPS_PER_WAVE steps per wave).
-//   Hits go through the per-wave LDS ring of saved accumulator blocks as in mfma_scan_kernel.  The ring walk counts its pairs, takes
-//   ONE returned atomic on JoinEmit::total for the walk and writes (key_a, key_b, hamming, prefix bits) with vector stores --
-//   the self-join orders the keys, the cross join routes the held side's key by JoinEmit::sgpr_side_is_b (the held side takes
-//   the part the SGPR side has in join_scan_kernel).  Pairs past `capacity` are counted and not written.
-//   LINK (mfma_join_kernel<W, false, true>, isccsearch_join_components): the ring is walked ONCE -- per pair the two rows' labels are
-//   loaded and united (link_pair of join.hip.h), the labelled pairs counted, one atomic per walk; nothing is written.
-//   OVERLAP (mfma_join_kernel<W, false, false, true>, isccsearch_join_overlaps): the ring is walked twice as for the pairs -- only a pair
-//   whose rows carry two different labels is counted (overlap_pair of join.hip.h), one returned atomic per walk (overlap_slots), and
-//   the second walk writes the pair's two directed hits (overlap_write).
-//   CROSS + OVERLAP (mfma_join_kernel<W, true, false, true>, isccsearch_join_overlaps_between): the same two walks over the pairs of
-//   two tables; overlap_pair<true> drops the pairs of one asset key when JoinEmit::skip_same_key says so.
+//   Hits go through the per-wave LDS ring of saved accumulator blocks as in mfma_scan_kernel.  The ring walk (`process_ring`) is this
+//   kernel's emit path; join.hip.h's file comment describes the forms F and CROSS once for both kernels.  The held side takes the part
+//   the SGPR side has in join_scan_kernel (JoinEmit::keys_a, labels_a, sgpr_side_is_b).  PAIRS and OVERLAP walk the ring twice (count,
+//   ONE returned atomic on JoinEmit::total for the walk, write; each walk rcount / 2 <= RING_E / 2 trips), LINK once.
 #pragma once
 
 #include "join.hip.h"
@@ -33,10 +26,10 @@
 namespace isk {
 
 // LDS image of a chunk: B fragments [groups][W][64] v4i | thr[groups * 32] (float) | popc[groups * 32] | the waves' rings
-template <int W, bool CROSS, bool LINK = false, bool OVERLAP = false>
+template <int W, JoinForm F, bool CROSS>
 __global__ __launch_bounds__(MBLOCK, mfma_min_waves<W>()) void mfma_join_kernel(const MfmaJoinParams p, const uint32_t groups) {
-    static_assert(!(LINK && CROSS), "components are those of one table");
-    static_assert(!(OVERLAP && LINK), "overlaps are a form of their own");
+    static_assert(join_form_exists(F, CROSS), "no such join form");
+    constexpr bool LINK = F == JoinForm::LINK, OVERLAP = F == JoinForm::OVERLAP;
     constexpr int MT = 2;       // row tiles (32 rows) per wave and step
     constexpr uint32_t WAVES = MBLOCK / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];

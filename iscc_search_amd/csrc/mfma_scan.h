@@ -28,6 +28,7 @@ int launch_mfma_scan(int W, int mode, bool pack, uint32_t blocks_x, uint32_t gro
 // ---- the joins on the matrix cores (mfma_join_kernel.hip.h): a block HOLDS a chunk of `groups` * 32 rows of one segment in LDS and
 // streams the other segment, 64 rows per wave and step
 struct JoinEmit;                  // join.hip.h: what only the emit path reads
+enum class JoinForm : int;        // join.hip.h: what a join leaves behind for its pairs (PAIRS, LINK, OVERLAP)
 struct MfmaJoinParams {
     const uint64_t* col_q[4];     // the held segment's columns (word-major); JoinEmit::keys_a are its keys
     const uint64_t* col_s[4];     // the streamed segment's; JoinEmit::keys_b
@@ -54,9 +55,7 @@ inline uint32_t mfma_join_blocks_x(uint64_t n_streamed) {
 }
 // rows of the held segment per chunk: mfma_groups_per_chunk(W, n_held, false) * 32
 // grid = (blocks_x, chunks); p.chunk_base names the first of them.  Returns 0 or a hipError_t as launch_mfma_scan does
-// link: mfma_join_kernel<W, false, true>, whose ring walk unites the pairs' labels (JoinEmit::labels_a, labels_b, parent) and writes no pair
-// overlap: mfma_join_kernel<W, false, false, true>, whose ring walk writes two directed hits per pair of two different labels (JoinEmit::out_hits)
-int launch_mfma_join(int W, bool cross, uint32_t blocks_x, uint32_t chunks, uint32_t groups, hipStream_t st, const MfmaJoinParams& p, bool link = false,
-                     bool overlap = false);
+// (form, cross): the emit path of join.hip.h; a combination that join_form_exists does not list is refused like a chunk that does not fit
+int launch_mfma_join(int W, JoinForm form, bool cross, uint32_t blocks_x, uint32_t chunks, uint32_t groups, hipStream_t st, const MfmaJoinParams& p);
 
 }  // namespace isk

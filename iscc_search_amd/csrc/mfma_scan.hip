@@ -118,23 +118,15 @@ int launch_mfma_scan(int W, int mode, bool pack, uint32_t blocks_x, uint32_t gro
     return 0;
 }
 
-template <int W>
-static void launch_join_w(bool cross, bool link, bool overlap, dim3 grid, size_t lds, hipStream_t st, const MfmaJoinParams& p, uint32_t groups) {
-    if (overlap && cross) hipLaunchKernelGGL((mfma_join_kernel<W, true, false, true>), grid, dim3(MBLOCK), lds, st, p, groups);
-    else if (overlap) hipLaunchKernelGGL((mfma_join_kernel<W, false, false, true>), grid, dim3(MBLOCK), lds, st, p, groups);
-    else if (link) hipLaunchKernelGGL((mfma_join_kernel<W, false, true>), grid, dim3(MBLOCK), lds, st, p, groups);
-    else if (cross) hipLaunchKernelGGL((mfma_join_kernel<W, true>), grid, dim3(MBLOCK), lds, st, p, groups);
-    else hipLaunchKernelGGL((mfma_join_kernel<W, false>), grid, dim3(MBLOCK), lds, st, p, groups);
-}
-
-int launch_mfma_join(int W, bool cross, uint32_t blocks_x, uint32_t chunks, uint32_t groups, hipStream_t st, const MfmaJoinParams& p, bool link, bool overlap) {
+int launch_mfma_join(int W, JoinForm form, bool cross, uint32_t blocks_x, uint32_t chunks, uint32_t groups, hipStream_t st, const MfmaJoinParams& p) {
     static_assert(MFMA_JOIN_WAVES == MBLOCK / 64, "the grid rule counts the kernel's waves");
     const size_t lds = mfma_lds_bytes(W, groups);
-    // the group pipeline walks pairs of groups; grid.y is 16 bits; the LINK form is the self-join's only, and no form is both LINK and OVERLAP
-    if (W < 1 || W > 4 || lds > (size_t)MFMA_MAX_LDS || groups < 2 || (groups & 1) || !blocks_x || !chunks || chunks > MFMA_JOIN_MAX_CHUNKS || (link && cross) ||
-        (overlap && link)) return (int)hipErrorInvalidValue;
-    with_words(W, [&](auto w) { launch_join_w<decltype(w)::value>(cross, link, overlap, dim3(blocks_x, chunks), lds, st, p, groups); });
-    return 0;
+    // the group pipeline walks pairs of groups; grid.y is 16 bits
+    if (W < 1 || W > 4 || lds > (size_t)MFMA_MAX_LDS || groups < 2 || (groups & 1) || !blocks_x || !chunks || chunks > MFMA_JOIN_MAX_CHUNKS) return (int)hipErrorInvalidValue;
+    const bool exists = with_join_form(form, cross, [&](auto f) { with_words(W, [&](auto w) {
+        hipLaunchKernelGGL((mfma_join_kernel<decltype(w)::value, decltype(f)::form, decltype(f)::cross>), dim3(blocks_x, chunks), dim3(MBLOCK), lds, st, p, groups);
+    }); });
+    return exists ? 0 : (int)hipErrorInvalidValue;
 }
 
 }  // namespace isk

@@ -122,10 +122,10 @@ __global__ __launch_bounds__(BLOCK) void label_rows_kernel(const LabelParams p) 
 // isccsearch_join_overlaps: the label of row i of a simprint segment (128-bit keys: the asset is the FIRST key word) -- the rank of
 // its asset in asset_keys (strictly ascending), the search of label_rows_kernel at stride 2.  0xFFFFFFFF (no label) where the asset
 // is not listed, and where the row is a stop chunk: its entry in the segment's frequency column exceeds max_doc_freq (freq NULL:
-// no cut).  Every LISTED row, stop chunks included, adds 1 to chunks[rank]; counters[1] counts the listed rows, counters[2] the
+// no cut).  Every LISTED row, stop chunks included, adds 1 to chunks[rank]; *live_rows counts the listed rows, *stop_chunks the
 // stop chunks among them (one atomic per wave each).  Integer atomics: the result does not depend on their order.
-// isccsearch_join_overlaps_between runs it once per table; side_bit (0, or LABEL_SIDE_B of join.hip.h for table B) is set in every label
-// given, and `counters` points one pair of counters further for table B.
+// isccsearch_join_overlaps_between runs it once per table, each with its own two counters; side_bit (0, or LABEL_SIDE_B of join.hip.h
+// for table B) is set in every label given.
 // Bounds: the row loop runs ceil(n / grid size) trips, the search at most 64 (hi - lo halves; n_assets < 2^32 is checked by the host).
 struct OverlapLabelParams {
     const uint64_t* keys;          // the segment's key column [n][2]
@@ -133,7 +133,8 @@ struct OverlapLabelParams {
     const uint32_t* freq;          // the segment's frequency column [n], or NULL
     uint32_t* out;                 // [n]
     uint32_t* chunks;              // [n_assets], zeroed
-    unsigned long long* counters;  // [4]: the call's {pairs, live rows, stop chunks, records}; [1] and [2] are written
+    unsigned long long* live_rows;    // this side's two counters among the call's
+    unsigned long long* stop_chunks;
     uint64_t n, n_assets;
     uint32_t max_doc_freq;
     uint32_t side_bit;             // set in every label given (ranks do not reach it: the host bounds n_assets)
@@ -168,8 +169,8 @@ __global__ __launch_bounds__(BLOCK) void label_chunks_kernel(const OverlapLabelP
         stop += (uint32_t)__shfl_xor((int)stop, d, 64);
     }
     if ((threadIdx.x & 63) == 0) {
-        if (live) atomicAdd(p.counters + 1, (unsigned long long)live);
-        if (stop) atomicAdd(p.counters + 2, (unsigned long long)stop);
+        if (live) atomicAdd(p.live_rows, (unsigned long long)live);
+        if (stop) atomicAdd(p.stop_chunks, (unsigned long long)stop);
     }
 }
 

@@ -434,18 +434,9 @@ class HipTable(TableChecks):
         pairs, retried once with exactly the total when more were found.  More than ``max_pairs`` chunk pairs raise ValueError:
         the cap is never applied silently.
         """
-        asset_keys = np.ascontiguousarray(asset_keys, dtype=np.uint64)
-        if asset_keys.ndim != 1:
-            raise ValueError("asset_keys must be shaped [n_assets]")
-        n_assets = asset_keys.shape[0]
-        call = self.engine._lib.isccsearch_join_overlaps
-        chunks = np.zeros(n_assets, dtype=np.uint32)
-        info = np.zeros(4, dtype=np.uint64)
-        records = self._overlap_records("isccsearch_join_overlaps", max_pairs, info, lambda capacity, out: call(
-            self.engine.handle, self.id, int(max_hamming), int(max_doc_freq), int(dup_limit), n_assets, _lib.ptr(asset_keys) if n_assets else None,
-            capacity, out, _lib.ptr(chunks), _lib.ptr(info)))
-        names = ("chunk_pairs", "records", "live_rows", "stop_chunks")
-        return records, chunks, dict(zip(names, (int(v) for v in info)))
+        records, (chunks,), info, _ = self._overlaps("isccsearch_join_overlaps", (self.id,), (asset_keys,), ("live_rows", "stop_chunks"),
+                                                     max_hamming, max_doc_freq, max_pairs, dup_limit)
+        return records, chunks, info
 
     def join_segments(self, max_hamming, asset_keys, max_doc_freq, max_pairs, dup_limit=1000):
         # type: (int, np.ndarray, int, int, int) -> tuple
@@ -457,44 +448,9 @@ class HipTable(TableChecks):
         consecutive chunks of ``dst`` from ``first_dst`` on, ``src < dst``, with the byte range on either side -- sorted by (src, dst,
         first_dst - first_src, first_src).  Capacity, retry and ValueError as for ``join_overlaps``.
         """
-        asset_keys = np.ascontiguousarray(asset_keys, dtype=np.uint64)
-        if asset_keys.ndim != 1:
-            raise ValueError("asset_keys must be shaped [n_assets]")
-        n_assets = asset_keys.shape[0]
-        call = self.engine._lib.isccsearch_join_segments
-        chunks = np.zeros(n_assets, dtype=np.uint32)
-        info = np.zeros(5, dtype=np.uint64)
-        held = []
-
-        def once(capacity, out):
-            held[:] = [np.empty(capacity, dtype=_lib.SEGMENT_DTYPE)]
-            return call(self.engine.handle, self.id, int(max_hamming), int(max_doc_freq), int(dup_limit), n_assets,
-                        _lib.ptr(asset_keys) if n_assets else None, capacity, out, _lib.ptr(held[0]) if capacity else None, _lib.ptr(chunks), _lib.ptr(info))
-
-        records = self._overlap_records("isccsearch_join_segments", max_pairs, info, once)
-        names = ("chunk_pairs", "records", "live_rows", "stop_chunks", "segments")
-        return records, chunks, dict(zip(names, (int(v) for v in info))), held[0][: int(info[4])]
-
-    def _overlap_records(self, symbol, max_pairs, info, call):
-        # type: (str, int, np.ndarray, object) -> np.ndarray
-        """
-        The records of one overlap join of the library: ``call(capacity, out_pairs)`` with room for ``min(max_pairs, 2^20)`` chunk
-        pairs, retried once with exactly the total (``info[0]``) when that did not fit; more than ``max_pairs`` raise ValueError.
-        """
-        capacity = min(int(max_pairs), 1 << 20)
-        for attempt in range(2):
-            records = np.empty(2 * capacity, dtype=_lib.OVERLAP_DTYPE)
-            rc = call(capacity, _lib.ptr(records) if capacity else None)
-            if rc == -errno.ENOSPC or rc == 0:
-                n = int(info[0])
-                if n > max_pairs:
-                    raise ValueError(f"{n} chunk pairs exceed max_pairs={max_pairs}")
-                if rc == -errno.ENOSPC and attempt == 0:
-                    capacity = n
-                    continue
-            _lib.check(rc)
-            return records[: int(info[1])]
-        raise RuntimeError(f"{symbol}: the retry with the reported total did not fit")
+        records, (chunks,), info, segments = self._overlaps("isccsearch_join_segments", (self.id,), (asset_keys,), ("live_rows", "stop_chunks", "segments"),
+                                                            max_hamming, max_doc_freq, max_pairs, dup_limit, segments=True)
+        return records, chunks, info, segments
 
     def join_overlaps_between(self, other, max_hamming, asset_keys_a, asset_keys_b, max_doc_freq, max_pairs, dup_limit=1000, skip_same_asset=True):
         # type: (HipTable, int, np.ndarray, np.ndarray, int, int, int, bool) -> tuple
@@ -513,44 +469,78 @@ class HipTable(TableChecks):
         """
         if getattr(other, "engine", None) is not self.engine:
             raise ValueError("join_overlaps_between needs two tables of one engine: the other table belongs to another engine")
-        asset_keys_a = np.ascontiguousarray(asset_keys_a, dtype=np.uint64)
-        asset_keys_b = np.ascontiguousarray(asset_keys_b, dtype=np.uint64)
-        if asset_keys_a.ndim != 1 or asset_keys_b.ndim != 1:
-            raise ValueError("asset_keys_a and asset_keys_b must be shaped [n_assets]")
-        n_a, n_b = asset_keys_a.shape[0], asset_keys_b.shape[0]
-        call = self.engine._lib.isccsearch_join_overlaps_between
-        chunks_a = np.zeros(n_a, dtype=np.uint32)
-        chunks_b = np.zeros(n_b, dtype=np.uint32)
-        info = np.zeros(6, dtype=np.uint64)
         flags = _lib.OVERLAPS_SKIP_SAME_ASSET if skip_same_asset else 0
-        records = self._overlap_records("isccsearch_join_overlaps_between", max_pairs, info, lambda capacity, out: call(
-            self.engine.handle, self.id, other.id, int(max_hamming), int(max_doc_freq), int(dup_limit),
-            n_a, _lib.ptr(asset_keys_a) if n_a else None, n_b, _lib.ptr(asset_keys_b) if n_b else None, flags,
-            capacity, out, _lib.ptr(chunks_a), _lib.ptr(chunks_b), _lib.ptr(info)))
-        names = ("chunk_pairs", "records", "live_rows_a", "stop_chunks_a", "live_rows_b", "stop_chunks_b")
-        return records, chunks_a, chunks_b, dict(zip(names, (int(v) for v in info)))
+        records, (chunks_a, chunks_b), info, _ = self._overlaps(
+            "isccsearch_join_overlaps_between", (self.id, other.id), (asset_keys_a, asset_keys_b), ("live_rows_a", "stop_chunks_a", "live_rows_b", "stop_chunks_b"),
+            max_hamming, max_doc_freq, max_pairs, dup_limit, flags=(flags,))
+        return records, chunks_a, chunks_b, info
+
+    def _overlaps(self, symbol, tables, asset_keys, names, max_hamming, max_doc_freq, max_pairs, dup_limit, flags=(), segments=False):
+        # type: (str, tuple, tuple, tuple, int, int, int, int, tuple, bool) -> tuple
+        """
+        One overlap join of the library over ``tables`` (one, or two with ``flags``), each with its ``asset_keys``: ``(records, chunks per
+        table, info, segments or None)``; ``names`` are those of ``info`` behind ``"chunk_pairs"`` and ``"records"``.
+        """
+        asset_keys = [np.ascontiguousarray(k, dtype=np.uint64) for k in asset_keys]
+        if any(k.ndim != 1 for k in asset_keys):
+            raise ValueError(("asset_keys" if len(asset_keys) == 1 else "asset_keys_a and asset_keys_b") + " must be shaped [n_assets]")
+        call = getattr(self.engine._lib, symbol)
+        chunks = [np.zeros(k.shape[0], dtype=np.uint32) for k in asset_keys]
+        info = np.zeros(2 + len(names), dtype=np.uint64)
+        sides = [arg for k in asset_keys for arg in (k.shape[0], _lib.ptr(k) if k.shape[0] else None)]
+        runs = []
+
+        # the three C argument lists, in this one order:
+        #   isccsearch_join_overlaps:         h, table,            max_hamming, max_doc_freq, dup_limit, n, keys,                          capacity, out_pairs,               out_chunks,               out_info
+        #   isccsearch_join_segments:         h, table,            max_hamming, max_doc_freq, dup_limit, n, keys,                          capacity, out_pairs, out_segments, out_chunks,               out_info
+        #   isccsearch_join_overlaps_between: h, table_a, table_b, max_hamming, max_doc_freq, dup_limit, n_a, keys_a, n_b, keys_b, flags, capacity, out_pairs,               out_chunks_a, out_chunks_b, out_info
+        def once(capacity):
+            records = np.empty(2 * capacity, dtype=_lib.OVERLAP_DTYPE)
+            runs[:] = [np.empty(capacity, dtype=_lib.SEGMENT_DTYPE)] if segments else []
+            rc = call(self.engine.handle, *tables, int(max_hamming), int(max_doc_freq), int(dup_limit), *sides, *flags, capacity,
+                      _lib.ptr(records) if capacity else None, *((_lib.ptr(r) if capacity else None) for r in runs), *(_lib.ptr(c) for c in chunks), _lib.ptr(info))
+            # (info is written only by a call that ran: after any other refusal it holds no total)
+            return rc, int(info[0]) if rc in (0, -errno.ENOSPC) else 0, records[: int(info[1])]
+
+        records = self._retried(symbol, max_pairs, "chunk pairs", once)
+        info = dict(zip(("chunk_pairs", "records") + tuple(names), (int(v) for v in info)))
+        return records, chunks, info, runs[0][: info["segments"]] if segments else None
 
     def _join(self, symbol, tables, max_hamming_by_prefix, max_pairs):
         # type: (str, tuple, object, int) -> tuple
-        """One join call of the library, retried once with exactly the reported total when that did not fit."""
+        """One pair join of the library: ``(keys_a, keys_b, hamming, prefix_bits)``."""
         mh = np.ascontiguousarray(max_hamming_by_prefix, dtype=np.int16)
         if mh.shape != (_lib.MAX_BYTES + 1,):
             raise ValueError(f"max_hamming_by_prefix must have {_lib.MAX_BYTES + 1} entries (prefix bytes 0..{_lib.MAX_BYTES})")
         call = getattr(self.engine._lib, symbol)
         total = ctypes.c_uint64()
-        capacity = min(int(max_pairs), 1 << 20)
-        for attempt in range(2):
+
+        def once(capacity):
             kshape = (capacity, 2) if self.key_words == 2 else (capacity,)
             out = (np.empty(kshape, np.uint64), np.empty(kshape, np.uint64), np.empty(capacity, np.uint32), np.empty(capacity, np.uint16))
             rc = call(self.engine.handle, *tables, _lib.ptr(mh), capacity, *(_lib.ptr(a) for a in out), ctypes.byref(total))
             n = int(total.value)
+            return rc, n, tuple(a[:n] for a in out)
+
+        return self._retried(symbol, max_pairs, "pairs", once)
+
+    @staticmethod
+    def _retried(symbol, max_pairs, what, once):
+        # type: (str, int, str, object) -> object
+        """
+        ``once(capacity)`` -> ``(rc, total, result)``: one join call of the library with room for ``min(max_pairs, 2^20)``, retried once
+        with exactly the reported total when that did not fit; a total above ``max_pairs`` raises ValueError.
+        """
+        capacity = min(int(max_pairs), 1 << 20)
+        for attempt in range(2):
+            rc, n, result = once(capacity)
             if n > max_pairs:
-                raise ValueError(f"{n} pairs exceed max_pairs={max_pairs}")
+                raise ValueError(f"{n} {what} exceed max_pairs={max_pairs}")
             if rc == -errno.ENOSPC and attempt == 0:
                 capacity = n
                 continue
             _lib.check(rc)
-            return tuple(a[:n] for a in out)
+            return result
         raise RuntimeError(f"{symbol}: the retry with the reported total did not fit")
 
     def doc_freq(self, q_words, q_nbytes=None, dup_limit=1000):

@@ -136,6 +136,23 @@ def test_same_asset_pairs_take_no_slot(hip_engine):
         check(hip_engine, t, keys, words, np.array([7, 9], dtype=np.uint64), 0)
 
 
+def test_every_pair_takes_a_slot(hip_engine):
+    """
+    300 identical rows of 300 listed assets, one chunk each: every candidate of the emit path takes a slot (the dense cases above are
+    dense in pairs that take none).  The ring fills within a step and every lane takes many slots, so the count pass and the write
+    pass have to agree on every one of the 44 850 chunk pairs.
+    """
+    n = 300
+    words = np.full((n, 1), 0x0123456789ABCDEF, dtype=np.uint64)
+    asset_keys = np.arange(1, n + 1, dtype=np.uint64)
+    keys = chunk_keys(asset_keys)
+    with dropping(sp_table(hip_engine, 8, keys, words)) as (t,):
+        rec, chunks, info = check(hip_engine, t, keys, words, asset_keys, 0)
+        assert info["chunk_pairs"] == n * (n - 1) // 2 == 44_850 and info["records"] == len(rec) == n * (n - 1) == 89_700
+        assert bool(np.all(rec["matched"] == 1)) and bool(np.all(rec["sum_hamming"] == 0)) and bool(np.all(rec["chunk_pairs"] == 1))
+        assert chunks.tolist() == [1] * n
+
+
 def test_stop_chunks(hip_engine):
     rng = np.random.default_rng(50)
     boiler = np.uint64(0x5555AAAA3333CCCC)

@@ -2,8 +2,8 @@
 The device cross join of two simprint tables into asset overlaps (``isccsearch_join_overlaps_between`` through
 ``HipTable.join_overlaps_between``) and ``find_shared_matches`` on an MI355X.
 
-Every case runs on both kernels -- ``forced(engine)`` (the launch on the matrix cores, ``mfma_join_kernel<W, true, false, true>``) and
-``valu(engine)`` (``join_scan_kernel<W, MASK, true, false, true>``), the ``join_launches`` / ``join_mfma_launches`` counters saying which
+Every case runs on both kernels -- ``forced(engine)`` (the launch on the matrix cores, ``mfma_join_kernel`` in its cross OVERLAP form) and
+``valu(engine)`` (``join_scan_kernel`` in the same form), the ``join_launches`` / ``join_mfma_launches`` counters saying which
 ran -- and compares records, both chunk arrays and info for exact equality with the host model (``tests/overlap_between_model.py``) and
 with each other.  The shapes are the smallest at which the two emit paths and the held / streamed roles change: each table is held
 (the one with more rows) in one case and streamed in the other, across the 1 024-row chunk, the 2 048-row slab and the second block.
@@ -170,6 +170,23 @@ def test_same_asset_pairs_take_no_slot(hip_engine):
                 assert tuples(rec) == [(0, 0, n, 0, 0, n * n), (0, 1, n, 0, 0, 2 * n), (0, 0, n, 1, 0, n * n), (1, 0, 2, 1, 0, 2 * n)]
                 assert info["chunk_pairs"] == n * n + 2 * n and info["records"] == 4
         check(hip_engine, ta, tb, (ka, wa, np.array([7], dtype=np.uint64)), (kb, wb, np.array([7, 9], dtype=np.uint64)), 0)
+
+
+def test_every_pair_takes_a_slot(hip_engine):
+    """
+    Two tables of 300 identical rows, 300 listed assets of one chunk each on either side, no asset key in both: every candidate of the
+    emit path takes a slot, 90 000 chunk pairs, so the count pass and the write pass have to agree on every one of them.
+    """
+    n = 300
+    code = 0x0123456789ABCDEF
+    listed_a, listed_b = np.arange(1, n + 1, dtype=np.uint64), np.arange(n + 1, 2 * n + 1, dtype=np.uint64)
+    side_a = (chunk_keys(listed_a), np.full((n, 1), code, dtype=np.uint64), listed_a)
+    side_b = (chunk_keys(listed_b), np.full((n, 1), code, dtype=np.uint64), listed_b)
+    with dropping(sp_table(hip_engine, 8, *side_a[:2]), sp_table(hip_engine, 8, *side_b[:2])) as (ta, tb):
+        rec, chunks_a, chunks_b, info = check(hip_engine, ta, tb, side_a, side_b, 0, skip=True)
+        assert info["chunk_pairs"] == n * n == 90_000 and info["records"] == len(rec) == 2 * n * n == 180_000
+        assert bool(np.all(rec["matched"] == 1)) and bool(np.all(rec["sum_hamming"] == 0)) and bool(np.all(rec["chunk_pairs"] == 1))
+        assert chunks_a.tolist() == [1] * n and chunks_b.tolist() == [1] * n
 
 
 def test_stop_chunks_per_table(hip_engine):
