@@ -331,6 +331,9 @@ const OptionDesc* find_option(const char* name) {
     return nullptr;
 }
 
+// the scratch set of the simprint entry points
+#include "simprint_scratch.hip.h"
+
 }  // namespace
 
 struct PendingSearch;
@@ -361,21 +364,7 @@ struct isccsearch_handle {
     PinBuf<unsigned char> p_block;
     DevBuf<uint64_t> d_misc;        // moves / gather rows / single query
     DevBuf<uint64_t> d_misc2;
-    // isccsearch_simprint_score: the neighbour lists of one request stay on the device with their rows; simprint_score.hip's buffers
-    DevBuf<isk::Record> d_sp_rec;
-    DevBuf<uint32_t> d_sp_rows, d_sp_nbest, d_sp_offs, d_sp_freqq, d_sp_unknown, d_sp_entry[2], d_sp_order[2], d_sp_matches, d_sp_nassets;
-    DevBuf<uint32_t> d_sp_cnt, d_sp_dofg;       // isccsearch_simprint_exact: list lengths of every lookup, the lookup of every given simprint
-    DevBuf<unsigned char> d_sp_best, d_sp_temp;
-    DevBuf<uint64_t> d_sp_asset[2];
-    DevBuf<double> d_sp_score[2], d_sp_tab, d_sp_ws, d_sp_idfq;
-    // isccsearch_simprint_score_many: request keys / sort payloads per entry, per-request offsets and counts, chunks per result
-    DevBuf<uint32_t> d_spm_req[2], d_spm_idx[2], d_spm_qbeg, d_spm_nassets, d_spm_astart, d_spm_estart, d_spm_cnt, d_spm_cpos;
-    std::vector<uint32_t> h_sp_qbeg, h_sp_qcount;     // (host side of a round: kept, so that a scoring call allocates nothing here)
-    PinBuf<double> p_sp_tab;
-    PinBuf<unsigned char> p_sp_out;
-    // the similarity / IDF tables on the device are those of (bits, total_assets, dup_limit):
-    uint32_t sp_tab_bits = 0, sp_tab_dup = 0xFFFFFFFFu;
-    int64_t sp_tab_total = -1;
+    SimprintScratch sp;             // isccsearch_simprint_score / _score_many / _exact (simprint_scratch.hip.h)
     // isccsearch_match_assets: every unit list of a call stays on the device for asset_score.hip
     DevBuf<isk::Record> d_am_rec, d_am_rec2;      // first lists / second INSTANCE pass
     DevBuf<uint32_t> d_am_cnt, d_am_cnt2, d_am_off;   // counts (+ overflow flags) / second pass counts / slot offsets + query list

@@ -3,22 +3,33 @@
 // Needs Batch, ResultBlock, record_hint and the query checks of isccsearch.hip, get_table of store.hip.h.
 extern "C" {
 static_assert(isksp::MAX_QUERY_SIMPRINTS == ISCCSEARCH_MAX_SCORED_SIMPRINTS, "header and kernels disagree");
-// isccsearch_simprint_score: where a search leaves its lists for the scoring kernels instead of handing them to the host
+// The simprint entry points: where a search leaves its lists for the scoring kernels instead of handing them to the host, what it
+// queues behind every batch's select, and what it keeps of the pinned block after the batch's synchronisation
 struct ScoreSink {
-    isksp::Buffers buf{};
+    SimprintScratch& sp;        // sized for the search by the caller (for_search / for_exact_search)
     int h_max = -1;
     uint32_t dup_limit = 0;
     uint32_t entries = 0;       // best (asset, query) entries appended so far -- known after each batch's synchronisation
     uint32_t max_count = 0;     // longest neighbour list
     bool unknown_any = false;   // some query's own document frequency could not be read off its list
     bool exact = false;         // isccsearch_simprint_exact: the lists are collision lists; only their lengths are kept per batch (no marking)
-    // ... and when ONE batch holds every lookup, its hits / offsets are prepared behind its select, so that the number of entries
-    // arrives with the batch's own synchronisation
-    const uint32_t* d_of_g = nullptr;
-    uint32_t nd = 0, ng = 0;
-    bool prepared = false;
+    uint32_t nd = 0, ng = 0;    // ... of nd distinct lookups for ng simprints as given (sp.d_of_g)
+    bool prepared = false;      // ... whose hits / offsets were prepared behind the search: `entries` is known
     uint32_t* q_count = nullptr;    // when set: [nq] length of every query's neighbour list (capped at k)
-};
+
+    // (exact) ONE batch holds every lookup: hits / offsets are prepared behind its select, so that the number of entries arrives with
+    // the batch's own synchronisation
+    bool holds_every_lookup(uint32_t pos, uint32_t m) const { return exact && pos == 0 && m == nd; }
+    // where the records of queries pos .. and their segment rows (nullptr: not wanted) go
+    isk::Record* records(uint32_t pos, uint32_t k) const { return sp.rec.p + (size_t)pos * k; }
+    uint32_t* rows(uint32_t pos, uint32_t k) const { return exact ? nullptr : sp.rows.p + (size_t)pos * k; }
+    // behind the select of queries [pos, pos + m), whose lists are final on the device (or will be redone and this queued again): mark
+    // the best chunk of every (asset, query) and append them to the request's entry list -- or keep the collision lists' lengths;
+    // `d_info` travels to the host with the batch's block
+    hipError_t queue_behind_select(uint32_t pos, uint32_t m, uint32_t k, const uint32_t* d_cnt, uint32_t* d_info, hipStream_t stream) const;
+    // after the synchronisation: the info words and the lists' lengths of the pinned block
+    void take(uint32_t pos, uint32_t m, uint32_t k, const uint32_t* p_cnt, const uint32_t* p_info);
+};      // (both are defined beside the scoring calls, simprint_api.hip.h)
 
 // What a search_locked call wants back -- ONE of:
 //   lists         keys / hamming / prefix_bits [nq][k] and count [nq] in the caller's arrays
@@ -96,9 +107,9 @@ struct LockedBatch : LockedCall {
           direct(one_copy && b.bytes() <= DIRECT_RESULT_BYTES && !sink), d_base(direct ? c.h->p_block.p : c.h->d_block.p),
           p_rec(b.records(c.h->p_block.p)), p_cnt(b.counts(c.h->p_block.p)),
           // (a sink keeps the records on the device)
-          batch(c.h, c.t, m_, len_, c.k, sink ? c.h->d_sp_rec.p + (size_t)pos_ * c.k : b.records(d_base), b.counts(d_base)), seg(c.t.sole_segment()) {
+          batch(c.h, c.t, m_, len_, c.k, sink ? sink->records(pos_, c.k) : b.records(d_base), b.counts(d_base)), seg(c.t.sole_segment()) {
         batch.radius = radius;
-        if (sink) { if (!sink->exact) batch.d_out_rows = h->d_sp_rows.p + (size_t)pos * k; batch.d_out_kth = blk.extra(d_base); }
+        if (sink) { batch.d_out_rows = sink->rows(pos, k); batch.d_out_kth = blk.extra(d_base); }
         if (one_copy) { batch.d_flags = blk.flags(d_base); batch.h_flags = blk.flags(h->p_block.p); }
     }
 
@@ -165,16 +176,8 @@ struct LockedBatch : LockedCall {
         }
         if (direct) return 0;                                  // already written where the host reads it
         if (sink) {
-            // the lists are final on the device (or will be redone and this queued again): mark the best chunk of every
-            // (asset, query), append them to the request's entry list; the host gets counts, flags, k-th distances and info
-            if (sink->exact) {
-                HIPOK(hipMemcpyAsync(h->d_sp_cnt.p + pos, batch.d_out_cnt, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToDevice, h->stream));
-                if (pos == 0 && m == sink->nd && sink->d_of_g)
-                    HIPOK(isksp::exact_prepare(sink->buf, batch.d_out_cnt, sink->d_of_g, sink->nd, sink->ng, k, blk.info(d_base), h->stream));
-            } else {
-                isksp::BatchArgs ba{pos, m, k, batch.d_out_cnt, sink->h_max, sink->dup_limit, sink->entries, blk.info(d_base)};
-                HIPOK(isksp::queue_batch(sink->buf, ba, h->stream));
-            }
+            // the host gets counts, flags, k-th distances and info
+            HIPOK(sink->queue_behind_select(pos, m, k, batch.d_out_cnt, blk.info(d_base), h->stream));
             HIPOK(hipMemcpyAsync(h->p_block.p, h->d_block.p, blk.bytes(), hipMemcpyDeviceToHost, h->stream));
             return 0;
         }
@@ -287,17 +290,7 @@ struct LockedBatch : LockedCall {
     void hand_out() {
         const bool none = batch.jobs.empty();
         if (sink) {
-            if (none) return;
-            const uint32_t* p_info = blk.info(h->p_block.p);
-            if (!sink->exact) {
-                sink->entries = p_info[0];
-                sink->unknown_any = sink->unknown_any || p_info[1] != 0;
-            } else if (pos == 0 && m == sink->nd && sink->d_of_g) {
-                sink->entries = p_info[0];
-                sink->prepared = true;
-            }
-            for (uint32_t i = 0; i < m; ++i) sink->max_count = std::max(sink->max_count, std::min(p_cnt[i], k));
-            if (sink->q_count) for (uint32_t i = 0; i < m; ++i) sink->q_count[pos + i] = std::min(p_cnt[i], k);
+            if (!none) sink->take(pos, m, k, p_cnt, blk.info(h->p_block.p));
         } else if (out.freq) {
             for (uint32_t i = 0; i < m; ++i) out.freq[order[pos + i]] = none ? 0 : p_cnt[i];
             if (out.collisions) for (uint32_t i = 0; i < m; ++i) out.collisions[order[pos + i]] = none ? 0 : blk.extra(h->p_block.p)[i];

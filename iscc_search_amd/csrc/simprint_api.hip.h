@@ -1,5 +1,27 @@
 // simprint_api.hip.h -- the three simprint entry points: a search whose lists stay on the device (ScoreSink) and the scoring of
-// simprint_score.hip behind it.  Needs search_locked and ScoreSink of search_api.hip.h, ensure_freq_column of store.hip.h.
+// simprint_score.hip behind it, on the handle's SimprintScratch, staged through ScoreStaging (simprint_scratch.hip.h).
+// Needs search_locked and ScoreSink of search_api.hip.h, ensure_freq_column of store.hip.h.
+// What a ScoreSink (search_api.hip.h) does with a batch of the search: the approximate requests mark and compact it, a hard-boundary
+// request keeps the lengths of its collision lists -- and prepares hits and offsets at once when the batch holds every lookup
+hipError_t ScoreSink::queue_behind_select(uint32_t pos, uint32_t m, uint32_t k, const uint32_t* d_cnt, uint32_t* d_info, hipStream_t stream) const {
+    const isksp::Buffers buf = sp.buffers();
+    if (!exact) return isksp::queue_batch(buf, isksp::BatchArgs{pos, m, k, d_cnt, h_max, dup_limit, entries, d_info}, stream);
+    const hipError_t e = hipMemcpyAsync(sp.cnt.p + pos, d_cnt, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream);
+    if (e != hipSuccess || !holds_every_lookup(pos, m)) return e;
+    return isksp::exact_prepare(buf, d_cnt, sp.d_of_g.p, nd, ng, k, d_info, stream);
+}
+void ScoreSink::take(uint32_t pos, uint32_t m, uint32_t k, const uint32_t* p_cnt, const uint32_t* p_info) {
+    if (!exact) {
+        entries = p_info[0];
+        unknown_any = unknown_any || p_info[1] != 0;
+    } else if (holds_every_lookup(pos, m)) {
+        entries = p_info[0];
+        prepared = true;
+    }
+    for (uint32_t i = 0; i < m; ++i) max_count = std::max(max_count, std::min(p_cnt[i], k));
+    if (q_count) for (uint32_t i = 0; i < m; ++i) q_count[pos + i] = std::min(p_cnt[i], k);
+}
+
 namespace {
 // The match threshold on the integer distance, the table's frequency column and the similarity / IDF tables of one scoring call
 // (isccsearch_simprint_score and _many); h->mu is held.
@@ -16,69 +38,28 @@ int simprint_setup(H* h, Table& t, Segment& s, double threshold, int64_t total_a
     if (dup_limit && (rc = ensure_freq_column(h, t, s, dup_limit))) return rc;
     // similarity and IDF values come from the HOST's arithmetic (log() of libm is what CPython's math.log calls; lmdb_ops.py:67-81)
     const uint32_t n_idf = dup_limit + 1;
-    if (h->sp_tab_bits != bits || h->sp_tab_dup != dup_limit || h->sp_tab_total != total_assets) {
+    if (h->sp.tab_bits != bits || h->sp.tab_dup != dup_limit || h->sp.tab_total != total_assets) {
         const size_t words = (size_t)bits + 1 + n_idf;
-        if ((rc = h->p_sp_tab.ensure(words))) return rc;
-        if ((rc = h->d_sp_tab.ensure(words))) return rc;
+        if ((rc = h->sp.p_tab.ensure(words))) return rc;
+        if ((rc = h->sp.tab.ensure(words))) return rc;
         HIPOK(hipStreamSynchronize(h->stream));      // (a previous upload may still be reading the staging block)
-        double* tab = h->p_sp_tab.p;
+        double* tab = h->sp.p_tab.p;
         for (uint32_t d = 0; d <= bits; ++d) tab[d] = 1.0 - (double)d / (double)bits;
         auto idf = [&](uint32_t freq) { return total_assets <= 0 ? 0.0 : std::log(1.0 + (double)total_assets / (double)(1 + (uint64_t)freq)); };
         if (dup_limit) for (uint32_t f = 0; f <= dup_limit; ++f) tab[bits + 1 + f] = idf(f);
         else tab[bits + 1] = idf(1);
-        HIPOK(hipMemcpyAsync(h->d_sp_tab.p, tab, words * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        h->sp_tab_bits = bits; h->sp_tab_dup = dup_limit; h->sp_tab_total = total_assets;
+        HIPOK(hipMemcpyAsync(h->sp.tab.p, tab, words * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        h->sp.tab_bits = bits; h->sp.tab_dup = dup_limit; h->sp.tab_total = total_assets;
     }
     return 0;
-}
-
-// device buffers of a scoring call over nq query simprints with k neighbours each (entries == 0: the search's; else the scoring's)
-int simprint_buffers(H* h, uint32_t nq, uint32_t k, uint32_t entries) {
-    int rc;
-    if (entries == 0) {
-        const size_t slots = (size_t)nq * k;
-        if ((rc = h->d_sp_rec.ensure(slots))) return rc;
-        if ((rc = h->d_sp_rows.ensure(slots))) return rc;
-        if ((rc = h->d_sp_best.ensure(slots))) return rc;
-        if ((rc = h->d_sp_nbest.ensure(nq))) return rc;
-        if ((rc = h->d_sp_offs.ensure(nq))) return rc;
-        if ((rc = h->d_sp_freqq.ensure(nq))) return rc;
-        if ((rc = h->d_sp_unknown.ensure(nq))) return rc;
-        if ((rc = h->d_sp_nassets.ensure(1))) return rc;
-        for (int i = 0; i < 2; ++i) {
-            if ((rc = h->d_sp_asset[i].ensure(slots))) return rc;
-            if ((rc = h->d_sp_entry[i].ensure(slots))) return rc;
-        }
-        return 0;
-    }
-    for (int i = 0; i < 2; ++i) {
-        if ((rc = h->d_sp_score[i].ensure(entries))) return rc;
-        if ((rc = h->d_sp_order[i].ensure(entries))) return rc;
-    }
-    if ((rc = h->d_sp_matches.ensure(entries))) return rc;
-    if ((rc = h->d_sp_ws.ensure(entries))) return rc;
-    if ((rc = h->d_sp_idfq.ensure(nq))) return rc;
-    return 0;
-}
-
-void simprint_bind(H* h, isksp::Buffers& b) {
-    b.rec = reinterpret_cast<const isccsearch_record*>(h->d_sp_rec.p);
-    b.rows = h->d_sp_rows.p; b.best = h->d_sp_best.p; b.nbest = h->d_sp_nbest.p; b.offs = h->d_sp_offs.p;
-    b.freq_q = h->d_sp_freqq.p; b.unknown = h->d_sp_unknown.p; b.n_assets = h->d_sp_nassets.p;
-    for (int i = 0; i < 2; ++i) {
-        b.c_asset[i] = h->d_sp_asset[i].p; b.c_entry[i] = h->d_sp_entry[i].p;
-        b.score[i] = h->d_sp_score[i].p; b.order[i] = h->d_sp_order[i].p;
-    }
-    b.matches = h->d_sp_matches.p; b.ws = h->d_sp_ws.p; b.idf_q = h->d_sp_idfq.p;
-    b.temp = h->d_sp_temp.p; b.temp_bytes = h->d_sp_temp.n;
 }
 
 // rare: a query simprint with k equal stored rows and k < dup_limit -- its document frequency needs the collision scan
 int simprint_unknown_freq(H* h, uint32_t table, Table& t, uint32_t nq, const uint64_t* q_words, uint32_t dup_limit) {
     int rc;
     std::vector<uint32_t> unk(nq), fq(nq);
-    HIPOK(hipMemcpyAsync(unk.data(), h->d_sp_unknown.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPOK(hipMemcpyAsync(fq.data(), h->d_sp_freqq.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPOK(hipMemcpyAsync(unk.data(), h->sp.unknown.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPOK(hipMemcpyAsync(fq.data(), h->sp.freq_q.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     HIPOK(hipStreamSynchronize(h->stream));
     std::vector<uint32_t> which;
     for (uint32_t q = 0; q < nq; ++q) if (unk[q]) which.push_back(q);
@@ -87,7 +68,7 @@ int simprint_unknown_freq(H* h, uint32_t table, Table& t, uint32_t nq, const uin
     std::vector<uint32_t> freq(which.size());
     if ((rc = search_locked(h, table, (uint32_t)which.size(), qw.data(), nullptr, dup_limit, 0, SearchOut::doc_freq(freq.data())))) return rc;
     for (size_t i = 0; i < which.size(); ++i) fq[which[i]] = freq[i];
-    HIPOK(hipMemcpyAsync(h->d_sp_freqq.p, fq.data(), (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPOK(hipMemcpyAsync(h->sp.freq_q.p, fq.data(), (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     HIPOK(hipStreamSynchronize(h->stream));       // (fq leaves scope)
     return 0;
 }
@@ -115,8 +96,9 @@ int simprint_score_rounds(H* h, uint32_t table, uint32_t n_req, const uint32_t* 
     const uint32_t k = count, bits = 8 * (uint32_t)t.max_bytes, W = (uint32_t)t.max_words;
     int h_max = -1;
     if ((rc = simprint_setup(h, t, s, threshold, total_assets, dup_limit, h_max))) return rc;
-    std::vector<uint32_t>& qbeg = h->h_sp_qbeg;
-    std::vector<uint32_t>& q_count = h->h_sp_qcount;
+    SimprintScratch& sp = h->sp;
+    std::vector<uint32_t>& qbeg = sp.h_qbeg;
+    std::vector<uint32_t>& q_count = sp.h_qcount;
     for (uint32_t r0 = 0; r0 < n_req;) {
         const uint32_t base = req_offsets[r0];
         uint32_t r1 = r0 + 1;
@@ -125,13 +107,12 @@ int simprint_score_rounds(H* h, uint32_t table, uint32_t n_req, const uint32_t* 
         const uint64_t* const qw = q_words + (size_t)base * t.max_words;
         if (nq == 0) { r0 = r1; continue; }
         h->stats.searches += 1;
-        if ((rc = simprint_buffers(h, nq, k, 0))) return rc;
+        if ((rc = sp.for_search(nq, k))) return rc;
         q_count.assign(nq, 0);
-        ScoreSink sink;
+        ScoreSink sink{sp};
         sink.h_max = h_max;
         sink.dup_limit = dup_limit;
         sink.q_count = q_count.data();
-        simprint_bind(h, sink.buf);
         if ((rc = search_locked(h, table, nq, qw, nullptr, k, max_hamming < 0 ? -1 : max_hamming, SearchOut::to_sink(&sink)))) return rc;
         uint32_t words = 0;                // LDS words of the score kernel: the most 64-bit words one request's range touches
         qbeg.resize(nr + 1);
@@ -148,69 +129,41 @@ int simprint_score_rounds(H* h, uint32_t table, uint32_t n_req, const uint32_t* 
         if (entries == 0) { r0 = r1; continue; }
         if (sink.unknown_any && (rc = simprint_unknown_freq(h, table, t, nq, qw, dup_limit))) return rc;
         const uint32_t cap = (uint32_t)std::min<uint64_t>((uint64_t)nr * limit, entries);
-        if ((rc = simprint_buffers(h, nq, k, entries))) return rc;
-        if (nr == 1) {
-            if ((rc = h->d_sp_temp.ensure(isksp::sort_temp_bytes(entries)))) return rc;
-        } else {
-            for (int i = 0; i < 2; ++i) {
-                if ((rc = h->d_spm_req[i].ensure(entries))) return rc;
-                if ((rc = h->d_spm_idx[i].ensure(entries))) return rc;
-            }
-            if ((rc = h->d_spm_qbeg.ensure(nr + 1))) return rc;
-            if ((rc = h->d_spm_nassets.ensure(nr))) return rc;
-            if ((rc = h->d_spm_astart.ensure(nr + 1))) return rc;
-            if ((rc = h->d_spm_estart.ensure(nr + 1))) return rc;
-            if ((rc = h->d_spm_cnt.ensure(cap))) return rc;
-            if ((rc = h->d_spm_cpos.ensure(cap))) return rc;
-            if ((rc = h->d_sp_temp.ensure(isksp::many_temp_bytes(entries, cap)))) return rc;
-        }
-        simprint_bind(h, sink.buf);
-        // outputs in pinned memory, written by the emit kernels themselves, compact: {info[nr][4] | results[cap] | chunks | chunk words}
-        const size_t res_off = ((size_t)nr * 16 + 15) / 16 * 16, chunk_off = res_off + (size_t)cap * sizeof(isccsearch_simprint_result);
-        const size_t chunk_cap = out_chunks ? (size_t)std::min<uint64_t>((uint64_t)limit * nq, entries) : 0;
-        const size_t words_off = chunk_off + chunk_cap * sizeof(isccsearch_simprint_chunk);
-        if ((rc = h->p_sp_out.ensure(words_off + chunk_cap * W * 8))) return rc;
-        unsigned char* const po = h->p_sp_out.p;
+        if ((rc = nr == 1 ? sp.for_scoring(nq, entries) : sp.for_round(nq, entries, nr, cap))) return rc;
+        isksp::Buffers buf = sp.buffers();
+        // outputs in pinned memory, written by the emit kernels themselves
+        const ScoreStaging st{nr, cap, out_chunks ? (size_t)std::min<uint64_t>((uint64_t)limit * nq, entries) : 0, W};
+        if ((rc = sp.p_out.ensure(st.bytes()))) return rc;
+        unsigned char* const po = sp.p_out.p;
         isksp::ScoreArgs sa{};
         sa.nq = nq; sa.k = k; sa.entries = entries; sa.limit = limit;
-        sa.sim_tab = h->d_sp_tab.p; sa.idf_tab = h->d_sp_tab.p + bits + 1; sa.dup_limit = dup_limit;
+        sa.sim_tab = sp.tab.p; sa.idf_tab = sp.tab.p + bits + 1; sa.dup_limit = dup_limit;
         sa.freq_col = dup_limit ? s.freq : nullptr;
         set_cols(sa.col, s, s.W);
         sa.W = W;
-        sa.out_info = reinterpret_cast<uint32_t*>(po);
-        sa.out_results = reinterpret_cast<isccsearch_simprint_result*>(po + res_off);
-        sa.out_chunks = out_chunks ? reinterpret_cast<isccsearch_simprint_chunk*>(po + chunk_off) : nullptr;
-        sa.out_chunk_words = out_chunks ? reinterpret_cast<uint64_t*>(po + words_off) : nullptr;
+        sa.out_info = st.info(po); sa.out_results = st.results(po); sa.out_chunks = st.chunks(po); sa.out_chunk_words = st.words(po);
         if (nr == 1) {
-            HIPOK(isksp::queue_score(sink.buf, sa, h->stream));
+            HIPOK(isksp::queue_score(buf, sa, h->stream));
         } else {
-            isksp::ManyBuffers mb{};
-            for (int i = 0; i < 2; ++i) { mb.req[i] = h->d_spm_req[i].p; mb.idx[i] = h->d_spm_idx[i].p; }
-            mb.qbeg = h->d_spm_qbeg.p; mb.n_assets = h->d_spm_nassets.p; mb.a_start = h->d_spm_astart.p; mb.e_start = h->d_spm_estart.p;
-            mb.cnt = h->d_spm_cnt.p; mb.c_pos = h->d_spm_cpos.p;
+            const isksp::ManyBuffers mb = sp.many_buffers();
             HIPOK(hipMemcpyAsync(mb.qbeg, qbeg.data(), (size_t)(nr + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
             isksp::ScoreManyArgs ma{sa, nr, cap, words};
-            HIPOK(isksp::queue_score_many(sink.buf, mb, ma, h->stream));
+            HIPOK(isksp::queue_score_many(buf, mb, ma, h->stream));
         }
         HIPOK(hipStreamSynchronize(h->stream));       // (qbeg is read by the kernels until here)
-        // into the caller's regions: request r's results at r x limit, its chunks at limit x req_offsets[r]
-        const uint32_t* info = reinterpret_cast<const uint32_t*>(po);
-        size_t res_at = 0, chunk_at = 0;
-        for (uint32_t r = 0; r < nr; ++r) {
-            const uint32_t n = info[4 * r], c = info[4 * r + 3];
-            uint32_t* oi = out_info + 4 * (size_t)(r0 + r);
-            oi[0] = n; oi[1] = info[4 * r + 1]; oi[3] = c;
-            memcpy(out_results + (size_t)(r0 + r) * limit, po + res_off + res_at * sizeof(isccsearch_simprint_result), (size_t)n * sizeof(isccsearch_simprint_result));
-            if (out_chunks && c) {
-                const size_t dst = (size_t)limit * req_offsets[r0 + r];
-                memcpy(out_chunks + dst, po + chunk_off + chunk_at * sizeof(isccsearch_simprint_chunk), (size_t)c * sizeof(isccsearch_simprint_chunk));
-                memcpy(out_chunk_words + dst * W, po + words_off + chunk_at * W * 8, (size_t)c * W * 8);
-            }
-            res_at += n;
-            chunk_at += c;
-        }
+        st.copy_out(po, limit, req_offsets + r0, out_results + (size_t)r0 * limit, out_chunks, out_chunk_words, out_info + 4 * (size_t)r0);
         r0 = r1;
     }
+    return 0;
+}
+
+// what isccsearch_simprint_score and isccsearch_simprint_score_many check alike, and first
+int check_score_args(const isccsearch_handle* h, uint32_t count, int32_t max_hamming, uint32_t dup_limit, uint32_t limit) {
+    if (!h) return fail(-EINVAL, "handle is NULL");
+    if (int rc = check_count(count)) return rc;
+    if (max_hamming > 256) return fail(-EINVAL, "max_hamming %d exceeds 256", max_hamming);
+    if (dup_limit > ISCCSEARCH_MAX_K) return fail(-EINVAL, "dup_limit %u exceeds ISCCSEARCH_MAX_K (%d)", dup_limit, ISCCSEARCH_MAX_K);
+    if (limit < 1) return fail(-EINVAL, "limit must be >= 1");
     return 0;
 }
 }  // namespace
@@ -222,11 +175,7 @@ int isccsearch_simprint_score(isccsearch_handle* h, uint32_t table, uint32_t nq,
                               int64_t total_assets, uint32_t dup_limit,
                               isccsearch_simprint_result* out_results, isccsearch_simprint_chunk* out_chunks,
                               uint64_t* out_chunk_words, uint32_t* out_info) {
-    if (!h) return fail(-EINVAL, "handle is NULL");
-    if (int rc = check_count(count)) return rc;
-    if (max_hamming > 256) return fail(-EINVAL, "max_hamming %d exceeds 256", max_hamming);
-    if (dup_limit > ISCCSEARCH_MAX_K) return fail(-EINVAL, "dup_limit %u exceeds ISCCSEARCH_MAX_K (%d)", dup_limit, ISCCSEARCH_MAX_K);
-    if (limit < 1) return fail(-EINVAL, "limit must be >= 1");
+    if (int rc = check_score_args(h, count, max_hamming, dup_limit, limit)) return rc;
     if (!out_info) return fail(-EINVAL, "NULL argument");
     out_info[0] = out_info[1] = out_info[2] = out_info[3] = 0;
     if (nq == 0) return 0;
@@ -244,11 +193,7 @@ int isccsearch_simprint_score_many(isccsearch_handle* h, uint32_t table, uint32_
                                    int64_t total_assets, uint32_t dup_limit,
                                    isccsearch_simprint_result* out_results, isccsearch_simprint_chunk* out_chunks,
                                    uint64_t* out_chunk_words, uint32_t* out_info) {
-    if (!h) return fail(-EINVAL, "handle is NULL");
-    if (int rc = check_count(count)) return rc;
-    if (max_hamming > 256) return fail(-EINVAL, "max_hamming %d exceeds 256", max_hamming);
-    if (dup_limit > ISCCSEARCH_MAX_K) return fail(-EINVAL, "dup_limit %u exceeds ISCCSEARCH_MAX_K (%d)", dup_limit, ISCCSEARCH_MAX_K);
-    if (limit < 1) return fail(-EINVAL, "limit must be >= 1");
+    if (int rc = check_score_args(h, count, max_hamming, dup_limit, limit)) return rc;
     if (n_req == 0) return 0;
     if (!out_info || !req_offsets) return fail(-EINVAL, "NULL argument");
     memset(out_info, 0, (size_t)n_req * 4 * sizeof(uint32_t));
@@ -295,22 +240,15 @@ int isccsearch_simprint_exact(isccsearch_handle* h, uint32_t table, uint32_t n_d
     HIPOK(hipSetDevice(h->device));
     h->stats.searches += 1;
     const uint32_t k = std::min<uint32_t>(dup_limit, ISCCSEARCH_MAX_K), nd = n_distinct, ng = n_given;
-    if ((rc = h->d_sp_rec.ensure((size_t)nd * k))) return rc;
-    if ((rc = h->d_sp_cnt.ensure(nd))) return rc;
-    if ((rc = h->d_sp_freqq.ensure(nd))) return rc;
-    if ((rc = h->d_sp_dofg.ensure(ng))) return rc;
-    if ((rc = h->d_sp_nbest.ensure(ng))) return rc;
-    if ((rc = h->d_sp_unknown.ensure(ng))) return rc;
-    if ((rc = h->d_sp_offs.ensure(ng))) return rc;
-    if ((rc = h->d_sp_nassets.ensure(1))) return rc;
-    ScoreSink sink;
+    SimprintScratch& sp = h->sp;
+    if ((rc = sp.for_exact_search(nd, ng, k))) return rc;
+    ScoreSink sink{sp};
     sink.exact = true;
-    simprint_bind(h, sink.buf);
+    sink.nd = nd; sink.ng = ng;
     // (the lookup of every given simprint goes up first: when one batch holds all lookups, hits and offsets are prepared behind its
     //  select and the number of entries arrives with the batch's own synchronisation)
-    HIPOK(hipMemcpyAsync(h->d_sp_dofg.p, given, (size_t)ng * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+    HIPOK(hipMemcpyAsync(sp.d_of_g.p, given, (size_t)ng * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
     HIPOK(hipStreamSynchronize(h->stream));           // (`given` is the caller's memory)
-    sink.d_of_g = h->d_sp_dofg.p; sink.nd = nd; sink.ng = ng;
     // every row equal to a query simprint, ascending key, at most dup_limit per simprint (lmdb_ops.py:197-210): the lists stay on the device
     if ((rc = search_locked(h, table, nd, q_words, nullptr, k, 0, SearchOut::to_sink(&sink)))) return rc;
     out_info[2] = sink.max_count;
@@ -320,37 +258,25 @@ int isccsearch_simprint_exact(isccsearch_handle* h, uint32_t table, uint32_t n_d
         if ((rc = h->d_block.ensure(isksp::INFO_WORDS * sizeof(uint32_t)))) return rc;
         if ((rc = h->p_block.ensure(isksp::INFO_WORDS * sizeof(uint32_t)))) return rc;
         uint32_t* const d_info = reinterpret_cast<uint32_t*>(h->d_block.p);
-        HIPOK(isksp::exact_prepare(sink.buf, h->d_sp_cnt.p, h->d_sp_dofg.p, nd, ng, k, d_info, h->stream));
+        HIPOK(isksp::exact_prepare(sp.buffers(), sp.cnt.p, sp.d_of_g.p, nd, ng, k, d_info, h->stream));
         HIPOK(hipMemcpyAsync(h->p_block.p, d_info, isksp::INFO_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
         HIPOK(hipStreamSynchronize(h->stream));
         entries = reinterpret_cast<const uint32_t*>(h->p_block.p)[0];
     }
     if (entries == 0) return 0;
-    for (int i = 0; i < 2; ++i) {
-        if ((rc = h->d_sp_asset[i].ensure(entries))) return rc;
-        if ((rc = h->d_sp_entry[i].ensure(entries))) return rc;
-        if ((rc = h->d_sp_score[i].ensure(entries))) return rc;
-        if ((rc = h->d_sp_order[i].ensure(entries))) return rc;
-    }
-    if ((rc = h->d_sp_matches.ensure(entries))) return rc;
-    if ((rc = h->d_sp_temp.ensure(isksp::sort_temp_bytes(entries)))) return rc;
-    simprint_bind(h, sink.buf);
-    const size_t res_off = 16, chunk_off = res_off + (size_t)limit * sizeof(isccsearch_simprint_result);
-    const size_t chunk_cap = out_chunks ? entries : 0;
-    if ((rc = h->p_sp_out.ensure(chunk_off + chunk_cap * sizeof(isccsearch_simprint_chunk)))) return rc;
-    unsigned char* const po = h->p_sp_out.p;
+    if ((rc = sp.for_exact_scoring(entries))) return rc;
+    isksp::Buffers buf = sp.buffers();
+    const ScoreStaging st{1, limit, out_chunks ? entries : 0, 0};
+    if ((rc = sp.p_out.ensure(st.bytes()))) return rc;
+    unsigned char* const po = sp.p_out.p;
     isksp::ExactArgs ea{};
     ea.nd = nd; ea.ng = ng; ea.k = k; ea.entries = entries; ea.limit = limit; ea.queried = queried;
-    ea.d_of_g = h->d_sp_dofg.p; ea.threshold = threshold;
-    ea.out_info = reinterpret_cast<uint32_t*>(po);
-    ea.out_results = reinterpret_cast<isccsearch_simprint_result*>(po + res_off);
-    ea.out_chunks = out_chunks ? reinterpret_cast<isccsearch_simprint_chunk*>(po + chunk_off) : nullptr;
-    HIPOK(isksp::queue_exact(sink.buf, ea, h->stream));
+    ea.d_of_g = sp.d_of_g.p; ea.threshold = threshold;
+    ea.out_info = st.info(po); ea.out_results = st.results(po); ea.out_chunks = st.chunks(po);
+    HIPOK(isksp::queue_exact(buf, ea, h->stream));
     HIPOK(hipStreamSynchronize(h->stream));
-    const uint32_t* info = reinterpret_cast<const uint32_t*>(po);
-    out_info[0] = info[0]; out_info[1] = info[1]; out_info[3] = info[3];
-    memcpy(out_results, po + res_off, (size_t)info[0] * sizeof(isccsearch_simprint_result));
-    if (out_chunks) memcpy(out_chunks, po + chunk_off, (size_t)info[3] * sizeof(isccsearch_simprint_chunk));
+    const uint32_t first_query = 0;
+    st.copy_out(po, limit, &first_query, out_results, out_chunks, nullptr, out_info);
     return 0;
 }
 }  // extern "C"

@@ -6,19 +6,31 @@
 // additions, order (-score, asset), first `limit`.  Input: the neighbour lists as select_kernel left them in
 // device memory -- records [nq][k] ascending (hamming, key), the segment row of every record, counts [nq].
 //
-//   per batch of <= 1 024 query simprints (queued behind its select_kernel, before the batch's one synchronisation):
+// The stages, once; the three pipelines below are lists of them.
+//   per batch of <= 1 024 query simprints (queue_batch, queued behind its select_kernel, before the batch's one synchronisation):
 //     mark     one block per query: matches = the prefix with hamming <= h_max; first occurrence of every asset in it
 //              (LDS hash: asset -> smallest rank) = the best chunk of (asset, query); the query's own document
 //              frequency from its hamming-0 prefix
 //     offsets  exclusive scan of the per-query best counts (one block)
 //     compact  the best entries of the batch, in (query, rank) order, appended to (asset[], entry[])
-//   once per request (queue_score; a round of isccsearch_simprint_score_many that holds one request takes it too):
-//     stable radix sort by asset (rocPRIM) -> every asset's entries adjacent, ascending query
-//     score    one thread per asset run, sequential float64 sums in the reference's order (no contraction into fused
-//              multiply-adds: -ffp-contract=off; IEEE rounding); IDF and similarity values come from host-computed tables
+//   once per request or round, over the entries:
+//     by asset stable radix sort by asset (rocPRIM) -> every asset's entries adjacent, ascending query
+//     weights  per sorted entry its IDF weight, weight x similarity and query index, contiguous; values from host-computed tables
 //              (log() of the host libm = CPython's math.log)
-//     stable radix sort by score, descending (assets are ascending already: ties keep ascending asset order)
-//     emit     the first `limit` assets (+ their matched chunks) written straight into pinned host memory
+//     score    one thread per run of entries, sequential float64 sums in the reference's order (no contraction into fused
+//              multiply-adds: -ffp-contract=off; IEEE rounding), one LDS row of a bit per query simprint per thread
+//     by score stable radix sort by score, descending (assets are ascending already: ties keep ascending asset order)
+//     emit     the first `limit` assets (+ the chunk records of their entries) written straight into pinned host memory
+// Where the pipelines differ:
+//   queue_score       (one request; a round of isccsearch_simprint_score_many that holds one request takes it too)
+//                     by asset, weights, score with a run = an asset, by score, emit with a block per result
+//   queue_score_many  (a round of several requests) a stable sort by request behind each of the two sorts, so that a run = a
+//                     (request, asset) pair and every request's assets end up in (-score, asset) order: two more sorts, their key
+//                     and gather kernels, and a scan of the chunks per result.  The same score kernel, instantiated for such runs;
+//                     emit with a wave per result.  See ManyBuffers.
+//   queue_exact       (hard-boundary requests) the entries are collisions (exact_prepare and a compaction of its own instead of
+//                     queue_batch); by asset, weights and score in the exact form (coverage x quality, no similarity), by score, the
+//                     same emit kernel writing collision records.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -81,17 +93,12 @@ struct ScoreArgs {
     uint64_t* out_chunk_words;                 // nullable [limit * nq * W]
     uint32_t* out_info;                        // [4] {results, assets matched, -, chunks written}
 };
-// sort by asset -> score -> sort by score -> emit
 hipError_t queue_score(Buffers& b, const ScoreArgs& a, hipStream_t stream);
 
 // Many requests in one call (a round of two or more requests of isccsearch_simprint_score_many): the query simprints of a round
 // are the concatenation of its requests' (request r: queries [qbeg[r], qbeg[r + 1]) of the round), searched, marked and compacted
-// as ONE request by queue_batch -- so the entries are grouped by request already -- then
-//     stable radix sort by asset, stable radix sort by request -> every (request, asset) run adjacent, ascending query
-//     score    the same score_kernel with a run = (request, asset): the unmatched sum over the run's own request only; assets
-//              counted per request
-//     stable radix sort by score (descending), stable radix sort by request -> every request's assets in (-score, asset) order
-//     emit     one wave per written result (never a block per (request, rank) slot): results, compact, in request order
+// as ONE request by queue_batch -- so the entries are grouped by request already.  The score kernel runs the unmatched sum over the
+// run's own request only and counts assets per request; emit never takes a block per (request, rank) slot.
 // Pinned outputs are staged compactly: request r's results follow those of the requests before it, its chunks likewise;
 // out_info[4 r ..] = {results, assets matched, -, chunks written} -- the host moves them into the caller's per-request regions.
 struct ManyBuffers {

@@ -32,6 +32,20 @@ __device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t* wtot /
     return before + incl - v;
 }
 
+// adds one value per thread of the block into *total (shared, zeroed before the last barrier; complete after the next one): a
+// shuffle sum per wave, then one atomic per wave that has something to add
+__device__ __forceinline__ void block_add(uint32_t v, uint32_t* total) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    if ((threadIdx.x & 63) == 0 && v) atomicAdd(total, v);
+}
+
+// this thread's share of the distinct assets among the first n records of a list that ascends by key (an asset's rows are adjacent)
+__device__ __forceinline__ uint32_t distinct_assets(const isccsearch_record* r, uint32_t n) {
+    uint32_t mine = 0;
+    for (uint32_t i = threadIdx.x; i < n; i += BLOCK) mine += (i == 0 || r[i].key_hi != r[i - 1].key_hi) ? 1u : 0u;
+    return mine;
+}
+
 // ---------------------------------------------------------------------------------------------
 // mark_kernel: one block per query simprint of the batch.
 //   matches   = the prefix of the list with hamming <= h_max (the list ascends by (hamming, key)): the reference's threshold
@@ -107,10 +121,8 @@ __global__ __launch_bounds__(BLOCK) void mark_kernel(const MarkParams p) {
     }
     // the query's own document frequency
     const uint32_t m0 = p.dup_limit ? (n0 < p.dup_limit ? n0 : p.dup_limit) : 0;
-    uint32_t dist = 0;
-    for (uint32_t i = tid; i < m0; i += BLOCK) dist += (i == 0 || r[i].key_hi != r[i - 1].key_hi) ? 1u : 0u;
-    for (int off = 32; off > 0; off >>= 1) { mine += __shfl_down(mine, off); dist += __shfl_down(dist, off); }
-    if ((tid & 63) == 0) { if (mine) atomicAdd(&s_best, mine); if (dist) atomicAdd(&s_dist, dist); }
+    block_add(mine, &s_best);
+    block_add(distinct_assets(r, m0), &s_dist);
     __syncthreads();
     if (tid == 0) {
         p.nbest[q] = s_best;
@@ -344,6 +356,45 @@ __global__ void score_kernel(const P p) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// The chunk record of a matched entry (emit_kernel, emit_many_kernel): the query simprint it matched, counted from q0 (the first
+// query simprint of its request), the stored chunk's key, distance, document frequency and code words, at position `at` of the
+// pinned chunk arrays.
+// ---------------------------------------------------------------------------------------------
+struct ChunkParams {
+    const isccsearch_record* rec;
+    const uint32_t* rows;
+    const uint32_t* freq_col;
+    const uint64_t* col[4];
+    isccsearch_simprint_chunk* out_chunks;      // nullptr: no chunks wanted
+    uint64_t* out_chunk_words;
+    uint32_t k, W, dup_limit;
+};
+__device__ __forceinline__ void write_chunk(const ChunkParams& p, uint32_t ent, uint32_t q0, uint32_t at) {
+    const isccsearch_record& rec = p.rec[ent];
+    const uint32_t row = p.rows[ent];
+    isccsearch_simprint_chunk c;
+    c.query = ent / p.k - q0;
+    c.reserved = 0;
+    c.key_lo = rec.key_lo;
+    c.hamming = rec.hamming;
+    c.freq = p.dup_limit ? p.freq_col[row] : 1u;
+    p.out_chunks[at] = c;
+    for (uint32_t w = 0; w < p.W; ++w) p.out_chunk_words[(uint64_t)at * p.W + w] = p.col[w][row];
+}
+// ... and of a collision (queue_exact): an entry is (given simprint g) * k + rank, its record belongs to distinct lookup d_of_g[g];
+// stored simprint == query simprint, score 1.0 (lmdb_ops.py:228-235), so no code words
+__device__ __forceinline__ void write_collision(const ChunkParams& p, const uint32_t* d_of_g, const uint32_t* freq_d, uint32_t ent, uint32_t at) {
+    isccsearch_simprint_chunk c;
+    c.query = ent / p.k;
+    c.reserved = 0;
+    const uint32_t d = d_of_g[c.query];
+    c.key_lo = p.rec[(uint64_t)d * p.k + ent % p.k].key_lo;
+    c.hamming = 0;
+    c.freq = freq_d[d];
+    p.out_chunks[at] = c;
+}
+
+// ---------------------------------------------------------------------------------------------
 // emit_kernel: block r writes result r of the first min(limit, assets) runs in (-score, asset) order -- and its matched
 // chunks -- into pinned host memory; its chunks start behind those of the results before it.
 // ---------------------------------------------------------------------------------------------
@@ -354,16 +405,11 @@ struct EmitParams {
     const uint32_t* entry;
     const uint32_t* matches;
     const uint32_t* n_assets;
-    const isccsearch_record* rec;
-    const uint32_t* rows;
-    const uint32_t* freq_col;
-    const uint64_t* col[4];
+    ChunkParams c;
     isccsearch_simprint_result* out_results;
-    isccsearch_simprint_chunk* out_chunks;
-    uint64_t* out_chunk_words;
     uint32_t* out_info;
-    uint32_t limit, k, W, dup_limit;
-    // hard-boundary requests (queue_exact): an entry is (given simprint g) * k + rank; its record belongs to distinct lookup d_of_g[g]
+    uint32_t limit;
+    // hard-boundary requests (queue_exact): the chunks are collisions
     const uint32_t* d_of_g;         // nullptr: the approximate path
     const uint32_t* freq_d;         // document frequency per distinct lookup
 };
@@ -379,8 +425,7 @@ __global__ __launch_bounds__(BLOCK) void emit_kernel(const EmitParams p) {
     // chunks of the results before this one (block n - 1 also adds its own: the total)
     uint32_t before = 0;
     for (uint32_t i = tid; i < r; i += BLOCK) before += p.matches[p.order[i]];
-    for (int off = 32; off > 0; off >>= 1) before += __shfl_down(before, off);
-    if ((tid & 63) == 0 && before) atomicAdd(&s_first, before);
+    block_add(before, &s_first);
     __syncthreads();
     const uint32_t at = s_first, e = p.order[r], m = p.matches[e];
     if (tid == 0) {
@@ -390,29 +435,13 @@ __global__ __launch_bounds__(BLOCK) void emit_kernel(const EmitParams p) {
         res.matches = m;
         res.first_chunk = at;
         p.out_results[r] = res;
-        if (r == n - 1) p.out_info[3] = p.out_chunks ? at + m : 0;
+        if (r == n - 1) p.out_info[3] = p.c.out_chunks ? at + m : 0;
     }
-    if (!p.out_chunks) return;
+    if (!p.c.out_chunks) return;
     for (uint32_t j = tid; j < m; j += BLOCK) {
         const uint32_t ent = p.entry[e + j];
-        isccsearch_simprint_chunk c;
-        c.query = ent / p.k;
-        c.reserved = 0;
-        if (p.d_of_g) {                       // a collision: stored simprint == query simprint, score 1.0 (lmdb_ops.py:228-235)
-            const uint32_t d = p.d_of_g[c.query];
-            c.key_lo = p.rec[(uint64_t)d * p.k + ent % p.k].key_lo;
-            c.hamming = 0;
-            c.freq = p.freq_d[d];
-            p.out_chunks[at + j] = c;
-            continue;
-        }
-        const isccsearch_record& rec = p.rec[ent];
-        const uint32_t row = p.rows[ent];
-        c.key_lo = rec.key_lo;
-        c.hamming = rec.hamming;
-        c.freq = p.dup_limit ? p.freq_col[row] : 1u;
-        p.out_chunks[at + j] = c;
-        for (uint32_t w = 0; w < p.W; ++w) p.out_chunk_words[(uint64_t)(at + j) * p.W + w] = p.col[w][row];
+        if (p.d_of_g) write_collision(p.c, p.d_of_g, p.freq_d, ent, at + j);
+        else write_chunk(p.c, ent, 0, at + j);
     }
 }
 
@@ -436,11 +465,7 @@ __global__ __launch_bounds__(BLOCK) void exact_freq_kernel(const isccsearch_reco
     if (tid == 0) total = 0;
     __syncthreads();
     const uint32_t n = cnt[d] < k ? cnt[d] : k;
-    const isccsearch_record* r = rec + (uint64_t)d * k;
-    uint32_t mine = 0;
-    for (uint32_t i = tid; i < n; i += BLOCK) mine += (i == 0 || r[i].key_hi != r[i - 1].key_hi) ? 1u : 0u;
-    for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off);
-    if ((tid & 63) == 0 && mine) atomicAdd(&total, mine);
+    block_add(distinct_assets(rec + (uint64_t)d * k, n), &total);
     __syncthreads();
     if (tid == 0) freq_d[d] = total;
 }
@@ -634,15 +659,10 @@ struct EmitManyParams {
     const uint32_t* e_start;
     const uint32_t* c_pos;
     const uint32_t* qbeg;
-    const isccsearch_record* rec;
-    const uint32_t* rows;
-    const uint32_t* freq_col;
-    const uint64_t* col[4];
+    ChunkParams c;
     isccsearch_simprint_result* out_results;
-    isccsearch_simprint_chunk* out_chunks;
-    uint64_t* out_chunk_words;
     uint32_t* out_info;
-    uint32_t n_req, k, W, dup_limit;
+    uint32_t n_req;
 };
 __global__ __launch_bounds__(BLOCK) void emit_many_kernel(const EmitManyParams p) {
     const uint32_t lane = threadIdx.x & 63;
@@ -660,26 +680,13 @@ __global__ __launch_bounds__(BLOCK) void emit_many_kernel(const EmitManyParams p
             res.matches = m;
             res.first_chunk = rel;
             p.out_results[t] = res;
-            if (j == n - 1) p.out_info[4 * r + 3] = p.out_chunks ? rel + m : 0;
+            if (j == n - 1) p.out_info[4 * r + 3] = p.c.out_chunks ? rel + m : 0;
         }
-        if (!p.out_chunks) continue;
+        if (!p.c.out_chunks) continue;
         const uint32_t q0 = p.qbeg[r];
-        for (uint32_t jj = lane; jj < m; jj += 64) {
-            const uint32_t ent = p.entry[e + jj];
-            const isccsearch_record& rec = p.rec[ent];
-            const uint32_t row = p.rows[ent];
-            isccsearch_simprint_chunk c;
-            c.query = ent / p.k - q0;
-            c.reserved = 0;
-            c.key_lo = rec.key_lo;
-            c.hamming = rec.hamming;
-            c.freq = p.dup_limit ? p.freq_col[row] : 1u;
-            p.out_chunks[at + jj] = c;
-            for (uint32_t w = 0; w < p.W; ++w) p.out_chunk_words[(uint64_t)(at + jj) * p.W + w] = p.col[w][row];
-        }
+        for (uint32_t jj = lane; jj < m; jj += 64) write_chunk(p.c, p.entry[e + jj], q0, at + jj);
     }
 }
-
 
 uint32_t log2_slots(uint32_t k) {   // hash slots of mark_kernel: the power of two >= 2 k (>= 64)
     uint32_t l = 6;
@@ -717,33 +724,68 @@ hipError_t queue_batch(const Buffers& b, const BatchArgs& a, hipStream_t stream)
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// The stages the three pipelines share (simprint_score.h lists them); each queue_* below is the list of what differs.
+// ---------------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t MAX_WORDS = MAX_QUERY_SIMPRINTS / 64;   // LDS words per thread a score kernel is launched with at most
+
+// stable by asset: (c_asset, c_entry)[0] -> [1]
+hipError_t sort_by_asset(const Buffers& b, uint32_t entries, hipStream_t stream) {
+    size_t bytes = b.temp_bytes;
+    return rocprim::radix_sort_pairs(b.temp, bytes, b.c_asset[0], b.c_asset[1], b.c_entry[0], b.c_entry[1], entries, 0, 64, stream);
+}
+// stable by score, descending: (score, order)[0] -> [1].  Until it runs its outputs are free: the weights (score[1]) and query
+// indices (order[1]) of the approximate pipelines, the lookup index (order[1]) and frequency (score[1]) per entry of the exact one
+// live there meanwhile
+hipError_t sort_by_score(const Buffers& b, uint32_t entries, hipStream_t stream) {
+    size_t bytes = b.temp_bytes;
+    return rocprim::radix_sort_pairs_desc(b.temp, bytes, b.score[0], b.score[1], b.order[0], b.order[1], entries, 0, 64, stream);
+}
+// weights_kernel over the entries in `entry`'s order
+void queue_weights(const Buffers& b, const ScoreArgs& a, const uint32_t* entry, hipStream_t stream) {
+    const WeightParams wp{entry, b.rec, b.rows, a.freq_col, b.freq_q, a.sim_tab, a.idf_tab, b.score[1], b.ws, b.order[1], b.idf_q,
+                          b.n_assets, a.entries, a.nq, a.k, a.dup_limit};
+    const uint32_t wn = a.entries > a.nq ? a.entries : a.nq;
+    hipLaunchKernelGGL(weights_kernel, dim3((wn + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, wp);
+}
+// a score kernel, one thread per sorted entry with one LDS row of `words` u64 per thread: as many threads as keep a block <= 64 KB
+template <class P>
+void queue_scoring(void (*kernel)(P), const P& p, uint32_t entries, uint32_t words, hipStream_t stream) {
+    const uint32_t T = words <= 32 ? 256 : (words <= 64 ? 128 : 64);
+    hipLaunchKernelGGL(kernel, dim3((entries + T - 1) / T), dim3(T), (size_t)words * T * 8, stream, p);
+}
+// what the chunk records of the approximate pipelines are made of
+ChunkParams chunk_params(const Buffers& b, const ScoreArgs& a) {
+    ChunkParams c{b.rec, b.rows, a.freq_col, {}, a.out_chunks, a.out_chunk_words, a.k, a.W, a.dup_limit};
+    for (uint32_t w = 0; w < 4; ++w) c.col[w] = a.col[w];
+    return c;
+}
+// emit_kernel: a block per result that can exist
+void queue_emit(const EmitParams& ep, uint32_t entries, hipStream_t stream) {
+    hipLaunchKernelGGL(emit_kernel, dim3(ep.limit < entries ? ep.limit : entries), dim3(BLOCK), 0, stream, ep);
+}
+}  // namespace
+
+// (every queue_* refuses more LDS words than a score kernel can have before it launches anything.  The entry points bound a
+//  request at MAX_QUERY_SIMPRINTS query simprints, so no call reaches these refusals today.)
 hipError_t queue_exact(Buffers& b, const ExactArgs& a, hipStream_t stream) {
     hipError_t e;
+    const uint32_t words = (a.nd + 63) / 64;
+    if (words > MAX_WORDS) return hipErrorInvalidValue;
     // (the caller has run exact_prepare: hits / offsets / entries are in place and `entries` is known)
     ExactCompactParams cp{b.rec, a.d_of_g, b.nbest, b.offs, b.c_asset[0], b.c_entry[0], a.k};
     hipLaunchKernelGGL(exact_compact_kernel, dim3(a.ng), dim3(BLOCK), 0, stream, cp);
-    size_t bytes = b.temp_bytes;
-    e = rocprim::radix_sort_pairs(b.temp, bytes, b.c_asset[0], b.c_asset[1], b.c_entry[0], b.c_entry[1], a.entries, 0, 64, stream);
-    if (e != hipSuccess) return e;
-    // (the outputs of the second sort are free until it runs: the per-entry lookup index and frequency live there meanwhile)
+    if ((e = sort_by_asset(b, a.entries, stream)) != hipSuccess) return e;
     uint32_t* const e_d = b.order[1];
     uint32_t* const e_f = reinterpret_cast<uint32_t*>(b.score[1]);
     hipLaunchKernelGGL(exact_weights_kernel, dim3((a.entries + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, b.c_entry[1], a.d_of_g, b.freq_q, e_d, e_f, b.n_assets, a.entries, a.k);
-    const uint32_t words = (a.nd + 63) / 64;
-    const uint32_t T = words <= 32 ? 256 : (words <= 64 ? 128 : 64);
-    if (words > MAX_QUERY_SIMPRINTS / 64) return hipErrorInvalidValue;
-    ExactScoreParams sp{b.c_asset[1], e_d, e_f, b.score[0], b.order[0], b.matches, b.n_assets, a.entries, words, a.queried, a.threshold};
-    hipLaunchKernelGGL(exact_score_kernel, dim3((a.entries + T - 1) / T), dim3(T), (size_t)words * T * 8, stream, sp);
-    bytes = b.temp_bytes;
-    e = rocprim::radix_sort_pairs_desc(b.temp, bytes, b.score[0], b.score[1], b.order[0], b.order[1], a.entries, 0, 64, stream);
-    if (e != hipSuccess) return e;
-    EmitParams ep{};
-    ep.score = b.score[1]; ep.order = b.order[1]; ep.asset = b.c_asset[1]; ep.entry = b.c_entry[1]; ep.matches = b.matches;
-    ep.n_assets = b.n_assets; ep.rec = b.rec; ep.rows = nullptr; ep.freq_col = nullptr;
-    ep.out_results = a.out_results; ep.out_chunks = a.out_chunks; ep.out_chunk_words = nullptr; ep.out_info = a.out_info;
-    ep.limit = a.limit; ep.k = a.k; ep.W = 0; ep.dup_limit = 0;
-    ep.d_of_g = a.d_of_g; ep.freq_d = b.freq_q;
-    hipLaunchKernelGGL(emit_kernel, dim3(a.limit < a.entries ? a.limit : a.entries), dim3(BLOCK), 0, stream, ep);
+    const ExactScoreParams sp{b.c_asset[1], e_d, e_f, b.score[0], b.order[0], b.matches, b.n_assets, a.entries, words, a.queried, a.threshold};
+    queue_scoring(exact_score_kernel, sp, a.entries, words, stream);
+    if ((e = sort_by_score(b, a.entries, stream)) != hipSuccess) return e;
+    const ChunkParams collisions{b.rec, nullptr, nullptr, {}, a.out_chunks, nullptr, a.k, 0, 0};
+    queue_emit(EmitParams{b.score[1], b.order[1], b.c_asset[1], b.c_entry[1], b.matches, b.n_assets, collisions, a.out_results, a.out_info, a.limit, a.d_of_g, b.freq_q},
+               a.entries, stream);
     return hipGetLastError();
 }
 
@@ -757,29 +799,15 @@ hipError_t exact_prepare(const Buffers& b, const uint32_t* cnt, const uint32_t* 
 
 hipError_t queue_score(Buffers& b, const ScoreArgs& a, hipStream_t stream) {
     hipError_t e;
-    size_t bytes = b.temp_bytes;
-    e = rocprim::radix_sort_pairs(b.temp, bytes, b.c_asset[0], b.c_asset[1], b.c_entry[0], b.c_entry[1], a.entries, 0, 64, stream);
-    if (e != hipSuccess) return e;
-    // (the outputs of the second sort are free until it runs: weights and query indices live there meanwhile)
-    WeightParams wp{b.c_entry[1], b.rec, b.rows, a.freq_col, b.freq_q, a.sim_tab, a.idf_tab, b.score[1], b.ws, b.order[1], b.idf_q,
-                    b.n_assets, a.entries, a.nq, a.k, a.dup_limit};
-    const uint32_t wn = a.entries > a.nq ? a.entries : a.nq;
-    hipLaunchKernelGGL(weights_kernel, dim3((wn + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, wp);
     const uint32_t words = (a.nq + 63) / 64;
-    const uint32_t T = words <= 32 ? 256 : (words <= 64 ? 128 : 64);         // one LDS row of `words` u64 per thread, <= 64 KB per block
-    if (words > MAX_QUERY_SIMPRINTS / 64) return hipErrorInvalidValue;
-    ScoreParams sp{b.c_asset[1], b.score[1], b.ws, b.order[1], b.idf_q, b.score[0], b.order[0], b.matches, b.n_assets, a.entries, a.nq, words};
-    hipLaunchKernelGGL(score_kernel<ScoreParams>, dim3((a.entries + T - 1) / T), dim3(T), (size_t)words * T * 8, stream, sp);
-    bytes = b.temp_bytes;
-    e = rocprim::radix_sort_pairs_desc(b.temp, bytes, b.score[0], b.score[1], b.order[0], b.order[1], a.entries, 0, 64, stream);
-    if (e != hipSuccess) return e;
-    EmitParams ep{};
-    ep.score = b.score[1]; ep.order = b.order[1]; ep.asset = b.c_asset[1]; ep.entry = b.c_entry[1]; ep.matches = b.matches;
-    ep.n_assets = b.n_assets; ep.rec = b.rec; ep.rows = b.rows; ep.freq_col = a.freq_col;
-    for (uint32_t w = 0; w < 4; ++w) ep.col[w] = a.col[w];
-    ep.out_results = a.out_results; ep.out_chunks = a.out_chunks; ep.out_chunk_words = a.out_chunk_words; ep.out_info = a.out_info;
-    ep.limit = a.limit; ep.k = a.k; ep.W = a.W; ep.dup_limit = a.dup_limit;
-    hipLaunchKernelGGL(emit_kernel, dim3(a.limit < a.entries ? a.limit : a.entries), dim3(BLOCK), 0, stream, ep);
+    if (words > MAX_WORDS) return hipErrorInvalidValue;
+    if ((e = sort_by_asset(b, a.entries, stream)) != hipSuccess) return e;
+    queue_weights(b, a, b.c_entry[1], stream);
+    const ScoreParams sp{b.c_asset[1], b.score[1], b.ws, b.order[1], b.idf_q, b.score[0], b.order[0], b.matches, b.n_assets, a.entries, a.nq, words};
+    queue_scoring(score_kernel<ScoreParams>, sp, a.entries, words, stream);
+    if ((e = sort_by_score(b, a.entries, stream)) != hipSuccess) return e;
+    queue_emit(EmitParams{b.score[1], b.order[1], b.c_asset[1], b.c_entry[1], b.matches, b.n_assets, chunk_params(b, a), a.out_results, a.out_info, a.limit, nullptr, nullptr},
+               a.entries, stream);
     return hipGetLastError();
 }
 
@@ -797,47 +825,33 @@ hipError_t queue_score_many(Buffers& b, const ManyBuffers& mb, const ScoreManyAr
     const uint32_t nr = ma.n_req, grid = (a.entries + BLOCK - 1) / BLOCK;
     uint32_t req_bits = 1;                                   // request keys 0 .. n_req (n_req: the non-heads of the regrouping sort)
     while ((1u << req_bits) <= nr) ++req_bits;
-    if (ma.words == 0 || ma.words > MAX_QUERY_SIMPRINTS / 64) return hipErrorInvalidValue;
+    if (ma.words == 0 || ma.words > MAX_WORDS) return hipErrorInvalidValue;
+    // stable by request: (req, idx)[0] -> [1]
+    auto sort_by_request = [&] {
+        size_t bytes = b.temp_bytes;
+        return rocprim::radix_sort_pairs(b.temp, bytes, mb.req[0], mb.req[1], mb.idx[0], mb.idx[1], a.entries, 0, (int)req_bits, stream);
+    };
     // (request, asset) order: stable by asset, then stable by request
-    size_t bytes = b.temp_bytes;
-    e = rocprim::radix_sort_pairs(b.temp, bytes, b.c_asset[0], b.c_asset[1], b.c_entry[0], b.c_entry[1], a.entries, 0, 64, stream);
-    if (e != hipSuccess) return e;
+    if ((e = sort_by_asset(b, a.entries, stream)) != hipSuccess) return e;
     hipLaunchKernelGGL(req_key_kernel, dim3(grid), dim3(BLOCK), 0, stream, b.c_entry[1], mb.qbeg, nr, a.k, mb.req[0], mb.idx[0], a.entries);
-    bytes = b.temp_bytes;
-    e = rocprim::radix_sort_pairs(b.temp, bytes, mb.req[0], mb.req[1], mb.idx[0], mb.idx[1], a.entries, 0, (int)req_bits, stream);
-    if (e != hipSuccess) return e;
+    if ((e = sort_by_request()) != hipSuccess) return e;
     hipLaunchKernelGGL(gather_kernel, dim3(grid), dim3(BLOCK), 0, stream, mb.idx[1], b.c_asset[1], b.c_entry[1], b.c_asset[0], b.c_entry[0], a.entries);
-    // (weights and query indices in the outputs of the score sort, as queue_score)
-    WeightParams wp{b.c_entry[0], b.rec, b.rows, a.freq_col, b.freq_q, a.sim_tab, a.idf_tab, b.score[1], b.ws, b.order[1], b.idf_q,
-                    b.n_assets, a.entries, a.nq, a.k, a.dup_limit};
-    const uint32_t wn = a.entries > a.nq ? a.entries : a.nq;
-    hipLaunchKernelGGL(weights_kernel, dim3((wn + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, wp);
-    e = hipMemsetAsync(mb.n_assets, 0, (size_t)nr * sizeof(uint32_t), stream);
-    if (e != hipSuccess) return e;
-    const uint32_t T = ma.words <= 32 ? 256 : (ma.words <= 64 ? 128 : 64);     // one LDS row of `words` u64 per thread, <= 64 KB per block
-    ScoreManyParams sp{b.c_asset[0], mb.req[1], b.score[1], b.ws, b.order[1], b.idf_q, mb.qbeg, b.score[0], b.order[0], b.matches, mb.n_assets,
-                       a.entries, a.nq, ma.words};
-    hipLaunchKernelGGL(score_kernel<ScoreManyParams>, dim3((a.entries + T - 1) / T), dim3(T), (size_t)ma.words * T * 8, stream, sp);
+    queue_weights(b, a, b.c_entry[0], stream);
+    if ((e = hipMemsetAsync(mb.n_assets, 0, (size_t)nr * sizeof(uint32_t), stream)) != hipSuccess) return e;
+    const ScoreManyParams sp{b.c_asset[0], mb.req[1], b.score[1], b.ws, b.order[1], b.idf_q, mb.qbeg, b.score[0], b.order[0], b.matches, mb.n_assets,
+                             a.entries, a.nq, ma.words};
+    queue_scoring(score_kernel<ScoreManyParams>, sp, a.entries, ma.words, stream);
     // every request's assets in (-score, asset) order: stable by score (descending), then stable by request
-    bytes = b.temp_bytes;
-    e = rocprim::radix_sort_pairs_desc(b.temp, bytes, b.score[0], b.score[1], b.order[0], b.order[1], a.entries, 0, 64, stream);
-    if (e != hipSuccess) return e;
+    if ((e = sort_by_score(b, a.entries, stream)) != hipSuccess) return e;
     hipLaunchKernelGGL(head_key_kernel, dim3(grid), dim3(BLOCK), 0, stream, b.score[1], b.order[1], mb.req[1], nr, mb.req[0], mb.idx[0], a.entries);
-    bytes = b.temp_bytes;
-    e = rocprim::radix_sort_pairs(b.temp, bytes, mb.req[0], mb.req[1], mb.idx[0], mb.idx[1], a.entries, 0, (int)req_bits, stream);
-    if (e != hipSuccess) return e;
+    if ((e = sort_by_request()) != hipSuccess) return e;
     hipLaunchKernelGGL(req_scan_kernel, dim3(1), dim3(BLOCK), 0, stream, mb.n_assets, nr, a.limit, mb.a_start, mb.e_start, a.out_info);
     hipLaunchKernelGGL(result_chunks_kernel, dim3((ma.cap + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, mb.e_start, mb.a_start, mb.idx[1], b.matches, nr, mb.cnt, ma.cap);
-    bytes = b.temp_bytes;
+    size_t bytes = b.temp_bytes;
     e = rocprim::exclusive_scan(b.temp, bytes, mb.cnt, mb.c_pos, 0u, ma.cap, rocprim::plus<uint32_t>(), stream);
     if (e != hipSuccess) return e;
-    EmitManyParams ep{};
-    ep.score = b.score[0]; ep.idx = mb.idx[1]; ep.asset = b.c_asset[0]; ep.entry = b.c_entry[0]; ep.matches = b.matches;
-    ep.a_start = mb.a_start; ep.e_start = mb.e_start; ep.c_pos = mb.c_pos; ep.qbeg = mb.qbeg;
-    ep.rec = b.rec; ep.rows = b.rows; ep.freq_col = a.freq_col;
-    for (uint32_t w = 0; w < 4; ++w) ep.col[w] = a.col[w];
-    ep.out_results = a.out_results; ep.out_chunks = a.out_chunks; ep.out_chunk_words = a.out_chunk_words; ep.out_info = a.out_info;
-    ep.n_req = nr; ep.k = a.k; ep.W = a.W; ep.dup_limit = a.dup_limit;
+    const EmitManyParams ep{b.score[0], mb.idx[1], b.c_asset[0], b.c_entry[0], b.matches, mb.a_start, mb.e_start, mb.c_pos, mb.qbeg,
+                            chunk_params(b, a), a.out_results, a.out_info, nr};
     const uint32_t waves_wanted = ma.cap, blocks = std::min<uint32_t>((waves_wanted + 3) / 4, 2048);
     hipLaunchKernelGGL(emit_many_kernel, dim3(blocks ? blocks : 1), dim3(BLOCK), 0, stream, ep);
     return hipGetLastError();

@@ -106,6 +106,15 @@ def test_many_rounds_and_a_request_too_large_for_one(indexes, hip_engine):
     huge = [flip_bits(pool[i % len(pool)], i % 7) for i in range(MAX_SCORED_SIMPRINTS + 10)]
     got = idx.search_raw_many([reqs[0], huge, reqs[1]], **kw)
     assert _key(got) == _key([idx.search_raw(r, **kw) for r in (reqs[0], huge, reqs[1])])
+    # one call whose rounds mix the two pipelines, scratch and staging reused in between: 6 000 + 1 000 + 1 000 simprints are a round
+    # of three requests (the many form), the 8 000 behind them a round of one (the single form) -- the smallest such shape
+    mixed = [[flip_bits(pool[i % len(pool)], (i // len(pool)) % 5) for i in range(n)] for n in (6000, 1000, 1000, 8000)]
+    kw = dict(kw, limit=2)
+    idx.search_raw(mixed[3], **kw)                                          # (warm-up: the lazy frequency column)
+    before = hip_engine.stats()["searches"]
+    got = idx.search_raw_many(mixed, **kw)
+    assert hip_engine.stats()["searches"] - before == 2
+    assert _key(got) == _key([idx.search_raw(r, **kw) for r in mixed])
 
 
 def test_radius_path_and_its_error(hip_engine):
