@@ -477,7 +477,8 @@ int isccsearch_join_overlaps(isccsearch_handle* h, uint32_t table, int32_t max_h
  * Reference counterpart: IsccChunkMatch (schema.py:445-530) carries offset and size of a matched chunk for ONE query asset; the
  * reference has no index-wide form. */
 typedef struct isccsearch_segment {
-    uint32_t src, dst;              /* labels (ranks in asset_keys), src < dst */
+    uint32_t src, dst;              /* labels (ranks in asset_keys), src < dst; isccsearch_join_segments_between: src a rank in
+                                       asset_keys_a, dst a rank in asset_keys_b */
     uint32_t first_src, first_dst;  /* ordinals of the run's first chunk pair */
     uint32_t length;                /* chunk pairs in the run */
     uint32_t sum_hamming;           /* their distances, summed */
@@ -542,6 +543,60 @@ int isccsearch_join_overlaps_between(isccsearch_handle* h, uint32_t table_a, uin
                                      uint32_t* out_chunks_a,               /* [n_assets_a] */
                                      uint32_t* out_chunks_b,               /* [n_assets_b] */
                                      uint64_t* out_info                    /* [6] */);
+
+/* WHERE the assets of two tables share chunks: isccsearch_join_overlaps_between, and from the same join launch the chunk pairs of every
+ * pair (asset of table_a, asset of table_b) as aligned runs -- "chunks 40..95 of asset a of my catalogue are chunks 3..58 of asset b of
+ * that registry".  Tables, the two label spaces, asset_keys_a / asset_keys_b, max_hamming, max_doc_freq, dup_limit (stop chunks per
+ * table), flags (ISCCSEARCH_OVERLAPS_SKIP_SAME_ASSET) and capacity as for isccsearch_join_overlaps_between; the chunk pairs are exactly
+ * its chunk pairs.
+ *   ORDINAL of a row: its rank within its asset IN ITS OWN TABLE by ascending second key word (offset, size) -- the rule of
+ *                         isccsearch_join_segments, applied per table.  Every row of that table counts: the rows of unlisted assets
+ *                         do not matter (they are other assets), a stop chunk keeps its place and splits a run, and the rows the
+ *                         OTHER table holds of the same asset key count nothing.
+ *   SEGMENT: for a pair (asset a of table_a, asset b of table_b) let P be its chunk pairs as (o_a, o_b, hamming).  A segment is a maximal
+ *                         set {(o_a + t, o_b + t) : t = 0 .. length - 1} in P: a run on one diagonal o_b - o_a.  Every chunk pair lies
+ *                         in exactly one segment, so the lengths of the segments of (a, b) add up to the chunk_pairs of the overlap
+ *                         record (`reserved` 0, a, b), which equals that of (`reserved` 1, b, a).
+ *   out_pairs[2 * capacity], out_chunks_a[n_assets_a], out_chunks_b[n_assets_b], out_info[0 .. 5]: byte for byte what
+ *                         isccsearch_join_overlaps_between returns for the same arguments.
+ *   out_segments[capacity]  one isccsearch_segment per segment.  `src` is ALWAYS the label of the table_a asset (its rank in
+ *                         asset_keys_a) and `dst` the label of the table_b asset (its rank in asset_keys_b), without any side bit: there
+ *                         is no src < dst rule between the two label spaces and no second direction.  first_src, begin_src and end_src
+ *                         come from table_a's ordinals and keys, the _dst fields from table_b's.  Sorted ascending by (src, dst,
+ *                         first_dst - first_src as a signed value, first_src).  Every field is an integer defined by the set of chunk
+ *                         pairs and the two tables' keys alone: which kernel ran, which table was held and the order in which pairs
+ *                         were found never show.
+ *   out_info[7]           {chunk pairs found, records written, live rows a, stop chunks a, live rows b, stop chunks b, segments
+ *                         written}.
+ * Capacity protocol as for isccsearch_join_overlaps_between: more than `capacity` chunk pairs return -ENOSPC with out_info[0] exact and
+ * every other output unspecified, and a retry with exactly that capacity succeeds; pairs past the capacity are counted and not written.
+ * Device memory: 352 bytes per chunk pair of the capacity (the 192 of isccsearch_join_overlaps_between; 64 for the pairs keyed by
+ * diagonal, unsorted and sorted, 96 for the runs before and after their reduction), 28 bytes per row of BOTH tables (4 as
+ * isccsearch_join_overlaps_between; the sorted keys, 16, the sorted rows and the ordinals, 4 each, the two tables' side by side in one
+ * buffer each) and 12 per listed asset of both sides, besides rocPRIM's temporary storage (the largest need of any step, both tables'
+ * key sorts among them); kept by the handle as its other scratch buffers are.
+ * -EINVAL and -E2BIG as for isccsearch_join_overlaps_between, all checked on the host before anything is launched, the outputs left
+ * untouched; out_segments may be NULL only when capacity is 0, like out_pairs.  -E2BIG also for a segment of 2^31 rows or more in
+ * EITHER table: the difference of two ordinals travels as 32 bits.
+ * One lock covers the call; everything runs on the handle's one stream.  The two frequency columns are built first (each build drains
+ * the stream), then labelling (once per table), the ONE join launch isccsearch_join_between would make for the two tables, then the
+ * stage of isccsearch_join_segments over the two tables -- ordinals (one sort of the keys per table), the pairs keyed (the hit whose
+ * label lacks the side bit is table_a's, whichever table was held) and sorted, run heads, a reduction per run, the byte ranges
+ * gathered from either table's key column --, then sort and reduction of isccsearch_join_overlaps_between, and ONE synchronisation
+ * comes before the counters are read.  If either table has no row or capacity is 0 nothing of the stage is sized, allocated or queued;
+ * chunks and info are filled all the same.
+ * Reference counterpart: IsccChunkMatch (schema.py:445-530) carries offset and size of a matched chunk for ONE query asset; the
+ * reference has no index-wide form. */
+int isccsearch_join_segments_between(isccsearch_handle* h, uint32_t table_a, uint32_t table_b, int32_t max_hamming,
+                                     uint32_t max_doc_freq, uint32_t dup_limit,
+                                     uint32_t n_assets_a, const uint64_t* asset_keys_a,
+                                     uint32_t n_assets_b, const uint64_t* asset_keys_b,
+                                     uint32_t flags, uint64_t capacity,    /* chunk pairs */
+                                     isccsearch_overlap* out_pairs,        /* [2 * capacity] */
+                                     isccsearch_segment* out_segments,     /* [capacity] */
+                                     uint32_t* out_chunks_a,               /* [n_assets_a] */
+                                     uint32_t* out_chunks_b,               /* [n_assets_b] */
+                                     uint64_t* out_info                    /* [7] */);
 
 /* Multi-GPU building blocks (row-range shards, one process per GPU).
  * search_device: same search, results left in caller-provided DEVICE memory

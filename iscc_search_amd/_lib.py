@@ -31,7 +31,7 @@ EXPORTS = (
     "isccsearch_add_synthetic", "isccsearch_search", "isccsearch_search_within", "isccsearch_search_many", "isccsearch_doc_freq", "isccsearch_doc_freq_counted", "isccsearch_get_freq",
     "isccsearch_simprint_score", "isccsearch_simprint_score_many", "isccsearch_simprint_exact", "isccsearch_match_assets",
     "isccsearch_join_within", "isccsearch_join_between", "isccsearch_join_components", "isccsearch_join_overlaps",
-    "isccsearch_join_segments", "isccsearch_join_overlaps_between",
+    "isccsearch_join_segments", "isccsearch_join_overlaps_between", "isccsearch_join_segments_between",
     "isccsearch_search_device", "isccsearch_search_within_device", "isccsearch_merge_device",
     "isccsearch_search_device_async", "isccsearch_merge_device_after", "isccsearch_merge_many_after", "isccsearch_stream",
 )
@@ -51,7 +51,7 @@ ASSET_QUERIES_MAX = 1024      # asset queries per isccsearch_match_assets call (
 # isccsearch_overlap (isccsearch_join_overlaps): one ordered pair of assets that share chunks
 OVERLAP_DTYPE = np.dtype([("src", "<u4"), ("dst", "<u4"), ("matched", "<u4"), ("reserved", "<u4"), ("sum_hamming", "<u8"), ("chunk_pairs", "<u8")])
 assert OVERLAP_DTYPE.itemsize == 32
-# isccsearch_segment (isccsearch_join_segments): one aligned run of chunk pairs of two assets
+# isccsearch_segment (isccsearch_join_segments, isccsearch_join_segments_between): one aligned run of chunk pairs of two assets
 SEGMENT_DTYPE = np.dtype([("src", "<u4"), ("dst", "<u4"), ("first_src", "<u4"), ("first_dst", "<u4"), ("length", "<u4"), ("sum_hamming", "<u4"),
                           ("begin_src", "<u4"), ("begin_dst", "<u4"), ("end_src", "<u8"), ("end_dst", "<u8")])
 assert SEGMENT_DTYPE.itemsize == 48
@@ -205,6 +205,7 @@ def load_library():
         "isccsearch_join_overlaps": (i, [vp, u32, ctypes.c_int32, u32, u32, u32, u64p, u64, vp, u32p, u64p]),
         "isccsearch_join_segments": (i, [vp, u32, ctypes.c_int32, u32, u32, u32, u64p, u64, vp, vp, u32p, u64p]),
         "isccsearch_join_overlaps_between": (i, [vp, u32, u32, ctypes.c_int32, u32, u32, u32, u64p, u32, u64p, u32, u64, vp, u32p, u32p, u64p]),
+        "isccsearch_join_segments_between": (i, [vp, u32, u32, ctypes.c_int32, u32, u32, u32, u64p, u32, u64p, u32, u64, vp, vp, u32p, u32p, u64p]),
         "isccsearch_search_device": (i, [vp, u32, u32, u64p, u8p, u32, vp, vp]),
         "isccsearch_search_within_device": (i, [vp, u32, u32, u64p, u8p, u32, u32, vp, vp]),
         "isccsearch_merge_device": (i, [vp, u32, u32, u32, i, vp, vp, u64, u64, u64p, u32p, u16p, u32p]),

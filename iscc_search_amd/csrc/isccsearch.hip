@@ -392,6 +392,7 @@ struct isccsearch_handle {
     DevBuf<uint32_t> d_ov_chunks;
     // isccsearch_join_segments (segments.hip): the segment's keys sorted, the rows {sorted | ordinals}, the pair keys of one call
     // {keyed | sorted} and its runs {one-pair | reduced: the segments}
+    // (isccsearch_join_segments_between: the same buffers, each of the row buffers' parts holding table A's rows first and table B's behind)
     DevBuf<isksg::RowKey> d_sg_keys;
     DevBuf<uint32_t> d_sg_rows;
     DevBuf<isksg::PairKey> d_sg_pairs;

@@ -4,7 +4,8 @@
 // (unionfind.hip.h) instead of written; and isccsearch_join_overlaps: the self-join of a simprint table in the launches' OVERLAP form,
 // whose directed hits overlap.hip sorts and reduces to one record per ordered pair of assets; and isccsearch_join_segments: the same
 // call, whose chunk pairs segments.hip turns into aligned runs before they are reduced; and isccsearch_join_overlaps_between: the
-// cross join of two simprint tables in the same OVERLAP form, with a label space per table.
+// cross join of two simprint tables in the same OVERLAP form, with a label space per table; and isccsearch_join_segments_between:
+// that call with the same stage of segments.hip over the two tables.
 // Needs the store of isccsearch.hip (Segment, Table; get_table of store.hip.h) and its scratch buffers.
 namespace {
 // one launch of the join kernel (join.hip.h) in the form (form, cross); false: that form is not instantiated
@@ -370,8 +371,9 @@ extern "C" int isccsearch_join_components(isccsearch_handle* h, uint32_t table, 
 }
 
 // The overlap joins: isccsearch_join_overlaps and isccsearch_join_segments over ONE side (the self-join of a simprint table's one segment)
-// and isccsearch_join_overlaps_between over TWO (the one cross-join launch isccsearch_join_between would make for the two segments, the
-// side with more rows held, by join_add's rule), all in the launches' OVERLAP form.  Per side label_chunks_kernel (its own asset keys,
+// and isccsearch_join_overlaps_between and isccsearch_join_segments_between over TWO (the one cross-join launch isccsearch_join_between
+// would make for the two segments, the side with more rows held, by join_add's rule), all in the launches' OVERLAP form.  Per side
+// label_chunks_kernel (its own asset keys,
 // frequency column, chunks and counters; the host never sees the tables' keys; the second side's labels carry isk::LABEL_SIDE_B), then
 // the join launch, then the aggregation of overlap.hip, all on one stream; the counters and the chunks per asset come back behind ONE
 // synchronisation, then the records are copied.  The hit buffer is filled with ones first, so that the aggregation runs over
@@ -379,12 +381,15 @@ extern "C" int isccsearch_join_components(isccsearch_handle* h, uint32_t table, 
 // queued (each build drains the stream).  Everything the device code relies on -- asset keys ascending and few enough that no label
 // is UF_NONE (two sides: 2^31 - 1, the side bit), rows and hit positions below 2^32 -- is checked before anything is launched.
 //
-// `segments` (isccsearch_join_segments, one side only): the stage of segments.hip is queued between the join launch and the
-// aggregation, which overwrites the hit buffer that stage reads.  Without the flag nothing of that stage is sized, allocated or queued.
+// `segments` (isccsearch_join_segments, isccsearch_join_segments_between): the stage of segments.hip is queued between the join launch
+// and the aggregation, which overwrites the hit buffer that stage reads.  One side: it is the stage's source and destination.  Two
+// sides: table_a is the source and table_b the destination, whichever of them the launch held.  Without the flag nothing of that
+// stage is sized, allocated or queued.
 //
 // Two sides: the sort by (src, dst) puts the records of direction A -> B (src without the side bit) before those of B -> A; the bit moves
 // into `reserved` on the host, after the copy.
 namespace {
+static_assert(isksg::SIDE_B == isk::LABEL_SIDE_B, "segments.hip tells the sides of a cross join apart by the labels' side bit");
 struct OverlapSide {
     uint32_t table;               // the caller's arguments
     uint32_t n_assets;
@@ -440,7 +445,9 @@ int join_overlap_sides(isccsearch_handle* h, const char* name, OverlapSide* side
             return cross ? fail(-E2BIG, "a segment of %llu rows in table %u: row numbers travel as 32 bits", (unsigned long long)s.n, sides[x].table)
                          : fail(-E2BIG, "a segment of %llu rows: row numbers travel as 32 bits", (unsigned long long)s.n);
         if (segments && s.n >= (1ull << 31))
-            return fail(-E2BIG, "a segment of %llu rows: the difference of two chunk ordinals travels as 32 bits", (unsigned long long)s.n);
+            return cross ? fail(-E2BIG, "a segment of %llu rows in table %u: the difference of two chunk ordinals travels as 32 bits", (unsigned long long)s.n,
+                                sides[x].table)
+                         : fail(-E2BIG, "a segment of %llu rows: the difference of two chunk ordinals travels as 32 bits", (unsigned long long)s.n);
         all_assets += sides[x].n_assets;
         all_rows += s.n;
     }
@@ -453,10 +460,14 @@ int join_overlap_sides(isccsearch_handle* h, const char* name, OverlapSide* side
     // side by side (A first): asset keys, chunks per asset, row labels; for m = 2 * capacity hits {appended | sorted}, one-hit records,
     // records and rocPRIM's temporary storage: 192 bytes per chunk pair of the capacity.
     // With `segments`, in buffers of their own, for the capacity pair keys {keyed | sorted} and runs {one-pair | reduced}: 160 bytes more per
-    // chunk pair; for the rows sorted keys, sorted rows and ordinals: 24 bytes per row; rocPRIM's temporary storage is shared, the larger
-    // of the two stages' needs.  Nothing is queued for the hits when there is no launch or no room.
+    // chunk pair; for the rows sorted keys, sorted rows and ordinals: 24 bytes per row, both sides' in one buffer each (the stage's source
+    // side first) as the row labels are; rocPRIM's temporary storage is shared, the larger of the two stages' needs.  Nothing is queued
+    // for the hits when there is no launch or no room.
     const uint64_t m = 2 * capacity;
     const bool run = m && launch, locate = segments && run;
+    // the stage's sides: table_a and table_b, or the one table twice
+    const isksg::Side sg_src{reinterpret_cast<const isksg::RowKey*>(sides[0].seg->keys), sides[0].seg->n};
+    const isksg::Side sg_dst{reinterpret_cast<const isksg::RowKey*>(sides[n_sides - 1].seg->keys), sides[n_sides - 1].seg->n};
     size_t temp_bytes = 0;
     if ((rc = h->d_join_live_keys.ensure(all_assets))) return rc;
     if ((rc = h->d_ov_chunks.ensure(all_assets))) return rc;
@@ -466,10 +477,10 @@ int join_overlap_sides(isccsearch_handle* h, const char* name, OverlapSide* side
         if ((rc = iskov::aggregate_temp_bytes(m, &temp_bytes, &err))) return fail(rc, "%s", err.c_str());
         if (locate) {
             size_t locate_bytes = 0;
-            if ((rc = isksg::locate_temp_bytes(A.n, capacity, &locate_bytes, &err))) return fail(rc, "%s", err.c_str());
+            if ((rc = isksg::locate_temp_bytes(sg_src.n, sg_dst.n, capacity, &locate_bytes, &err))) return fail(rc, "%s", err.c_str());
             temp_bytes = std::max(temp_bytes, locate_bytes);
-            if ((rc = h->d_sg_keys.ensure(A.n))) return rc;
-            if ((rc = h->d_sg_rows.ensure(2 * A.n))) return rc;
+            if ((rc = h->d_sg_keys.ensure(all_rows))) return rc;
+            if ((rc = h->d_sg_rows.ensure(2 * all_rows))) return rc;
             if ((rc = h->d_sg_pairs.ensure(m))) return rc;
             if ((rc = h->d_sg_runs.ensure(m))) return rc;
         }
@@ -507,8 +518,8 @@ int join_overlap_sides(isccsearch_handle* h, const char* name, OverlapSide* side
     }
     if (locate) {                                     // reads the hits the aggregation below overwrites
         std::string err;
-        if ((rc = isksg::locate(reinterpret_cast<const isksg::RowKey*>(A.keys), A.n, h->d_ov_hits.p, capacity, h->d_sg_keys.p, h->d_sg_rows.p,
-                                h->d_sg_rows.p + A.n, h->d_sg_pairs.p, h->d_sg_runs.p, counters + OV_SEGMENTS, h->d_ov_temp.p, temp_bytes, h->stream, &err)))
+        if ((rc = isksg::locate(sg_src, sg_dst, h->d_ov_hits.p, capacity, h->d_sg_keys.p, h->d_sg_rows.p, h->d_sg_rows.p + all_rows, h->d_sg_pairs.p,
+                                h->d_sg_runs.p, counters + OV_SEGMENTS, h->d_ov_temp.p, temp_bytes, h->stream, &err)))
             return fail(rc, "%s", err.c_str());
     }
     if (run) {
@@ -578,4 +589,15 @@ extern "C" int isccsearch_join_overlaps_between(isccsearch_handle* h, uint32_t t
                                      isccsearch_overlap* out_pairs, uint32_t* out_chunks_a, uint32_t* out_chunks_b, uint64_t* out_info) {
     OverlapSide sides[2] = {{table_a, n_assets_a, asset_keys_a, out_chunks_a, nullptr, nullptr}, {table_b, n_assets_b, asset_keys_b, out_chunks_b, nullptr, nullptr}};
     return join_overlap_sides(h, "join_overlaps_between", sides, 2, max_hamming, max_doc_freq, dup_limit, flags, capacity, out_pairs, out_info, false, nullptr);
+}
+
+// isccsearch_join_overlaps_between and, from the same join launch, the chunk pairs of every pair (asset of table_a, asset of table_b) as
+// aligned runs (segments.hip, table_a its source side and table_b its destination side).
+extern "C" int isccsearch_join_segments_between(isccsearch_handle* h, uint32_t table_a, uint32_t table_b, int32_t max_hamming,
+                                     uint32_t max_doc_freq, uint32_t dup_limit, uint32_t n_assets_a, const uint64_t* asset_keys_a,
+                                     uint32_t n_assets_b, const uint64_t* asset_keys_b, uint32_t flags, uint64_t capacity,
+                                     isccsearch_overlap* out_pairs, isccsearch_segment* out_segments, uint32_t* out_chunks_a, uint32_t* out_chunks_b,
+                                     uint64_t* out_info) {
+    OverlapSide sides[2] = {{table_a, n_assets_a, asset_keys_a, out_chunks_a, nullptr, nullptr}, {table_b, n_assets_b, asset_keys_b, out_chunks_b, nullptr, nullptr}};
+    return join_overlap_sides(h, "join_segments_between", sides, 2, max_hamming, max_doc_freq, dup_limit, flags, capacity, out_pairs, out_info, true, out_segments);
 }

@@ -475,6 +475,27 @@ class HipTable(TableChecks):
             max_hamming, max_doc_freq, max_pairs, dup_limit, flags=(flags,))
         return records, chunks_a, chunks_b, info
 
+    def join_segments_between(self, other, max_hamming, asset_keys_a, asset_keys_b, max_doc_freq, max_pairs, dup_limit=1000, skip_same_asset=True):
+        # type: (HipTable, int, np.ndarray, np.ndarray, int, int, int, bool) -> tuple
+        """
+        ``join_overlaps_between`` and, from the same join launch, WHERE the assets share chunks (``isccsearch_join_segments_between``).
+        Returns ``(records, chunks_a, chunks_b, info, segments)``: the first three as ``join_overlaps_between`` returns them, ``info``
+        with ``"segments"`` besides its six counts, and one ``SEGMENT_DTYPE`` record per aligned run of chunk pairs -- ``length``
+        consecutive chunks of asset ``src`` OF THIS TABLE from ordinal ``first_src`` on (a chunk's ordinal is its rank within its asset
+        in its own table by offset, then size) that match the consecutive chunks of asset ``dst`` OF ``other`` from ``first_dst`` on,
+        with the byte range on either side.  ``src`` is always a label of this side and ``dst`` of the other: one record per run, no
+        second direction.  Sorted by (src, dst, first_dst - first_src, first_src).  Capacity, retry and ValueError as for
+        ``join_overlaps_between``.  Both tables must belong to one engine.
+        """
+        if getattr(other, "engine", None) is not self.engine:
+            raise ValueError("join_segments_between needs two tables of one engine: the other table belongs to another engine")
+        flags = _lib.OVERLAPS_SKIP_SAME_ASSET if skip_same_asset else 0
+        records, (chunks_a, chunks_b), info, segments = self._overlaps(
+            "isccsearch_join_segments_between", (self.id, other.id), (asset_keys_a, asset_keys_b),
+            ("live_rows_a", "stop_chunks_a", "live_rows_b", "stop_chunks_b", "segments"), max_hamming, max_doc_freq, max_pairs, dup_limit, flags=(flags,),
+            segments=True)
+        return records, chunks_a, chunks_b, info, segments
+
     def _overlaps(self, symbol, tables, asset_keys, names, max_hamming, max_doc_freq, max_pairs, dup_limit, flags=(), segments=False):
         # type: (str, tuple, tuple, tuple, int, int, int, int, tuple, bool) -> tuple
         """
@@ -490,10 +511,11 @@ class HipTable(TableChecks):
         sides = [arg for k in asset_keys for arg in (k.shape[0], _lib.ptr(k) if k.shape[0] else None)]
         runs = []
 
-        # the three C argument lists, in this one order:
+        # the four C argument lists, in this one order:
         #   isccsearch_join_overlaps:         h, table,            max_hamming, max_doc_freq, dup_limit, n, keys,                          capacity, out_pairs,               out_chunks,               out_info
         #   isccsearch_join_segments:         h, table,            max_hamming, max_doc_freq, dup_limit, n, keys,                          capacity, out_pairs, out_segments, out_chunks,               out_info
         #   isccsearch_join_overlaps_between: h, table_a, table_b, max_hamming, max_doc_freq, dup_limit, n_a, keys_a, n_b, keys_b, flags, capacity, out_pairs,               out_chunks_a, out_chunks_b, out_info
+        #   isccsearch_join_segments_between: h, table_a, table_b, max_hamming, max_doc_freq, dup_limit, n_a, keys_a, n_b, keys_b, flags, capacity, out_pairs, out_segments, out_chunks_a, out_chunks_b, out_info
         def once(capacity):
             records = np.empty(2 * capacity, dtype=_lib.OVERLAP_DTYPE)
             runs[:] = [np.empty(capacity, dtype=_lib.SEGMENT_DTYPE)] if segments else []

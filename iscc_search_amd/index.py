@@ -382,8 +382,8 @@ class HipIndex:
                                                          bool(segments), int(min_segment), int(max_gap))]
 
     def find_shared_matches(self, other, min_chunks=1, min_coverage=None, simprint_types=None, threshold=None, max_doc_freq=100,
-                            max_pairs=1_000_000, include_same_id=False):
-        # type: (HipIndex, int, Optional[float], Optional[List[str]], Optional[float], int, int, bool) -> List[SharedMatch]
+                            max_pairs=1_000_000, include_same_id=False, segments=False, min_segment=1, max_gap=0):
+        # type: (HipIndex, int, Optional[float], Optional[List[str]], Optional[float], int, int, bool, bool, int, int) -> List[SharedMatch]
         """
         Every pair (asset a of this index, asset b of ``other``) that share content, as ``find_shared_content`` defines it within one
         index: which assets of this catalogue contain a clip, a quoted passage or a sampled loop of an asset of that registry.  Found
@@ -395,6 +395,11 @@ class HipIndex:
         asset's chunks.  An asset both indexes hold (one ISCC-ID body) pairs with itself only with ``include_same_id``.  Score,
         ``min_chunks``, ``min_coverage``, ``simprint_types``, ``max_pairs`` and the order (score descending, then (key_a, key_b)) as
         for ``find_shared_content``; each side's ISCC-IDs carry its own realm.  Both indexes must live on one engine.
+
+        ``segments=True`` also says WHERE, from the same cross join (``HipSimprintIndex.overlaps_between_located``): every
+        ``SharedChunks`` carries ``segments``, a list of ``SharedSegment`` -- "chunks 40..95 of a are chunks 3..58 of b", with the byte
+        range on either side -- as ``find_shared_content`` defines them, a being this index's asset and a chunk's rank counted among
+        its asset's chunks in its own index.  ``min_segment`` and ``max_gap`` as there.  Neither changes which pairs are listed.
         """
         if other is self:
             raise ValueError("find_shared_matches compares two indexes: find_shared_content lists the pairs within one")
@@ -409,7 +414,8 @@ class HipIndex:
         (tables_a, bodies_a, realm_a), (tables_b, bodies_b, realm_b) = sides
         return [SharedMatch(codec.iscc_id_from_int(a, realm_a), codec.iscc_id_from_int(b, realm_b), score, types)
                 for a, b, score, types in shared_matches("find_shared_matches", tables_a, tables_b, bodies_a, bodies_b, threshold, max_doc_freq,
-                                                         max_pairs, min_chunks, min_coverage, not include_same_id)]
+                                                         max_pairs, min_chunks, min_coverage, not include_same_id, bool(segments), int(min_segment),
+                                                         int(max_gap))]
 
     # -- bulk search -------------------------------------------------------------------------------
     def _prepare_many(self, queries):

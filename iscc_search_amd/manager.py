@@ -304,9 +304,9 @@ class HipIndexManager:
         return idx_a.find_matches(idx_b, min_score=min_score, unit_types=unit_types, max_pairs=max_pairs)
 
     def find_shared_matches(self, index_a, index_b, min_chunks=1, min_coverage=None, simprint_types=None, threshold=None, max_doc_freq=100,
-                            max_pairs=1_000_000, include_same_id=False):
-        # type: (str, str, int, Optional[float], Optional[List[str]], Optional[float], int, int, bool) -> List[SharedMatch]
-        """Asset pairs (a of ``index_a``, b of ``index_b``) that share chunks (``HipIndex.find_shared_matches``).  Not available on a sharded index."""
+                            max_pairs=1_000_000, include_same_id=False, segments=False, min_segment=1, max_gap=0):
+        # type: (str, str, int, Optional[float], Optional[List[str]], Optional[float], int, int, bool, bool, int, int) -> List[SharedMatch]
+        """Asset pairs (a of ``index_a``, b of ``index_b``) that share chunks, and where (``HipIndex.find_shared_matches``).  Not available on a sharded index."""
         self._refuse_sharded("find_shared_matches")
         if index_a == index_b:
             raise ValueError(f"find_shared_matches compares two indexes, got '{index_a}' twice: find_shared_content lists the pairs within one index")
@@ -314,7 +314,8 @@ class HipIndexManager:
             idx_a = self._index(index_a)
             idx_b = self._index(index_b)
         return idx_a.find_shared_matches(idx_b, min_chunks=min_chunks, min_coverage=min_coverage, simprint_types=simprint_types, threshold=threshold,
-                                         max_doc_freq=max_doc_freq, max_pairs=max_pairs, include_same_id=include_same_id)
+                                         max_doc_freq=max_doc_freq, max_pairs=max_pairs, include_same_id=include_same_id,
+                                         segments=segments, min_segment=min_segment, max_gap=max_gap)
 
     def close(self):
         # type: () -> None

@@ -472,6 +472,17 @@ class HipIndex128:
         """``HipTable.join_overlaps_between`` with the table of ``other``: the assets are the first 8 bytes of the 16-byte keys."""
         return self._table.join_overlaps_between(other._table, max_hamming, asset_keys_a, asset_keys_b, max_doc_freq, max_pairs, dup_limit, skip_same_asset)
 
+    @property
+    def joins_segments_between(self):
+        # type: () -> bool
+        """Whether the table's cross join also locates the shared chunks (``isccsearch_join_segments_between``; a sharded table does not)."""
+        return hasattr(self._table, "join_segments_between")
+
+    def join_segments_between(self, other, max_hamming, asset_keys_a, asset_keys_b, max_doc_freq, max_pairs, dup_limit=1000, skip_same_asset=True):
+        # type: (HipIndex128, int, np.ndarray, np.ndarray, int, int, int, bool) -> tuple
+        """``HipTable.join_segments_between`` with the table of ``other``: the assets are the first 8 bytes of the 16-byte keys."""
+        return self._table.join_segments_between(other._table, max_hamming, asset_keys_a, asset_keys_b, max_doc_freq, max_pairs, dup_limit, skip_same_asset)
+
     def get_freq(self, keys, dup_limit=1000):
         # type: (list[bytes], int) -> np.ndarray
         """Document frequency of the vector stored under each key (0 for absent keys), from the frequency column."""

@@ -5,7 +5,8 @@ unit type -> ``HipNphdIndex``, and asset key -> {unit_type: body} as indexed.  A
 on the device where the pairs were (``find_duplicate_groups``, ``HipTable.join_components``).  And asset pairs that share CHUNKS, by a
 self-join of every simprint table aggregated on the device (``find_shared_content``, ``HipSimprintIndex.overlaps``; with
 ``segments=True`` the same join also locates the shared chunks, ``HipSimprintIndex.overlaps_located``) -- or, between two
-indexes, by a cross join of the two tables of every simprint type (``find_shared_matches``, ``HipSimprintIndex.overlaps_between``).
+indexes, by a cross join of the two tables of every simprint type (``find_shared_matches``, ``HipSimprintIndex.overlaps_between``;
+with ``segments=True`` ``HipSimprintIndex.overlaps_between_located``).
 """
 
 from dataclasses import dataclass
@@ -266,25 +267,34 @@ def _rank_shared(by_pair, min_chunks, min_coverage):
     return out
 
 
-def shared_matches(caller, tables_a, tables_b, bodies_a, bodies_b, threshold, max_doc_freq, max_pairs, min_chunks, min_coverage, skip_same_asset):
-    # type: (str, dict, dict, dict, dict, float, int, int, int, Optional[float], bool) -> list
+def shared_matches(caller, tables_a, tables_b, bodies_a, bodies_b, threshold, max_doc_freq, max_pairs, min_chunks, min_coverage, skip_same_asset,
+                   segments=False, min_segment=1, max_gap=0):
+    # type: (str, dict, dict, dict, dict, float, int, int, int, Optional[float], bool, bool, int, int) -> list
     """
     [(key_a, key_b, score, {sp_type: SharedChunks})] of the pairs (asset of side a, asset of side b) that share chunks: ONE cross join
     per simprint type BOTH sides have a table for (sorted type order) over the assets ``bodies_x[sp_type]`` of either side.  Per type a
     pair has two device records, a -> b (``reserved`` 0) and b -> a (1); coverage, the type's score, ``score``, what is kept and the
     order are those of ``shared_content``.  Stop chunks are decided per table; ``skip_same_asset`` keeps an asset held by both sides
     from pairing with itself.  More than ``max_pairs`` chunk pairs in one pair of tables raise ValueError; tables without the join (a
-    sharded engine's) raise NotImplementedError naming ``caller``.
+    sharded engine's) raise NotImplementedError naming ``caller``.  ``segments``: the same join also says WHERE
+    (``HipSimprintIndex.overlaps_between_located``), and every ``SharedChunks`` carries its ``SharedSegment`` list, merged and cut as in
+    ``shared_content`` (``_located``); a is the asset of side a, which is ``src`` of every device segment.
     """
     by_pair = {}  # type: Dict[tuple, Dict[str, SharedChunks]]
+    joins = "joins_segments_between" if segments else "joins_overlaps_between"
     for sp_type in sorted(set(tables_a) & set(tables_b)):
         table_a, table_b = tables_a[sp_type], tables_b[sp_type]
-        if not (getattr(table_a, "joins_overlaps_between", False) and getattr(table_b, "joins_overlaps_between", False)):
+        if not (getattr(table_a, joins, False) and getattr(table_b, joins, False)):
             raise NotImplementedError(f"{caller} needs a single-GPU engine: pairs across shards need their rows exchanged")
         listed_a, listed_b = sorted(bodies_a.get(sp_type, ())), sorted(bodies_b.get(sp_type, ()))
         if not listed_a or not listed_b:
             continue
-        records, chunks_a, chunks_b, _ = table_a.overlaps_between(table_b, listed_a, listed_b, threshold, max_doc_freq, max_pairs, skip_same_asset)
+        located = None
+        if segments:
+            records, chunks_a, chunks_b, _, runs = table_a.overlaps_between_located(table_b, listed_a, listed_b, threshold, max_doc_freq, max_pairs, skip_same_asset)
+            located = _located(runs, table_a.ndim, min_segment, max_gap)
+        else:
+            records, chunks_a, chunks_b, _ = table_a.overlaps_between(table_b, listed_a, listed_b, threshold, max_doc_freq, max_pairs, skip_same_asset)
         keys_a = [int.from_bytes(b, "big") for b in listed_a]
         keys_b = [int.from_bytes(b, "big") for b in listed_b]
         ndim = table_a.ndim
@@ -297,5 +307,6 @@ def shared_matches(caller, tables_a, tables_b, bodies_a, bodies_b, threshold, ma
                 continue
             matched_b, sum_b, _ = rows[(1, b, a)]
             by_pair.setdefault((keys_a[a], keys_b[b]), {})[sp_type] = SharedChunks(
-                matched_a, chunks_a[a], matched_b, chunks_b[b], pairs, (matched_a - sum_a / ndim) / chunks_a[a], (matched_b - sum_b / ndim) / chunks_b[b])
+                matched_a, chunks_a[a], matched_b, chunks_b[b], pairs, (matched_a - sum_a / ndim) / chunks_a[a], (matched_b - sum_b / ndim) / chunks_b[b],
+                None if located is None else located.get((a, b), []))
     return _rank_shared(by_pair, min_chunks, min_coverage)

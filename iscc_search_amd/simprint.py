@@ -541,8 +541,14 @@ class HipSimprintIndex:
         ``(records, chunks_a, chunks_b, info)`` as it returns them, an asset's label being its position in its side's list.  More
         than ``max_pairs`` matching chunk pairs raise ValueError, and so do tables of different ``ndim``.
         """
+        return self._index.join_overlaps_between(other._index, *self._between_args("overlaps_between", other, bodies_a, bodies_b, threshold, max_doc_freq),
+                                                 max_pairs, max(DOC_FREQ_DUP_LIMIT, int(max_doc_freq)), skip_same_asset)
+
+    def _between_args(self, caller, other, bodies_a, bodies_b, threshold, max_doc_freq):
+        # type: (str, HipSimprintIndex, list[bytes], list[bytes], float, int) -> tuple
+        """``(max_hamming, asset_keys_a, asset_keys_b, max_doc_freq)`` of a cross join with ``other``, or the ValueError naming ``caller``."""
         if other.ndim != self.ndim:
-            raise ValueError(f"overlaps_between needs simprints of one length: this table holds {self.ndim} bits, the other {other.ndim}")
+            raise ValueError(f"{caller} needs simprints of one length: this table holds {self.ndim} bits, the other {other.ndim}")
         sides = []
         for name, bodies in (("bodies_a", bodies_a), ("bodies_b", bodies_b)):
             keys = np.frombuffer(b"".join(bytes(b) for b in bodies), dtype=">u8").astype(np.uint64)
@@ -551,9 +557,25 @@ class HipSimprintIndex:
             if len(keys) > 1 and not bool(np.all(keys[1:] > keys[:-1])):
                 raise ValueError(f"{name} must be ascending without repeats: an asset's label is its position")
             sides.append(keys)
-        dup_limit = max(DOC_FREQ_DUP_LIMIT, int(max_doc_freq))
-        return self._index.join_overlaps_between(other._index, self._radius_for(threshold), sides[0], sides[1], int(max_doc_freq), max_pairs,
-                                                 dup_limit, skip_same_asset)
+        return self._radius_for(threshold), sides[0], sides[1], int(max_doc_freq)
+
+    @property
+    def joins_segments_between(self):
+        # type: () -> bool
+        """Whether ``overlaps_between_located`` is available (a single-GPU table; a sharded one has no cross join)."""
+        return self._index.joins_segments_between
+
+    def overlaps_between_located(self, other, bodies_a, bodies_b, threshold, max_doc_freq, max_pairs, skip_same_asset=True):
+        # type: (HipSimprintIndex, list[bytes], list[bytes], float, int, int, bool) -> tuple
+        """
+        ``overlaps_between`` and WHERE the assets share chunks, from the same cross join (``HipTable.join_segments_between``):
+        ``(records, chunks_a, chunks_b, info, segments)`` as it returns them.  A segment says that ``length`` consecutive chunks of
+        asset ``src`` of this table (by offset, from chunk ``first_src`` on: bytes ``begin_src`` .. ``end_src``) match consecutive
+        chunks of asset ``dst`` of ``other`` (from ``first_dst``, bytes ``begin_dst`` .. ``end_dst``); ``src`` is a position in
+        ``bodies_a`` and ``dst`` one in ``bodies_b``, always.
+        """
+        return self._index.join_segments_between(other._index, *self._between_args("overlaps_between_located", other, bodies_a, bodies_b, threshold, max_doc_freq),
+                                                 max_pairs, max(DOC_FREQ_DUP_LIMIT, int(max_doc_freq)), skip_same_asset)
 
     def doc_freq(self, simprints, dup_limit=1000):
         # type: (list[bytes], int) -> list[int]

@@ -42,12 +42,19 @@ isccsearch_join_overlaps on the tables of --overlaps, whose planted runs of 4-8 
 legs A B A (join_overlaps, join_segments, join_overlaps), each one warm-up call and the median of --reps; the tool asserts that both
 calls agree on chunk pairs and records and that the segments' lengths add up to the chunk pairs.
 
+--segments-between: isccsearch_join_segments_between (join_overlaps_between plus the two-table run detection of csrc/segments.hip, from
+one join launch) against isccsearch_join_overlaps_between on the two tables of --overlaps-between, whose planted runs of 4-8 chunks are
+the segments to find.  On either kernel three legs A B A (join_overlaps_between, join_segments_between, join_overlaps_between), each one
+warm-up call and the median of --reps; the tool asserts that both calls agree on chunk pairs and records and that the segments' lengths
+add up to the chunk pairs.  Its output is what profiles/join_segments_between_rate.txt records.
+
 usage: python tools/bench_duplicates.py [--mfma both] [--reps 5] [--sizes 65536,262144,1048576,4194304] [--nphd-sizes 262144,1048576] [--tau 6]
        python tools/bench_duplicates.py --between [--rows-a N --rows-b M] [the same options]
        python tools/bench_duplicates.py --components [--sizes 1048576 --nphd-sizes 1048576] [--dense-rows 1048576 --cluster 1000]
        python tools/bench_duplicates.py --overlaps [--sizes 65536,262144,1048576] [--shared 3] [--search-rows 65536]
        python tools/bench_duplicates.py --overlaps-between [--sizes 65536,262144,1048576] [--shared 3]
        python tools/bench_duplicates.py --segments [--sizes 65536,1048576] [--shared 3]
+       python tools/bench_duplicates.py --segments-between [--sizes 65536,262144,1048576] [--shared 3]
 """
 
 import argparse
@@ -349,6 +356,34 @@ def run_overlaps_between(engine, nbytes, n, tau, reps, shared_pct):
         tb.drop()
 
 
+def run_segments_between(engine, nbytes, n, tau, reps, shared_pct):
+    """join_overlaps_between, join_segments_between, join_overlaps_between (A B A) on two simprint tables of n rows each, on either kernel."""
+    rng = np.random.default_rng(2424 + n + nbytes)
+    (keys_a, words_a, assets_a), (keys_b, words_b, assets_b) = simprint_two_tables(rng, n, nbytes, 16, shared_pct)
+    ta, tb = engine.open_table(_lib.METRIC_HAMMING, 2, nbytes), engine.open_table(_lib.METRIC_HAMMING, 2, nbytes)
+    try:
+        for t, keys, words in ((ta, keys_a, words_a), (tb, keys_b, words_b)):
+            for lo in range(0, n, 1 << 18):
+                t.add(keys[lo:lo + (1 << 18)], words[lo:lo + (1 << 18)], None, trusted_unique=True)
+        overlaps = lambda: ta.join_overlaps_between(tb, tau, assets_a, assets_b, 0, 1 << 22)      # noqa: E731
+        segments = lambda: ta.join_segments_between(tb, tau, assets_a, assets_b, 0, 1 << 22)      # noqa: E731
+        out = {"join": "segments_between", "table": f"simprints {8 * nbytes}-bit", "rows_a": n, "rows_b": n, "assets_a": len(assets_a),
+               "assets_b": len(assets_b), "tau": tau, "kernels": []}
+        for mfma in (False, True):
+            a1, info_a = leg(engine, mfma, overlaps, reps, found=lambda o: o[3])
+            b, info_b = leg(engine, mfma, segments, reps, found=lambda o: (o[3], int(o[4]["length"].sum()), int(o[4]["length"].max()) if len(o[4]) else 0))
+            a2, _ = leg(engine, mfma, overlaps, reps, found=lambda o: o[3])
+            info_b, in_runs, longest = info_b
+            assert {k: info_b[k] for k in info_a} == info_a and in_runs == info_b["chunk_pairs"], "join_segments_between disagrees with join_overlaps_between"
+            out["kernels"].append(dict(kernel="mfma" if mfma else "valu", overlaps_between_seconds=[round(a1, 5), round(a2, 5)],
+                                       segments_between_seconds=round(b, 5), segments_minus_overlaps_seconds=round(b - (a1 + a2) / 2, 5),
+                                       chunk_pairs=info_b["chunk_pairs"], records=info_b["records"], segments=info_b["segments"], longest_run=longest))
+        return out
+    finally:
+        ta.drop()
+        tb.drop()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--mfma", choices=("0", "1", "both"), default="both", help="the kernel: XOR + popcount, matrix cores, or A B A over both")
@@ -365,7 +400,9 @@ def main():
     ap.add_argument("--overlaps", action="store_true", help="join_overlaps against join_within on simprint tables (A B A over both kernels)")
     ap.add_argument("--overlaps-between", action="store_true", help="join_overlaps_between against join_between on two simprint tables (A B A over both kernels)")
     ap.add_argument("--segments", action="store_true", help="join_segments against join_overlaps on simprint tables (A B A on either kernel)")
-    ap.add_argument("--shared", type=int, default=3, help="--overlaps, --overlaps-between, --segments: per cent of the assets that contain a run of another asset's chunks")
+    ap.add_argument("--segments-between", action="store_true",
+                    help="join_segments_between against join_overlaps_between on two simprint tables (A B A on either kernel)")
+    ap.add_argument("--shared", type=int, default=3, help="--overlaps, --overlaps-between, --segments, --segments-between: per cent of the assets that contain a run of another asset's chunks")
     ap.add_argument("--search-rows", type=int, default=65536, help="--overlaps: tables of up to this many rows also time one search_raw per asset")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args()
@@ -373,6 +410,11 @@ def main():
     nphd_sizes = [int(s) for s in a.nphd_sizes.split(",") if s]
     engine = HipEngine(a.device)
     try:
+        if a.segments_between:
+            for nbytes in (8, 16):
+                for n in sizes:
+                    print(json.dumps(run_segments_between(engine, nbytes, n, a.tau * nbytes // 8, a.reps, a.shared)), flush=True)
+            return
         if a.overlaps_between:
             for nbytes in (8, 16):
                 for n in sizes:
