@@ -434,9 +434,7 @@ class HipTable(TableChecks):
         pairs, retried once with exactly the total when more were found.  More than ``max_pairs`` chunk pairs raise ValueError:
         the cap is never applied silently.
         """
-        records, (chunks,), info, _ = self._overlaps("isccsearch_join_overlaps", (self.id,), (asset_keys,), ("live_rows", "stop_chunks"),
-                                                     max_hamming, max_doc_freq, max_pairs, dup_limit)
-        return records, chunks, info
+        return self._overlaps(None, False, (asset_keys,), max_hamming, max_doc_freq, max_pairs, dup_limit)[:3]
 
     def join_segments(self, max_hamming, asset_keys, max_doc_freq, max_pairs, dup_limit=1000):
         # type: (int, np.ndarray, int, int, int) -> tuple
@@ -448,9 +446,7 @@ class HipTable(TableChecks):
         consecutive chunks of ``dst`` from ``first_dst`` on, ``src < dst``, with the byte range on either side -- sorted by (src, dst,
         first_dst - first_src, first_src).  Capacity, retry and ValueError as for ``join_overlaps``.
         """
-        records, (chunks,), info, segments = self._overlaps("isccsearch_join_segments", (self.id,), (asset_keys,), ("live_rows", "stop_chunks", "segments"),
-                                                            max_hamming, max_doc_freq, max_pairs, dup_limit, segments=True)
-        return records, chunks, info, segments
+        return self._overlaps(None, True, (asset_keys,), max_hamming, max_doc_freq, max_pairs, dup_limit)
 
     def join_overlaps_between(self, other, max_hamming, asset_keys_a, asset_keys_b, max_doc_freq, max_pairs, dup_limit=1000, skip_same_asset=True):
         # type: (HipTable, int, np.ndarray, np.ndarray, int, int, int, bool) -> tuple
@@ -467,13 +463,7 @@ class HipTable(TableChecks):
         chunk pairs, retried once with exactly the total when more were found.  More than ``max_pairs`` chunk pairs raise
         ValueError: the cap is never applied silently.  Both tables must belong to one engine.
         """
-        if getattr(other, "engine", None) is not self.engine:
-            raise ValueError("join_overlaps_between needs two tables of one engine: the other table belongs to another engine")
-        flags = _lib.OVERLAPS_SKIP_SAME_ASSET if skip_same_asset else 0
-        records, (chunks_a, chunks_b), info, _ = self._overlaps(
-            "isccsearch_join_overlaps_between", (self.id, other.id), (asset_keys_a, asset_keys_b), ("live_rows_a", "stop_chunks_a", "live_rows_b", "stop_chunks_b"),
-            max_hamming, max_doc_freq, max_pairs, dup_limit, flags=(flags,))
-        return records, chunks_a, chunks_b, info
+        return self._overlaps(other, False, (asset_keys_a, asset_keys_b), max_hamming, max_doc_freq, max_pairs, dup_limit, skip_same_asset)[:4]
 
     def join_segments_between(self, other, max_hamming, asset_keys_a, asset_keys_b, max_doc_freq, max_pairs, dup_limit=1000, skip_same_asset=True):
         # type: (HipTable, int, np.ndarray, np.ndarray, int, int, int, bool) -> tuple
@@ -487,21 +477,23 @@ class HipTable(TableChecks):
         second direction.  Sorted by (src, dst, first_dst - first_src, first_src).  Capacity, retry and ValueError as for
         ``join_overlaps_between``.  Both tables must belong to one engine.
         """
-        if getattr(other, "engine", None) is not self.engine:
-            raise ValueError("join_segments_between needs two tables of one engine: the other table belongs to another engine")
-        flags = _lib.OVERLAPS_SKIP_SAME_ASSET if skip_same_asset else 0
-        records, (chunks_a, chunks_b), info, segments = self._overlaps(
-            "isccsearch_join_segments_between", (self.id, other.id), (asset_keys_a, asset_keys_b),
-            ("live_rows_a", "stop_chunks_a", "live_rows_b", "stop_chunks_b", "segments"), max_hamming, max_doc_freq, max_pairs, dup_limit, flags=(flags,),
-            segments=True)
-        return records, chunks_a, chunks_b, info, segments
+        return self._overlaps(other, True, (asset_keys_a, asset_keys_b), max_hamming, max_doc_freq, max_pairs, dup_limit, skip_same_asset)
 
-    def _overlaps(self, symbol, tables, asset_keys, names, max_hamming, max_doc_freq, max_pairs, dup_limit, flags=(), segments=False):
-        # type: (str, tuple, tuple, tuple, int, int, int, int, tuple, bool) -> tuple
+    def _overlaps(self, other, segments, asset_keys, max_hamming, max_doc_freq, max_pairs, dup_limit, skip_same_asset=True):
+        # type: (HipTable | None, bool, tuple, int, int, int, int, bool) -> tuple
         """
-        One overlap join of the library over ``tables`` (one, or two with ``flags``), each with its ``asset_keys``: ``(records, chunks per
-        table, info, segments or None)``; ``names`` are those of ``info`` behind ``"chunk_pairs"`` and ``"records"``.
+        One overlap join of the library, the form selected by ``(other, segments)`` as ``join_overlap_sides`` selects it: this table
+        with itself (``other`` None, one array in ``asset_keys``) or with ``other`` (two arrays, ``skip_same_asset`` as the flag word);
+        ``(records, chunks per table ..., info, segments or None)``.
         """
+        name = ("join_segments" if segments else "join_overlaps") + ("" if other is None else "_between")
+        if other is not None and getattr(other, "engine", None) is not self.engine:
+            raise ValueError(f"{name} needs two tables of one engine: the other table belongs to another engine")
+        symbol = "isccsearch_" + name
+        tables = (self.id,) if other is None else (self.id, other.id)
+        flags = () if other is None else (_lib.OVERLAPS_SKIP_SAME_ASSET if skip_same_asset else 0,)
+        names = tuple(n + side for side in (("",) if other is None else ("_a", "_b")) for n in ("live_rows", "stop_chunks"))
+        names += ("segments",) if segments else ()
         asset_keys = [np.ascontiguousarray(k, dtype=np.uint64) for k in asset_keys]
         if any(k.ndim != 1 for k in asset_keys):
             raise ValueError(("asset_keys" if len(asset_keys) == 1 else "asset_keys_a and asset_keys_b") + " must be shaped [n_assets]")
@@ -525,8 +517,8 @@ class HipTable(TableChecks):
             return rc, int(info[0]) if rc in (0, -errno.ENOSPC) else 0, records[: int(info[1])]
 
         records = self._retried(symbol, max_pairs, "chunk pairs", once)
-        info = dict(zip(("chunk_pairs", "records") + tuple(names), (int(v) for v in info)))
-        return records, chunks, info, runs[0][: info["segments"]] if segments else None
+        info = dict(zip(("chunk_pairs", "records") + names, (int(v) for v in info)))
+        return (records, *chunks, info, runs[0][: info["segments"]] if segments else None)
 
     def _join(self, symbol, tables, max_hamming_by_prefix, max_pairs):
         # type: (str, tuple, object, int) -> tuple

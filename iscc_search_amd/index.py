@@ -22,8 +22,7 @@ import numpy as np
 from iscc_search_amd import chunk_match, codec, snapshot, unit_match
 from iscc_search_amd._lib import MAX_K
 from iscc_search_amd.nphd import HipNphdIndex
-from iscc_search_amd.pairs import (DuplicateGroup, DuplicatePair, IndexMatch, SharedContent, SharedMatch, group_side, join_sides, shared_content,
-                                   shared_matches)
+from iscc_search_amd.pairs import DuplicateGroup, DuplicatePair, IndexMatch, SharedContent, SharedMatch, group_side, join_sides, shared_sides
 from iscc_search_amd.schema import IsccAddResult, IsccEntry, IsccGlobalMatch, IsccQuery, IsccSearchResult, Status
 from iscc_search_amd.simprint import HipSimprintIndex, pack_chunk_pointer, unpack_chunk_pointer
 from iscc_search_amd.unit_match import INSTANCE_FIRST_K, UnitMatches, _checked_limit, _is_instance, _unit_map, _unit_max_hamming  # noqa: F401
@@ -296,6 +295,14 @@ class HipIndex:
             tables = {t: idx for t, idx in self._unit_tables.items() if unit_types is None or t in unit_types}
             return (tables, dict(self._asset_units)), self._realm_id or 0
 
+    def _shared_side(self, simprint_types=None):
+        # type: (Optional[List[str]]) -> tuple
+        """This index as one side of a shared-content join (``pairs.shared_sides``): its simprint tables restricted to
+        ``simprint_types`` with the asset bodies each holds, and its realm."""
+        with self._lock:
+            tables = {t: idx for t, idx in self._sp_tables.items() if simprint_types is None or t in simprint_types}
+            return (tables, {t: list(self._sp_assets.get(t, {})) for t in tables}), self._realm_id or 0
+
     def find_duplicates(self, min_score=None, unit_types=None, max_pairs=1_000_000):
         # type: (Optional[float], Optional[List[str]], int) -> List[DuplicatePair]
         """
@@ -355,7 +362,7 @@ class HipIndex:
         """
         Every pair of assets {a, b} that share content: in some simprint type a chunk of a and a chunk of b whose similarity passes
         ``threshold`` (default: ``match_threshold_simprints``) -- a clip inside a longer video, a quoted passage, a sampled loop.
-        Found by ONE self-join per simprint table, aggregated on the device (``HipSimprintIndex.overlaps``), instead of a
+        Found by ONE self-join per simprint table, aggregated on the device (``HipSimprintIndex.shared``), instead of a
         ``search_assets`` by simprints per asset and its top-``limit`` cut.  Chunks of one asset never pair with each other, and a chunk
         whose simprint more than ``max_doc_freq`` assets hold (black frames, licence text; 0: no cut) pairs with nothing, though it
         still counts among its asset's chunks.  Per type ``SharedChunks`` says how many chunks of each asset found a match and
@@ -365,7 +372,7 @@ class HipIndex:
         type (and ``score >= min_coverage``, if given); ordered by score descending, then (key_a, key_b).  ``simprint_types``
         restricts the tables joined.  More than ``max_pairs`` matching chunk pairs in one table raise ValueError.
 
-        ``segments=True`` also says WHERE, from the same join (``HipSimprintIndex.overlaps_located``): every ``SharedChunks`` carries
+        ``segments=True`` also says WHERE, from the same join (``HipSimprintIndex.shared``): every ``SharedChunks`` carries
         ``segments``, a list of ``SharedSegment`` -- "chunks 40..95 of a are chunks 3..58 of b", with the byte range on either side,
         the number of matched chunk pairs and their mean similarity.  A segment is a run of consecutive chunks of a (ranked by offset
         within the asset, stop chunks keeping their place) that match consecutive chunks of b.  Runs of one pair in one alignment that
@@ -373,13 +380,10 @@ class HipIndex:
         ``min_segment`` matched chunks are dropped.  Ordered by (offset_a, offset_b).  Neither changes which pairs are listed.
         """
         threshold = self._opts.match_threshold_simprints if threshold is None else float(threshold)
-        with self._lock:
-            tables = {t: idx for t, idx in self._sp_tables.items() if simprint_types is None or t in simprint_types}
-            bodies = {t: list(self._sp_assets.get(t, {})) for t in tables}
-            realm = self._realm_id or 0
+        side, realm = self._shared_side(simprint_types)
         return [SharedContent(codec.iscc_id_from_int(a, realm), codec.iscc_id_from_int(b, realm), score, types)
-                for a, b, score, types in shared_content("find_shared_content", tables, bodies, threshold, max_doc_freq, max_pairs, min_chunks, min_coverage,
-                                                         bool(segments), int(min_segment), int(max_gap))]
+                for a, b, score, types in shared_sides("find_shared_content", side, side, threshold, max_doc_freq, max_pairs, min_chunks, min_coverage,
+                                                       True, bool(segments), int(min_segment), int(max_gap))]
 
     def find_shared_matches(self, other, min_chunks=1, min_coverage=None, simprint_types=None, threshold=None, max_doc_freq=100,
                             max_pairs=1_000_000, include_same_id=False, segments=False, min_segment=1, max_gap=0):
@@ -388,7 +392,7 @@ class HipIndex:
         Every pair (asset a of this index, asset b of ``other``) that share content, as ``find_shared_content`` defines it within one
         index: which assets of this catalogue contain a clip, a quoted passage or a sampled loop of an asset of that registry.  Found
         by ONE cross join per simprint type both indexes have a table for, aggregated on the device
-        (``HipSimprintIndex.overlaps_between``), instead of a simprint search per asset or a self-join of a copy of both.
+        (``HipSimprintIndex.shared``), instead of a simprint search per asset or a self-join of a copy of both.
         ``threshold`` defaults to the OTHER index's ``match_threshold_simprints`` (as ``find_matches`` scores with the other index's
         options): ``coverage_a`` is what ``other``'s ``search_raw`` by a's simprints scores b with under constant IDF.  A chunk whose
         simprint more than ``max_doc_freq`` assets of ITS OWN index hold pairs with nothing (0: no cut) but still counts among its
@@ -396,7 +400,7 @@ class HipIndex:
         ``min_chunks``, ``min_coverage``, ``simprint_types``, ``max_pairs`` and the order (score descending, then (key_a, key_b)) as
         for ``find_shared_content``; each side's ISCC-IDs carry its own realm.  Both indexes must live on one engine.
 
-        ``segments=True`` also says WHERE, from the same cross join (``HipSimprintIndex.overlaps_between_located``): every
+        ``segments=True`` also says WHERE, from the same cross join (``HipSimprintIndex.shared``): every
         ``SharedChunks`` carries ``segments``, a list of ``SharedSegment`` -- "chunks 40..95 of a are chunks 3..58 of b", with the byte
         range on either side -- as ``find_shared_content`` defines them, a being this index's asset and a chunk's rank counted among
         its asset's chunks in its own index.  ``min_segment`` and ``max_gap`` as there.  Neither changes which pairs are listed.
@@ -406,16 +410,11 @@ class HipIndex:
         if other._engine is not self._engine:
             raise ValueError("find_shared_matches needs both indexes on one engine: their tables must share the device's memory")
         threshold = other._opts.match_threshold_simprints if threshold is None else float(threshold)
-        sides = []
-        for idx in (self, other):
-            with idx._lock:
-                tables = {t: table for t, table in idx._sp_tables.items() if simprint_types is None or t in simprint_types}
-                sides.append((tables, {t: list(idx._sp_assets.get(t, {})) for t in tables}, idx._realm_id or 0))
-        (tables_a, bodies_a, realm_a), (tables_b, bodies_b, realm_b) = sides
+        side_a, realm_a = self._shared_side(simprint_types)
+        side_b, realm_b = other._shared_side(simprint_types)
         return [SharedMatch(codec.iscc_id_from_int(a, realm_a), codec.iscc_id_from_int(b, realm_b), score, types)
-                for a, b, score, types in shared_matches("find_shared_matches", tables_a, tables_b, bodies_a, bodies_b, threshold, max_doc_freq,
-                                                         max_pairs, min_chunks, min_coverage, not include_same_id, bool(segments), int(min_segment),
-                                                         int(max_gap))]
+                for a, b, score, types in shared_sides("find_shared_matches", side_a, side_b, threshold, max_doc_freq, max_pairs, min_chunks, min_coverage,
+                                                       not include_same_id, bool(segments), int(min_segment), int(max_gap))]
 
     # -- bulk search -------------------------------------------------------------------------------
     def _prepare_many(self, queries):

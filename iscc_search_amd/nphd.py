@@ -439,49 +439,33 @@ class HipIndex128:
         q_words, _ = pack_bytes(self._vectors(vectors), self._table.max_words)
         return self._table.simprint_exact(q_words, given, queried, dup_limit, threshold, limit, detailed)
 
-    @property
-    def joins_overlaps(self):
-        # type: () -> bool
-        """Whether the table joins itself into asset overlaps (``isccsearch_join_overlaps``; a sharded table does not)."""
-        return hasattr(self._table, "join_overlaps")
+    @staticmethod
+    def _shared_method(other, segments):
+        # type: (HipIndex128 | None, bool) -> str
+        """The ``HipTable`` method of one shared-content join form, selected by ``(other, segments)`` as ``join_overlap_sides`` is."""
+        return ("join_segments" if segments else "join_overlaps") + ("" if other is None else "_between")
 
-    def join_overlaps(self, max_hamming, asset_keys, max_doc_freq, max_pairs, dup_limit=1000):
-        # type: (int, np.ndarray, int, int, int) -> tuple
-        """``HipTable.join_overlaps``: the assets are the first 8 bytes of the 16-byte keys, as big-endian integers."""
-        return self._table.join_overlaps(max_hamming, asset_keys, max_doc_freq, max_pairs, dup_limit)
+    def joins_shared(self, other=None, segments=False):
+        # type: (HipIndex128 | None, bool) -> bool
+        """Whether the table -- and that of ``other``, for a cross join -- has this form of the join (a sharded table has none)."""
+        method = self._shared_method(other, segments)
+        return hasattr(self._table, method) and (other is None or hasattr(other._table, method))
 
-    @property
-    def joins_segments(self):
-        # type: () -> bool
-        """Whether the table's self-join also locates the shared chunks (``isccsearch_join_segments``; a sharded table does not)."""
-        return hasattr(self._table, "join_segments")
-
-    def join_segments(self, max_hamming, asset_keys, max_doc_freq, max_pairs, dup_limit=1000):
-        # type: (int, np.ndarray, int, int, int) -> tuple
-        """``HipTable.join_segments``: the assets are the first 8 bytes of the 16-byte keys, as big-endian integers."""
-        return self._table.join_segments(max_hamming, asset_keys, max_doc_freq, max_pairs, dup_limit)
-
-    @property
-    def joins_overlaps_between(self):
-        # type: () -> bool
-        """Whether the table joins another into asset overlaps (``isccsearch_join_overlaps_between``; a sharded table does not)."""
-        return hasattr(self._table, "join_overlaps_between")
-
-    def join_overlaps_between(self, other, max_hamming, asset_keys_a, asset_keys_b, max_doc_freq, max_pairs, dup_limit=1000, skip_same_asset=True):
-        # type: (HipIndex128, int, np.ndarray, np.ndarray, int, int, int, bool) -> tuple
-        """``HipTable.join_overlaps_between`` with the table of ``other``: the assets are the first 8 bytes of the 16-byte keys."""
-        return self._table.join_overlaps_between(other._table, max_hamming, asset_keys_a, asset_keys_b, max_doc_freq, max_pairs, dup_limit, skip_same_asset)
-
-    @property
-    def joins_segments_between(self):
-        # type: () -> bool
-        """Whether the table's cross join also locates the shared chunks (``isccsearch_join_segments_between``; a sharded table does not)."""
-        return hasattr(self._table, "join_segments_between")
-
-    def join_segments_between(self, other, max_hamming, asset_keys_a, asset_keys_b, max_doc_freq, max_pairs, dup_limit=1000, skip_same_asset=True):
-        # type: (HipIndex128, int, np.ndarray, np.ndarray, int, int, int, bool) -> tuple
-        """``HipTable.join_segments_between`` with the table of ``other``: the assets are the first 8 bytes of the 16-byte keys."""
-        return self._table.join_segments_between(other._table, max_hamming, asset_keys_a, asset_keys_b, max_doc_freq, max_pairs, dup_limit, skip_same_asset)
+    def join_shared(self, asset_keys_a, max_hamming, max_doc_freq, max_pairs, dup_limit=1000, other=None, asset_keys_b=None, skip_same_asset=True,
+                    segments=False):
+        # type: (np.ndarray, int, int, int, int, HipIndex128 | None, np.ndarray | None, bool, bool) -> tuple
+        """
+        The ``HipTable`` join of the table with itself (``join_overlaps`` / ``join_segments``) or with that of ``other``
+        (``join_overlaps_between`` / ``join_segments_between``), in one shape: ``(records, chunks_a, chunks_b, info, segments or None)``,
+        ``chunks_b`` being ``chunks_a`` for a self-join.  The assets are the first 8 bytes of the 16-byte keys, as big-endian integers.
+        """
+        join = getattr(self._table, self._shared_method(other, segments))
+        if other is None:
+            records, chunks_a, *rest = join(max_hamming, asset_keys_a, max_doc_freq, max_pairs, dup_limit)
+            chunks_b = chunks_a
+        else:
+            records, chunks_a, chunks_b, *rest = join(other._table, max_hamming, asset_keys_a, asset_keys_b, max_doc_freq, max_pairs, dup_limit, skip_same_asset)
+        return records, chunks_a, chunks_b, rest[0], rest[1] if segments else None
 
     def get_freq(self, keys, dup_limit=1000):
         # type: (list[bytes], int) -> np.ndarray

@@ -3,10 +3,9 @@ Asset pairs by device joins: the host side of ``HipIndex.find_duplicates`` (``Hi
 (``HipTable.join_between``), scored as ``search_assets`` scores (``unit_match``).  A *side* of a join is ``(tables, asset_units)``:
 unit type -> ``HipNphdIndex``, and asset key -> {unit_type: body} as indexed.  And asset GROUPS by the same joins with a union-find
 on the device where the pairs were (``find_duplicate_groups``, ``HipTable.join_components``).  And asset pairs that share CHUNKS, by a
-self-join of every simprint table aggregated on the device (``find_shared_content``, ``HipSimprintIndex.overlaps``; with
-``segments=True`` the same join also locates the shared chunks, ``HipSimprintIndex.overlaps_located``) -- or, between two
-indexes, by a cross join of the two tables of every simprint type (``find_shared_matches``, ``HipSimprintIndex.overlaps_between``;
-with ``segments=True`` ``HipSimprintIndex.overlaps_between_located``).
+join of the simprint tables aggregated on the device (``shared_sides``, ``HipSimprintIndex.shared``): a self-join per table for
+``find_shared_content``, a cross join of the two tables of every type for ``find_shared_matches``; with ``segments=True`` the same
+join also locates the shared chunks.
 """
 
 from dataclasses import dataclass
@@ -209,45 +208,53 @@ def _located(records, ndim, min_segment, max_gap):
     return out
 
 
-def shared_content(caller, tables, bodies, threshold, max_doc_freq, max_pairs, min_chunks, min_coverage, segments=False, min_segment=1, max_gap=0):
-    # type: (str, dict, dict, float, int, int, int, Optional[float], bool, int, int) -> list
+def shared_sides(caller, side_a, side_b, threshold, max_doc_freq, max_pairs, min_chunks, min_coverage, skip_same_asset, segments, min_segment,
+                 max_gap):
+    # type: (str, tuple, tuple, float, int, int, int, Optional[float], bool, bool, int, int) -> list
     """
-    [(key_a, key_b, score, {sp_type: SharedChunks})] of the asset pairs that share chunks, key_a < key_b: ONE self-join per simprint
-    type in ``tables`` (sp_type -> ``HipSimprintIndex``, sorted type order) over the assets ``bodies[sp_type]`` (8-byte bodies).  Per
-    type a pair has two device records, (a, b) and (b, a); ``coverage_x = (matched_x - sum_hamming_x / ndim) / chunks_x`` and the
-    type's score is the larger coverage (the smaller work lies inside the larger).  ``score`` is the mean of the types' scores over
-    the types in which the pair has a record -- the rule ``chunk_match.rank_simprint_matches`` uses across types.  Kept: pairs with
-    ``max(matched_a, matched_b) >= min_chunks`` in some type and ``score >= min_coverage`` (if given); ordered by score descending,
-    then (key_a, key_b).  More than ``max_pairs`` chunk pairs in one table raise ValueError; tables without the join (a sharded
-    engine's) raise NotImplementedError naming ``caller``.  ``segments``: the same join also says WHERE
-    (``HipSimprintIndex.overlaps_located``), and every ``SharedChunks`` carries its ``SharedSegment`` list, merged over gaps of at most
-    ``max_gap`` chunks and cut at ``min_segment`` chunks (``_located``); a is ``src``, since labels are ranks of ascending keys.
+    [(key_a, key_b, score, {sp_type: SharedChunks})] of the pairs (asset of side a, asset of side b) that share chunks: ONE join per
+    simprint type both sides have a table for, in sorted type order (``HipSimprintIndex.shared``) -- a self-join where ``side_b`` is
+    ``side_a``, and then key_a < key_b -- over the assets ``bodies[sp_type]`` (8-byte bodies) of either side.  Per type a pair has two
+    device records, a -> b and b -> a (``reserved`` 1 in a cross join, where labels are per side); ``coverage_x = (matched_x -
+    sum_hamming_x / ndim) / chunks_x`` and the type's score is the larger coverage (the smaller work lies inside the larger).
+    ``score`` is the mean of the types' scores over the types in which the pair has a record -- the rule
+    ``chunk_match.rank_simprint_matches`` uses across types.  Kept: pairs with ``max(matched_a, matched_b) >= min_chunks`` in some type
+    and ``score >= min_coverage`` (if given); ordered by score descending, then (key_a, key_b).  Stop chunks are decided per table;
+    ``skip_same_asset`` keeps an asset held by both sides from pairing with itself.  More than ``max_pairs`` chunk pairs in one join
+    raise ValueError; tables without the join (a sharded engine's) raise NotImplementedError naming ``caller``.  ``segments``: the same
+    join also says WHERE, and every ``SharedChunks`` carries its ``SharedSegment`` list, merged over gaps of at most ``max_gap`` chunks
+    and cut at ``min_segment`` chunks (``_located``); a is ``src`` of every device segment -- the asset of side a, or in a self-join
+    the smaller label, labels being ranks of ascending keys.
     """
+    (tables_a, bodies_a), (tables_b, bodies_b) = side_a, side_b
+    within = side_b is side_a
     by_pair = {}  # type: Dict[tuple, Dict[str, SharedChunks]]
-    for sp_type in sorted(tables):
-        table = tables[sp_type]
-        if not (getattr(table, "joins_segments", False) if segments else table.joins_overlaps):
+    for sp_type in sorted(set(tables_a) & set(tables_b)):
+        table_a, table_b = tables_a[sp_type], tables_b[sp_type]
+        if not table_a.joins_shared(None if within else table_b, segments):
             raise NotImplementedError(f"{caller} needs a single-GPU engine: pairs across shards need their rows exchanged")
-        listed = sorted(bodies.get(sp_type, ()))
-        if not listed:
+        listed_a = sorted(bodies_a.get(sp_type, ()))
+        listed_b = listed_a if within else sorted(bodies_b.get(sp_type, ()))
+        if not listed_a or not listed_b:
             continue
-        located = None
-        if segments:
-            records, chunks, _, runs = table.overlaps_located(listed, threshold, max_doc_freq, max_pairs)
-            located = _located(runs, table.ndim, min_segment, max_gap)
-        else:
-            records, chunks, _ = table.overlaps(listed, threshold, max_doc_freq, max_pairs)
-        keys = [int.from_bytes(b, "big") for b in listed]
-        ndim = table.ndim
-        chunks = chunks.tolist()
-        rows = {(s, d): (m, h, p) for s, d, m, h, p in zip(records["src"].tolist(), records["dst"].tolist(), records["matched"].tolist(),
-                                                          records["sum_hamming"].tolist(), records["chunk_pairs"].tolist())}
-        for (a, b), (matched_a, sum_a, pairs) in rows.items():
-            if a > b:
+        records, chunks_a, chunks_b, _, runs = table_a.shared(listed_a, threshold, max_doc_freq, max_pairs, None if within else table_b,
+                                                              None if within else listed_b, skip_same_asset, segments)
+        located = _located(runs, table_a.ndim, min_segment, max_gap) if segments else None
+        keys_a = [int.from_bytes(b, "big") for b in listed_a]
+        keys_b = keys_a if within else [int.from_bytes(b, "big") for b in listed_b]
+        ndim = table_a.ndim
+        chunks_a = chunks_a.tolist()
+        chunks_b = chunks_a if within else chunks_b.tolist()
+        rows = {(r, s, d): (m, h, p) for r, s, d, m, h, p in zip(records["reserved"].tolist(), records["src"].tolist(), records["dst"].tolist(),
+                                                                records["matched"].tolist(), records["sum_hamming"].tolist(),
+                                                                records["chunk_pairs"].tolist())}
+        back = 0 if within else 1       # a self-join's records are all of direction 0: the pair's first is the one with a < b
+        for (direction, a, b), (matched_a, sum_a, pairs) in rows.items():
+            if direction or (within and a > b):
                 continue
-            matched_b, sum_b, _ = rows[(b, a)]
-            by_pair.setdefault((keys[a], keys[b]), {})[sp_type] = SharedChunks(
-                matched_a, chunks[a], matched_b, chunks[b], pairs, (matched_a - sum_a / ndim) / chunks[a], (matched_b - sum_b / ndim) / chunks[b],
+            matched_b, sum_b, _ = rows[(back, b, a)]
+            by_pair.setdefault((keys_a[a], keys_b[b]), {})[sp_type] = SharedChunks(
+                matched_a, chunks_a[a], matched_b, chunks_b[b], pairs, (matched_a - sum_a / ndim) / chunks_a[a], (matched_b - sum_b / ndim) / chunks_b[b],
                 None if located is None else located.get((a, b), []))
     return _rank_shared(by_pair, min_chunks, min_coverage)
 
@@ -265,48 +272,3 @@ def _rank_shared(by_pair, min_chunks, min_coverage):
         out.append((a, b, score, types))
     out.sort(key=lambda r: (-r[2], r[0], r[1]))
     return out
-
-
-def shared_matches(caller, tables_a, tables_b, bodies_a, bodies_b, threshold, max_doc_freq, max_pairs, min_chunks, min_coverage, skip_same_asset,
-                   segments=False, min_segment=1, max_gap=0):
-    # type: (str, dict, dict, dict, dict, float, int, int, int, Optional[float], bool, bool, int, int) -> list
-    """
-    [(key_a, key_b, score, {sp_type: SharedChunks})] of the pairs (asset of side a, asset of side b) that share chunks: ONE cross join
-    per simprint type BOTH sides have a table for (sorted type order) over the assets ``bodies_x[sp_type]`` of either side.  Per type a
-    pair has two device records, a -> b (``reserved`` 0) and b -> a (1); coverage, the type's score, ``score``, what is kept and the
-    order are those of ``shared_content``.  Stop chunks are decided per table; ``skip_same_asset`` keeps an asset held by both sides
-    from pairing with itself.  More than ``max_pairs`` chunk pairs in one pair of tables raise ValueError; tables without the join (a
-    sharded engine's) raise NotImplementedError naming ``caller``.  ``segments``: the same join also says WHERE
-    (``HipSimprintIndex.overlaps_between_located``), and every ``SharedChunks`` carries its ``SharedSegment`` list, merged and cut as in
-    ``shared_content`` (``_located``); a is the asset of side a, which is ``src`` of every device segment.
-    """
-    by_pair = {}  # type: Dict[tuple, Dict[str, SharedChunks]]
-    joins = "joins_segments_between" if segments else "joins_overlaps_between"
-    for sp_type in sorted(set(tables_a) & set(tables_b)):
-        table_a, table_b = tables_a[sp_type], tables_b[sp_type]
-        if not (getattr(table_a, joins, False) and getattr(table_b, joins, False)):
-            raise NotImplementedError(f"{caller} needs a single-GPU engine: pairs across shards need their rows exchanged")
-        listed_a, listed_b = sorted(bodies_a.get(sp_type, ())), sorted(bodies_b.get(sp_type, ()))
-        if not listed_a or not listed_b:
-            continue
-        located = None
-        if segments:
-            records, chunks_a, chunks_b, _, runs = table_a.overlaps_between_located(table_b, listed_a, listed_b, threshold, max_doc_freq, max_pairs, skip_same_asset)
-            located = _located(runs, table_a.ndim, min_segment, max_gap)
-        else:
-            records, chunks_a, chunks_b, _ = table_a.overlaps_between(table_b, listed_a, listed_b, threshold, max_doc_freq, max_pairs, skip_same_asset)
-        keys_a = [int.from_bytes(b, "big") for b in listed_a]
-        keys_b = [int.from_bytes(b, "big") for b in listed_b]
-        ndim = table_a.ndim
-        chunks_a, chunks_b = chunks_a.tolist(), chunks_b.tolist()
-        rows = {(r, s, d): (m, h, p) for r, s, d, m, h, p in zip(records["reserved"].tolist(), records["src"].tolist(), records["dst"].tolist(),
-                                                                records["matched"].tolist(), records["sum_hamming"].tolist(),
-                                                                records["chunk_pairs"].tolist())}
-        for (direction, a, b), (matched_a, sum_a, pairs) in rows.items():
-            if direction:
-                continue
-            matched_b, sum_b, _ = rows[(1, b, a)]
-            by_pair.setdefault((keys_a[a], keys_b[b]), {})[sp_type] = SharedChunks(
-                matched_a, chunks_a[a], matched_b, chunks_b[b], pairs, (matched_a - sum_a / ndim) / chunks_a[a], (matched_b - sum_b / ndim) / chunks_b[b],
-                None if located is None else located.get((a, b), []))
-    return _rank_shared(by_pair, min_chunks, min_coverage)

@@ -478,104 +478,46 @@ class HipSimprintIndex:
         results.sort(key=lambda r: (-r.score, r.iscc_id_body))
         return results[:limit]
 
-    @property
-    def joins_overlaps(self):
-        # type: () -> bool
-        """Whether ``overlaps`` is available (a single-GPU table; a sharded one has no self-join)."""
-        return self._index.joins_overlaps
+    def joins_shared(self, other=None, segments=False):
+        # type: (HipSimprintIndex | None, bool) -> bool
+        """Whether ``shared`` is available in this form (single-GPU tables; a sharded one has neither a self-join nor a cross join)."""
+        return self._index.joins_shared(None if other is None else other._index, segments)
 
-    def overlaps(self, asset_bodies, threshold, max_doc_freq, max_pairs):
-        # type: (list[bytes], float, int, int) -> tuple
+    def shared(self, bodies_a, threshold, max_doc_freq, max_pairs, other=None, bodies_b=None, skip_same_asset=True, segments=False):
+        # type: (list[bytes], float, int, int, HipSimprintIndex | None, list[bytes] | None, bool, bool) -> tuple
         """
-        The pairs of assets among ``asset_bodies`` (8-byte ISCC-ID bodies, ascending, no repeats) that share chunks: two chunks of
-        two assets match when their similarity ``1 - d / ndim`` passes ``threshold`` (the radius of ``search_raw``, ``_radius_for``);
-        a chunk whose simprint more than ``max_doc_freq`` assets hold (0: no cut; counted as ``doc_freq`` counts, up to
-        ``DOC_FREQ_DUP_LIMIT`` rows) matches nothing.  One self-join of the table on the device (``HipTable.join_overlaps``) --
-        ``(records, chunks, info)`` as it returns them, an asset's label being its position in ``asset_bodies``.  More than
-        ``max_pairs`` matching chunk pairs raise ValueError.
+        The pairs of assets that share chunks, by ONE join on the device, its form selected by ``(other, segments)`` as
+        ``join_overlap_sides`` is: among ``bodies_a`` within this table (``HipTable.join_overlaps``), or an asset of this table among
+        ``bodies_a`` with one of ``other`` among ``bodies_b`` (``HipTable.join_overlaps_between``); both lists are 8-byte ISCC-ID
+        bodies, ascending, no repeats.  Two chunks of two assets match when their similarity ``1 - d / ndim`` passes ``threshold``
+        (the radius of ``search_raw``, ``_radius_for``); a chunk whose simprint more than ``max_doc_freq`` assets OF ITS OWN TABLE
+        hold (0: no cut; counted as ``doc_freq`` counts, up to ``DOC_FREQ_DUP_LIMIT`` rows) matches nothing.  ``skip_same_asset``:
+        the chunks of one ISCC-ID body held by both tables do not pair.  Returns ``(records, chunks_a, chunks_b, info, segments)``
+        as the table's join returns them, an asset's label being its position in its side's list; ``chunks_b`` is ``chunks_a`` for a
+        self-join.  ``segments``: the same join also says WHERE (``HipTable.join_segments`` / ``join_segments_between``; else None) --
+        ``length`` consecutive chunks of asset ``src`` (by offset, from chunk ``first_src`` on: bytes ``begin_src`` .. ``end_src``)
+        match consecutive chunks of asset ``dst`` (from ``first_dst``, bytes ``begin_dst`` .. ``end_dst``); ``src < dst`` in a
+        self-join, ``src`` a position in ``bodies_a`` and ``dst`` one in ``bodies_b`` in a cross join.  More than ``max_pairs``
+        matching chunk pairs raise ValueError, and so do tables of different ``ndim``.
         """
-        return self._index.join_overlaps(self._radius_for(threshold), self._asset_keys(asset_bodies), int(max_doc_freq), max_pairs,
-                                         max(DOC_FREQ_DUP_LIMIT, int(max_doc_freq)))
+        if other is not None and other.ndim != self.ndim:
+            raise ValueError(f"shared needs simprints of one length: this table holds {self.ndim} bits, the other {other.ndim}")
+        max_doc_freq = int(max_doc_freq)
+        return self._index.join_shared(
+            self._asset_keys("bodies_a", bodies_a), self._radius_for(threshold), max_doc_freq, max_pairs, max(DOC_FREQ_DUP_LIMIT, max_doc_freq),
+            None if other is None else other._index, None if other is None else self._asset_keys("bodies_b", bodies_b), skip_same_asset, segments)
 
     @staticmethod
-    def _asset_keys(asset_bodies):
-        # type: (list[bytes]) -> np.ndarray
-        """The uint64 keys of ``asset_bodies``, which must be 8-byte ISCC-ID bodies, ascending, without repeats."""
-        keys = np.frombuffer(b"".join(bytes(b) for b in asset_bodies), dtype=">u8").astype(np.uint64)
-        if len(keys) != len(asset_bodies):
-            raise ValueError("asset_bodies must be 8-byte ISCC-ID bodies")
+    def _asset_keys(name, bodies):
+        # type: (str, list[bytes]) -> np.ndarray
+        """The uint64 keys of ``bodies``, which must be 8-byte ISCC-ID bodies, ascending, without repeats; ``name``: the argument they came in as."""
+        raw = b"".join(bytes(b) for b in bodies)
+        if len(raw) != 8 * len(bodies):
+            raise ValueError(f"{name} must be 8-byte ISCC-ID bodies")
+        keys = np.frombuffer(raw, dtype=">u8").astype(np.uint64)
         if len(keys) > 1 and not bool(np.all(keys[1:] > keys[:-1])):
-            raise ValueError("asset_bodies must be ascending without repeats: an asset's label is its position")
+            raise ValueError(f"{name} must be ascending without repeats: an asset's label is its position")
         return keys
-
-    @property
-    def joins_segments(self):
-        # type: () -> bool
-        """Whether ``overlaps_located`` is available (a single-GPU table; a sharded one has no self-join)."""
-        return self._index.joins_segments
-
-    def overlaps_located(self, asset_bodies, threshold, max_doc_freq, max_pairs):
-        # type: (list[bytes], float, int, int) -> tuple
-        """
-        ``overlaps`` and WHERE the assets share chunks, from the same self-join (``HipTable.join_segments``):
-        ``(records, chunks, info, segments)`` as it returns them.  A segment says that ``length`` consecutive chunks of asset ``src``
-        (by offset, from chunk ``first_src`` on: bytes ``begin_src`` .. ``end_src``) match consecutive chunks of asset ``dst``
-        (from ``first_dst``, bytes ``begin_dst`` .. ``end_dst``); ``src < dst`` are positions in ``asset_bodies``.
-        """
-        return self._index.join_segments(self._radius_for(threshold), self._asset_keys(asset_bodies), int(max_doc_freq), max_pairs,
-                                         max(DOC_FREQ_DUP_LIMIT, int(max_doc_freq)))
-
-    @property
-    def joins_overlaps_between(self):
-        # type: () -> bool
-        """Whether ``overlaps_between`` is available (a single-GPU table; a sharded one has no cross join)."""
-        return self._index.joins_overlaps_between
-
-    def overlaps_between(self, other, bodies_a, bodies_b, threshold, max_doc_freq, max_pairs, skip_same_asset=True):
-        # type: (HipSimprintIndex, list[bytes], list[bytes], float, int, int, bool) -> tuple
-        """
-        The pairs (asset of this table among ``bodies_a``, asset of ``other`` among ``bodies_b``) that share chunks; both lists are
-        8-byte ISCC-ID bodies, ascending, no repeats.  Chunks match as in ``overlaps`` (``_radius_for(threshold)``); a chunk whose
-        simprint more than ``max_doc_freq`` assets OF ITS OWN TABLE hold matches nothing.  ``skip_same_asset``: the chunks of one
-        ISCC-ID body held by both tables do not pair.  One cross join on the device (``HipTable.join_overlaps_between``) --
-        ``(records, chunks_a, chunks_b, info)`` as it returns them, an asset's label being its position in its side's list.  More
-        than ``max_pairs`` matching chunk pairs raise ValueError, and so do tables of different ``ndim``.
-        """
-        return self._index.join_overlaps_between(other._index, *self._between_args("overlaps_between", other, bodies_a, bodies_b, threshold, max_doc_freq),
-                                                 max_pairs, max(DOC_FREQ_DUP_LIMIT, int(max_doc_freq)), skip_same_asset)
-
-    def _between_args(self, caller, other, bodies_a, bodies_b, threshold, max_doc_freq):
-        # type: (str, HipSimprintIndex, list[bytes], list[bytes], float, int) -> tuple
-        """``(max_hamming, asset_keys_a, asset_keys_b, max_doc_freq)`` of a cross join with ``other``, or the ValueError naming ``caller``."""
-        if other.ndim != self.ndim:
-            raise ValueError(f"{caller} needs simprints of one length: this table holds {self.ndim} bits, the other {other.ndim}")
-        sides = []
-        for name, bodies in (("bodies_a", bodies_a), ("bodies_b", bodies_b)):
-            keys = np.frombuffer(b"".join(bytes(b) for b in bodies), dtype=">u8").astype(np.uint64)
-            if len(keys) != len(bodies):
-                raise ValueError(f"{name} must be 8-byte ISCC-ID bodies")
-            if len(keys) > 1 and not bool(np.all(keys[1:] > keys[:-1])):
-                raise ValueError(f"{name} must be ascending without repeats: an asset's label is its position")
-            sides.append(keys)
-        return self._radius_for(threshold), sides[0], sides[1], int(max_doc_freq)
-
-    @property
-    def joins_segments_between(self):
-        # type: () -> bool
-        """Whether ``overlaps_between_located`` is available (a single-GPU table; a sharded one has no cross join)."""
-        return self._index.joins_segments_between
-
-    def overlaps_between_located(self, other, bodies_a, bodies_b, threshold, max_doc_freq, max_pairs, skip_same_asset=True):
-        # type: (HipSimprintIndex, list[bytes], list[bytes], float, int, int, bool) -> tuple
-        """
-        ``overlaps_between`` and WHERE the assets share chunks, from the same cross join (``HipTable.join_segments_between``):
-        ``(records, chunks_a, chunks_b, info, segments)`` as it returns them.  A segment says that ``length`` consecutive chunks of
-        asset ``src`` of this table (by offset, from chunk ``first_src`` on: bytes ``begin_src`` .. ``end_src``) match consecutive
-        chunks of asset ``dst`` of ``other`` (from ``first_dst``, bytes ``begin_dst`` .. ``end_dst``); ``src`` is a position in
-        ``bodies_a`` and ``dst`` one in ``bodies_b``, always.
-        """
-        return self._index.join_segments_between(other._index, *self._between_args("overlaps_between_located", other, bodies_a, bodies_b, threshold, max_doc_freq),
-                                                 max_pairs, max(DOC_FREQ_DUP_LIMIT, int(max_doc_freq)), skip_same_asset)
 
     def doc_freq(self, simprints, dup_limit=1000):
         # type: (list[bytes], int) -> list[int]
