@@ -316,6 +316,24 @@ int isccsearch_simprint_exact(isccsearch_handle* h, uint32_t table, uint32_t n_d
                               uint32_t n_given, const uint32_t* given, uint32_t queried, uint32_t dup_limit, double threshold, uint32_t limit,
                               isccsearch_simprint_result* out_results, isccsearch_simprint_chunk* out_chunks, uint32_t* out_info);
 
+/* Many hard-boundary requests against ONE table in one call, each searched and scored on its own: what isccsearch_simprint_exact
+ * returns for every request alone -- assets, matches, order, first_chunk and the chunks' `query` relative to the request, the
+ * float64 scores bit for bit.  Request r holds the DISTINCT simprints q_words[distinct_offsets[r] .. distinct_offsets[r + 1]) and
+ * the given ones given[given_offsets[r] .. given_offsets[r + 1]) (both offset arrays [n_req + 1], non-decreasing; empty requests are
+ * allowed); a `given` value is the index of the simprint among ITS REQUEST's distinct ones (local, 0-based); queried[r] = the
+ * query simprints request r was given (its coverage denominator, >= its given count).  A simprint asked by two requests is looked
+ * up twice.  At most ISCCSEARCH_MAX_SCORED_SIMPRINTS distinct and as many given simprints per request (-E2BIG).  dup_limit,
+ * threshold and limit are shared.  The library cuts the requests into rounds of at most ISCCSEARCH_MAX_SCORED_SIMPRINTS given and
+ * at most as many distinct simprints (never splitting a request); a round is ONE search of its distinct simprints at distance 0,
+ * k = min(dup_limit, ISCCSEARCH_MAX_K) rows each, and one scoring pipeline that keeps the requests apart.
+ * Outputs per request r: out_results[r * limit ..]; out_chunks (nullable) request r's starting at k * given_offsets[r]
+ * (out_chunks[k * given_offsets[n_req]]); out_info[4 r .. 4 r + 4) = {results written, assets kept, longest collision list OF
+ * THIS REQUEST, chunks written}.  128-bit-key Hamming tables only. */
+int isccsearch_simprint_exact_many(isccsearch_handle* h, uint32_t table, uint32_t n_req, const uint32_t* distinct_offsets, const uint64_t* q_words,
+                                   const uint32_t* given_offsets, const uint32_t* given, const uint32_t* queried,
+                                   uint32_t dup_limit, double threshold, uint32_t limit,
+                                   isccsearch_simprint_result* out_results, isccsearch_simprint_chunk* out_chunks, uint32_t* out_info);
+
 /* Many asset queries in one call, scored on the device: what UsearchIndex.search_assets does for the units of ONE query
  * (iscc_search/indexes/usearch/index.py:786-839 -- one search per similarity unit, :2024-2045, one prefix match per INSTANCE
  * unit, :1957-2045; the max per (asset, unit type), the threshold, sum(s ** e) / sum(s) over the confident types, the

@@ -29,7 +29,8 @@ EXPORTS = (
     "isccsearch_size", "isccsearch_add", "isccsearch_remove", "isccsearch_contains", "isccsearch_get",
     "isccsearch_segments", "isccsearch_export", "isccsearch_add_columns",
     "isccsearch_add_synthetic", "isccsearch_search", "isccsearch_search_within", "isccsearch_search_many", "isccsearch_doc_freq", "isccsearch_doc_freq_counted", "isccsearch_get_freq",
-    "isccsearch_simprint_score", "isccsearch_simprint_score_many", "isccsearch_simprint_exact", "isccsearch_match_assets",
+    "isccsearch_simprint_score", "isccsearch_simprint_score_many", "isccsearch_simprint_exact", "isccsearch_simprint_exact_many",
+    "isccsearch_match_assets",
     "isccsearch_join_within", "isccsearch_join_between", "isccsearch_join_components", "isccsearch_join_overlaps",
     "isccsearch_join_segments", "isccsearch_join_overlaps_between", "isccsearch_join_segments_between",
     "isccsearch_search_device", "isccsearch_search_within_device", "isccsearch_merge_device",
@@ -197,6 +198,7 @@ def load_library():
         "isccsearch_simprint_score": (i, [vp, u32, u32, u64p, u32, ctypes.c_int32, ctypes.c_double, u32, ctypes.c_int64, u32, vp, vp, vp, u32p]),
         "isccsearch_simprint_score_many": (i, [vp, u32, u32, u32p, u64p, u32, ctypes.c_int32, ctypes.c_double, u32, ctypes.c_int64, u32, vp, vp, vp, u32p]),
         "isccsearch_simprint_exact": (i, [vp, u32, u32, u64p, u32, u32p, u32, u32, ctypes.c_double, u32, vp, vp, u32p]),
+        "isccsearch_simprint_exact_many": (i, [vp, u32, u32, u32p, u64p, u32p, u32p, u32p, u32, ctypes.c_double, u32, vp, vp, u32p]),
         "isccsearch_match_assets": (i, [vp, u32, u32p, vp, u32, u32, u32, u64p, u8p, vp, vp, ctypes.c_double, i, u32,
                                         u64p, vp, u32p, u8p, vp, u32p]),
         "isccsearch_join_within": (i, [vp, u32, vp, u64, u64p, u64p, u32p, u16p, u64p]),

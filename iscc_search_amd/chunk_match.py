@@ -37,12 +37,12 @@ def search_simprints(idx, query, limit, exact=False):
     return rank_simprint_matches(idx, per_type, limit)
 
 
-def search_simprints_many(idx, prepared, limit):
-    # type: (object, list, int) -> Dict[int, list]
+def search_simprints_many(idx, prepared, limit, exact=False):
+    # type: (object, list, int, bool) -> Dict[int, list]
     """
-    The approximate simprint searches of ``search_simprints`` for every prepared query: per simprint type one
-    ``search_raw_many`` over the queries that carry it, with ``search_simprints``' arguments.  Returns query index ->
-    [(simprint type, SimprintMatchRaw list)] in each query's type order.
+    The simprint searches of ``search_simprints`` for every prepared query: per simprint type one ``search_raw_many`` -- with
+    ``exact`` one ``search_exact_many`` -- over the queries that carry it, with ``search_simprints``' arguments.  Returns query
+    index -> [(simprint type, SimprintMatchRaw list)] in each query's type order.
     """
     if not idx._sp_tables:
         return {}
@@ -54,10 +54,14 @@ def search_simprints_many(idx, prepared, limit):
                 requests.setdefault(sp_type, []).append((i, [codec.decode_base64(_sp_string(s)) for s in simprint_objs]))
     found = {}  # type: Dict[tuple, list]
     for sp_type, items in requests.items():
-        raws = idx._sp_tables[sp_type].search_raw_many(
-            [q_bytes for _, q_bytes in items], limit=limit * 2, threshold=idx._opts.match_threshold_simprints, detailed=True,
-            total_assets=total_assets, device_doc_freq=True,
-        )
+        if exact:
+            raws = idx._sp_tables[sp_type].search_exact_many(
+                [q_bytes for _, q_bytes in items], limit=limit * 2, threshold=idx._opts.match_threshold_simprints, detailed=True)
+        else:
+            raws = idx._sp_tables[sp_type].search_raw_many(
+                [q_bytes for _, q_bytes in items], limit=limit * 2, threshold=idx._opts.match_threshold_simprints, detailed=True,
+                total_assets=total_assets, device_doc_freq=True,
+            )
         for (i, _), raw in zip(items, raws):
             found[(i, sp_type)] = raw
     return {i: [(t, found[(i, t)]) for t in (query.simprints or {}) if (i, t) in found] for i, (query, _, _) in enumerate(prepared)}

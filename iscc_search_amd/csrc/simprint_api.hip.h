@@ -1,4 +1,4 @@
-// simprint_api.hip.h -- the three simprint entry points: a search whose lists stay on the device (ScoreSink) and the scoring of
+// simprint_api.hip.h -- the four simprint entry points: a search whose lists stay on the device (ScoreSink) and the scoring of
 // simprint_score.hip behind it, on the handle's SimprintScratch, staged through ScoreStaging (simprint_scratch.hip.h).
 // Needs search_locked and ScoreSink of search_api.hip.h, ensure_freq_column of store.hip.h.
 // What a ScoreSink (search_api.hip.h) does with a batch of the search: the approximate requests mark and compact it, a hard-boundary
@@ -151,7 +151,106 @@ int simprint_score_rounds(H* h, uint32_t table, uint32_t n_req, const uint32_t* 
             HIPOK(isksp::queue_score_many(buf, mb, ma, h->stream));
         }
         HIPOK(hipStreamSynchronize(h->stream));       // (qbeg is read by the kernels until here)
-        st.copy_out(po, limit, req_offsets + r0, out_results + (size_t)r0 * limit, out_chunks, out_chunk_words, out_info + 4 * (size_t)r0);
+        st.copy_out(po, limit, limit, req_offsets + r0, out_results + (size_t)r0 * limit, out_chunks, out_chunk_words, out_info + 4 * (size_t)r0);
+        r0 = r1;
+    }
+    return 0;
+}
+
+// The hard-boundary search and scoring of isccsearch_simprint_exact and _exact_many once their arguments are checked (out_info zeroed;
+// request r = the distinct simprints [distinct_offsets[r], distinct_offsets[r + 1]) and the given ones [given_offsets[r],
+// given_offsets[r + 1]), whose `given` values are local to the request): consecutive requests of at most MAX_QUERY_SIMPRINTS given
+// and at most as many distinct simprints form a round, a request is never split.  A round is ONE search at distance 0 over its
+// distinct simprints with the collision lists left on the device, and one scoring: a round of one request takes queue_exact's
+// pipeline, a round of several queue_exact_many's (which returns per request what queue_exact would).
+int simprint_exact_rounds(H* h, uint32_t table, uint32_t n_req, const uint32_t* distinct_offsets, const uint64_t* q_words,
+                          const uint32_t* given_offsets, const uint32_t* given, const uint32_t* queried,
+                          uint32_t dup_limit, double threshold, uint32_t limit,
+                          isccsearch_simprint_result* out_results, isccsearch_simprint_chunk* out_chunks, uint32_t* out_info) {
+    std::lock_guard<std::mutex> lk(h->mu);
+    Table* tp;
+    int rc = get_table(h, table, tp);
+    if (rc) return rc;
+    Table& t = *tp;
+    if (t.metric != ISCCSEARCH_METRIC_HAMMING || t.key_words != 2)
+        return fail(-EINVAL, "simprint scoring is defined for fixed-length (Hamming) tables with 128-bit chunk-pointer keys");
+    Segment& s = t.seg[t.max_bytes];
+    if (s.n == 0) return 0;
+    HIPOK(hipSetDevice(h->device));
+    const uint32_t k = std::min<uint32_t>(dup_limit, ISCCSEARCH_MAX_K);
+    SimprintScratch& sp = h->sp;
+    std::vector<uint32_t>& beg = sp.h_qbeg;         // {gbeg [nr + 1] | dbeg [nr + 1] | queried [nr]} of the round
+    std::vector<uint32_t>& d_count = sp.h_qcount;   // length of every lookup's collision list
+    std::vector<uint32_t>& d_of_g = sp.h_dofg;
+    for (uint32_t r0 = 0; r0 < n_req;) {
+        const uint32_t gbase = given_offsets[r0], dbase = distinct_offsets[r0];
+        uint32_t r1 = r0 + 1;
+        while (r1 < n_req && given_offsets[r1 + 1] - gbase <= isksp::MAX_QUERY_SIMPRINTS && distinct_offsets[r1 + 1] - dbase <= isksp::MAX_QUERY_SIMPRINTS) ++r1;
+        const uint32_t ng = given_offsets[r1] - gbase, nd = distinct_offsets[r1] - dbase, nr = r1 - r0;
+        if (ng == 0 || nd == 0) { r0 = r1; continue; }      // (given simprints index distinct ones: ng > 0 has nd > 0)
+        h->stats.searches += 1;
+        if ((rc = sp.for_exact_search(nd, ng, k))) return rc;
+        // the round-global lookup of every given simprint, and where every request's given and distinct simprints begin
+        beg.resize(3 * ((size_t)nr + 1));
+        uint32_t* const gbeg = beg.data(), * const dbeg = gbeg + nr + 1, * const qd = dbeg + nr + 1;
+        d_of_g.resize(ng);
+        uint32_t words = 0;                // LDS words of the score kernel: those of the request with the most distinct simprints
+        for (uint32_t r = 0; r < nr; ++r) {
+            gbeg[r] = given_offsets[r0 + r] - gbase;
+            dbeg[r] = distinct_offsets[r0 + r] - dbase;
+            qd[r] = queried[r0 + r];
+            for (uint32_t g = given_offsets[r0 + r]; g < given_offsets[r0 + r + 1]; ++g) d_of_g[g - gbase] = given[g] + dbeg[r];
+            words = std::max(words, (distinct_offsets[r0 + r + 1] - distinct_offsets[r0 + r] + 63) / 64);
+        }
+        gbeg[nr] = ng; dbeg[nr] = nd; qd[nr] = 0;
+        d_count.assign(nd, 0);
+        ScoreSink sink{sp};
+        sink.exact = true;
+        sink.nd = nd; sink.ng = ng;
+        sink.q_count = d_count.data();
+        // (the lookup of every given simprint goes up first: when one batch holds all lookups, hits and offsets are prepared behind its
+        //  select and the number of entries arrives with the batch's own synchronisation)
+        HIPOK(hipMemcpyAsync(sp.d_of_g.p, d_of_g.data(), (size_t)ng * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        HIPOK(hipStreamSynchronize(h->stream));           // (d_of_g is rewritten by the next round)
+        // every row equal to a query simprint, ascending key, at most dup_limit per simprint (lmdb_ops.py:197-210): the lists stay on the device
+        if ((rc = search_locked(h, table, nd, q_words + (size_t)dbase * t.max_words, nullptr, k, 0, SearchOut::to_sink(&sink)))) return rc;
+        for (uint32_t r = 0; r < nr; ++r) {
+            uint32_t longest = 0;
+            for (uint32_t d = dbeg[r]; d < dbeg[r + 1]; ++d) longest = std::max(longest, d_count[d]);
+            out_info[4 * (size_t)(r0 + r) + 2] = longest;
+        }
+        uint32_t entries = sink.entries;
+        if (!sink.prepared) {
+            // several batches of lookups: hits per given simprint and their offsets now; the number of entries comes back with one small copy
+            if ((rc = h->d_block.ensure(isksp::INFO_WORDS * sizeof(uint32_t)))) return rc;
+            if ((rc = h->p_block.ensure(isksp::INFO_WORDS * sizeof(uint32_t)))) return rc;
+            uint32_t* const d_info = reinterpret_cast<uint32_t*>(h->d_block.p);
+            HIPOK(isksp::exact_prepare(sp.buffers(), sp.cnt.p, sp.d_of_g.p, nd, ng, k, d_info, h->stream));
+            HIPOK(hipMemcpyAsync(h->p_block.p, d_info, isksp::INFO_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+            HIPOK(hipStreamSynchronize(h->stream));
+            entries = reinterpret_cast<const uint32_t*>(h->p_block.p)[0];
+        }
+        if (entries == 0) { r0 = r1; continue; }
+        const uint32_t cap = nr == 1 ? limit : (uint32_t)std::min<uint64_t>((uint64_t)nr * limit, entries);
+        if ((rc = nr == 1 ? sp.for_exact_scoring(entries) : sp.for_exact_round(entries, nr, cap))) return rc;
+        isksp::Buffers buf = sp.buffers();
+        const ScoreStaging st{nr, cap, out_chunks ? entries : 0, 0};
+        if ((rc = sp.p_out.ensure(st.bytes()))) return rc;
+        unsigned char* const po = sp.p_out.p;
+        isksp::ExactArgs ea{};
+        ea.nd = nd; ea.ng = ng; ea.k = k; ea.entries = entries; ea.limit = limit; ea.queried = qd[0];
+        ea.d_of_g = sp.d_of_g.p; ea.threshold = threshold;
+        ea.out_info = st.info(po); ea.out_results = st.results(po); ea.out_chunks = st.chunks(po);
+        if (nr == 1) {
+            HIPOK(isksp::queue_exact(buf, ea, h->stream));
+        } else {
+            const isksp::ManyBuffers mb = sp.many_buffers();
+            HIPOK(hipMemcpyAsync(mb.qbeg, beg.data(), beg.size() * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+            const isksp::ExactManyArgs ma{ea, nr, cap, words, mb.qbeg + nr + 1, mb.qbeg + 2 * ((size_t)nr + 1)};
+            HIPOK(isksp::queue_exact_many(buf, mb, ma, h->stream));
+        }
+        HIPOK(hipStreamSynchronize(h->stream));       // (beg is read by the copy until here)
+        st.copy_out(po, limit, k, given_offsets + r0, out_results + (size_t)r0 * limit, out_chunks, nullptr, out_info + 4 * (size_t)r0);
         r0 = r1;
     }
     return 0;
@@ -228,55 +327,51 @@ int isccsearch_simprint_exact(isccsearch_handle* h, uint32_t table, uint32_t n_d
     if (!(threshold == threshold)) return fail(-EINVAL, "threshold is not a number");
     for (uint32_t g = 0; g < n_given; ++g)
         if (given[g] >= n_distinct) return fail(-EINVAL, "given[%u] = %u is no index into the %u distinct simprints", g, given[g], n_distinct);
-    std::lock_guard<std::mutex> lk(h->mu);
-    Table* tp;
-    int rc = get_table(h, table, tp);
-    if (rc) return rc;
-    Table& t = *tp;
-    if (t.metric != ISCCSEARCH_METRIC_HAMMING || t.key_words != 2)
-        return fail(-EINVAL, "simprint scoring is defined for fixed-length (Hamming) tables with 128-bit chunk-pointer keys");
-    Segment& s = t.seg[t.max_bytes];
-    if (s.n == 0) return 0;
-    HIPOK(hipSetDevice(h->device));
-    h->stats.searches += 1;
-    const uint32_t k = std::min<uint32_t>(dup_limit, ISCCSEARCH_MAX_K), nd = n_distinct, ng = n_given;
-    SimprintScratch& sp = h->sp;
-    if ((rc = sp.for_exact_search(nd, ng, k))) return rc;
-    ScoreSink sink{sp};
-    sink.exact = true;
-    sink.nd = nd; sink.ng = ng;
-    // (the lookup of every given simprint goes up first: when one batch holds all lookups, hits and offsets are prepared behind its
-    //  select and the number of entries arrives with the batch's own synchronisation)
-    HIPOK(hipMemcpyAsync(sp.d_of_g.p, given, (size_t)ng * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
-    HIPOK(hipStreamSynchronize(h->stream));           // (`given` is the caller's memory)
-    // every row equal to a query simprint, ascending key, at most dup_limit per simprint (lmdb_ops.py:197-210): the lists stay on the device
-    if ((rc = search_locked(h, table, nd, q_words, nullptr, k, 0, SearchOut::to_sink(&sink)))) return rc;
-    out_info[2] = sink.max_count;
-    uint32_t entries = sink.entries;
-    if (!sink.prepared) {
-        // several batches of lookups: hits per given simprint and their offsets now; the number of entries comes back with one small copy
-        if ((rc = h->d_block.ensure(isksp::INFO_WORDS * sizeof(uint32_t)))) return rc;
-        if ((rc = h->p_block.ensure(isksp::INFO_WORDS * sizeof(uint32_t)))) return rc;
-        uint32_t* const d_info = reinterpret_cast<uint32_t*>(h->d_block.p);
-        HIPOK(isksp::exact_prepare(sp.buffers(), sp.cnt.p, sp.d_of_g.p, nd, ng, k, d_info, h->stream));
-        HIPOK(hipMemcpyAsync(h->p_block.p, d_info, isksp::INFO_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-        HIPOK(hipStreamSynchronize(h->stream));
-        entries = reinterpret_cast<const uint32_t*>(h->p_block.p)[0];
+    // (one request whose given simprints begin at 0: a round of one, queue_exact's pipeline)
+    const uint32_t distinct_offsets[2] = {0, n_distinct}, given_offsets[2] = {0, n_given};
+    return simprint_exact_rounds(h, table, 1, distinct_offsets, q_words, given_offsets, given, &queried, dup_limit, threshold, limit,
+                                 out_results, out_chunks, out_info);
+}
+
+// Many hard-boundary requests against one table, each searched and scored on its own (lmdb_ops.py:169-301 per request); see include/isccsearch.h.
+int isccsearch_simprint_exact_many(isccsearch_handle* h, uint32_t table, uint32_t n_req, const uint32_t* distinct_offsets, const uint64_t* q_words,
+                                   const uint32_t* given_offsets, const uint32_t* given, const uint32_t* queried,
+                                   uint32_t dup_limit, double threshold, uint32_t limit,
+                                   isccsearch_simprint_result* out_results, isccsearch_simprint_chunk* out_chunks, uint32_t* out_info) {
+    if (!h) return fail(-EINVAL, "handle is NULL");
+    if (dup_limit < 1) return fail(-EINVAL, "dup_limit must be >= 1");
+    if (limit < 1) return fail(-EINVAL, "limit must be >= 1");
+    if (n_req == 0) return 0;
+    if (!out_info || !distinct_offsets || !given_offsets || !queried) return fail(-EINVAL, "NULL argument");
+    memset(out_info, 0, (size_t)n_req * 4 * sizeof(uint32_t));
+    for (uint32_t r = 0; r < n_req; ++r) {
+        if (distinct_offsets[r + 1] < distinct_offsets[r]) return fail(-EINVAL, "distinct_offsets must not decrease (request %u)", r);
+        if (given_offsets[r + 1] < given_offsets[r]) return fail(-EINVAL, "given_offsets must not decrease (request %u)", r);
     }
-    if (entries == 0) return 0;
-    if ((rc = sp.for_exact_scoring(entries))) return rc;
-    isksp::Buffers buf = sp.buffers();
-    const ScoreStaging st{1, limit, out_chunks ? entries : 0, 0};
-    if ((rc = sp.p_out.ensure(st.bytes()))) return rc;
-    unsigned char* const po = sp.p_out.p;
-    isksp::ExactArgs ea{};
-    ea.nd = nd; ea.ng = ng; ea.k = k; ea.entries = entries; ea.limit = limit; ea.queried = queried;
-    ea.d_of_g = sp.d_of_g.p; ea.threshold = threshold;
-    ea.out_info = st.info(po); ea.out_results = st.results(po); ea.out_chunks = st.chunks(po);
-    HIPOK(isksp::queue_exact(buf, ea, h->stream));
-    HIPOK(hipStreamSynchronize(h->stream));
-    const uint32_t first_query = 0;
-    st.copy_out(po, limit, &first_query, out_results, out_chunks, nullptr, out_info);
-    return 0;
+    for (uint32_t r = 0; r < n_req; ++r) {
+        const uint32_t nd = distinct_offsets[r + 1] - distinct_offsets[r], ng = given_offsets[r + 1] - given_offsets[r];
+        if (nd > isksp::MAX_QUERY_SIMPRINTS || ng > isksp::MAX_QUERY_SIMPRINTS)
+            return fail(-E2BIG, "request %u: %u / %u query simprints exceed the %u one scoring call takes", r, nd, ng, isksp::MAX_QUERY_SIMPRINTS);
+    }
+    for (uint32_t r = 0; r < n_req; ++r) {
+        const uint32_t ng = given_offsets[r + 1] - given_offsets[r];
+        if (queried[r] < ng)
+            return fail(-EINVAL, "request %u: queried (%u) counts every query simprint as given: it cannot be below its given simprints (%u)", r, queried[r], ng);
+    }
+    if (given_offsets[n_req] == given_offsets[0]) return 0;
+    if (!q_words || !given || !out_results) return fail(-EINVAL, "NULL argument");
+    for (uint32_t r = 0; r < n_req; ++r) {
+        const uint32_t nd = distinct_offsets[r + 1] - distinct_offsets[r];
+        for (uint32_t g = given_offsets[r]; g < given_offsets[r + 1]; ++g)
+            if (given[g] >= nd) return fail(-EINVAL, "request %u: given[%u] = %u is no index into its %u distinct simprints", r, g, given[g], nd);
+    }
+    const uint32_t k = std::min<uint32_t>(dup_limit, ISCCSEARCH_MAX_K);
+    if ((uint64_t)limit * n_req > 0xFFFFFFFFull)
+        return fail(-E2BIG, "limit %u x %u requests exceeds the 32-bit result addressing", limit, n_req);
+    if ((uint64_t)k * given_offsets[n_req] > 0xFFFFFFFFull)
+        return fail(-E2BIG, "%u collisions x %u given simprints exceed the 32-bit chunk addressing", k, given_offsets[n_req]);
+    if (!(threshold == threshold)) return fail(-EINVAL, "threshold is not a number");
+    return simprint_exact_rounds(h, table, n_req, distinct_offsets, q_words, given_offsets, given, queried, dup_limit, threshold, limit,
+                                 out_results, out_chunks, out_info);
 }
 }  // extern "C"

@@ -6,7 +6,7 @@
 // additions, order (-score, asset), first `limit`.  Input: the neighbour lists as select_kernel left them in
 // device memory -- records [nq][k] ascending (hamming, key), the segment row of every record, counts [nq].
 //
-// The stages, once; the three pipelines below are lists of them.
+// The stages, once; the four pipelines below are lists of them.
 //   per batch of <= 1 024 query simprints (queue_batch, queued behind its select_kernel, before the batch's one synchronisation):
 //     mark     one block per query: matches = the prefix with hamming <= h_max; first occurrence of every asset in it
 //              (LDS hash: asset -> smallest rank) = the best chunk of (asset, query); the query's own document
@@ -31,6 +31,10 @@
 //   queue_exact       (hard-boundary requests) the entries are collisions (exact_prepare and a compaction of its own instead of
 //                     queue_batch); by asset, weights and score in the exact form (coverage x quality, no similarity), by score, the
 //                     same emit kernel writing collision records.
+//   queue_exact_many  (a round of several hard-boundary requests) queue_exact's stages with queue_score_many's regrouping: the
+//                     compaction of the round's collisions, by asset, by request, weights, the exact score kernel instantiated for
+//                     (request, asset) runs, by score, by request, the scan of the chunks per result, emit with a wave per result
+//                     writing collision records.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -133,5 +137,20 @@ struct ExactArgs {
     uint32_t* out_info;                        // pinned [4]
 };
 hipError_t queue_exact(Buffers& b, const ExactArgs& a, hipStream_t stream);
+
+// Many hard-boundary requests in one call (a round of two or more requests of isccsearch_simprint_exact_many): the round's lookups
+// are the concatenation of its requests' DISTINCT simprints (request r: lookups [dbeg[r], dbeg[r + 1])), its given simprints that of
+// theirs (request r: [gbeg[r], gbeg[r + 1]) -- ManyBuffers::qbeg holds gbeg), d_of_g is round-global.  exact_prepare has run over the
+// whole round.  A lookup belongs to one request, so the LDS row of a (request, asset) run holds the words of its request only.
+// Pinned outputs are staged as queue_score_many's; a chunk's `query` is relative to its request's first given simprint.
+struct ExactManyArgs {
+    ExactArgs e;                    // nd / ng / entries of the round (queried unused); out_results [cap]; out_chunks [entries]; out_info [n_req * 4]
+    uint32_t n_req;
+    uint32_t cap;                   // min(entries, n_req x limit): results the round can write at most
+    uint32_t words;                 // LDS words per thread of the score kernel: ceil(distinct simprints / 64) of the largest request
+    const uint32_t* dbeg;           // [n_req + 1] device
+    const uint32_t* queried;        // [n_req] device: query simprints every request was given (coverage denominator)
+};
+hipError_t queue_exact_many(Buffers& b, const ManyBuffers& mb, const ExactManyArgs& a, hipStream_t stream);
 
 }  // namespace isksp

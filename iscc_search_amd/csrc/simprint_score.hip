@@ -381,13 +381,15 @@ __device__ __forceinline__ void write_chunk(const ChunkParams& p, uint32_t ent, 
     p.out_chunks[at] = c;
     for (uint32_t w = 0; w < p.W; ++w) p.out_chunk_words[(uint64_t)at * p.W + w] = p.col[w][row];
 }
-// ... and of a collision (queue_exact): an entry is (given simprint g) * k + rank, its record belongs to distinct lookup d_of_g[g];
-// stored simprint == query simprint, score 1.0 (lmdb_ops.py:228-235), so no code words
-__device__ __forceinline__ void write_collision(const ChunkParams& p, const uint32_t* d_of_g, const uint32_t* freq_d, uint32_t ent, uint32_t at) {
+// ... and of a collision (queue_exact, queue_exact_many): an entry is (given simprint g) * k + rank, its record belongs to distinct
+// lookup d_of_g[g]; stored simprint == query simprint, score 1.0 (lmdb_ops.py:228-235), so no code words.  `query` counts from g0,
+// the first given simprint of the entry's request
+__device__ __forceinline__ void write_collision(const ChunkParams& p, const uint32_t* d_of_g, const uint32_t* freq_d, uint32_t ent, uint32_t g0, uint32_t at) {
     isccsearch_simprint_chunk c;
-    c.query = ent / p.k;
+    const uint32_t g = ent / p.k;
+    c.query = g - g0;
     c.reserved = 0;
-    const uint32_t d = d_of_g[c.query];
+    const uint32_t d = d_of_g[g];
     c.key_lo = p.rec[(uint64_t)d * p.k + ent % p.k].key_lo;
     c.hamming = 0;
     c.freq = freq_d[d];
@@ -440,7 +442,7 @@ __global__ __launch_bounds__(BLOCK) void emit_kernel(const EmitParams p) {
     if (!p.c.out_chunks) return;
     for (uint32_t j = tid; j < m; j += BLOCK) {
         const uint32_t ent = p.entry[e + j];
-        if (p.d_of_g) write_collision(p.c, p.d_of_g, p.freq_d, ent, at + j);
+        if (p.d_of_g) write_collision(p.c, p.d_of_g, p.freq_d, ent, 0, at + j);
         else write_chunk(p.c, ent, 0, at + j);
     }
 }
@@ -516,27 +518,62 @@ struct ExactScoreParams {
     uint32_t entries, words, queried;
     double threshold;
 };
-__global__ void exact_score_kernel(const ExactScoreParams p) {
+// ... of a round of several requests (queue_exact_many): a run is a (request, asset) pair, the bit of lookup d in the thread's LDS row
+// is d - dbeg[request] (the row holds the words of the run's own request only), coverage is over the request's own `queried`, and the
+// kept assets are counted per request
+struct ExactScoreManyParams {
+    const uint64_t* asset;          // sorted by (request, asset)
+    const uint32_t* req;            // sorted
+    const uint32_t* e_d;
+    const uint32_t* e_f;
+    const uint32_t* dbeg;           // [n_req + 1] first distinct lookup of every request in the round
+    const uint32_t* queried;        // [n_req]
+    double* score;
+    uint32_t* order;
+    uint32_t* matches;
+    uint32_t* n_assets;             // [n_req]
+    uint32_t entries, words;        // words: the most LDS words one request's lookups take
+    double threshold;
+};
+template <class P>
+__global__ void exact_score_kernel(const P p) {
 #pragma clang fp contract(off)
+    constexpr bool MANY = std::is_same<P, ExactScoreManyParams>::value;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned long long* mask = reinterpret_cast<unsigned long long*>(smem);
     const uint32_t T = blockDim.x, tid = threadIdx.x;
     const uint32_t e = blockIdx.x * T + tid;
     bool counted = false;
+    uint32_t r = 0;
     if (e < p.entries) {
         const uint64_t a = p.asset[e];
-        const bool head = e == 0 || p.asset[e - 1] != a;
+        bool head;
+        if constexpr (MANY) {
+            r = p.req[e];
+            head = e == 0 || p.asset[e - 1] != a || p.req[e - 1] != r;
+        } else {
+            head = e == 0 || p.asset[e - 1] != a;
+        }
         p.order[e] = e;
         double score = -1.0;
         uint32_t len = 0;
         if (head) {
             // query_to_best_freq (:277-283): one entry per distinct matched query simprint, in first-seen order; the frequency of a
             // collision's stored simprint is that of the query simprint itself, so "best" is that one value
-            for (uint32_t w = 0; w < p.words; ++w) mask[w * T + tid] = 0;
+            uint32_t words = p.words, d0 = 0, queried;
+            if constexpr (MANY) {
+                d0 = p.dbeg[r];
+                words = (p.dbeg[r + 1] - d0 + 63) >> 6;               // (<= p.words: the launch's LDS row)
+                queried = p.queried[r];
+            } else {
+                queried = p.queried;
+            }
+            for (uint32_t w = 0; w < words; ++w) mask[w * T + tid] = 0;
             uint32_t distinct = 0, fmin = 0xFFFFFFFFu, fmax = 0;
             uint32_t j = e;
             for (; j < p.entries && p.asset[j] == a; ++j) {
-                const uint32_t d = p.e_d[j], f = p.e_f[j];
+                if constexpr (MANY) { if (p.req[j] != r) break; }
+                const uint32_t d = p.e_d[j] - d0, f = p.e_f[j];
                 const unsigned long long bit = 1ull << (d & 63);
                 unsigned long long& word = mask[(d >> 6) * T + tid];
                 if (!(word & bit)) {
@@ -551,10 +588,10 @@ __global__ void exact_score_kernel(const ExactScoreParams p) {
             if (distinct > 1 && fmin != fmax) {                       // (:291-299)
                 const double min_inv = 1.0 / (double)fmax, max_inv = 1.0 / (double)fmin;
                 const double span = max_inv - min_inv;
-                for (uint32_t w = 0; w < p.words; ++w) mask[w * T + tid] = 0;
+                for (uint32_t w = 0; w < words; ++w) mask[w * T + tid] = 0;
                 double sum = 0.0;
                 for (uint32_t i = e; i < j; ++i) {
-                    const uint32_t d = p.e_d[i];
+                    const uint32_t d = p.e_d[i] - d0;
                     const unsigned long long bit = 1ull << (d & 63);
                     unsigned long long& word = mask[(d >> 6) * T + tid];
                     if (!(word & bit)) {
@@ -566,7 +603,7 @@ __global__ void exact_score_kernel(const ExactScoreParams p) {
                 }
                 quality = sum / (double)distinct;
             }
-            const double coverage = (double)distinct / (double)p.queried;
+            const double coverage = (double)distinct / (double)queried;
             score = coverage * quality;
             if (score < p.threshold) score = -1.0;                    // (:222-223) dropped: sorts behind every kept asset
             else counted = true;
@@ -574,8 +611,12 @@ __global__ void exact_score_kernel(const ExactScoreParams p) {
         p.score[e] = score;
         p.matches[e] = len;
     }
-    const unsigned long long kept = __ballot(counted);
-    if ((tid & 63) == 0 && kept) atomicAdd(p.n_assets, (uint32_t)__popcll(kept));
+    if constexpr (MANY) {
+        if (counted) atomicAdd(&p.n_assets[r], 1u);
+    } else {
+        const unsigned long long kept = __ballot(counted);
+        if ((tid & 63) == 0 && kept) atomicAdd(p.n_assets, (uint32_t)__popcll(kept));
+    }
 }
 
 // =====================================================================================================================
@@ -664,7 +705,16 @@ struct EmitManyParams {
     uint32_t* out_info;
     uint32_t n_req;
 };
-__global__ __launch_bounds__(BLOCK) void emit_many_kernel(const EmitManyParams p) {
+// ... of hard-boundary requests (queue_exact_many): the chunks are collisions; m.qbeg = the first GIVEN simprint of every request
+struct EmitExactManyParams {
+    EmitManyParams m;
+    const uint32_t* d_of_g;         // distinct lookup of every given simprint, round-global
+    const uint32_t* freq_d;         // document frequency per distinct lookup
+};
+template <class P>
+__global__ __launch_bounds__(BLOCK) void emit_many_kernel(const P pp) {
+    constexpr bool EXACT = std::is_same<P, EmitExactManyParams>::value;
+    const EmitManyParams& p = [&]() -> const EmitManyParams& { if constexpr (EXACT) return pp.m; else return pp; }();
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t waves = gridDim.x * (BLOCK / 64);
     const uint32_t total = p.e_start[p.n_req];
@@ -684,7 +734,10 @@ __global__ __launch_bounds__(BLOCK) void emit_many_kernel(const EmitManyParams p
         }
         if (!p.c.out_chunks) continue;
         const uint32_t q0 = p.qbeg[r];
-        for (uint32_t jj = lane; jj < m; jj += 64) write_chunk(p.c, p.entry[e + jj], q0, at + jj);
+        for (uint32_t jj = lane; jj < m; jj += 64) {
+            if constexpr (EXACT) write_collision(p.c, pp.d_of_g, pp.freq_d, p.entry[e + jj], q0, at + jj);
+            else write_chunk(p.c, p.entry[e + jj], q0, at + jj);
+        }
     }
 }
 
@@ -725,7 +778,7 @@ hipError_t queue_batch(const Buffers& b, const BatchArgs& a, hipStream_t stream)
 }
 
 // ---------------------------------------------------------------------------------------------
-// The stages the three pipelines share (simprint_score.h lists them); each queue_* below is the list of what differs.
+// The stages the four pipelines share (simprint_score.h lists them); each queue_* below is the list of what differs.
 // ---------------------------------------------------------------------------------------------
 namespace {
 constexpr uint32_t MAX_WORDS = MAX_QUERY_SIMPRINTS / 64;   // LDS words per thread a score kernel is launched with at most
@@ -781,7 +834,7 @@ hipError_t queue_exact(Buffers& b, const ExactArgs& a, hipStream_t stream) {
     uint32_t* const e_f = reinterpret_cast<uint32_t*>(b.score[1]);
     hipLaunchKernelGGL(exact_weights_kernel, dim3((a.entries + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, b.c_entry[1], a.d_of_g, b.freq_q, e_d, e_f, b.n_assets, a.entries, a.k);
     const ExactScoreParams sp{b.c_asset[1], e_d, e_f, b.score[0], b.order[0], b.matches, b.n_assets, a.entries, words, a.queried, a.threshold};
-    queue_scoring(exact_score_kernel, sp, a.entries, words, stream);
+    queue_scoring(exact_score_kernel<ExactScoreParams>, sp, a.entries, words, stream);
     if ((e = sort_by_score(b, a.entries, stream)) != hipSuccess) return e;
     const ChunkParams collisions{b.rec, nullptr, nullptr, {}, a.out_chunks, nullptr, a.k, 0, 0};
     queue_emit(EmitParams{b.score[1], b.order[1], b.c_asset[1], b.c_entry[1], b.matches, b.n_assets, collisions, a.out_results, a.out_info, a.limit, a.d_of_g, b.freq_q},
@@ -853,7 +906,54 @@ hipError_t queue_score_many(Buffers& b, const ManyBuffers& mb, const ScoreManyAr
     const EmitManyParams ep{b.score[0], mb.idx[1], b.c_asset[0], b.c_entry[0], b.matches, mb.a_start, mb.e_start, mb.c_pos, mb.qbeg,
                             chunk_params(b, a), a.out_results, a.out_info, nr};
     const uint32_t waves_wanted = ma.cap, blocks = std::min<uint32_t>((waves_wanted + 3) / 4, 2048);
-    hipLaunchKernelGGL(emit_many_kernel, dim3(blocks ? blocks : 1), dim3(BLOCK), 0, stream, ep);
+    hipLaunchKernelGGL(emit_many_kernel<EmitManyParams>, dim3(blocks ? blocks : 1), dim3(BLOCK), 0, stream, ep);
+    return hipGetLastError();
+}
+
+hipError_t queue_exact_many(Buffers& b, const ManyBuffers& mb, const ExactManyArgs& ma, hipStream_t stream) {
+    const ExactArgs& a = ma.e;
+    hipError_t e;
+    const uint32_t nr = ma.n_req, grid = (a.entries + BLOCK - 1) / BLOCK;
+    uint32_t req_bits = 1;                                   // request keys 0 .. n_req (n_req: the non-heads and the dropped assets)
+    while ((1u << req_bits) <= nr) ++req_bits;
+    if (ma.words == 0 || ma.words > MAX_WORDS) return hipErrorInvalidValue;
+    auto sort_by_request = [&] {
+        size_t bytes = b.temp_bytes;
+        return rocprim::radix_sort_pairs(b.temp, bytes, mb.req[0], mb.req[1], mb.idx[0], mb.idx[1], a.entries, 0, (int)req_bits, stream);
+    };
+    // (the caller has run exact_prepare over the round's lookups and given simprints: hits / offsets / entries are in place)
+    ExactCompactParams cp{b.rec, a.d_of_g, b.nbest, b.offs, b.c_asset[0], b.c_entry[0], a.k};
+    hipLaunchKernelGGL(exact_compact_kernel, dim3(a.ng), dim3(BLOCK), 0, stream, cp);
+    // (request, asset) order: stable by asset, then stable by request (an entry's request is that of its given simprint; mb.qbeg
+    // holds the first GIVEN simprint of every request).  The compaction wrote the entries in visiting order -- given simprint
+    // ascending, then key -- and BOTH sorts are stable, so inside a (request, asset) run the entries are still in that order: the
+    // first-seen order of exact_score_kernel's distinct matched simprints is the reference's, per request.
+    if ((e = sort_by_asset(b, a.entries, stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(req_key_kernel, dim3(grid), dim3(BLOCK), 0, stream, b.c_entry[1], mb.qbeg, nr, a.k, mb.req[0], mb.idx[0], a.entries);
+    if ((e = sort_by_request()) != hipSuccess) return e;
+    hipLaunchKernelGGL(gather_kernel, dim3(grid), dim3(BLOCK), 0, stream, mb.idx[1], b.c_asset[1], b.c_entry[1], b.c_asset[0], b.c_entry[0], a.entries);
+    uint32_t* const e_d = b.order[1];
+    uint32_t* const e_f = reinterpret_cast<uint32_t*>(b.score[1]);
+    hipLaunchKernelGGL(exact_weights_kernel, dim3(grid), dim3(BLOCK), 0, stream, b.c_entry[0], a.d_of_g, b.freq_q, e_d, e_f, b.n_assets, a.entries, a.k);
+    if ((e = hipMemsetAsync(mb.n_assets, 0, (size_t)nr * sizeof(uint32_t), stream)) != hipSuccess) return e;
+    const ExactScoreManyParams sp{b.c_asset[0], mb.req[1], e_d, e_f, ma.dbeg, ma.queried, b.score[0], b.order[0], b.matches, mb.n_assets,
+                                  a.entries, ma.words, a.threshold};
+    queue_scoring(exact_score_kernel<ExactScoreManyParams>, sp, a.entries, ma.words, stream);
+    // every request's kept assets in (-score, asset) order: stable by score (descending), then stable by request (a dropped asset's
+    // score is -1: it goes behind every request with the non-heads)
+    if ((e = sort_by_score(b, a.entries, stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(head_key_kernel, dim3(grid), dim3(BLOCK), 0, stream, b.score[1], b.order[1], mb.req[1], nr, mb.req[0], mb.idx[0], a.entries);
+    if ((e = sort_by_request()) != hipSuccess) return e;
+    hipLaunchKernelGGL(req_scan_kernel, dim3(1), dim3(BLOCK), 0, stream, mb.n_assets, nr, a.limit, mb.a_start, mb.e_start, a.out_info);
+    hipLaunchKernelGGL(result_chunks_kernel, dim3((ma.cap + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, stream, mb.e_start, mb.a_start, mb.idx[1], b.matches, nr, mb.cnt, ma.cap);
+    size_t bytes = b.temp_bytes;
+    e = rocprim::exclusive_scan(b.temp, bytes, mb.cnt, mb.c_pos, 0u, ma.cap, rocprim::plus<uint32_t>(), stream);
+    if (e != hipSuccess) return e;
+    const ChunkParams collisions{b.rec, nullptr, nullptr, {}, a.out_chunks, nullptr, a.k, 0, 0};
+    const EmitExactManyParams ep{{b.score[0], mb.idx[1], b.c_asset[0], b.c_entry[0], b.matches, mb.a_start, mb.e_start, mb.c_pos, mb.qbeg,
+                                  collisions, a.out_results, a.out_info, nr}, a.d_of_g, b.freq_q};
+    const uint32_t blocks = std::min<uint32_t>((ma.cap + 3) / 4, 2048);
+    hipLaunchKernelGGL(emit_many_kernel<EmitExactManyParams>, dim3(blocks ? blocks : 1), dim3(BLOCK), 0, stream, ep);
     return hipGetLastError();
 }
 

@@ -19,10 +19,11 @@ struct SimprintScratch {
     DevBuf<uint64_t> asset[2];
     DevBuf<double> score[2], ws, idf_q;
     DevBuf<unsigned char> temp;
-    DevBuf<uint32_t> cnt, d_of_g;       // isccsearch_simprint_exact: list lengths of every lookup, the lookup of every given simprint
+    DevBuf<uint32_t> cnt, d_of_g;       // isccsearch_simprint_exact(_many): list lengths of every lookup, the lookup of every given simprint
     // a round of several requests (ManyBuffers): request keys / sort payloads per entry, per-request offsets and counts, chunks per result
     struct { DevBuf<uint32_t> req[2], idx[2], qbeg, n_assets, a_start, e_start, cnt, c_pos; } many;
     std::vector<uint32_t> h_qbeg, h_qcount;     // (host side of a round: kept, so that a scoring call allocates nothing here)
+    std::vector<uint32_t> h_dofg;               // (... of a hard-boundary round: the round-global lookup of every given simprint)
     // the similarity / IDF tables on the device are those of (bits, total_assets, dup_limit):
     DevBuf<double> tab;
     PinBuf<double> p_tab;
@@ -74,6 +75,19 @@ struct SimprintScratch {
         return temp.ensure(isksp::sort_temp_bytes(entries));
     }
 
+    // ... or that of a round of nr > 1 hard-boundary requests that writes at most `cap` results (queue_exact_many); many.qbeg holds
+    // {gbeg [nr + 1] | dbeg [nr + 1] | queried [nr]}
+    int for_exact_round(uint32_t entries, uint32_t nr, uint32_t cap) {
+        int rc;
+        if ((rc = ensure_all(entries, asset[0], entry[0], asset[1], entry[1], score[0], order[0], score[1], order[1], matches))) return rc;
+        if ((rc = ensure_all(entries, many.req[0], many.idx[0], many.req[1], many.idx[1]))) return rc;
+        if ((rc = many.qbeg.ensure(3 * ((size_t)nr + 1)))) return rc;
+        if ((rc = ensure_all((size_t)nr + 1, many.a_start, many.e_start))) return rc;
+        if ((rc = many.n_assets.ensure(nr))) return rc;
+        if ((rc = ensure_all(cap, many.cnt, many.c_pos))) return rc;
+        return temp.ensure(isksp::many_temp_bytes(entries, cap));
+    }
+
     // -- the buffers as the kernels take them (after the sizing: a buffer that grew has moved) -----------------------------------
     isksp::Buffers buffers() const {
         isksp::Buffers b{};
@@ -108,9 +122,10 @@ struct ScoreStaging {
     // (nullptr tells the emit kernels that no chunks are wanted)
     isccsearch_simprint_chunk* chunks(unsigned char* base) const { return chunk_cap ? reinterpret_cast<isccsearch_simprint_chunk*>(base + chunks_off()) : nullptr; }
     uint64_t* words(unsigned char* base) const { return chunk_cap && W ? reinterpret_cast<uint64_t*>(base + words_off()) : nullptr; }
-    // Into the caller's regions: request r's results at r x limit, its chunks (and their words) at limit x first_query[r], its counts
-    // in out_info[4 r ..] (word 2, the longest list, is the search's and stays)
-    void copy_out(unsigned char* base, uint32_t limit, const uint32_t* first_query, isccsearch_simprint_result* out_results,
+    // Into the caller's regions: request r's results at r x limit, its chunks (and their words) at chunk_stride x first_query[r] (the
+    // most chunks a query simprint can have: `limit` of an approximate request, k of a hard-boundary one), its counts in
+    // out_info[4 r ..] (word 2, the longest list, is the search's and stays)
+    void copy_out(unsigned char* base, uint32_t limit, uint32_t chunk_stride, const uint32_t* first_query, isccsearch_simprint_result* out_results,
                   isccsearch_simprint_chunk* out_chunks, uint64_t* out_chunk_words, uint32_t* out_info) const {
         const uint32_t* in = info(base);
         size_t res_at = 0, chunk_at = 0;
@@ -119,7 +134,7 @@ struct ScoreStaging {
             out_info[4 * r] = n; out_info[4 * r + 1] = in[4 * r + 1]; out_info[4 * r + 3] = c;
             memcpy(out_results + r * limit, results(base) + res_at, (size_t)n * sizeof(isccsearch_simprint_result));
             if (chunk_cap && c) {
-                const size_t dst = (size_t)limit * first_query[r];
+                const size_t dst = (size_t)chunk_stride * first_query[r];
                 memcpy(out_chunks + dst, chunks(base) + chunk_at, (size_t)c * sizeof(isccsearch_simprint_chunk));
                 if (W) memcpy(out_chunk_words + dst * W, words(base) + chunk_at * W, (size_t)c * W * sizeof(uint64_t));
             }

@@ -685,6 +685,36 @@ class HipTable(TableChecks):
         n, c = int(info[0]), int(info[3])
         return results[:n], (chunks[:c] if detailed else None), tuple(int(x) for x in info)
 
+    def simprint_exact_many(self, q_words, distinct_offsets, given, given_offsets, queried, dup_limit, threshold, limit, detailed):
+        # type: (np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray, int, float, int, bool) -> tuple
+        """
+        ``simprint_exact`` for many requests in one call (``isccsearch_simprint_exact_many``): request r holds the distinct query
+        simprints ``q_words[distinct_offsets[r]:distinct_offsets[r + 1]]`` and the given ones ``given[given_offsets[r]:given_offsets[r + 1]]``
+        (indices among ITS distinct simprints); ``queried[r]`` = the query simprints it was given.  Returns (results [n_req, limit]
+        ``SIMPRINT_RESULT_DTYPE``, chunks [k x given simprints] ``SIMPRINT_CHUNK_DTYPE`` or None, info uint32 [n_req, 4]), k =
+        min(dup_limit, MAX_K): request r's results are ``results[r, :info[r, 0]]``, its chunks ``chunks[k * given_offsets[r]:][:info[r, 3]]``.
+        """
+        q_words = self._words(q_words)
+        distinct_offsets = np.ascontiguousarray(distinct_offsets, dtype=np.uint32)
+        given_offsets = np.ascontiguousarray(given_offsets, dtype=np.uint32)
+        given = np.ascontiguousarray(given, dtype=np.uint32)
+        queried = np.ascontiguousarray(queried, dtype=np.uint32)
+        n_req = queried.shape[0]
+        if distinct_offsets.shape[0] != n_req + 1 or given_offsets.shape[0] != n_req + 1:
+            raise ValueError("offsets must hold n_req + 1 entries")
+        if n_req and (int(distinct_offsets[-1]) > q_words.shape[0] or int(given_offsets[-1]) > given.shape[0]):
+            raise ValueError("offsets must lie within the distinct and the given simprints")
+        limit = int(limit)
+        results = np.empty((n_req, limit), dtype=_lib.SIMPRINT_RESULT_DTYPE)
+        info = np.zeros((n_req, 4), dtype=np.uint32)
+        cap = int(min(dup_limit, _lib.MAX_K)) * given.shape[0]
+        chunks = np.empty(cap, dtype=_lib.SIMPRINT_CHUNK_DTYPE) if detailed else None
+        if n_req and q_words.shape[0] and given.shape[0]:
+            _lib.check(self.engine._lib.isccsearch_simprint_exact_many(
+                self.engine.handle, self.id, n_req, _lib.ptr(distinct_offsets), _lib.ptr(q_words), _lib.ptr(given_offsets), _lib.ptr(given),
+                _lib.ptr(queried), int(dup_limit), float(threshold), limit, _lib.ptr(results), _lib.ptr(chunks), _lib.ptr(info)))
+        return results, chunks, info
+
     def search_device(self, q_words, q_nbytes, k, d_records_ptr, d_counts_ptr, max_hamming=None, consumer_stream=None, hint=None):
         # type: (np.ndarray, np.ndarray | None, int, int, int, int | None, int | None, int | None) -> None
         """

@@ -458,8 +458,8 @@ class HipIndex:
         is searched, with the same exception naming its index in ``queries``.  The unit part runs as ``match_units_many``
         (batches of up to 1 024 queries).  The ``chunk_matches`` of queries with simprints: per simprint type ONE
         ``search_raw_many`` over every query that carries it (on a single-GPU engine one library call, scored per query on the
-        device), then the ranking of ``search_assets`` per query.  With ``exact=True`` they are answered per query by the
-        collision search of ``search_assets``.
+        device), then the ranking of ``search_assets`` per query.  With ``exact=True`` the collision search is batched the same
+        way: per simprint type ONE ``search_exact_many`` (on a single-GPU engine one library search per round of 8 192 simprints).
         """
         if not 1 <= limit <= MAX_K:
             # outside the engine's range search_assets itself decides (its limit checks depend on the query's units)
@@ -474,15 +474,12 @@ class HipIndex:
         unit_idx = [i for i, (query, _, _) in enumerate(prepared) if query.units]
         m = unit_match.match_prepared(self._engine, self._unit_tables, self._opts, [prepared[i] for i in unit_idx], limit) if unit_idx else None
         row_of = {i: r for r, i in enumerate(unit_idx)}
-        sp_raw = {} if exact else chunk_match.search_simprints_many(self, prepared, limit)
+        sp_raw = chunk_match.search_simprints_many(self, prepared, limit, exact=exact)
         results = []
         for i, (query, query_iscc_id, _) in enumerate(prepared):
             chunk_matches = []
             if self._sp_tables and query.simprints:
-                if exact:
-                    chunk_matches = chunk_match.search_simprints(self, query, limit, exact=True)
-                else:
-                    chunk_matches = chunk_match.rank_simprint_matches(self, sp_raw.get(i, []), limit)
+                chunk_matches = chunk_match.rank_simprint_matches(self, sp_raw.get(i, []), limit)
             matches = []
             r = row_of.get(i)
             if r is not None:

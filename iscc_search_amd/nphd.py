@@ -439,6 +439,18 @@ class HipIndex128:
         q_words, _ = pack_bytes(self._vectors(vectors), self._table.max_words)
         return self._table.simprint_exact(q_words, given, queried, dup_limit, threshold, limit, detailed)
 
+    @property
+    def scores_exact_many_on_device(self):
+        # type: () -> bool
+        """Whether the table scores many hard-boundary searches in one call (``isccsearch_simprint_exact_many``; sharded tables and the CPU oracle's do not)."""
+        return hasattr(self._table, "simprint_exact_many")
+
+    def exact_assets_many(self, vectors, distinct_offsets, given, given_offsets, queried, dup_limit, threshold, limit, detailed):
+        # type: (np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray, int, float, int, bool) -> tuple
+        """``HipTable.simprint_exact_many`` for byte vectors: request r holds the distinct simprints ``vectors[distinct_offsets[r]:distinct_offsets[r + 1]]``."""
+        q_words, _ = pack_bytes(self._vectors(vectors), self._table.max_words)
+        return self._table.simprint_exact_many(q_words, distinct_offsets, given, given_offsets, queried, dup_limit, threshold, limit, detailed)
+
     @staticmethod
     def _shared_method(other, segments):
         # type: (HipIndex128 | None, bool) -> str

@@ -21,6 +21,9 @@ from iscc_search_amd.nphd import HipIndex128, words_to_key128
 
 CHUNK_POINTER_BYTES = 16
 EXACT_DEVICE_FROM = 128     # query simprints from which a hard-boundary search is scored on the device (isccsearch_simprint_exact)
+EXACT_MANY_FROM = 4         # batchable requests from which search_exact_many batches them: 2 requests lose to the loop (0.68x at 1 simprint,
+                            # 0.99x at 16), 4 win (1.23x / 1.67x) on the 10 M-chunk table (profiles/simprint_exact_many_10m.txt)
+EXACT_MANY_CHUNK_RECORDS = 1 << 26   # chunk records (24 bytes each) the output block of one isccsearch_simprint_exact_many call holds at most
 EXACT_FIRST_K = 64          # records per lookup a hard-boundary search asks for first (a full list is asked again up to dup_limit)
 DOC_FREQ_DUP_LIMIT = 1000   # duplicates looked at per simprint when counting its assets: the reference's safety cap
                             # (count_doc_freq(dup_limit=1000), lmdb_ops.py:139-166); HipIndex128.get_freq / doc_freq share it
@@ -410,18 +413,80 @@ class HipSimprintIndex:
         memory; document frequencies, the matches of every asset in visiting order, coverage x quality in the reference's float64
         operations, threshold, order and cut are kernels of ``csrc/simprint_score.hip``.
         """
-        index_of = {sp: i for i, sp in enumerate(distinct)}
-        valid = [sp for sp in given if sp in index_of]              # (a simprint of another length matches nothing)
-        lookups = np.fromiter((index_of[sp] for sp in valid), dtype=np.uint32, count=len(valid))
+        valid, lookups = self._exact_lookups(given, distinct)
         results, chunks, _ = self._index.exact_assets(_pack_simprints(distinct), lookups, len(given), max(1, dup_limit), threshold, limit, detailed)
+        return self._unpack_exact(len(given), valid, results, chunks, detailed)
+
+    @staticmethod
+    def _exact_lookups(given, distinct):
+        # type: (list[bytes], list[bytes]) -> tuple[list[bytes], np.ndarray]
+        """The given simprints of valid length (one of another length matches nothing) and, for each, its index among ``distinct``."""
+        index_of = {sp: i for i, sp in enumerate(distinct)}
+        valid = [sp for sp in given if sp in index_of]
+        return valid, np.fromiter((index_of[sp] for sp in valid), dtype=np.uint32, count=len(valid))
+
+    @staticmethod
+    def _unpack_exact(queried, valid, results, chunks, detailed):
+        # type: (int, list[bytes], np.ndarray, np.ndarray | None, bool) -> list[SimprintMatchRaw]
+        """One hard-boundary request's device results as ``SimprintMatchRaw``: ``chunks`` are the request's, their ``query`` a position in ``valid``."""
         body = [a.to_bytes(8, "big") for a in results["asset"].tolist()]
         scores, matches = results["score"].tolist(), results["matches"].tolist()
         if not detailed:
-            return [SimprintMatchRaw(b, s, len(given), m, None) for b, s, m in zip(body, scores, matches)]
+            return [SimprintMatchRaw(b, s, queried, m, None) for b, s, m in zip(body, scores, matches)]
         key_lo = chunks["key_lo"]
         cols = zip(chunks["query"].tolist(), (key_lo >> np.uint64(32)).tolist(), (key_lo & np.uint64(0xFFFFFFFF)).tolist(), chunks["freq"].tolist())
         detail = [MatchedChunkRaw(valid[g], valid[g], 1.0, o, z, f) for g, o, z, f in cols]
-        return [SimprintMatchRaw(b, s, len(given), m, detail[f : f + m]) for b, s, m, f in zip(body, scores, matches, results["first_chunk"].tolist())]
+        return [SimprintMatchRaw(b, s, queried, m, detail[f : f + m]) for b, s, m, f in zip(body, scores, matches, results["first_chunk"].tolist())]
+
+    def search_exact_many(self, requests, limit=10, threshold=0.0, detailed=False, dup_limit=1000):
+        # type: (list[list[bytes]], int, float, bool, int) -> list[list[SimprintMatchRaw]]
+        """
+        ``search_exact`` for many requests: result i equals ``search_exact(requests[i], limit, threshold, detailed, dup_limit)``, an
+        exception included (the first request in order that raises decides it).  On a table that scores many hard-boundary
+        requests itself (``isccsearch_simprint_exact_many``) every request with a simprint of the table's length and at most
+        ``MAX_SCORED_SIMPRINTS`` given simprints is looked up and scored on the device, in rounds of at most that many simprints,
+        one library search per round; a simprint of another length is left out of the lookups and counted in ``queried``.  The
+        others -- empty requests, those with only simprints of another length, larger ones, every request on other tables
+        (sharded, the CPU oracle), and all of them when fewer than ``EXACT_MANY_FROM`` can be batched (the loop is as fast or
+        faster there) -- run through ``search_exact``.
+        """
+        requests = [[bytes(s) for s in r] for r in requests]
+        one = lambda r: self.search_exact(r, limit=limit, threshold=threshold, detailed=detailed, dup_limit=dup_limit)
+        # (limit < 1 and a NaN threshold: search_exact's own answer, which depends on the path a request's size takes)
+        if len(self._index) == 0 or not self._index.scores_exact_many_on_device or limit < 1 or threshold != threshold:
+            return [one(r) for r in requests]
+        nbytes = self.ndim // 8
+        packed = {}      # request index -> (distinct simprints, given simprints of valid length, their lookups)
+        for i, given in enumerate(requests):
+            if given and len(given) <= MAX_SCORED_SIMPRINTS:
+                distinct = [sp for sp in dict.fromkeys(given) if len(sp) == nbytes]
+                if distinct:
+                    packed[i] = (distinct, *self._exact_lookups(given, distinct))
+        if len(packed) < EXACT_MANY_FROM:
+            return [one(r) for r in requests]
+        out = [None] * len(requests)  # type: list
+        k = min(max(1, dup_limit), MAX_K)
+        # (the chunk records of a call lie at k x given simprints: with chunks wanted a call takes what keeps that block under EXACT_MANY_CHUNK_RECORDS)
+        per_call = max(1, EXACT_MANY_CHUNK_RECORDS // k) if detailed else None
+        batched = list(packed)
+        while batched:
+            n, taken = 0, 0
+            while n < len(batched) and (n == 0 or per_call is None or taken + len(packed[batched[n]][1]) <= per_call):
+                taken += len(packed[batched[n]][1])
+                n += 1
+            call, batched = batched[:n], batched[n:]
+            d_off = np.zeros(len(call) + 1, dtype=np.uint32)
+            g_off = np.zeros(len(call) + 1, dtype=np.uint32)
+            d_off[1:] = np.cumsum([len(packed[i][0]) for i in call])
+            g_off[1:] = np.cumsum([len(packed[i][1]) for i in call])
+            results, chunks, info = self._index.exact_assets_many(
+                _pack_simprints([sp for i in call for sp in packed[i][0]]), d_off, np.concatenate([packed[i][2] for i in call]), g_off,
+                np.fromiter((len(requests[i]) for i in call), dtype=np.uint32, count=len(call)), max(1, dup_limit), threshold, limit, detailed)
+            for j, i in enumerate(call):
+                at = k * int(g_off[j])
+                out[i] = self._unpack_exact(len(requests[i]), packed[i][1], results[j, : int(info[j, 0])],
+                                            chunks[at : at + int(info[j, 3])] if detailed else None, detailed)
+        return [one(r) if res is None else res for r, res in zip(requests, out)]
 
     def _search_exact_host(self, simprints, distinct, limit, threshold, detailed, dup_limit):
         # type: (list[bytes], list[bytes], int, float, bool, int) -> list[SimprintMatchRaw]

@@ -5,12 +5,18 @@ loop, in one run, on one 128-bit simprint table of --chunks chunk fingerprints (
 
     python tools/bench_simprint_many.py                      # 10 M chunks, 1 024 requests x {16, 64} simprints, limits {20, 200}
     python tools/bench_simprint_many.py --chunks 1000000 --requests 256
+    python tools/bench_simprint_many.py --exact              # hard-boundary requests: search_exact_many beside the search_exact loop
 
 Requests: stored chunks with two bits flipped (approximate matches), threshold 0.75, detailed, device document frequencies
 (the arguments search_assets uses).  Per (simprints per request, limit) the two forms alternate --repeats times after a
 warm-up; every repeat prints requests/s of each, and the summary their medians and spread, the library searches and scan
 launches per batch (engine.stats()), and whether both forms returned identical results (scores compared with ==).
 Then search_assets_many against per-call search_assets on a manager index whose queries carry units and one simprint type.
+
+--exact: the hard-boundary mode on the same table instead -- HipSimprintIndex.search_exact_many (isccsearch_simprint_exact_many)
+beside a loop of search_exact, requests of stored chunks as they are (collisions), limit 20, detailed, dup_limit 1 000 (the
+arguments search_assets(exact=True) uses), at --requests requests of 16, 64 and 200 simprints and at 2 requests of 1 simprint
+(--exact-shapes 2x1,4x1,8x16: other (requests x simprints) shapes, e.g. the small ones that decide EXACT_MANY_FROM).
 """
 
 import argparse
@@ -104,6 +110,52 @@ def raw_bench(eng, idx, pool, args, n_assets, rng):
                                   loop=stats["loop"], many=stats["many"])), flush=True)
 
 
+def exact_bench(eng, idx, pool, args, rng):
+    in_lib = [0.0]
+    for name in ("exact_assets", "exact_assets_many", "search_arrays"):     # wall time inside the library calls of either form
+        inner = getattr(idx._index, name)
+
+        def timed(*a, _inner=inner, **kw):
+            t = time.perf_counter()
+            try:
+                return _inner(*a, **kw)
+            finally:
+                in_lib[0] += time.perf_counter() - t
+
+        setattr(idx._index, name, timed)
+    for n_req, nsp in args.exact_shapes:
+        q = pool[rng.integers(0, len(pool), size=n_req * nsp)]
+        reqs = [[bytes(r) for r in q[i * nsp:(i + 1) * nsp]] for i in range(n_req)]
+        kw = dict(limit=20, threshold=0.0, detailed=True, dup_limit=args.dup_limit)
+        loop = lambda: [idx.search_exact(r, **kw) for r in reqs]
+        many = lambda: idx.search_exact_many(reqs, **kw)
+        first = many()
+        ok = same(loop(), first)                     # (also the warm-up of both)
+        rates = {"loop": [], "many": []}
+        lib_ms = {"loop": [], "many": []}
+        stats = {}
+        for rep in range(args.repeats):
+            for form, fn in (("loop", loop), ("many", many)) if rep % 2 == 0 else (("many", many), ("loop", loop)):
+                s0 = eng.stats()
+                in_lib[0] = 0.0
+                t0 = time.perf_counter()
+                fn()
+                dt = time.perf_counter() - t0
+                s1 = eng.stats()
+                rates[form].append(n_req / dt)
+                lib_ms[form].append(in_lib[0] * 1e3)
+                stats[form] = dict(searches_per_batch=s1["searches"] - s0["searches"], scan_launches_per_batch=s1["scan_launches"] - s0["scan_launches"],
+                                   mfma_launches_per_batch=s1["mfma_launches"] - s0["mfma_launches"])
+                print(json.dumps(dict(repeat=rep, requests=n_req, simprints=nsp, form=form, requests_per_s=round(n_req / dt, 1),
+                                      ms_per_batch=round(dt * 1e3, 2), ms_in_library_per_batch=round(in_lib[0] * 1e3, 2))), flush=True)
+        lo, ma = spread(rates["loop"]), spread(rates["many"])
+        print(json.dumps(dict(summary="search_exact", chunks=idx.size, requests=n_req, simprints=nsp, limit=20, dup_limit=args.dup_limit, identical=ok,
+                              results=sum(len(r) for r in first), loop_requests_per_s=lo, many_requests_per_s=ma,
+                              speedup=round(ma["median"] / lo["median"], 2),
+                              loop_ms_in_library=spread(lib_ms["loop"])["median"], many_ms_in_library=spread(lib_ms["many"])["median"],
+                              loop=stats["loop"], many=stats["many"])), flush=True)
+
+
 def assets_bench(args, rng):
     m = HipIndexManager("hip:///")
     m.create_index(IsccIndex(name="bench"))
@@ -155,7 +207,12 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--manager-assets", type=int, default=20_000)
     ap.add_argument("--skip-raw", action="store_true")
+    ap.add_argument("--exact", action="store_true", help="the hard-boundary mode: search_exact_many beside the search_exact loop, and nothing else")
+    ap.add_argument("--dup-limit", type=int, default=1000, help="--exact: collisions listed per simprint (the rows per lookup of the batched form)")
+    ap.add_argument("--exact-shapes", default=None, help="requests x simprints per request, comma-separated (default: REQUESTSx16,REQUESTSx64,REQUESTSx200,2x1)")
     args = ap.parse_args()
+    shapes = args.exact_shapes or f"{args.requests}x16,{args.requests}x64,{args.requests}x200,2x1"
+    args.exact_shapes = [tuple(int(v) for v in item.split("x")) for item in shapes.split(",")]
     rng = np.random.default_rng(0)
     if not args.skip_raw:
         eng = HipEngine(0)
@@ -164,10 +221,14 @@ def main():
         t0 = time.perf_counter()
         idx, pool = build(eng, args.chunks, rng)
         print(json.dumps(dict(table="simprints ndim 128", chunks=idx.size, assets=args.chunks // CHUNKS_PER_ASSET, build_s=round(time.perf_counter() - t0, 1))), flush=True)
-        raw_bench(eng, idx, pool, args, args.chunks // CHUNKS_PER_ASSET, rng)
+        if args.exact:
+            exact_bench(eng, idx, pool, args, rng)
+        else:
+            raw_bench(eng, idx, pool, args, args.chunks // CHUNKS_PER_ASSET, rng)
         idx.close()
         eng.close()
-    assets_bench(args, rng)
+    if not args.exact:
+        assets_bench(args, rng)
 
 
 if __name__ == "__main__":
