@@ -139,7 +139,8 @@ struct Batch {
 
     // (+ 1e-9: a product within rounding of an integer counts as that integer, so that a row outside the radius lies beyond the
     //  ratio by >= 1e-9 / bits -- orders of magnitude more than the rounding of the k-th distance the caller compares with it)
-    int ratio_bits(const Job& j) const { const int bits = 8 * (int)j.pbytes; return std::min(bits, (int)std::floor(radius_ratio * bits + 1e-9)); }
+    int ratio_bits(int bits) const { return std::min(bits, (int)std::floor(radius_ratio * bits + 1e-9)); }
+    int ratio_bits(const Job& j) const { return ratio_bits(8 * (int)j.pbytes); }
     // the fixed threshold of a job's range-limited pass, or -1
     int job_radius(const Job& j) const {
         if (radius >= 0) return radius;

@@ -202,6 +202,17 @@ struct LockedBatch : LockedCall {
         }
         return worst;
     }
+    // ratio: every query holds k rows and its k-th lies inside the radius of its own compared prefix -- in bits, as the segments listed
+    // their rows.  (Not worst_ratio() <= radius_ratio: h / 192 and ratio + 1/32 round apart as doubles, and a k-th row at exactly
+    // 11/192 + 1/32 = 17/192, which its segment lists, was taken for a miss.)
+    bool kth_within_ratio() const {
+        for (uint32_t i = 0; i < m; ++i) {
+            if (p_cnt[i] < k) return false;
+            const isk::Record& r = p_rec[(size_t)i * k + k - 1];
+            if ((int)r.hamming > batch.ratio_bits((int)r.prefix_bits)) return false;
+        }
+        return true;
+    }
     // repair (tight): the queries in `short_q` (positions in this batch) alone, as a range-limited search under the whole hint -- which
     // neither reads nor updates a hint.  spec_ok: each of them holds k rows now and no list overflowed; their lists are spliced in.
     int repair(const std::vector<uint32_t>& short_q) {
@@ -243,8 +254,8 @@ struct LockedBatch : LockedCall {
     // verify: does the settled speculative step stand (spec_ok)?
     int verify() {
         int rc;
-        // (ratio: a row outside a radius lies beyond floor(ratio x bits) + 1 bits, strictly farther than the worst k-th NPHD)
-        if (spec == Spec::ratio) spec_ok = batch.complete(p_cnt, k) && worst_ratio() <= batch.radius_ratio;
+        // (ratio: a row outside a radius lies at floor(ratio x bits) + 1 bits or beyond, strictly farther than any k-th row inside its own)
+        if (spec == Spec::ratio) spec_ok = batch.complete(p_cnt, k) && kth_within_ratio();
         else if (spec != Spec::tight) spec_ok = batch.complete(p_cnt, seg->n);
         else {
             std::vector<uint32_t> short_q;          // (hintable: k <= rows, so a query is short of k)

@@ -409,6 +409,7 @@ def test_tables_of_several_code_lengths_speculate_per_segment(hip_engine):
     An ISCC-UNIT index holds 64 / 128 / 192 / 256-bit codes in ONE NPHD table.  Small batches over it are first tried with every
     segment listing its rows within (previous k-th NPHD) x compared bits + 2, merged and verified; near-duplicates, a query
     inside a cluster that overflows one segment's list, and queries of another length (their own hint) -- all against the oracle.
+    (On these random codes the 64-bit prefix fills the lists; lengths that interleave and tie: tests/test_gpu_nphd_mixed.py.)
     """
     from oracle import oracle_topk
 

@@ -161,7 +161,8 @@ def test_hamming_fixed_lengths_128bit_keys(hip_engine, nbytes):
 
 
 def test_nphd_mixed_lengths_vs_oracle(hip_engine):
-    """NPHD over 64/128/192/256-bit (and odd) code lengths, queries of every length."""
+    """NPHD over 64/128/192/256-bit (and odd) code lengths, queries of every length.
+    (Random codes: the 32-bit prefix fills the lists; lengths that interleave and tie: tests/test_gpu_nphd_mixed.py.)"""
     rng = np.random.default_rng(11)
     n, k = 60000, 20
     t = hip_engine.open_table(METRIC_NPHD, 1, 32)
