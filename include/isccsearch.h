@@ -105,7 +105,8 @@ typedef struct isccsearch_stats {
     /* with option "count_candidates" = 1: candidate-list entries the scan launches appended (summed over queries; the lists of the LAST pipeline run of
        every batch, read back after its synchronisation), and the batches they were counted over */
     uint64_t candidates, candidate_batches;
-    /* kernel launches of isccsearch_join_within / isccsearch_join_between, and how many of them ran on the matrix cores */
+    /* kernel launches of isccsearch_join_within / isccsearch_join_between (and of the other join calls: components, degrees, live pairs,
+       overlaps), and how many of them ran on the matrix cores */
     uint64_t join_launches, join_mfma_launches;
     /* queries that a fixed-radius pass of a large batch (option "radius_batches") left short of k rows and that were asked again,
        alone, under the whole hint -- counted when that second pass completed them (the step is then one of spec_hits) */
@@ -413,6 +414,40 @@ int isccsearch_join_between(isccsearch_handle* h, uint32_t table_a, uint32_t tab
 int isccsearch_join_components(isccsearch_handle* h, uint32_t table, const int16_t* max_hamming /* [33] */,
                                uint64_t n_live, const uint64_t* live_keys, const uint32_t* live_labels,
                                uint32_t n_labels, uint32_t* parent /* in/out [n_labels] */, uint64_t* out_links);
+
+/* The DEGREE of every listed row under the pairs of isccsearch_join_within, without the pairs: max_hamming, the prefix rule, the
+ * masking and the launches (one per pair of segments, la <= lb, the larger segment held, the same dispatch between the kernels) are
+ * those of isccsearch_join_within, but a row pair within its threshold is not written -- it adds 1 to a counter of either row on
+ * the device.  Memory: 4 bytes per listed key and 4 bytes per row (and the 8 bytes of every listed key), whatever the number of
+ * pairs, in the handle's scratch buffers; the call has no capacity and no -ENOSPC.  Which rows are the hubs of a table, and how
+ * many near-duplicates each row has, is answered without materialising h * (h - 1) / 2 pairs per hub of h rows.
+ *   live_keys[n_live]    strictly ascending: the rows that take part.  The LABEL of a row is the index of its key here.  A row
+ *                        whose key is not listed is compared but never counted.  A listed key the table does not hold does
+ *                        nothing; its degree is 0.  May be NULL only when n_live is 0 (as out_degree).
+ *   out_degree[n_live]   out_degree[i]: the number of OTHER listed rows within the threshold of the row of live_keys[i].
+ *   *out_links           the number of such pairs: sum(out_degree) == 2 * *out_links.  With every key of the table listed it is
+ *                        the *out_total of isccsearch_join_within.
+ * With fewer than two rows or n_live < 2 nothing is launched and the outputs are still filled (zeros).
+ * -EINVAL, each naming the offending index, all checked on the host before anything is launched, the outputs left untouched:
+ * a NULL argument; a table with key_words != 1; n_live >= 2^32 - 1 (the value that means "no label"); live_keys not strictly
+ * ascending.  One lock covers the call; everything runs on the handle's one stream and ONE synchronisation comes before the
+ * results are copied.  The launches count in stats join_launches / join_mfma_launches.
+ * No reference counterpart (the reference has no index-wide join). */
+int isccsearch_join_degrees(isccsearch_handle* h, uint32_t table, const int16_t* max_hamming /* [33] */,
+                            uint64_t n_live, const uint64_t* live_keys,
+                            uint32_t* out_degree /* [n_live] */, uint64_t* out_links);
+
+/* isccsearch_join_within over the listed rows only: the pairs of isccsearch_join_within whose two rows' keys are both in
+ * live_keys (strictly ascending; NULL only when n_live is 0; a row whose key is not listed is compared but takes no room and is
+ * not counted; a listed key the table does not hold does nothing).  Outputs, their order and the capacity protocol are those of
+ * isccsearch_join_within: -ENOSPC with *out_total exact, and a retry with exactly that capacity succeeds.  With every key of the
+ * table listed the outputs are byte for byte those of isccsearch_join_within.  With fewer than two rows or n_live < 2 nothing is
+ * launched and *out_total is 0.  Device memory: that of isccsearch_join_within plus 8 bytes per listed key and 4 bytes per row.
+ * -EINVAL and execution as for isccsearch_join_degrees (64-bit keys only). */
+int isccsearch_join_within_live(isccsearch_handle* h, uint32_t table, const int16_t* max_hamming /* [33] */,
+                                uint64_t n_live, const uint64_t* live_keys, uint64_t capacity,
+                                uint64_t* out_keys_a, uint64_t* out_keys_b,
+                                uint32_t* out_hamming, uint16_t* out_prefix_bits, uint64_t* out_total);
 
 /* The pairs of ASSETS that share chunks: a self-join of ONE simprint table (HAMMING, key_words 2, one code length of ndim bits),
  * aggregated on the device.  A row is a chunk; its asset is the first key word (the ISCC-ID body), the second is

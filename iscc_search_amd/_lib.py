@@ -31,7 +31,8 @@ EXPORTS = (
     "isccsearch_add_synthetic", "isccsearch_search", "isccsearch_search_within", "isccsearch_search_many", "isccsearch_doc_freq", "isccsearch_doc_freq_counted", "isccsearch_get_freq",
     "isccsearch_simprint_score", "isccsearch_simprint_score_many", "isccsearch_simprint_exact", "isccsearch_simprint_exact_many",
     "isccsearch_match_assets",
-    "isccsearch_join_within", "isccsearch_join_between", "isccsearch_join_components", "isccsearch_join_overlaps",
+    "isccsearch_join_within", "isccsearch_join_between", "isccsearch_join_components", "isccsearch_join_degrees",
+    "isccsearch_join_within_live", "isccsearch_join_overlaps",
     "isccsearch_join_segments", "isccsearch_join_overlaps_between", "isccsearch_join_segments_between",
     "isccsearch_search_device", "isccsearch_search_within_device", "isccsearch_merge_device",
     "isccsearch_search_device_async", "isccsearch_merge_device_after", "isccsearch_merge_many_after", "isccsearch_stream",
@@ -204,6 +205,8 @@ def load_library():
         "isccsearch_join_within": (i, [vp, u32, vp, u64, u64p, u64p, u32p, u16p, u64p]),
         "isccsearch_join_between": (i, [vp, u32, u32, vp, u64, u64p, u64p, u32p, u16p, u64p]),
         "isccsearch_join_components": (i, [vp, u32, vp, u64, u64p, u32p, u32, u32p, u64p]),
+        "isccsearch_join_degrees": (i, [vp, u32, vp, u64, u64p, u32p, u64p]),
+        "isccsearch_join_within_live": (i, [vp, u32, vp, u64, u64p, u64, u64p, u64p, u32p, u16p, u64p]),
         "isccsearch_join_overlaps": (i, [vp, u32, ctypes.c_int32, u32, u32, u32, u64p, u64, vp, u32p, u64p]),
         "isccsearch_join_segments": (i, [vp, u32, ctypes.c_int32, u32, u32, u32, u64p, u64, vp, vp, u32p, u64p]),
         "isccsearch_join_overlaps_between": (i, [vp, u32, u32, ctypes.c_int32, u32, u32, u32, u64p, u32, u64p, u32, u64, vp, u32p, u32p, u64p]),

@@ -383,6 +383,8 @@ struct isccsearch_handle {
     // isccsearch_join_components: the caller's live keys and their labels, a label per row (segment by segment), the union-find array
     DevBuf<uint64_t> d_join_live_keys;
     DevBuf<uint32_t> d_join_live_labels, d_join_row_labels, d_join_parent;
+    // isccsearch_join_degrees: a counter per listed key (its live keys and row labels: the buffers above; isccsearch_join_within_live: those and the pairs')
+    DevBuf<uint32_t> d_join_degree;
     // isccsearch_join_overlaps: the hits of one call {appended | sorted}, the one-hit records and the reduced ones, rocPRIM's temporary
     // storage (overlap.hip), chunks per asset; its asset keys go to d_join_live_keys, its row labels to d_join_row_labels
     // (isccsearch_join_overlaps_between: the same buffers, keys, chunks and labels of table A first and of table B behind them)

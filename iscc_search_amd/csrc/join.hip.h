@@ -31,6 +31,14 @@
 //     hamming) (overlap_write), which overlap.hip sorts and reduces.  CROSS: the two tables' labels live in two spaces told apart by
 //     LABEL_SIDE_B, so they always differ; what a pair can share is its asset KEY, and with JoinEmit::skip_same_key such a pair takes
 //     no slot.
+//   JoinForm::DEGREE (isccsearch_join_degrees, the self-join only): ONE pass, nothing written -- labels as for LINK; every candidate of
+//     two labelled rows adds 1 to JoinEmit::degree of either label, and one atomic per wave adds those pairs to JoinEmit::total.  The
+//     interesting input is a row with 10^4 .. 10^5 partners, so no global atomic is issued per pair: here the wave sums its lanes' count
+//     for an A row and lane 0 adds it once, and a lane keeps a register counter per streamed row across the A rows and adds each once;
+//     mfma_join_kernel counts its held rows in LDS and flushes them when the block has streamed its last step, and a streamed row
+//     gets at most one global atomic per ring walk ("The join forms": the contention rule).
+//   JoinForm::LIVE (isccsearch_join_within_live, the self-join only): PAIRS over labelled rows -- a candidate takes a slot only if its
+//     two rows both have a label (live_pair, asked in both passes so that slots and count agree); everything else is PAIRS'.
 // A form is a template parameter, so that no form's code changes another's; join_form_exists says which are instantiated.  The emit
 // branches of the two kernels are kept as they stand on purpose: the XOR + popcount kernel's hot loop is register-allocated together
 // with its inlined emit path, and its machine code moves with any change to that path ("The join forms").
@@ -72,6 +80,9 @@ struct JoinEmit {
     // the CROSS + OVERLAP form (isccsearch_join_overlaps_between): keys_a / keys_b are read too (128-bit keys, the asset is the first
     // word) -- when this is set, a pair of rows of equal asset key takes no slot
     uint32_t skip_same_key;
+    // the DEGREE form (isccsearch_join_degrees): labels_a / labels_b as for LINK; a pair of two labelled rows adds 1 to either label's
+    // entry, and `total` counts those pairs.  The LIVE form reads labels_a / labels_b and PAIRS' fields.
+    uint32_t* degree;             // [labels], zeroed
 };
 // isccsearch_join_overlaps_between: a label of a row of table B carries this bit, a label of table A does not (ranks stay below 2^31 - 1,
 // so that no label is UF_NONE)
@@ -103,9 +114,10 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t c) {
 }
 
 // ---- what a join leaves behind for the pairs it finds (the file comment describes the forms)
-enum class JoinForm : int { PAIRS, LINK, OVERLAP };
-// what exists: every form over one table and over two, except LINK (components are those of one table)
-constexpr bool join_form_exists(JoinForm f, bool cross) { return !(f == JoinForm::LINK && cross); }
+enum class JoinForm : int { PAIRS, LINK, OVERLAP, DEGREE, LIVE };
+// what exists: PAIRS and OVERLAP over one table and over two; LINK, DEGREE and LIVE over one (components, degrees and live rows are
+// those of one table)
+constexpr bool join_form_exists(JoinForm f, bool cross) { return f == JoinForm::PAIRS || f == JoinForm::OVERLAP || !cross; }
 template <JoinForm F, bool CROSS> struct JoinFormTag {
     static constexpr JoinForm form = F;
     static constexpr bool cross = CROSS;
@@ -117,6 +129,8 @@ template <typename Fn> bool with_join_form(JoinForm form, bool cross, Fn&& f) {
         case JoinForm::PAIRS: cross ? f(JoinFormTag<JoinForm::PAIRS, true>{}) : f(JoinFormTag<JoinForm::PAIRS, false>{}); return true;
         case JoinForm::LINK: f(JoinFormTag<JoinForm::LINK, false>{}); return true;
         case JoinForm::OVERLAP: cross ? f(JoinFormTag<JoinForm::OVERLAP, true>{}) : f(JoinFormTag<JoinForm::OVERLAP, false>{}); return true;
+        case JoinForm::DEGREE: f(JoinFormTag<JoinForm::DEGREE, false>{}); return true;
+        case JoinForm::LIVE: f(JoinFormTag<JoinForm::LIVE, false>{}); return true;
     }
     return false;
 }
@@ -127,6 +141,12 @@ __device__ __forceinline__ uint32_t link_pair(const JoinEmit& e, uint64_t i, uin
     if (la == UF_NONE || lb == UF_NONE) return 0u;
     uf_union(e.parent, la, lb);
     return 1u;
+}
+
+// LIVE form of both emit paths, per pair (held / SGPR-side row i, streamed row j): true if both rows have a label.  Both passes of an
+// emit path call this, so the slots and the count agree.
+__device__ __forceinline__ bool live_pair(const JoinEmit& e, uint64_t i, uint64_t j) {
+    return e.labels_a[i] != UF_NONE && e.labels_b[j] != UF_NONE;
 }
 
 // OVERLAP form of both emit paths, per pair (held / SGPR-side row i, streamed row j): the two rows' labels; true if the pair takes a
@@ -173,7 +193,7 @@ __device__ __forceinline__ void overlap_write(const JoinEmit& e, uint64_t slot, 
 template <int W, bool MASK, JoinForm F, bool CROSS>
 __global__ __launch_bounds__(BLOCK) void join_scan_kernel(const JoinParams p) {
     static_assert(join_form_exists(F, CROSS), "no such join form");
-    constexpr bool LINK = F == JoinForm::LINK, OVERLAP = F == JoinForm::OVERLAP;
+    constexpr bool LINK = F == JoinForm::LINK, OVERLAP = F == JoinForm::OVERLAP, DEGREE = F == JoinForm::DEGREE, LIVE = F == JoinForm::LIVE;
     constexpr int TQ = JoinCfg<W>::TQ, U = JoinCfg<W>::U;
     constexpr uint32_t SLAB = JoinCfg<W>::SLAB;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -236,6 +256,44 @@ __global__ __launch_bounds__(BLOCK) void join_scan_kernel(const JoinParams p) {
         const JoinEmit& e = *p.e;
         uint32_t c = 0;
         const uint64_t a_end = a0 + TQ < p.n_a ? a0 + TQ : p.n_a;
+        if (DEGREE) {                              // one pass, nothing written; no global atomic per pair (the file comment: contention)
+            uint32_t lbl[U][2], cj[U][2];          // the lane's streamed rows: label, and the labelled A rows within tau across the i-loop
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int rr = 0; rr < 2; ++rr) {
+                    const uint64_t j = base + u * 128 + rr;
+                    lbl[u][rr] = j < p.n_b ? e.labels_b[j] : UF_NONE;
+                    cj[u][rr] = 0;
+                }
+#pragma unroll 1
+            for (uint64_t i = a0; i < a_end; ++i) {
+                const uint32_t la = e.labels_a[i];  // (wave-uniform)
+                if (la == UF_NONE) continue;
+                uint32_t al[W], ah[W];
+                a_row(i, al, ah);
+                uint32_t ci = 0;
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+#pragma unroll
+                    for (int rr = 0; rr < 2; ++rr) {
+                        const uint32_t one = is_pair(i, base + u * 128 + rr, dist(r, u, rr, al, ah)) && lbl[u][rr] != UF_NONE ? 1u : 0u;
+                        cj[u][rr] += one;
+                        ci += one;
+                    }
+                const uint32_t of_row = wave_sum(ci);
+                if (of_row != 0 && lane == 0) atomicAdd(e.degree + la, of_row);
+                c += ci;
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int rr = 0; rr < 2; ++rr)
+                    if (cj[u][rr] != 0) atomicAdd(e.degree + lbl[u][rr], cj[u][rr]);
+            const uint32_t counted = wave_sum(c);
+            if (counted != 0 && lane == 0) atomicAdd(e.total, (unsigned long long)counted);
+            return;
+        }
 #pragma unroll 1
         for (uint64_t i = a0; i < a_end; ++i) {
             uint32_t al[W], ah[W];
@@ -247,6 +305,7 @@ __global__ __launch_bounds__(BLOCK) void join_scan_kernel(const JoinParams p) {
                     const bool pair = is_pair(i, base + u * 128 + rr, dist(r, u, rr, al, ah));
                     if (LINK) c += pair ? link_pair(e, i, base + u * 128 + rr) : 0u;
                     else if (OVERLAP) { uint32_t la, lb; c += pair && overlap_pair<CROSS>(e, i, base + u * 128 + rr, la, lb) ? 1u : 0u; }
+                    else if (LIVE) c += pair && live_pair(e, i, base + u * 128 + rr) ? 1u : 0u;
                     else c += pair ? 1u : 0u;
                 }
         }
@@ -304,6 +363,7 @@ __global__ __launch_bounds__(BLOCK) void join_scan_kernel(const JoinParams p) {
                     const uint64_t j = base + u * 128 + rr;
                     const uint32_t h = dist(r, u, rr, al, ah);
                     if (!is_pair(i, j, h)) continue;
+                    if (LIVE && !live_pair(e, i, j)) continue;
                     if (slot < e.capacity) {
                         uint64_t ka_hi = kw == 2 ? e.keys_a[i * 2] : 0, ka_lo = e.keys_a[i * kw + kw - 1];
                         uint64_t kb_hi = kw == 2 ? e.keys_b[j * 2] : 0, kb_lo = e.keys_b[j * kw + kw - 1];

@@ -1,8 +1,9 @@
 // join_api.hip.h -- isccsearch_join_within and isccsearch_join_between: the self-join of a table and the cross join of two
 // tables by the XOR + popcount kernel of join.hip.h or, for launches over enough rows, its matrix-core form (mfma_join_kernel.hip.h);
 // and isccsearch_join_components: the self-join's launches in their LINK form, whose pairs are united in a union-find array
-// (unionfind.hip.h) instead of written; and isccsearch_join_overlaps: the self-join of a simprint table in the launches' OVERLAP form,
-// whose directed hits overlap.hip sorts and reduces to one record per ordered pair of assets; and isccsearch_join_segments: the same
+// (unionfind.hip.h) instead of written; and isccsearch_join_degrees: those launches in their DEGREE form, which leave a count per listed
+// row; and isccsearch_join_within_live: the self-join's pairs among the listed rows (the LIVE form); and isccsearch_join_overlaps:
+// the self-join of a simprint table in the launches' OVERLAP form, whose directed hits overlap.hip sorts and reduces to one record per ordered pair of assets; and isccsearch_join_segments: the same
 // call, whose chunk pairs segments.hip turns into aligned runs before they are reduced; and isccsearch_join_overlaps_between: the
 // cross join of two simprint tables in the same OVERLAP form, with a label space per table; and isccsearch_join_segments_between:
 // that call with the same stage of segments.hip over the two tables.
@@ -50,6 +51,7 @@ struct JoinPlan {
     uint32_t* parent = nullptr;                    // LINK: the union-find array
     uint4* out_hits = nullptr;                     // OVERLAP: [2 * capacity]
     bool skip_same_key = false;                    // OVERLAP, cross
+    uint32_t* degree = nullptr;                    // DEGREE: a counter per label
 };
 
 int join_check_args(isccsearch_handle* h, const int16_t* max_hamming, uint64_t capacity, uint64_t* out_keys_a, uint64_t* out_keys_b,
@@ -63,7 +65,7 @@ int join_check_args(isccsearch_handle* h, const int16_t* max_hamming, uint64_t c
 }
 
 // The plan of one call in the form (form, cross) and the call's counters, zeroed ([0] is the pair counter every launch adds to).  The
-// PAIRS form's output buffers are sized here; LINK and OVERLAP write none of them.
+// output buffers of PAIRS (and LIVE, which writes what PAIRS writes) are sized here; LINK, OVERLAP and DEGREE write none of them.
 int join_begin(isccsearch_handle* h, JoinPlan& plan, isk::JoinForm form, bool cross, uint32_t KW, uint64_t capacity, uint32_t n_counters = 1) {
     plan.form = form;
     plan.cross = cross;
@@ -71,7 +73,7 @@ int join_begin(isccsearch_handle* h, JoinPlan& plan, isk::JoinForm form, bool cr
     plan.capacity = capacity;
     plan.cap_alloc = std::max<uint64_t>(capacity, 1);
     int rc;
-    if (form == isk::JoinForm::PAIRS) {
+    if (form == isk::JoinForm::PAIRS || form == isk::JoinForm::LIVE) {
         if ((rc = h->d_join_keys.ensure(plan.cap_alloc * 2 * KW))) return rc;
         if ((rc = h->d_join_ham.ensure(plan.cap_alloc))) return rc;
         if ((rc = h->d_join_pb.ensure(plan.cap_alloc))) return rc;
@@ -83,7 +85,7 @@ int join_begin(isccsearch_handle* h, JoinPlan& plan, isk::JoinForm form, bool cr
 
 // One launch: segment A (one block per TQ rows, the rows in SGPRs) against segment B (streamed by every block) over a common
 // prefix of pbytes bytes under tau.  `same`: A and B are one segment (the self-join keeps row_a < row_b).  `sgpr_side_is_b`:
-// a cross join whose segment A belongs to the call's table_b.  labels_a / labels_b: a label per row of A / B, for LINK and OVERLAP.
+// a cross join whose segment A belongs to the call's table_b.  labels_a / labels_b: a label per row of A / B, for every form but PAIRS.
 // On the matrix cores (options mfma, join_mfma; both segments of at least join_mfma_min_rows rows) segment A is the HELD side --
 // chunks of its rows in LDS, what the SGPRs are to join_scan_kernel -- and B is streamed: the same roles, the same JoinEmit.
 int join_add(isccsearch_handle* h, JoinPlan& plan, Segment& A, Segment& B, uint32_t pbytes, int tau, bool same, bool sgpr_side_is_b,
@@ -102,6 +104,9 @@ int join_add(isccsearch_handle* h, JoinPlan& plan, Segment& A, Segment& B, uint3
     e.capacity = plan.capacity;
     e.total = reinterpret_cast<unsigned long long*>(h->d_join_total.p);
     switch (plan.form) {
+        case isk::JoinForm::LIVE:
+            e.labels_a = labels_a; e.labels_b = labels_b;
+            [[fallthrough]];
         case isk::JoinForm::PAIRS:
             e.keys_a = A.keys; e.keys_b = B.keys;
             e.out_keys_a = h->d_join_keys.p;
@@ -122,6 +127,10 @@ int join_add(isccsearch_handle* h, JoinPlan& plan, Segment& A, Segment& B, uint3
             e.keys_a = A.keys; e.keys_b = B.keys;      // (skip_same_key compares the rows' asset keys)
             e.skip_same_key = plan.skip_same_key ? 1u : 0u;
             break;
+        case isk::JoinForm::DEGREE:
+            e.labels_a = labels_a; e.labels_b = labels_b;
+            e.degree = plan.degree;
+            break;
     }
     // within one segment the last row pairs with no later one
     const uint64_t a_rows = same ? A.n - 1 : A.n;
@@ -139,8 +148,7 @@ int join_add(isccsearch_handle* h, JoinPlan& plan, Segment& A, Segment& B, uint3
         L.mp.mask_lo = (uint32_t)L.jp.mask; L.mp.mask_hi = (uint32_t)(L.jp.mask >> 32);
         L.mp.tau = L.jp.tau;
         L.mp.same = L.jp.same;
-        // (any count from 2^20 rows on sizes the chunk alike: as many groups as 40 KB of LDS hold)
-        L.groups = isk::mfma_groups_per_chunk((int)W, (uint32_t)std::min<uint64_t>(A.n, 1u << 20), false);
+        L.groups = isk::mfma_join_groups_per_chunk((int)W, A.n, plan.form);
         L.chunks = (A.n + L.groups * 32 - 1) / (L.groups * 32);
     }
     plan.launches.push_back(L);
@@ -160,6 +168,35 @@ template <typename Add> int join_self_pairs(Table& t, const int16_t* max_hamming
             const uint32_t a_len = t.seg[lb].n > t.seg[la].n ? lb : la, b_len = a_len == la ? lb : la;
             if (int rc = add(a_len, b_len, la, same)) return rc;
         }
+    }
+    return 0;
+}
+
+// A label per row of a table of 64-bit keys, segment by segment, queued on the handle's stream: live_keys (strictly ascending, checked by
+// the caller) and their labels go to the device, label_rows_kernel runs once per segment (the host never sees the table's keys), and
+// row_labels[l] names the labels of segment l in d_join_row_labels.  live_labels NULL: the label of a key is its index in live_keys.
+int join_label_rows(isccsearch_handle* h, Table& t, uint64_t n_live, const uint64_t* live_keys, const uint32_t* live_labels,
+                    uint32_t* (&row_labels)[ISCCSEARCH_MAX_BYTES + 1]) {
+    int rc;
+    if ((rc = h->d_join_live_keys.ensure(std::max<uint64_t>(n_live, 1)))) return rc;
+    if (live_labels && (rc = h->d_join_live_labels.ensure(std::max<uint64_t>(n_live, 1)))) return rc;
+    uint64_t all_rows = 0;
+    for (uint32_t l = 1; l <= ISCCSEARCH_MAX_BYTES; ++l) all_rows += t.seg[l].n;
+    if ((rc = h->d_join_row_labels.ensure(std::max<uint64_t>(all_rows, 1)))) return rc;
+    if (n_live) {
+        HIPOK(hipMemcpyAsync(h->d_join_live_keys.p, live_keys, n_live * 8, hipMemcpyHostToDevice, h->stream));
+        if (live_labels) HIPOK(hipMemcpyAsync(h->d_join_live_labels.p, live_labels, n_live * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    uint64_t rows = 0;
+    for (uint32_t l = 1; l <= ISCCSEARCH_MAX_BYTES; ++l) {
+        const Segment& s = t.seg[l];
+        row_labels[l] = nullptr;
+        if (!s.n) continue;
+        row_labels[l] = h->d_join_row_labels.p + rows;
+        rows += s.n;
+        isk::LabelParams lp{s.keys, h->d_join_live_keys.p, live_labels ? h->d_join_live_labels.p : nullptr, row_labels[l], s.n, n_live};
+        hipLaunchKernelGGL(isk::label_rows_kernel, dim3(row_blocks(s.n)), dim3(isk::BLOCK), 0, h->stream, lp);
+        HIPOK(hipGetLastError());
     }
     return 0;
 }
@@ -330,29 +367,11 @@ extern "C" int isccsearch_join_components(isccsearch_handle* h, uint32_t table, 
     HIPOK(hipSetDevice(h->device));
     JoinPlan plan;
     if ((rc = join_begin(h, plan, isk::JoinForm::LINK, false, 1, 0))) return rc;
-    if ((rc = h->d_join_live_keys.ensure(std::max<uint64_t>(n_live, 1)))) return rc;
-    if ((rc = h->d_join_live_labels.ensure(std::max<uint64_t>(n_live, 1)))) return rc;
-    uint64_t all_rows = 0;
-    for (uint32_t l = 1; l <= ISCCSEARCH_MAX_BYTES; ++l) all_rows += t.seg[l].n;
-    if ((rc = h->d_join_row_labels.ensure(std::max<uint64_t>(all_rows, 1)))) return rc;
     if ((rc = h->d_join_parent.ensure(n_labels))) return rc;
-    if (n_live) {
-        HIPOK(hipMemcpyAsync(h->d_join_live_keys.p, live_keys, n_live * 8, hipMemcpyHostToDevice, h->stream));
-        HIPOK(hipMemcpyAsync(h->d_join_live_labels.p, live_labels, n_live * 4, hipMemcpyHostToDevice, h->stream));
-    }
     HIPOK(hipMemcpyAsync(h->d_join_parent.p, parent, (size_t)n_labels * 4, hipMemcpyHostToDevice, h->stream));
     // a label per row, segment by segment
     uint32_t* row_labels[ISCCSEARCH_MAX_BYTES + 1] = {};
-    uint64_t rows = 0;
-    for (uint32_t l = 1; l <= ISCCSEARCH_MAX_BYTES; ++l) {
-        const Segment& s = t.seg[l];
-        if (!s.n) continue;
-        row_labels[l] = h->d_join_row_labels.p + rows;
-        rows += s.n;
-        isk::LabelParams lp{s.keys, h->d_join_live_keys.p, h->d_join_live_labels.p, row_labels[l], s.n, n_live};
-        hipLaunchKernelGGL(isk::label_rows_kernel, dim3(row_blocks(s.n)), dim3(isk::BLOCK), 0, h->stream, lp);
-        HIPOK(hipGetLastError());
-    }
+    if ((rc = join_label_rows(h, t, n_live, live_keys, live_labels, row_labels))) return rc;
     // the launches of isccsearch_join_within
     plan.parent = h->d_join_parent.p;
     rc = join_self_pairs(t, max_hamming, [&](uint32_t a_len, uint32_t b_len, uint32_t pbytes, bool same) {
@@ -368,6 +387,91 @@ extern "C" int isccsearch_join_components(isccsearch_handle* h, uint32_t table, 
     if ((rc = join_total(h, out_links))) return rc;
     memcpy(parent, flat.data(), (size_t)n_labels * 4);
     return 0;
+}
+
+// isccsearch_join_degrees and isccsearch_join_within_live: the launches of isccsearch_join_within over the rows whose keys are listed, the
+// label of a row being the index of its key in live_keys (join_label_rows without a label array).
+namespace {
+// what the two calls check alike, on the host, before anything is launched and before any output is touched; `t`: the table, locked
+int join_live_check(isccsearch_handle* h, const char* name, uint32_t table, uint64_t n_live, const uint64_t* live_keys, Table*& t) {
+    if (n_live >= isk::UF_NONE)
+        return fail(-EINVAL, "n_live must be below 2^32 - 1 (the value that means \"no label\"), got %llu", (unsigned long long)n_live);
+    if (int rc = check_ascending("live_keys", live_keys, n_live)) return rc;
+    if (int rc = get_table(h, table, t)) return rc;
+    if (t->key_words != 1) return fail(-EINVAL, "%s needs a table of 64-bit keys (key_words 1), table %u has key_words %d", name, table, t->key_words);
+    return 0;
+}
+uint64_t table_rows(const Table& t) {
+    uint64_t rows = 0;
+    for (uint32_t l = 1; l <= ISCCSEARCH_MAX_BYTES; ++l) rows += t.seg[l].n;
+    return rows;
+}
+}  // namespace
+
+// The launches of isccsearch_join_within in their DEGREE form between label_rows_kernel and the copies, all on one stream: a counter per
+// listed key (zeroed) and the links come back behind one synchronisation.
+extern "C" int isccsearch_join_degrees(isccsearch_handle* h, uint32_t table, const int16_t* max_hamming, uint64_t n_live, const uint64_t* live_keys,
+                            uint32_t* out_degree, uint64_t* out_links) {
+    if (!h) return fail(-EINVAL, "handle is NULL");
+    if (!max_hamming || !out_links || (n_live && (!live_keys || !out_degree))) return fail(-EINVAL, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    Table* tp;
+    int rc;
+    if ((rc = join_live_check(h, "join_degrees", table, n_live, live_keys, tp))) return rc;
+    Table& t = *tp;
+    if (n_live < 2 || table_rows(t) < 2) {            // no pair of listed rows: nothing is launched
+        if (n_live) memset(out_degree, 0, (size_t)n_live * 4);
+        *out_links = 0;
+        return 0;
+    }
+    HIPOK(hipSetDevice(h->device));
+    JoinPlan plan;
+    if ((rc = join_begin(h, plan, isk::JoinForm::DEGREE, false, 1, 0))) return rc;
+    if ((rc = h->d_join_degree.ensure(n_live))) return rc;
+    HIPOK(hipMemsetAsync(h->d_join_degree.p, 0, (size_t)n_live * 4, h->stream));
+    uint32_t* row_labels[ISCCSEARCH_MAX_BYTES + 1] = {};
+    if ((rc = join_label_rows(h, t, n_live, live_keys, nullptr, row_labels))) return rc;
+    plan.degree = h->d_join_degree.p;
+    rc = join_self_pairs(t, max_hamming, [&](uint32_t a_len, uint32_t b_len, uint32_t pbytes, bool same) {
+        return join_add(h, plan, t.seg[a_len], t.seg[b_len], pbytes, max_hamming[pbytes], same, false, row_labels[a_len], row_labels[b_len]);
+    });
+    if (rc) return rc;
+    if ((rc = join_run(h, plan))) return rc;
+    // the counters go to a copy first: the outputs change only once the whole call has succeeded
+    std::vector<uint32_t> degree(n_live);
+    uint64_t links = 0;
+    HIPOK(hipMemcpyAsync(degree.data(), h->d_join_degree.p, (size_t)n_live * 4, hipMemcpyDeviceToHost, h->stream));
+    if ((rc = join_total(h, &links))) return rc;
+    memcpy(out_degree, degree.data(), (size_t)n_live * 4);
+    *out_links = links;
+    return 0;
+}
+
+// The launches of isccsearch_join_within in their LIVE form behind label_rows_kernel; the tail is that of the pair joins.
+extern "C" int isccsearch_join_within_live(isccsearch_handle* h, uint32_t table, const int16_t* max_hamming, uint64_t n_live, const uint64_t* live_keys,
+                                uint64_t capacity, uint64_t* out_keys_a, uint64_t* out_keys_b, uint32_t* out_hamming, uint16_t* out_prefix_bits,
+                                uint64_t* out_total) {
+    if (!h) return fail(-EINVAL, "handle is NULL");
+    if (!max_hamming || !out_total || (n_live && !live_keys)) return fail(-EINVAL, "NULL argument");
+    if (capacity && (!out_keys_a || !out_keys_b || !out_hamming || !out_prefix_bits))
+        return fail(-EINVAL, "NULL output array with capacity %llu", (unsigned long long)capacity);
+    std::lock_guard<std::mutex> lk(h->mu);
+    Table* tp;
+    int rc;
+    if ((rc = join_live_check(h, "join_within_live", table, n_live, live_keys, tp))) return rc;
+    Table& t = *tp;
+    *out_total = 0;
+    if (n_live < 2 || table_rows(t) < 2) return 0;     // no pair of listed rows: nothing is launched
+    HIPOK(hipSetDevice(h->device));
+    JoinPlan plan;
+    if ((rc = join_begin(h, plan, isk::JoinForm::LIVE, false, 1, capacity))) return rc;
+    uint32_t* row_labels[ISCCSEARCH_MAX_BYTES + 1] = {};
+    if ((rc = join_label_rows(h, t, n_live, live_keys, nullptr, row_labels))) return rc;
+    rc = join_self_pairs(t, max_hamming, [&](uint32_t a_len, uint32_t b_len, uint32_t pbytes, bool same) {
+        return join_add(h, plan, t.seg[a_len], t.seg[b_len], pbytes, max_hamming[pbytes], same, false, row_labels[a_len], row_labels[b_len]);
+    });
+    if (rc) return rc;
+    return join_finish(h, plan, out_keys_a, out_keys_b, out_hamming, out_prefix_bits, out_total);
 }
 
 // The overlap joins: isccsearch_join_overlaps and isccsearch_join_segments over ONE side (the self-join of a simprint table's one segment)

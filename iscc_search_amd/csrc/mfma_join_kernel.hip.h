@@ -16,7 +16,12 @@
 //   Hits go through the per-wave LDS ring of saved accumulator blocks as in mfma_scan_kernel.  The ring walk (`process_ring`) is this
 //   kernel's emit path; join.hip.h's file comment describes the forms F and CROSS once for both kernels.  The held side takes the part
 //   the SGPR side has in join_scan_kernel (JoinEmit::keys_a, labels_a, sgpr_side_is_b).  PAIRS and OVERLAP walk the ring twice (count,
-//   ONE returned atomic on JoinEmit::total for the walk, write; each walk rcount / 2 <= RING_E / 2 trips), LINK once.
+//   ONE returned atomic on JoinEmit::total for the walk, write; each walk rcount / 2 <= RING_E / 2 trips; LIVE is PAIRS with live_pair
+//   asked in both walks), LINK once.
+//   DEGREE walks once too and issues no global atomic per pair: the held rows of the chunk are counted in an LDS array of groups * 32
+//   counters behind the rings (one LDS add per saved block: its 32 results belong to one held row), flushed to JoinEmit::degree
+//   when the block has streamed its last step -- so no wave of a DEGREE block returns before that barrier --, and the streamed rows
+//   of the step in two registers per lane, folded across the wave's halves: at most one global atomic per streamed row and walk.
 #pragma once
 
 #include "join.hip.h"
@@ -26,10 +31,11 @@
 namespace isk {
 
 // LDS image of a chunk: B fragments [groups][W][64] v4i | thr[groups * 32] (float) | popc[groups * 32] | the waves' rings
+// | DEGREE only: degree[groups * 32] (mfma_join_lds_bytes)
 template <int W, JoinForm F, bool CROSS>
 __global__ __launch_bounds__(MBLOCK, mfma_min_waves<W>()) void mfma_join_kernel(const MfmaJoinParams p, const uint32_t groups) {
     static_assert(join_form_exists(F, CROSS), "no such join form");
-    constexpr bool LINK = F == JoinForm::LINK, OVERLAP = F == JoinForm::OVERLAP;
+    constexpr bool LINK = F == JoinForm::LINK, OVERLAP = F == JoinForm::OVERLAP, DEGREE = F == JoinForm::DEGREE, LIVE = F == JoinForm::LIVE;
     constexpr int MT = 2;       // row tiles (32 rows) per wave and step
     constexpr uint32_t WAVES = MBLOCK / 64;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -78,6 +84,10 @@ __global__ __launch_bounds__(MBLOCK, mfma_min_waves<W>()) void mfma_join_kernel(
         lpop[ql] = pc;
         lthr[ql] = thr;
     }
+    // DEGREE: the chunk's counters, behind the rings
+    uint32_t* const ldeg = DEGREE ? reinterpret_cast<uint32_t*>(lpop + groups * 32) + WAVES * (PK_RING_ENTRIES * PK_RING_ENTRY_DWORDS) : nullptr;
+    if (DEGREE)
+        for (uint32_t ql = tid; ql < groups * 32; ql += MBLOCK) ldeg[ql] = 0;
     __syncthreads();
 
     const uint64_t stride = (uint64_t)live_blocks * WAVES;
@@ -85,7 +95,7 @@ __global__ __launch_bounds__(MBLOCK, mfma_min_waves<W>()) void mfma_join_kernel(
     constexpr bool SCALAR_STEPS = W >= 2;
     const uint32_t wave_u = SCALAR_STEPS ? (uint32_t)__builtin_amdgcn_readfirstlane((int)wave) : wave;
     uint64_t step = first + (uint64_t)blockIdx.x * WAVES + wave_u;
-    if (step >= nsteps) return;
+    if (!DEGREE && step >= nsteps) return;      // (DEGREE: a wave without a step runs no trip of the step loop and waits at the flush)
     const uint64_t last_row = p.n_s - 1;
 
     const uint32_t* col32[W];
@@ -114,6 +124,38 @@ __global__ __launch_bounds__(MBLOCK, mfma_min_waves<W>()) void mfma_join_kernel(
             return v <= thr && j <= last_row && (CROSS || !p.same || j > i);
         };
         uint32_t c = 0;
+        if (DEGREE) {                              // one walk, nothing written: LDS adds for the held rows, two registers for the streamed rows
+            const JoinEmit& e = *p.e;
+            // the lane's two streamed rows of this step (pair_at: head >> 16 is 0 or 1) and their labels
+            const uint64_t j0 = st * (32 * MT) + off0;
+            const uint32_t lb0 = j0 <= last_row ? e.labels_b[j0] : UF_NONE, lb1 = j0 + 4 <= last_row ? e.labels_b[j0 + 4] : UF_NONE;
+            uint32_t c0 = 0, c1 = 0;
+            for (uint32_t en = 0; en < rcount; en += 2) {
+                uint64_t i = q0, j = j0;            // (pair_at leaves them alone past the ring's count)
+                uint32_t hd;
+                const bool pair = pair_at(en + sub, i, j, hd);
+                const bool upper = j != j0;
+                const bool both = pair && (upper ? lb1 : lb0) != UF_NONE && e.labels_a[i] != UF_NONE;
+                // the 32 results of a saved block are of ONE held row: one LDS add per block, by the first lane of its half
+                const uint64_t hits = __builtin_amdgcn_ballot_w64(both);
+                const uint32_t of_block = (uint32_t)__builtin_popcount((uint32_t)(hits >> (32 * sub)));
+                if (ri == 0 && of_block != 0) atomicAdd(ldeg + (uint32_t)(i - q0), of_block);
+                c0 += both && !upper ? 1u : 0u;
+                c1 += both && upper ? 1u : 0u;
+            }
+            c = c0 + c1;
+            // lanes v and v + 32 hold the same two streamed rows: fold, the lower half adds
+            c0 += (uint32_t)__shfl_xor((int)c0, 32, 64);
+            c1 += (uint32_t)__shfl_xor((int)c1, 32, 64);
+            if (sub == 0) {
+                if (c0 != 0) atomicAdd(e.degree + lb0, c0);
+                if (c1 != 0) atomicAdd(e.degree + lb1, c1);
+            }
+            const uint32_t counted = wave_sum(c);
+            if (counted != 0 && lane == 0) atomicAdd(e.total, (unsigned long long)counted);
+            rcount = 0;
+            return;
+        }
         if (LINK) {                                // one walk: the labelled pairs are united as they are counted, nothing is written
             const JoinEmit& e = *p.e;
             for (uint32_t en = 0; en < rcount; en += 2) {
@@ -149,7 +191,7 @@ __global__ __launch_bounds__(MBLOCK, mfma_min_waves<W>()) void mfma_join_kernel(
         for (uint32_t en = 0; en < rcount; en += 2) {
             uint64_t i, j;
             uint32_t hd;
-            c += pair_at(en + sub, i, j, hd) ? 1u : 0u;
+            c += pair_at(en + sub, i, j, hd) && (!LIVE || live_pair(*p.e, i, j)) ? 1u : 0u;
         }
         // wave-inclusive prefix of the counts; lane 63 holds the walk's total
         uint32_t incl = c;
@@ -172,6 +214,7 @@ __global__ __launch_bounds__(MBLOCK, mfma_min_waves<W>()) void mfma_join_kernel(
                 uint64_t i, j;
                 uint32_t hd;
                 if (!pair_at(en + sub, i, j, hd)) continue;
+                if (LIVE && !live_pair(e, i, j)) continue;
                 if (slot < e.capacity) {
                     uint64_t ka_hi = kw == 2 ? e.keys_a[i * 2] : 0, ka_lo = e.keys_a[i * kw + kw - 1];
                     uint64_t kb_hi = kw == 2 ? e.keys_b[j * 2] : 0, kb_lo = e.keys_b[j * kw + kw - 1];
@@ -321,6 +364,14 @@ __global__ __launch_bounds__(MBLOCK, mfma_min_waves<W>()) void mfma_join_kernel(
 #pragma unroll
             for (int w = 0; w < W; ++w) x[t][w] = xn[t][w];
         if (rcount) process_ring(step);
+    }
+    if (DEGREE) {                                   // the block has streamed its last step: one global atomic per counted held row
+        __syncthreads();
+        const JoinEmit& e = *p.e;
+        for (uint32_t ql = tid; ql < groups * 32; ql += MBLOCK) {
+            const uint32_t d = ldeg[ql];
+            if (d != 0) atomicAdd(e.degree + e.labels_a[q0 + ql], d);      // (counted: the row exists and has a label)
+        }
     }
 }
 

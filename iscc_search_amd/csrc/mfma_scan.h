@@ -28,7 +28,7 @@ int launch_mfma_scan(int W, int mode, bool pack, uint32_t blocks_x, uint32_t gro
 // ---- the joins on the matrix cores (mfma_join_kernel.hip.h): a block HOLDS a chunk of `groups` * 32 rows of one segment in LDS and
 // streams the other segment, 64 rows per wave and step
 struct JoinEmit;                  // join.hip.h: what only the emit path reads
-enum class JoinForm : int;        // join.hip.h: what a join leaves behind for its pairs (PAIRS, LINK, OVERLAP)
+enum class JoinForm : int;        // join.hip.h: what a join leaves behind for its pairs (PAIRS, LINK, OVERLAP, DEGREE, LIVE)
 struct MfmaJoinParams {
     const uint64_t* col_q[4];     // the held segment's columns (word-major); JoinEmit::keys_a are its keys
     const uint64_t* col_s[4];     // the streamed segment's; JoinEmit::keys_b
@@ -53,8 +53,12 @@ __host__ __device__ inline uint32_t mfma_join_live_blocks(uint64_t steps, uint32
 inline uint32_t mfma_join_blocks_x(uint64_t n_streamed) {
     return mfma_join_live_blocks((n_streamed + MFMA_JOIN_STEP_ROWS - 1) / MFMA_JOIN_STEP_ROWS, MFMA_JOIN_MAX_BLOCKS_X);
 }
-// rows of the held segment per chunk: mfma_groups_per_chunk(W, n_held, false) * 32
-// grid = (blocks_x, chunks); p.chunk_base names the first of them.  Returns 0 or a hipError_t as launch_mfma_scan does
+// groups of the held segment (n_held rows) per chunk, and the chunk's LDS image: those of mfma_groups_per_chunk(W, n_held, false) and
+// mfma_lds_bytes for every form but DEGREE, whose image carries 4 bytes more per held row (its LDS counters) and whose chunk is as many
+// groups fewer as that takes to fit MFMA_MAX_LDS (64-bit codes: 30 groups for 32)
+uint32_t mfma_join_groups_per_chunk(int W, uint64_t n_held, JoinForm form);
+size_t mfma_join_lds_bytes(int W, uint32_t groups, JoinForm form);
+// grid = (blocks_x, chunks of `groups` = mfma_join_groups_per_chunk groups); p.chunk_base names the first of them.  Returns 0 or a hipError_t as launch_mfma_scan does
 // (form, cross): the emit path of join.hip.h; a combination that join_form_exists does not list is refused like a chunk that does not fit
 int launch_mfma_join(int W, JoinForm form, bool cross, uint32_t blocks_x, uint32_t chunks, uint32_t groups, hipStream_t st, const MfmaJoinParams& p);
 

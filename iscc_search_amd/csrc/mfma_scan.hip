@@ -118,9 +118,20 @@ int launch_mfma_scan(int W, int mode, bool pack, uint32_t blocks_x, uint32_t gro
     return 0;
 }
 
+// the joins' chunk: the scan's image; DEGREE adds a counter per held row behind the rings and gives up pairs of groups until that fits
+size_t mfma_join_lds_bytes(int W, uint32_t groups, JoinForm form) {
+    return mfma_lds_bytes(W, groups) + (form == JoinForm::DEGREE ? (size_t)groups * 32 * sizeof(uint32_t) : 0);
+}
+uint32_t mfma_join_groups_per_chunk(int W, uint64_t n_held, JoinForm form) {
+    // (any count from 2^20 rows on sizes the chunk alike: as many groups as 40 KB of LDS hold)
+    uint32_t g = mfma_groups_per_chunk(W, (uint32_t)(n_held < (1u << 20) ? n_held : 1u << 20), false);
+    while (g > 2 && mfma_join_lds_bytes(W, g, form) > (size_t)MFMA_MAX_LDS) g -= 2;
+    return g;
+}
+
 int launch_mfma_join(int W, JoinForm form, bool cross, uint32_t blocks_x, uint32_t chunks, uint32_t groups, hipStream_t st, const MfmaJoinParams& p) {
     static_assert(MFMA_JOIN_WAVES == MBLOCK / 64, "the grid rule counts the kernel's waves");
-    const size_t lds = mfma_lds_bytes(W, groups);
+    const size_t lds = mfma_join_lds_bytes(W, groups, form);
     // the group pipeline walks pairs of groups; grid.y is 16 bits
     if (W < 1 || W > 4 || lds > (size_t)MFMA_MAX_LDS || groups < 2 || (groups & 1) || !blocks_x || !chunks || chunks > MFMA_JOIN_MAX_CHUNKS) return (int)hipErrorInvalidValue;
     const bool exists = with_join_form(form, cross, [&](auto f) { with_words(W, [&](auto w) {

@@ -98,11 +98,12 @@ __global__ __launch_bounds__(BLOCK) void gather_u32_kernel(const uint32_t* src, 
 }
 
 // isccsearch_join_components: out[i] = the label of row i of a segment -- live_labels[r] where live_keys[r] (strictly ascending) is
-// the row's key, 0xFFFFFFFF (no label) where the key is not listed.  64-bit keys.
+// the row's key, 0xFFFFFFFF (no label) where the key is not listed.  64-bit keys.  isccsearch_join_degrees / _within_live: live_labels
+// NULL, the label is r itself (n_live < 2^32 - 1 is checked by the host).
 struct LabelParams {
     const uint64_t* keys;          // the segment's key column [n]
     const uint64_t* live_keys;     // [n_live]
-    const uint32_t* live_labels;   // [n_live]
+    const uint32_t* live_labels;   // [n_live], or NULL: the key's index
     uint32_t* out;                 // [n]
     uint64_t n, n_live;
 };
@@ -115,7 +116,7 @@ __global__ __launch_bounds__(BLOCK) void label_rows_kernel(const LabelParams p) 
             if (p.live_keys[mid] < key) lo = mid + 1;
             else hi = mid;
         }
-        p.out[i] = lo < p.n_live && p.live_keys[lo] == key ? p.live_labels[lo] : UF_NONE;
+        p.out[i] = lo < p.n_live && p.live_keys[lo] == key ? (p.live_labels ? p.live_labels[lo] : (uint32_t)lo) : UF_NONE;
     }
 }
 

@@ -369,15 +369,53 @@ class HipTable(TableChecks):
             _lib.check(self.engine._lib.isccsearch_search_within(self.engine.handle, self.id, nq, _lib.ptr(q_words), _lib.ptr(q_nbytes), k, int(max_hamming), *addr))
         return out
 
-    def join_within(self, max_hamming_by_prefix, max_pairs):
-        # type: (object, int) -> tuple
+    def join_within(self, max_hamming_by_prefix, max_pairs, live_keys=None):
+        # type: (object, int, np.ndarray | None) -> tuple
         """
         Every unordered pair of distinct rows within ``max_hamming_by_prefix[p]`` bits over their common prefix of p bytes
         (33 entries, p = 1..32; a negative entry excludes that prefix): ``(keys_a, keys_b, hamming, prefix_bits)``, key_a < key_b,
         sorted by (key_a, key_b).  One library call with room for ``min(max_pairs, 2^20)`` pairs, retried once with exactly
         the total when more were found.  More than ``max_pairs`` pairs raise ValueError: the cap is never applied silently.
+        ``live_keys`` (uint64, strictly ascending; 64-bit keys only): only the pairs whose two rows' keys are both listed
+        (``isccsearch_join_within_live``) -- the other rows are compared, but take no room and do not count towards ``max_pairs``.
         """
-        return self._join("isccsearch_join_within", (self.id,), max_hamming_by_prefix, max_pairs)
+        if live_keys is None:
+            return self._join("isccsearch_join_within", (self.id,), max_hamming_by_prefix, max_pairs)
+        live_keys = self._live_keys("join_within", live_keys)
+        n_live = live_keys.shape[0]
+        return self._join("isccsearch_join_within_live", (self.id,), max_hamming_by_prefix, max_pairs,
+                          (n_live, _lib.ptr(live_keys) if n_live else None))
+
+    def join_degrees(self, max_hamming_by_prefix, live_keys):
+        # type: (object, np.ndarray) -> tuple
+        """
+        ``(degrees, links)``: for every key of ``live_keys`` (uint64, strictly ascending) the number of OTHER listed rows that
+        ``join_within(max_hamming_by_prefix, ..)`` pairs its row with (uint32; 0 for a key the table does not hold), and the number
+        of such pairs -- ``degrees.sum() == 2 * links`` -- without the pairs: counted on the device (``isccsearch_join_degrees``), 4
+        bytes per listed key and per row whatever the number of pairs, so a row with 10^5 near-duplicates is a number and not 5 * 10^9
+        pairs.  A row whose key is not listed is compared but never counted.  64-bit keys only.
+        """
+        mh = np.ascontiguousarray(max_hamming_by_prefix, dtype=np.int16)
+        if mh.shape != (_lib.MAX_BYTES + 1,):
+            raise ValueError(f"max_hamming_by_prefix must have {_lib.MAX_BYTES + 1} entries (prefix bytes 0..{_lib.MAX_BYTES})")
+        live_keys = self._live_keys("join_degrees", live_keys)
+        n_live = live_keys.shape[0]
+        degrees = np.zeros(n_live, dtype=np.uint32)
+        links = ctypes.c_uint64()
+        _lib.check(self.engine._lib.isccsearch_join_degrees(
+            self.engine.handle, self.id, _lib.ptr(mh), n_live, _lib.ptr(live_keys) if n_live else None,
+            _lib.ptr(degrees) if n_live else None, ctypes.byref(links)))
+        return degrees, int(links.value)
+
+    def _live_keys(self, caller, live_keys):
+        # type: (str, np.ndarray) -> np.ndarray
+        """``live_keys`` of a join over listed rows as the library takes them: a C-contiguous uint64 array shaped [n_live]."""
+        if self.key_words != 1:
+            raise ValueError(f"{caller} with live_keys needs a table of 64-bit keys")
+        live_keys = np.ascontiguousarray(live_keys, dtype=np.uint64)
+        if live_keys.ndim != 1:
+            raise ValueError("live_keys must be shaped [n_live]")
+        return live_keys
 
     def join_between(self, other, max_hamming_by_prefix, max_pairs):
         # type: (HipTable, object, int) -> tuple
@@ -520,9 +558,10 @@ class HipTable(TableChecks):
         info = dict(zip(("chunk_pairs", "records") + names, (int(v) for v in info)))
         return (records, *chunks, info, runs[0][: info["segments"]] if segments else None)
 
-    def _join(self, symbol, tables, max_hamming_by_prefix, max_pairs):
-        # type: (str, tuple, object, int) -> tuple
-        """One pair join of the library: ``(keys_a, keys_b, hamming, prefix_bits)``."""
+    def _join(self, symbol, tables, max_hamming_by_prefix, max_pairs, live=()):
+        # type: (str, tuple, object, int, tuple) -> tuple
+        """One pair join of the library: ``(keys_a, keys_b, hamming, prefix_bits)``.  ``live``: the arguments between ``max_hamming``
+        and ``capacity`` (``isccsearch_join_within_live``: n_live, live_keys)."""
         mh = np.ascontiguousarray(max_hamming_by_prefix, dtype=np.int16)
         if mh.shape != (_lib.MAX_BYTES + 1,):
             raise ValueError(f"max_hamming_by_prefix must have {_lib.MAX_BYTES + 1} entries (prefix bytes 0..{_lib.MAX_BYTES})")
@@ -532,7 +571,7 @@ class HipTable(TableChecks):
         def once(capacity):
             kshape = (capacity, 2) if self.key_words == 2 else (capacity,)
             out = (np.empty(kshape, np.uint64), np.empty(kshape, np.uint64), np.empty(capacity, np.uint32), np.empty(capacity, np.uint16))
-            rc = call(self.engine.handle, *tables, _lib.ptr(mh), capacity, *(_lib.ptr(a) for a in out), ctypes.byref(total))
+            rc = call(self.engine.handle, *tables, _lib.ptr(mh), *live, capacity, *(_lib.ptr(a) for a in out), ctypes.byref(total))
             n = int(total.value)
             return rc, n, tuple(a[:n] for a in out)
 

@@ -22,7 +22,7 @@ import numpy as np
 from iscc_search_amd import chunk_match, codec, snapshot, unit_match
 from iscc_search_amd._lib import MAX_K
 from iscc_search_amd.nphd import HipNphdIndex
-from iscc_search_amd.pairs import DuplicateGroup, DuplicatePair, IndexMatch, SharedContent, SharedMatch, group_side, join_sides, shared_sides
+from iscc_search_amd.pairs import DuplicateGroup, DuplicatePair, Hub, IndexMatch, SharedContent, SharedMatch, group_side, hub_side, join_sides, shared_sides
 from iscc_search_amd.schema import IsccAddResult, IsccEntry, IsccGlobalMatch, IsccQuery, IsccSearchResult, Status
 from iscc_search_amd.simprint import HipSimprintIndex, pack_chunk_pointer, unpack_chunk_pointer
 from iscc_search_amd.unit_match import INSTANCE_FIRST_K, UnitMatches, _checked_limit, _is_instance, _unit_map, _unit_max_hamming  # noqa: F401
@@ -303,22 +303,28 @@ class HipIndex:
             tables = {t: idx for t, idx in self._sp_tables.items() if simprint_types is None or t in simprint_types}
             return (tables, {t: list(self._sp_assets.get(t, {})) for t in tables}), self._realm_id or 0
 
-    def find_duplicates(self, min_score=None, unit_types=None, max_pairs=1_000_000):
-        # type: (Optional[float], Optional[List[str]], int) -> List[DuplicatePair]
+    def find_duplicates(self, min_score=None, unit_types=None, max_pairs=1_000_000, max_degree=None):
+        # type: (Optional[float], Optional[List[str]], int, Optional[int]) -> List[DuplicatePair]
         """
         Every pair of assets {a, b} that ``search_assets(IsccQuery(iscc_id=a), limit=len(index))`` would list as b's match,
         with that score and the confident part of b's unit scores -- found by ONE self-join per unit table on the device
         (``HipTable.join_within``) instead of a search per asset.  Units are compared as they were indexed.  Pairs are
         aggregated over the unit types both assets carry, kept when one unit is confident (and the score is >= ``min_score``,
         if given), and ordered by score descending, then (key_a, key_b).  ``unit_types`` restricts the unit tables joined.
-        More than ``max_pairs`` unit pairs in one table raise ValueError.
+        More than ``max_pairs`` unit pairs in one table raise ValueError.  ``max_degree`` keeps HUBS out: an asset whose unit of a type
+        has more than ``max_degree`` near-duplicates among the assets that carry the type (``find_hubs`` lists them: a black frame,
+        silence, 10 000 re-uploads of one file -- h * (h - 1) / 2 pairs that would exceed ``max_pairs`` and hide every other pair)
+        takes no part in THAT table's join; it still pairs through its other unit types.  The degree is counted once, in the full
+        table, on the device.  None: no hub is left out and nothing is counted.
         """
+        if max_degree is not None and max_degree < 0:
+            raise ValueError(f"max_degree must be >= 0, got {max_degree}")
         side, realm = self._join_side(unit_types)
         return [DuplicatePair(codec.iscc_id_from_int(a, realm), codec.iscc_id_from_int(b, realm), score, types)
-                for a, b, score, types in join_sides("find_duplicates", side, side, self._opts, min_score, max_pairs)]
+                for a, b, score, types in join_sides("find_duplicates", side, side, self._opts, min_score, max_pairs, max_degree)]
 
-    def find_duplicate_groups(self, unit_types=None, threshold=None, min_size=2):
-        # type: (Optional[List[str]], Optional[float], int) -> List[DuplicateGroup]
+    def find_duplicate_groups(self, unit_types=None, threshold=None, min_size=2, max_degree=None):
+        # type: (Optional[List[str]], Optional[float], int, Optional[int]) -> List[DuplicateGroup]
         """
         The groups of near-duplicate assets: the connected components of the graph whose vertices are this index's assets and
         whose edges are exactly the pairs ``find_duplicates(unit_types=unit_types)`` lists on an index whose
@@ -328,13 +334,34 @@ class HipIndex:
         pairs there are, so 10 000 copies of one file are one group and not 5 * 10^7 pairs over ``max_pairs``.  Groups of at least
         ``min_size`` assets, by size descending, then by smallest key; ``iscc_ids`` ascending by key.  There is no
         ``min_score``: an aggregated score needs every table's unit scores per pair, which is what ``find_duplicates`` computes.
+        ``max_degree``: as for ``find_duplicates`` -- the hubs of a table link nothing in it, so the groups are the components of
+        ``find_duplicates(max_degree=max_degree)`` and nothing chains through a hub.
+        """
+        threshold = self._opts.match_threshold_units if threshold is None else float(threshold)
+        if not 0.0 < threshold <= 1.0:
+            raise ValueError(f"threshold must be in (0, 1], got {threshold}")
+        if max_degree is not None and max_degree < 0:
+            raise ValueError(f"max_degree must be >= 0, got {max_degree}")
+        side, realm = self._join_side(unit_types)
+        return [DuplicateGroup([codec.iscc_id_from_int(k, realm) for k in group.tolist()], len(group))
+                for group in group_side("find_duplicate_groups", side, threshold, min_size, max_degree)]
+
+    def find_hubs(self, min_degree=1, unit_types=None, threshold=None):
+        # type: (int, Optional[List[str]], Optional[float]) -> List[Hub]
+        """
+        Which assets are the hubs, and how many near-duplicates each asset has: every (asset, unit type) whose unit has at least
+        ``min_degree`` other assets within the threshold among the assets that carry the type as indexed -- the number of pairs
+        ``find_duplicates`` would owe to that unit alone, a registry's "most copied" list -- ordered by (-degree, iscc_id, unit_type).
+        Counted per row on the device (``HipTable.join_degrees``), 4 bytes per asset and per row however many pairs there are: no pair is
+        materialised.  ``threshold`` defaults to ``match_threshold_units`` (outside (0, 1]: ValueError); ``unit_types`` restricts the
+        unit tables counted.  ``max_degree`` of ``find_duplicates`` / ``find_duplicate_groups`` leaves out what this lists above it.
         """
         threshold = self._opts.match_threshold_units if threshold is None else float(threshold)
         if not 0.0 < threshold <= 1.0:
             raise ValueError(f"threshold must be in (0, 1], got {threshold}")
         side, realm = self._join_side(unit_types)
-        return [DuplicateGroup([codec.iscc_id_from_int(k, realm) for k in group.tolist()], len(group))
-                for group in group_side("find_duplicate_groups", side, threshold, min_size)]
+        return [Hub(codec.iscc_id_from_int(key, realm), unit_type, degree)
+                for key, unit_type, degree in hub_side("find_hubs", side, threshold, min_degree)]
 
     def find_matches(self, other, min_score=None, unit_types=None, max_pairs=1_000_000):
         # type: (HipIndex, Optional[float], Optional[List[str]], int) -> List[IndexMatch]

@@ -14,7 +14,7 @@ from typing import Dict, List, Optional
 from urllib.parse import parse_qs, urlparse
 
 from iscc_search_amd.index import HipIndex, HipOptions
-from iscc_search_amd.pairs import DuplicateGroup, DuplicatePair, IndexMatch, SharedContent, SharedMatch
+from iscc_search_amd.pairs import DuplicateGroup, DuplicatePair, Hub, IndexMatch, SharedContent, SharedMatch
 from iscc_search_amd.schema import IsccAddResult, IsccEntry, IsccIndex, IsccQuery, IsccSearchResult
 
 INDEX_NAME_RE = re.compile(r"^[a-z][a-z0-9]*$")
@@ -271,17 +271,23 @@ class HipIndexManager:
             raise FileNotFoundError(f"queries[{i}]: Asset '{queries[i].iscc_id}' not found in index '{index_name}'") from e
 
     # the pair finders are refused on a sharded index, and on one GPU a protocol call takes no lock: they need no mode
-    def find_duplicates(self, index_name, min_score=None, unit_types=None, max_pairs=1_000_000):
-        # type: (str, Optional[float], Optional[List[str]], int) -> List[DuplicatePair]
+    def find_duplicates(self, index_name, min_score=None, unit_types=None, max_pairs=1_000_000, max_degree=None):
+        # type: (str, Optional[float], Optional[List[str]], int, Optional[int]) -> List[DuplicatePair]
         """Near-duplicate asset pairs of one index (``HipIndex.find_duplicates``).  Not available on a sharded index."""
         self._refuse_sharded("find_duplicates")
-        return self._locked_index(index_name).find_duplicates(min_score=min_score, unit_types=unit_types, max_pairs=max_pairs)
+        return self._locked_index(index_name).find_duplicates(min_score=min_score, unit_types=unit_types, max_pairs=max_pairs, max_degree=max_degree)
 
-    def find_duplicate_groups(self, index_name, unit_types=None, threshold=None, min_size=2):
-        # type: (str, Optional[List[str]], Optional[float], int) -> List[DuplicateGroup]
+    def find_duplicate_groups(self, index_name, unit_types=None, threshold=None, min_size=2, max_degree=None):
+        # type: (str, Optional[List[str]], Optional[float], int, Optional[int]) -> List[DuplicateGroup]
         """Groups of near-duplicate assets of one index (``HipIndex.find_duplicate_groups``).  Not available on a sharded index."""
         self._refuse_sharded("find_duplicate_groups")
-        return self._locked_index(index_name).find_duplicate_groups(unit_types=unit_types, threshold=threshold, min_size=min_size)
+        return self._locked_index(index_name).find_duplicate_groups(unit_types=unit_types, threshold=threshold, min_size=min_size, max_degree=max_degree)
+
+    def find_hubs(self, index_name, min_degree=1, unit_types=None, threshold=None):
+        # type: (str, int, Optional[List[str]], Optional[float]) -> List[Hub]
+        """The assets of one index with many near-duplicates, per unit type (``HipIndex.find_hubs``).  Not available on a sharded index."""
+        self._refuse_sharded("find_hubs")
+        return self._locked_index(index_name).find_hubs(min_degree=min_degree, unit_types=unit_types, threshold=threshold)
 
     def find_shared_content(self, index_name, min_chunks=1, min_coverage=None, simprint_types=None, threshold=None, max_doc_freq=100, max_pairs=1_000_000,
                             segments=False, min_segment=1, max_gap=0):

@@ -5,7 +5,9 @@ unit type -> ``HipNphdIndex``, and asset key -> {unit_type: body} as indexed.  A
 on the device where the pairs were (``find_duplicate_groups``, ``HipTable.join_components``).  And asset pairs that share CHUNKS, by a
 join of the simprint tables aggregated on the device (``shared_sides``, ``HipSimprintIndex.shared``): a self-join per table for
 ``find_shared_content``, a cross join of the two tables of every type for ``find_shared_matches``; with ``segments=True`` the same
-join also locates the shared chunks.
+join also locates the shared chunks.  And the HUBS of a unit table -- rows with more near-duplicates than a caller wants to see as pairs (a black
+frame, silence, 10 000 re-uploads of one file) -- by a count per row on the device where the pairs were (``table_degrees``,
+``HipTable.join_degrees``): ``find_hubs`` lists them, and ``max_degree`` keeps them out of the pairs and the groups.
 """
 
 from dataclasses import dataclass
@@ -24,6 +26,15 @@ class DuplicatePair:
     iscc_id_b: str
     score: float
     types: Dict[str, float]   # the confident unit scores, in the unit order of asset a
+
+
+@dataclass
+class Hub:
+    """One entry of ``find_hubs``: an asset and how many other assets are near-duplicates of it in one unit type."""
+
+    iscc_id: str
+    unit_type: str
+    degree: int             # other assets that carry the type and whose unit is within the threshold of this asset's
 
 
 @dataclass
@@ -123,15 +134,51 @@ def _rank_pairs(pair_scores, units_a, thr, exp, min_score):
     return out
 
 
-def join_sides(caller, side_a, side_b, opts, min_score, max_pairs):
-    # type: (str, tuple, tuple, object, Optional[float], int) -> list
+def table_degrees(caller, units, unit_type, table, max_hamming):
+    # type: (str, Dict[int, Dict[str, bytes]], str, object, np.ndarray) -> tuple
+    """
+    ``(live_keys, degrees)`` of one unit table at ``max_hamming``: its live rows -- those of the assets that carry ``unit_type`` as
+    indexed, ascending by key; a row an update left behind in a table of a type its asset no longer carries is not among them --
+    and for each the number of other live rows within the threshold (``HipTable.join_degrees``: counted on the device, no pairs).
+    The one place that decides both, for ``find_hubs`` and for ``max_degree`` of the pairs and the groups.  Tables without
+    ``join_degrees`` (a sharded engine's) raise NotImplementedError naming ``caller``.
+    """
+    if not hasattr(table, "join_degrees"):
+        raise NotImplementedError(f"{caller} needs a single-GPU engine: pairs across shards need their rows exchanged")
+    live_keys = np.array(sorted(k for k, by_type in units.items() if unit_type in by_type), dtype=np.uint64)
+    degrees, _ = table.join_degrees(max_hamming, live_keys)
+    return live_keys, degrees
+
+
+def hub_side(caller, side, threshold, min_degree):
+    # type: (str, tuple, float, int) -> list
+    """[(key, unit_type, degree)] of every live row of ``side``'s unit tables with ``degree >= min_degree`` at ``match_threshold_units =
+    threshold`` (``table_degrees``), ordered by (-degree, key, unit_type)."""
+    tables, units = side
+    out = []
+    for unit_type in sorted(tables):
+        live_keys, degrees = table_degrees(caller, units, unit_type, tables[unit_type]._table, _unit_max_hamming(threshold, _is_instance(unit_type)))
+        keep = degrees >= min_degree
+        out.extend((k, unit_type, d) for k, d in zip(live_keys[keep].tolist(), degrees[keep].tolist()))
+    out.sort(key=lambda r: (-r[2], r[0], r[1]))
+    return out
+
+
+def join_sides(caller, side_a, side_b, opts, min_score, max_pairs, max_degree=None):
+    # type: (str, tuple, tuple, object, Optional[float], int, Optional[int]) -> list
     """
     The ranked pairs (``_rank_pairs``) of side a's assets with side b's: ONE join per unit type both sides have a table for --
     a self-join where ``side_b`` is ``side_a`` -- at the largest distance per code length that ``opts``' threshold still calls
     confident, aggregated over the unit types both assets carry.  More than ``max_pairs`` unit pairs in one table raise
     ValueError; tables without the join (a sharded engine's) raise NotImplementedError naming ``caller``.
+    ``max_degree`` (a self-join only): a live row with more than ``max_degree`` other live rows within its table's threshold is a HUB
+    of that table and is left out of that table's join (``join_within`` with ``live_keys``), so its pairs neither appear nor count
+    towards ``max_pairs``.  The degree is taken ONCE, in the full table (``table_degrees``), and not again after the hubs are gone: the
+    rule by which ``max_doc_freq`` decides stop chunks.  None: no degree pass, and the calls made are those without the argument.
     """
     (tables_a, units_a), (tables_b, units_b) = side_a, side_b
+    if max_degree is not None and side_b is not side_a:
+        raise ValueError(f"{caller}: max_degree is defined within one index")
     thr, exp = opts.match_threshold_units, opts.confidence_exponent
     pair_scores = {}  # type: Dict[tuple, Dict[str, float]]
     for unit_type in sorted(set(tables_a) & set(tables_b)):
@@ -140,21 +187,27 @@ def join_sides(caller, side_a, side_b, opts, min_score, max_pairs):
             raise NotImplementedError(f"{caller} needs a single-GPU engine: pairs across shards need their rows exchanged")
         instance = _is_instance(unit_type)
         max_hamming = _unit_max_hamming(thr, instance)
-        join = table_a.join_within(max_hamming, max_pairs) if side_b is side_a else table_a.join_between(table_b, max_hamming, max_pairs)
+        if max_degree is not None:
+            live_keys, degrees = table_degrees(caller, units_a, unit_type, table_a, max_hamming)
+            join = table_a.join_within(max_hamming, max_pairs, live_keys[degrees <= max_degree])
+        else:
+            join = table_a.join_within(max_hamming, max_pairs) if side_b is side_a else table_a.join_between(table_b, max_hamming, max_pairs)
         _merge_join(pair_scores, unit_type, join, instance, units_a, units_b)
     return _rank_pairs(pair_scores, units_a, thr, exp, min_score)
 
 
-def group_side(caller, side, threshold, min_size):
-    # type: (str, tuple, float, int) -> list
+def group_side(caller, side, threshold, min_size, max_degree=None):
+    # type: (str, tuple, float, int, Optional[int]) -> list
     """
     The connected components of ``side``'s assets under the pairs ``join_sides(caller, side, side, ...)`` lists at
     ``match_threshold_units = threshold``: one uint64 array of asset keys (ascending) per component of at least ``min_size``
     assets, by size descending, then by smallest key.  Labels are the ranks of the sorted asset keys, so a component's smallest
     label is its smallest key; ONE ``join_components`` per unit table, in sorted type order, carries one ``parent`` array through
     them all.  Per table the live rows are those of the assets that carry its type: a row an update left behind in a table of a
-    type its asset no longer carries links nothing (``_merge_join`` says the same for pairs).  Tables without ``join_components``
-    (a sharded engine's) raise NotImplementedError naming ``caller``.
+    type its asset no longer carries links nothing (``_merge_join`` says the same for pairs).  ``max_degree``: as for ``join_sides``
+    -- a table's hubs (``table_degrees``, taken once in the full table) are left out of its ``live_keys`` and link nothing there, so
+    nothing chains through them; None: no degree pass.  Tables without ``join_components`` (a sharded engine's) raise
+    NotImplementedError naming ``caller``.
     """
     tables, units = side
     keys = np.array(sorted(units), dtype=np.uint64)
@@ -167,9 +220,14 @@ def group_side(caller, side, threshold, min_size):
             raise NotImplementedError(f"{caller} needs a single-GPU engine: pairs across shards need their rows exchanged")
         if not len(keys):
             continue
-        live_keys = np.array(sorted(k for k, by_type in units.items() if unit_type in by_type), dtype=np.uint64)
+        max_hamming = _unit_max_hamming(threshold, _is_instance(unit_type))
+        if max_degree is not None:
+            live_keys, degrees = table_degrees(caller, units, unit_type, table, max_hamming)
+            live_keys = live_keys[degrees <= max_degree]
+        else:
+            live_keys = np.array(sorted(k for k, by_type in units.items() if unit_type in by_type), dtype=np.uint64)
         live_labels = np.searchsorted(keys, live_keys).astype(np.uint32)
-        table.join_components(_unit_max_hamming(threshold, _is_instance(unit_type)), live_keys, live_labels, parent)
+        table.join_components(max_hamming, live_keys, live_labels, parent)
     # parent is flat: parent[i] is the component's smallest label.  Members by (root, label); groups by (-size, root)
     roots, counts = np.unique(parent, return_counts=True)
     members = np.argsort(parent, kind="stable")

@@ -48,6 +48,17 @@ the segments to find.  On either kernel three legs A B A (join_overlaps_between,
 warm-up call and the median of --reps; the tool asserts that both calls agree on chunk pairs and records and that the segments' lengths
 add up to the chunk pairs.  Its output is what profiles/join_segments_between_rate.txt records.
 
+--degrees: isccsearch_join_degrees (the joins' DEGREE form: a count per row, no pairs) against isccsearch_join_within and
+isccsearch_join_components of the SAME build and run, on 64-bit HAMMING and 256-bit NPHD tables of host-generated rows (keys 1..n).
+(a) uniform random rows: per kernel five legs A B C B A (join_within, join_components, join_degrees, join_components, join_within), each
+one warm-up call and the median of --reps; `degrees_to_components` = join_degrees / mean of the two join_components legs -- they share
+the scan.  (b) the same rows with the code of row 0 planted in --hub rows (default 10 000: 5 * 10^7 pairs, over join_within's default
+max_pairs): legs B C B; the tool asserts that the calls agree on the links and that exactly the hub's rows have degree >= hub - 1.
+--baseline DIR: a built checkout of another commit (the parent).  Before anything else the existing modes (the pair join, --components,
+--overlaps) run from DIR, from this tree and from DIR again, every run a process of its own, their lines printed under the tree's name:
+this tree's join_within, join_components and join_overlaps between two runs of the baseline.  Its output is what
+profiles/join_degrees_rate.txt records.
+
 usage: python tools/bench_duplicates.py [--mfma both] [--reps 5] [--sizes 65536,262144,1048576,4194304] [--nphd-sizes 262144,1048576] [--tau 6]
        python tools/bench_duplicates.py --between [--rows-a N --rows-b M] [the same options]
        python tools/bench_duplicates.py --components [--sizes 1048576 --nphd-sizes 1048576] [--dense-rows 1048576 --cluster 1000]
@@ -55,12 +66,14 @@ usage: python tools/bench_duplicates.py [--mfma both] [--reps 5] [--sizes 65536,
        python tools/bench_duplicates.py --overlaps-between [--sizes 65536,262144,1048576] [--shared 3]
        python tools/bench_duplicates.py --segments [--sizes 65536,1048576] [--shared 3]
        python tools/bench_duplicates.py --segments-between [--sizes 65536,262144,1048576] [--shared 3]
+       python tools/bench_duplicates.py --degrees [--sizes 65536,1048576 --nphd-sizes 65536,1048576] [--hub 10000] [--baseline DIR]
 """
 
 import argparse
 import json
 import os
 import statistics
+import subprocess
 import sys
 import time
 
@@ -216,6 +229,70 @@ def run_dense(engine, n, cluster, reps):
         return out
     finally:
         t.drop()
+
+
+def degrees_call(t, mh, n):
+    """join_degrees over all rows of a table whose keys are 1..n"""
+    live_keys = np.arange(1, n + 1, dtype=np.uint64)
+    return lambda: t.join_degrees(mh, live_keys)
+
+
+def run_degrees(engine, metric, nbytes, n, tau, reps, hub):
+    """join_degrees against join_within and join_components: (a) random rows, A B C B A per kernel; (b) with a hub planted, B C B."""
+    rng = np.random.default_rng(1234 + n + nbytes)
+    W = nbytes // 8
+    words = rng.integers(0, 2**64, size=(n, W), dtype=np.uint64)
+    keys = np.arange(1, n + 1, dtype=np.uint64)
+    mh = np.full(_lib.MAX_BYTES + 1, -1, dtype=np.int16)
+    mh[nbytes] = tau
+    nb = None if metric == _lib.METRIC_HAMMING else np.full(n, nbytes, dtype=np.uint8)
+    lines = []
+    for planted in (0, hub):
+        if planted:
+            words[rng.choice(np.arange(1, n), size=planted - 1, replace=False)] = words[0]
+        t = engine.open_table(metric, 1, nbytes)
+        try:
+            for lo in range(0, n, 1 << 18):
+                t.add(keys[lo:lo + (1 << 18)], words[lo:lo + (1 << 18)], None if nb is None else nb[lo:lo + (1 << 18)])
+            within = lambda: t.join_within(mh, 1 << 20)                   # noqa: E731
+            components, degrees = components_call(t, mh, n), degrees_call(t, mh, n)
+            out = {"join": "degrees", "rows_are": f"random, one code in {planted} rows" if planted else "random", "table": table_name(metric, nbytes),
+                   "rows": n, "tau": tau}
+            for mfma in (False, True):
+                a1, f1 = leg(engine, mfma, within, reps) if not planted else (None, None)
+                b1, links_1 = leg(engine, mfma, components, reps, found=lambda o: o[0])
+                c, (degree, links) = leg(engine, mfma, degrees, reps, found=lambda o: o)
+                b2, links_2 = leg(engine, mfma, components, reps, found=lambda o: o[0])
+                a2, f2 = leg(engine, mfma, within, reps) if not planted else (None, None)
+                assert links_1 == links == links_2 and int(degree.sum(dtype=np.uint64)) == 2 * links, (links_1, links, links_2)
+                res = dict(components_seconds=[round(b1, 5), round(b2, 5)], degrees_seconds=round(c, 5),
+                           degrees_to_components=round(c / ((b1 + b2) / 2), 4), links=links, largest_degree=int(degree.max()))
+                if planted:
+                    # (the few pairs random rows have among themselves may have lost a row to the hub, or gained the hub's)
+                    assert links >= planted * (planted - 1) // 2 and int((degree >= planted - 1).sum()) == planted, (links, planted)
+                else:
+                    assert f1 == links == f2, f"join_within found {f1} and {f2} pairs, join_degrees {links} links"
+                    res.update(within_seconds=[round(a1, 5), round(a2, 5)], degrees_to_within=round(c / ((a1 + a2) / 2), 4))
+                out["mfma" if mfma else "valu"] = res
+            lines.append(out)
+        finally:
+            t.drop()
+    return lines
+
+
+def existing_modes(tree, name, sizes, nphd_sizes, reps, tau):
+    """The pair join, --components and --overlaps of the tool of ``tree`` (this one, or a built checkout of another commit), each in a
+    process of its own with that tree's package and library; their lines, printed under ``name``."""
+    env = {k: v for k, v in os.environ.items() if k != "ISCC_HIP_LIB"}
+    common = ["--sizes", sizes, "--reps", str(reps), "--tau", str(tau)]
+    for mode in (["--nphd-sizes", nphd_sizes], ["--components", "--dense-rows", "0", "--nphd-sizes", nphd_sizes], ["--overlaps", "--search-rows", "0"]):
+        cmd = [sys.executable, os.path.join(tree, "tools", "bench_duplicates.py"), *mode, *common]
+        done = subprocess.run(cmd, capture_output=True, text=True, cwd=tree, env=env)
+        if done.returncode != 0:
+            raise RuntimeError(f"{' '.join(cmd)} failed:\n{done.stdout}\n{done.stderr}")
+        for line in done.stdout.splitlines():
+            if line.startswith("{"):
+                print(json.dumps({"tree": name, **json.loads(line)}), flush=True)
 
 
 def simprint_rows(rng, n, nbytes, per_asset, shared_pct):
@@ -402,14 +479,26 @@ def main():
     ap.add_argument("--segments", action="store_true", help="join_segments against join_overlaps on simprint tables (A B A on either kernel)")
     ap.add_argument("--segments-between", action="store_true",
                     help="join_segments_between against join_overlaps_between on two simprint tables (A B A on either kernel)")
+    ap.add_argument("--degrees", action="store_true", help="join_degrees against join_within and join_components (A B C B A per kernel), random rows and a planted hub")
+    ap.add_argument("--hub", type=int, default=10_000, help="--degrees: rows that hold the planted code")
+    ap.add_argument("--baseline", default="", help="--degrees: a built checkout of another commit whose existing modes run before and after this tree's")
     ap.add_argument("--shared", type=int, default=3, help="--overlaps, --overlaps-between, --segments, --segments-between: per cent of the assets that contain a run of another asset's chunks")
     ap.add_argument("--search-rows", type=int, default=65536, help="--overlaps: tables of up to this many rows also time one search_raw per asset")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args()
     sizes = [int(s) for s in a.sizes.split(",") if s]
     nphd_sizes = [int(s) for s in a.nphd_sizes.split(",") if s]
+    if a.degrees and a.baseline:                     # (before this process opens the device: one process on the card at a time)
+        for tree, name in ((a.baseline, "baseline"), (ROOT, "this"), (a.baseline, "baseline")):
+            existing_modes(os.path.abspath(tree), name, a.sizes, a.nphd_sizes, a.reps, a.tau)
     engine = HipEngine(a.device)
     try:
+        if a.degrees:
+            for metric, nbytes, table_sizes in ((_lib.METRIC_HAMMING, 8, sizes), (_lib.METRIC_NPHD, 32, nphd_sizes)):
+                for n in table_sizes:
+                    for line in run_degrees(engine, metric, nbytes, n, a.tau * nbytes // 8, a.reps, min(a.hub, n // 2)):
+                        print(json.dumps(line), flush=True)
+            return
         if a.segments_between:
             for nbytes in (8, 16):
                 for n in sizes:
